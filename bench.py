@@ -2,25 +2,30 @@
 """Headline benchmark: images/sec of the YOLO TEST-mode hot path (conv forward + head decode + NMS)
 on N MI355X GPUs of one node, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload v3-608-b32-fp16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload v3-608-b32-fp16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one synthetic batch resident in HBM: float32 NHWC input ->
 libyolo_hip detect (75 fused convs + decode + NMS) [-> RCCL all-gather of the fixed-size box
 records when N > 1].  Images shard over ranks (weak scaling: every rank runs the full per-GPU batch).
+Input images and weight stream come from fixed seeds, so the same arguments give the same inputs in every run (the objectness
+biases are then re-centred on the product's own forward of a seeded batch: synth.calibrate_model).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run ... bench.py` started before this process touches the GPU; rank 0's JSON line is the
 child's stdout, the exit code is the child's).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, runs W warm-up and K timed steps, writes the last timed step's outputs when `--dump-outputs DIR` is given
+(`dump_outputs`) and prints ONE JSON line (rank 0): the contract fields (`ms_per_step` = milliseconds of one timed step), "config"
+and "forward_frac_of_mfma_peak".  `--full` adds everything else the benchmark measures, each outside the timed region:
   "parity":       the metric's second half, "post-NMS box-set match vs CPU ref": EVERY image of the first timed batch through the
                   TIMED engine (same plan, same batch size) and through the CPU fp32 oracle pipeline OUTSIDE the timed region --
                   max |logit - oracle logit| against a bound the HIP path cannot influence and the post-NMS box sets under the
                   gate of oracle/parity.py
   "roofline":     dominant kernel family (the implicit-GEMM conv tile with most device time): algorithmic FLOPs of its launches
                   / their device time measured with hipEvents on the launch stream (instrumented steps
-                  run right after the timed region; the events add bubbles so they never time `value`)
+                  run right after the timed region; the events add bubbles so they never time `value`); `--dump-kernels FILE` runs
+                  these passes without `--full` too
   "cpu_baseline": the CPU oracle (torch-CPU restatement of the reference's TF path + NumPy decode/NMS,
                   kind "port") timed on the host cores on the same batch: forward and decode + NMS apart.
   "one_stream" / "two_streams": (N = 1) the batch as one pass on one stream and as two half batches on two streams, ALWAYS both: the mode
@@ -210,6 +215,64 @@ def parity_report(eng, kind, size, anchors, ncls, x, ref_logits, threshold, iou_
     return rep
 
 
+def roofline(eng1, eng, infos, xs, batch, dtype, workload, steps, dump_kernels=None):
+    """Instrumented passes of `eng1` (hipEvents on the launch stream, right after the timed region): the roofline figures of the
+    dominant kernel family, and the per-kernel table written to `dump_kernels` if given."""
+    reps = max(3, min(10, steps))
+    ms = np.zeros(eng1.num_kernels, dtype=np.float64)
+    for r in range(reps):
+        ms += eng1.forward_timed(xs[r & 1])
+    ms /= reps
+    fam = {}
+    for k, ki in enumerate(infos):
+        f = fam.setdefault(ki.name.decode(), {"launches": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0})
+        f["launches"] += 1
+        f["ms"] += float(ms[k])
+        f["flops"] += ki.flops * batch
+        f["bytes"] += ki.bytes * batch + ki.weight_bytes
+    dom = max(fam, key=lambda n: fam[n]["ms"])
+    d = fam[dom]
+    achieved = d["flops"] / (d["ms"] * 1e-3) / 1e12
+    dom_symbol = next(ki.symbol.decode() for ki in infos if ki.name.decode() == dom)
+    roof = {"bound": "mfma", "kernel": dom, "kernel_symbol": dom_symbol, "achieved": round(achieved, 2), "peak": PEAK[dtype], "unit": "TFLOP/s",
+            "frac": round(achieved / PEAK[dtype], 4), "traffic": None,
+            "launches_per_step": d["launches"], "avg_launch_ms": round(d["ms"] / d["launches"], 5),
+            "algorithmic_gflop_per_launch": round(d["flops"] / d["launches"] / 1e9, 3),
+            "algorithmic_mb_per_launch": round(d["bytes"] / d["launches"] / 1e6, 3),
+            "forward_ms_sum_of_kernels": round(float(ms.sum()), 4),
+            "whole_forward_tflops": round(eng1.flops_per_image * batch / (float(ms.sum()) * 1e-3) / 1e12, 2),
+            "measured_on": "whole-batch launches, one stream, each kernel alone on the chip (instrumented passes of %s; the same launches "
+                           "`bench.py --streams 1` times and profiles/*kernel_stats*.csv hold)" %
+                           ("the timed engine" if eng1 is eng else "a streams = 1 engine of the same weights")}
+    pk = os.path.join(ROOT, "profiles", "r04_peaks.json")      # measured ceilings of this chip family (tools/probes/peak_probe.hip)
+    if os.path.exists(pk):
+        try:
+            pj = json.load(open(pk))
+            roof["sustained_peak"] = pj["mfma_f16_tflops_sustained"] if dtype == "fp16" else pj.get("mfma_f32_tflops_sustained")
+            roof["sustained_peak_note"] = pj.get("note")
+        except Exception:
+            pass
+    tj = os.path.join(ROOT, "profiles", "traffic.json")      # HBM bytes per launch from rocprofv3 --pmc passes, if recorded
+    if os.path.exists(tj):
+        try:
+            tw = json.load(open(tj)).get(workload, {})
+            rec = tw.get(dom_symbol) or tw.get(dom)
+            if rec:     # recorded under rocprofv3 --pmc for this kernel family (may predate a retune)
+                roof["traffic"] = rec["hbm_bytes_per_launch"]
+                roof["traffic_detail"] = dict(rec, source="profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE)")
+        except Exception:
+            pass
+    if dump_kernels:
+        rows = [{"kernel": k, "name": ki.name.decode(), "symbol": ki.symbol.decode(), "layer": ki.layer, "k": ki.ksize, "s": ki.stride, "cin": ki.cin,
+                 "cout": ki.cout, "out_hw": [ki.out_h, ki.out_w], "ms": round(float(ms[k]), 5),
+                 "tflops": round(ki.flops * batch / (ms[k] * 1e-3) / 1e12, 2) if ms[k] > 0 else 0.0,
+                 "gbps": round((ki.bytes * batch + ki.weight_bytes) / (ms[k] * 1e-3) / 1e9, 1) if ms[k] > 0 else 0.0}
+                for k, ki in enumerate(infos)]
+        with open(dump_kernels, "w") as f:
+            json.dump({"workload": workload, "families": fam, "kernels": rows}, f, indent=1)
+    return roof
+
+
 def timed_region(step, steps, warmup, world, device_sync, reduce_device):
     """The bench contract's timed region: W untimed warm-up steps, then EXACTLY K steps bracketed by a barrier +
     device synchronise on both sides; the MAX over ranks is the job's time.  Returns (elapsed seconds, result of the last step).
@@ -248,6 +311,32 @@ def contract_fields(rank, world, steps, warmup, batch, elapsed, dtype):
             "vs_baseline": None, "dtype": "f16" if dtype == "fp16" else "f32", "data": "synthetic"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, boxes, counts, status, limit=DUMP_LIMIT_BYTES):
+    """What the timed path returned in its last step (`ydist.detect_sharded`), as float arrays for comparing builds output by output:
+    boxes.npy  float32 [images, K, 6]: (x, y, w, h, prob, class index) per record, zeros in the slots past an image's count (they hold
+               no record and no defined value); counts.npy / status.npy float64 [images].  Images in rank order = global image order.
+    Should the boxes exceed `limit` bytes, a fixed seeded sample of images is written instead, its indices in images.npy."""
+    b = boxes.cpu().numpy()
+    b = b.reshape((-1,) + b.shape[-2:]).copy()
+    c = counts.cpu().numpy().reshape(-1)
+    s = status.cpu().numpy().reshape(-1)
+    b[..., 5] = np.ascontiguousarray(b[..., 5]).view(np.int32).astype(np.float32)
+    b[np.arange(b.shape[1])[None, :] >= c[:, None]] = 0.0
+    out = {"boxes": b, "counts": c.astype(np.float64), "status": s.astype(np.float64)}
+    per_image = b[0].nbytes + 3 * 8         # boxes + counts + status (+ images when sampled)
+    budget = limit - 4096                   # (the .npy headers)
+    if per_image * b.shape[0] > budget:
+        keep = np.sort(np.random.RandomState(0).choice(b.shape[0], max(1, budget // per_image), replace=False))
+        out = {k: v[keep] for k, v in out.items()}
+        out["images"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_workers(n):
     """`python bench.py --gpus N` as the driver calls it: start the N ranks as a child torch.distributed.run job.  This
     process has not touched the GPU (torch is not even imported yet), nothing is exec'd; the child's exit code is ours."""
@@ -269,21 +358,27 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="v3-608-b32-fp16", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity check of the timed plan against the CPU oracle")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB; see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need, outside the timed region: "
+                    "the comparison legs of the other stream mode, the per-kernel roofline passes, the CPU baseline and the parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the parity check of the timed plan against the CPU oracle")
     ap.add_argument("--force-tile", type=int, default=None, help="tuning hook: yolo_net_options.force_tile (one conv tile id wherever valid)")
     ap.add_argument("--max-boxes", type=int, default=256, help="box records per image (SURVEY 8e: K_max = 256 -> 196.7 KB per rank)")
     ap.add_argument("--autotune", action="store_true", help="time every conv tile per layer on the device first (default: built-in rules)")
     ap.add_argument("--streams", type=int, default=0, help="yolo_net_options.streams: 0 = the library's rule (two half batches on two HIP "
                     "streams where that was measured faster, e.g. the headline workload; config.streams says what ran), 1 = one pass, "
                     "2..4 = that many parts.  The per-kernel roofline figures are always those of whole-batch launches run alone (streams = 1)")
-    ap.add_argument("--no-one-stream-leg", action="store_true", help="skip the one-stream comparison legs around the timed region (N = 1, "
-                    "only when the timed engine runs on more than one stream)")
+    ap.add_argument("--no-one-stream-leg", action="store_true", help="(--full) skip the comparison legs of the other stream mode around "
+                    "the timed region (N = 1)")
     ap.add_argument("--f32-products", type=int, default=0, help="yolo_net_options.f32_products (float32 nets): 0 the library's rule, 1 native float32 MFMA everywhere, 2 nine bf16 products wherever possible")
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--iou-threshold", type=float, default=0.6)
-    ap.add_argument("--dump-kernels", default=None, help="write the per-kernel timing table (JSON) here")
+    ap.add_argument("--dump-kernels", default=None, help="write the per-kernel timing table (JSON) here (runs the roofline passes)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:        # before anything touches the GPU
         sys.exit(launch_workers(args.gpus))
@@ -332,14 +427,15 @@ def main():
     def one_stream_engine():
         return other_engine(1)
 
+    kernel_passes = args.full or args.dump_kernels is not None
     eng1 = eng
-    if world == 1 and eng.num_streams > 1:          # (N > 1: rank 0 builds it after the timed region, nothing beside the ranks' steps)
+    if kernel_passes and world == 1 and eng.num_streams > 1:    # (N > 1: rank 0 builds it after the timed region, nothing beside the ranks' steps)
         eng1 = one_stream_engine()
     # the OTHER way of running the batch, as comparison legs around the timed region (N = 1): one pass when `value` runs two halves, two
     # halves (an explicit choice: half-size arenas) when `value` runs one pass -- whatever the tuner decided on this box, both numbers are
     # in the line.  A batch of one image has no halves.
     eng_other = None
-    if world == 1 and not args.no_one_stream_leg:
+    if args.full and world == 1 and not args.no_one_stream_leg:
         if eng.num_streams > 1:
             eng_other = eng1
         elif batch >= 2:
@@ -361,68 +457,18 @@ def main():
     nboxes = counts.cpu().numpy()
     if st.any() and not os.environ.get("YOLO_BENCH_WRONG_RESULTS_OK"):      # (tools/ timing experiments with intentionally wrong kernels only)
         raise RuntimeError("candidate / box-record capacity exceeded during the benchmark: result would not match the reference")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, boxes, counts, status)
     if legs:
         one_stream.append(timed_steps(eng_other, xs, args.steps, 0, args.threshold, args.iou_threshold))
 
     out = None
     if rank == 0:
-        if eng1 is eng and eng.num_streams > 1:
+        if kernel_passes and eng1 is eng and eng.num_streams > 1:
             eng1 = one_stream_engine()
         total_images = args.steps * batch * world
-        # ---- roofline of the dominant kernel family, instrumented steps (hipEvents on the launch stream), one-stream engine
         infos = eng1.kernel_infos()
-        reps = max(3, min(10, args.steps))
-        ms = np.zeros(eng1.num_kernels, dtype=np.float64)
-        for r in range(reps):
-            ms += eng1.forward_timed(xs[r & 1])
-        ms /= reps
-        fam = {}
-        for k, ki in enumerate(infos):
-            f = fam.setdefault(ki.name.decode(), {"launches": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0})
-            f["launches"] += 1
-            f["ms"] += float(ms[k])
-            f["flops"] += ki.flops * batch
-            f["bytes"] += ki.bytes * batch + ki.weight_bytes
-        dom = max(fam, key=lambda n: fam[n]["ms"])
-        d = fam[dom]
-        achieved = d["flops"] / (d["ms"] * 1e-3) / 1e12
-        dom_symbol = next(ki.symbol.decode() for ki in infos if ki.name.decode() == dom)
-        roof = {"bound": "mfma", "kernel": dom, "kernel_symbol": dom_symbol, "achieved": round(achieved, 2), "peak": PEAK[dtype], "unit": "TFLOP/s",
-                "frac": round(achieved / PEAK[dtype], 4), "traffic": None,
-                "launches_per_step": d["launches"], "avg_launch_ms": round(d["ms"] / d["launches"], 5),
-                "algorithmic_gflop_per_launch": round(d["flops"] / d["launches"] / 1e9, 3),
-                "algorithmic_mb_per_launch": round(d["bytes"] / d["launches"] / 1e6, 3),
-                "forward_ms_sum_of_kernels": round(float(ms.sum()), 4),
-                "whole_forward_tflops": round(eng1.flops_per_image * batch / (float(ms.sum()) * 1e-3) / 1e12, 2),
-                "measured_on": "whole-batch launches, one stream, each kernel alone on the chip (instrumented passes of %s; the same launches "
-                               "`bench.py --streams 1` times and profiles/*kernel_stats*.csv hold)" %
-                               ("the timed engine" if eng1 is eng else "a streams = 1 engine of the same weights")}
-        pk = os.path.join(ROOT, "profiles", "r04_peaks.json")      # measured ceilings of this chip family (tools/probes/peak_probe.hip)
-        if os.path.exists(pk):
-            try:
-                pj = json.load(open(pk))
-                roof["sustained_peak"] = pj["mfma_f16_tflops_sustained"] if dtype == "fp16" else pj.get("mfma_f32_tflops_sustained")
-                roof["sustained_peak_note"] = pj.get("note")
-            except Exception:
-                pass
-        tj = os.path.join(ROOT, "profiles", "traffic.json")      # HBM bytes per launch from rocprofv3 --pmc passes, if recorded
-        if os.path.exists(tj):
-            try:
-                tw = json.load(open(tj)).get(args.workload, {})
-                rec = tw.get(dom_symbol) or tw.get(dom)
-                if rec:     # recorded under rocprofv3 --pmc for this kernel family (may predate a retune)
-                    roof["traffic"] = rec["hbm_bytes_per_launch"]
-                    roof["traffic_detail"] = dict(rec, source="profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE)")
-            except Exception:
-                pass
-        if args.dump_kernels:
-            rows = [{"kernel": k, "name": ki.name.decode(), "symbol": ki.symbol.decode(), "layer": ki.layer, "k": ki.ksize, "s": ki.stride, "cin": ki.cin,
-                     "cout": ki.cout, "out_hw": [ki.out_h, ki.out_w], "ms": round(float(ms[k]), 5),
-                     "tflops": round(ki.flops * batch / (ms[k] * 1e-3) / 1e12, 2) if ms[k] > 0 else 0.0,
-                     "gbps": round((ki.bytes * batch + ki.weight_bytes) / (ms[k] * 1e-3) / 1e9, 1) if ms[k] > 0 else 0.0}
-                    for k, ki in enumerate(infos)]
-            with open(args.dump_kernels, "w") as f:
-                json.dump({"workload": args.workload, "families": fam, "kernels": rows}, f, indent=1)
+        roof = roofline(eng1, eng, infos, xs, batch, dtype, args.workload, args.steps, args.dump_kernels) if kernel_passes else None
         out = contract_fields(rank, world, args.steps, args.warmup, batch, elapsed, dtype)
         out.update({
             "config": {"workload": args.workload, "network": kind, "input": [size, size, 3], "batch_per_gpu": batch,
@@ -439,33 +485,34 @@ def main():
                                                 "(exact partial products, float32 accumulation; 1 = native float32 MFMA everywhere)"
                                                 % (args.f32_products, sum("conv_igemm_emu" in ki.name.decode() for ki in infos), len(infos))}
                           if dtype == "fp32" else {})},
-            "roofline": roof,
+            **({"roofline": roof} if kernel_passes else {}),
             "forward_frac_of_mfma_peak": round(eng.flops_per_image * total_images / elapsed / 1e12 / (PEAK[dtype] * world), 4),
         })
-        if world == 1:
-            mine = "one_stream" if eng.num_streams == 1 else "two_streams"
-            out[mine] = {"streams": int(eng.num_streams), "value": out["value"], "unit": "images/sec", "ms_per_step": out["ms_per_step"],
-                         "role": "the timed region (`value`)"}
-        if legs:
-            dt1 = 0.5 * (one_stream[0] + one_stream[1])
-            other = "two_streams" if eng.num_streams == 1 else "one_stream"
-            out[other] = {"streams": int(eng_other.num_streams), "value": round(args.steps * batch / dt1, 2), "unit": "images/sec",
-                          "ms_per_step": round(dt1 / args.steps * 1e3, 4),
-                          "ms_per_step_before_after": [round(one_stream[0] / args.steps * 1e3, 4), round(one_stream[1] / args.steps * 1e3, 4)],
-                          "role": "comparison legs: same build, weights, inputs and K steps, timed right before and right after the timed "
-                                  "region (A / timed / A); `value` above is the %d-stream run" % eng.num_streams}
-        out["cpu_baseline"] = out["parity"] = None
-        # the CPU baseline is timed on rank 0 at N = 1 only (bench contract); the parity check (rank 0's TIMED engine, every image of
-        # its first batch, outside the timed region, before the process group goes away) runs at every N
-        time_cpu = world == 1 and not args.no_cpu_baseline
-        if time_cpu or not args.no_parity:
-            base, ref_logits, e_ref = cpu_baseline(kind, size, w, anchors, ncls, xs_host[0], dtype, time_it=time_cpu)
-            out["cpu_baseline"] = base
-            if not args.no_parity:
-                out["parity"] = parity_report(eng, kind, size, anchors, ncls, xs[0], ref_logits, args.threshold, args.iou_threshold, dtype, e_ref)
-        if world > 1:
-            out["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": 0, "kind": "port",
-                                   "sample": "not timed at N > 1: the CPU baseline is a property of the host, see the N = 1 line"}
+        if args.full:
+            if world == 1:
+                mine = "one_stream" if eng.num_streams == 1 else "two_streams"
+                out[mine] = {"streams": int(eng.num_streams), "value": out["value"], "unit": "images/sec", "ms_per_step": out["ms_per_step"],
+                             "role": "the timed region (`value`)"}
+            if legs:
+                dt1 = 0.5 * (one_stream[0] + one_stream[1])
+                other = "two_streams" if eng.num_streams == 1 else "one_stream"
+                out[other] = {"streams": int(eng_other.num_streams), "value": round(args.steps * batch / dt1, 2), "unit": "images/sec",
+                              "ms_per_step": round(dt1 / args.steps * 1e3, 4),
+                              "ms_per_step_before_after": [round(one_stream[0] / args.steps * 1e3, 4), round(one_stream[1] / args.steps * 1e3, 4)],
+                              "role": "comparison legs: same build, weights, inputs and K steps, timed right before and right after the timed "
+                                      "region (A / timed / A); `value` above is the %d-stream run" % eng.num_streams}
+            out["cpu_baseline"] = out["parity"] = None
+            # the CPU baseline is timed on rank 0 at N = 1 only (bench contract); the parity check (rank 0's TIMED engine, every image of
+            # its first batch, outside the timed region, before the process group goes away) runs at every N
+            time_cpu = world == 1 and not args.no_cpu_baseline
+            if time_cpu or not args.no_parity:
+                base, ref_logits, e_ref = cpu_baseline(kind, size, w, anchors, ncls, xs_host[0], dtype, time_it=time_cpu)
+                out["cpu_baseline"] = base
+                if not args.no_parity:
+                    out["parity"] = parity_report(eng, kind, size, anchors, ncls, xs[0], ref_logits, args.threshold, args.iou_threshold, dtype, e_ref)
+            if world > 1:
+                out["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": 0, "kind": "port",
+                                       "sample": "not timed at N > 1: the CPU baseline is a property of the host, see the N = 1 line"}
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
