@@ -29,7 +29,8 @@
 extern "C" {
 #endif
 
-#define YOLO_HIP_ABI_VERSION 5      /* 2: yolo_kernel_info.symbol; 3: yolo_net_num_streams, streams = 0 is the library's rule; 4: yolo_net_tune_streams; 5: yolo_net_set_streams */
+#define YOLO_HIP_ABI_VERSION 6      /* 2: yolo_kernel_info.symbol; 3: yolo_net_num_streams, streams = 0 is the library's rule; 4: yolo_net_tune_streams; 5: yolo_net_set_streams;
+                                       6: YOLO_DTYPE_MXF8, yolo_mx_quantize, yolo_mx_quantize_host */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -54,7 +55,11 @@ enum yolo_op {
     YOLO_OP_DETECTION = 8   /* layers.py:119-123 detection_layer (src = yolo layers)             */
 };
 
-enum yolo_dtype { YOLO_DTYPE_F32 = 0, YOLO_DTYPE_F16 = 1 };
+/* YOLO_DTYPE_MXF8 (ABI 6): the fp16 plan -- fp16 activations in memory, same kernels, fusions, arenas and streams -- except that every
+ * 3x3 / stride-1 conv with Cin % 128 == 0 and a map at most 100 wide (not pool-fused, not a head conv) multiplies on the block-scaled
+ * fp8 matrix cores: OCP MXFP8, e4m3fn elements with one E8M0 scale per 32 input channels (weights quantized once at load, activations
+ * inside the kernel), float32 accumulation, the fp16 epilogue.  yolo_net_describe() prints dtype=mxf8 and marks those convs. */
+enum yolo_dtype { YOLO_DTYPE_F32 = 0, YOLO_DTYPE_F16 = 1, YOLO_DTYPE_MXF8 = 2 };
 
 enum yolo_nms_mode {
     YOLO_NMS_AGNOSTIC = 0,  /* the reference: class_idx never consulted (base.py:195-209) */
@@ -95,7 +100,9 @@ typedef struct yolo_net_options {
                              * yolo_net_num_streams() tells what a net runs with.                              */
     int32_t force_tile;     /* 0: per-layer tile choice (cost model / autotune); t + 1: run conv tile id t on every
                              * conv layer that accepts it (0 = 4-wave kernel, 1-7 and 14 LDS-DMA tiles, 8-13 and 15-17
-                             * tap-reuse tiles): test and tuning hook, any value gives the same results up to summation order   */
+                             * tap-reuse tiles; 24 = the MXFP8 3x3 kernel, accepted only by a YOLO_DTYPE_MXF8 net that has a conv
+                             * it takes -- else yolo_net_create fails with YOLO_ERR_ARG): test and tuning hook, any value gives the
+                             * same results up to summation order   */
     int32_t guard_bytes;    /* test hook (guard-band canaries): this many extra, never-used bytes behind every planned activation
                              * tensor (rounded into the tensor's 4 KiB-aligned region); with keep_all = 1 no two tensors share bytes, so a
                              * pattern-filled workspace shows any kernel that writes outside its tensor (yolo_net_workspace_regions);
@@ -212,6 +219,15 @@ int yolo_net_forward_timed(yolo_net *net, const float *in_dev, int batch, float 
 
 /* debug / parity: copy one layer's output to host as dense float32 NHWC (needs keep_all; synchronous) */
 int yolo_net_read_layer(yolo_net *net, int layer, int batch, float *host_out, size_t n);
+
+/* MXFP8 quantizer of the MX conv kernel (ABI 6), for testing: `rows` x `channels` fp16 values (device, 16-byte aligned, channels % 32 == 0)
+ * -> q_dev[rows][channels] e4m3fn bytes and scale_dev[rows][channels / 32] E8M0 bytes, by the device function the kernel runs on its
+ * patches (OCP MX v1.0: e = floor(log2 amax) - 8, elements rounded to nearest even and saturated to +-448, amax 0 -> scale byte 0).
+ * stream: a hipStream_t or NULL.  Asynchronous. */
+int yolo_mx_quantize(const void *src_f16_dev, int rows, int channels, uint8_t *q_dev, uint8_t *scale_dev, void *stream);
+/* The same rule on the host, as yolo_net_load_weights applies it to the folded float32 weights of the MX convs (ABI 6, testing):
+ * rows x channels float32 values (host) -> q[rows][channels] e4m3fn bytes, scale[rows][channels / 32] E8M0 bytes. */
+int yolo_mx_quantize_host(const float *src, int rows, int channels, uint8_t *q, uint8_t *scale);
 
 /* ---- standalone decode + NMS (drop-in for find_bounding_boxes) --------------------- */
 size_t yolo_decode_scratch_bytes(const yolo_head_desc *head, int batch, int cand_capacity);

@@ -10,11 +10,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (YOLO_HIP_LIB: another build of the SAME library -- the sanitizer build of tests/test_sanitizer.py, A/B builds of tools/; no fallback of any kind)
 LIB_PATH = os.environ.get("YOLO_HIP_LIB") or os.path.join(_HERE, "libyolo_hip.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # enum yolo_op
 OP_INPUT, OP_CONV, OP_MAXPOOL, OP_ROUTE, OP_REORG, OP_SHORTCUT, OP_UPSAMPLE, OP_YOLO, OP_DETECTION = range(9)
-DTYPE_F32, DTYPE_F16 = 0, 1
+DTYPE_F32, DTYPE_F16, DTYPE_MXF8 = 0, 1, 2
 NMS_AGNOSTIC, NMS_PER_CLASS = 0, 1
 MAX_SRC, MAX_ANCHORS, MAX_SCALES = 4, 8, 4
 # Records per image every Python entry point asks for unless told otherwise.  The reference's lists are unbounded
@@ -85,6 +85,8 @@ SIGNATURES = {
     "yolo_net_kernel_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(KernelInfo)]),
     "yolo_net_forward_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yolo_net_read_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "yolo_mx_quantize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_mx_quantize_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "yolo_decode_scratch_bytes": (C.c_size_t, [C.POINTER(HeadDesc), C.c_int, C.c_int]),
     "yolo_decode_nms": (C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int,
                                   C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,

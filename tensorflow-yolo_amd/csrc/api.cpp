@@ -52,15 +52,37 @@ int zero_pair_counters(yolo_net *net) {
 extern "C" {
 
 int yolo_hip_abi_version(void) { return YOLO_HIP_ABI_VERSION; }
+
+int yolo_mx_quantize(const void *src_f16_dev, int rows, int channels, uint8_t *q_dev, uint8_t *scale_dev, void *stream) {
+    if (!src_f16_dev || !q_dev || !scale_dev || rows <= 0 || channels <= 0 || channels % 32)
+        return fail(YOLO_ERR_ARG, "yolo_mx_quantize: null pointer, or rows / channels not positive, or channels not a multiple of 32");
+    if ((uintptr_t)src_f16_dev % 16 || (uintptr_t)q_dev % 16)
+        return fail(YOLO_ERR_ARG, "yolo_mx_quantize: source and element buffers must be 16-byte aligned");
+    const hipError_t e = launch_mx_quantize(src_f16_dev, rows, channels, q_dev, scale_dev, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(YOLO_ERR_HIP, std::string("yolo_mx_quantize: ") + hipGetErrorString(e));
+    return YOLO_OK;
+}
+int yolo_mx_quantize_host(const float *src, int rows, int channels, uint8_t *q, uint8_t *scale) {
+    if (!src || !q || !scale || rows <= 0 || channels <= 0 || channels % 32)
+        return fail(YOLO_ERR_ARG, "yolo_mx_quantize_host: null pointer, or rows / channels not positive, or channels not a multiple of 32");
+    const size_t blocks = (size_t)rows * (size_t)(channels / 32);
+    for (size_t b = 0; b < blocks; ++b) scale[b] = mx_quant_block_host(src + 32 * b, q + 32 * b);
+    return YOLO_OK;
+}
 const char *yolo_last_error(void) { return get_error(); }
 
 int yolo_net_create(const yolo_layer_desc *layers, int n_layers, const yolo_net_options *opt, yolo_net **out) {
     if (!layers || !opt || !out || n_layers <= 0) return fail(YOLO_ERR_ARG, "yolo_net_create: null argument");
-    if (opt->dtype != YOLO_DTYPE_F16 && opt->dtype != YOLO_DTYPE_F32) return fail(YOLO_ERR_ARG, "yolo_net_create: bad dtype");
+    if (opt->dtype != YOLO_DTYPE_F16 && opt->dtype != YOLO_DTYPE_F32 && opt->dtype != YOLO_DTYPE_MXF8)
+        return fail(YOLO_ERR_ARG, "yolo_net_create: bad dtype");
     if (opt->max_batch <= 0) return fail(YOLO_ERR_ARG, "yolo_net_create: max_batch must be positive");
     yolo_net *net = new (std::nothrow) yolo_net();
     if (!net) return fail(YOLO_ERR_ARG, "out of host memory");
     net->opt = *opt;
+    if (opt->dtype == YOLO_DTYPE_MXF8) {      // the fp16 plan (storage, fusions, arenas, streams) with the eligible 3x3 convs on conv_mx.hip
+        net->opt.dtype = YOLO_DTYPE_F16;
+        net->mx = true;
+    }
     if (net->opt.cand_capacity <= 0) net->opt.cand_capacity = 4096;
     if (net->opt.max_boxes <= 0) net->opt.max_boxes = 256;
     if (net->opt.cand_capacity > 65536) {
@@ -78,7 +100,17 @@ int yolo_net_create(const yolo_layer_desc *layers, int n_layers, const yolo_net_
         delete net;
         return fail(rc, "yolo_net_create: " + err);
     }
-    if (net->opt.force_tile > 0)        // test / tuning hook: one tile id on every conv that accepts it
+    int n_mx = 0;
+    for (Kernel &k : net->kernels) {
+        k.mx = mx_eligible(net, k) ? 1 : 0;
+        n_mx += k.mx;
+    }
+    if (net->opt.force_tile == kMxTile + 1 && (!net->mx || !n_mx)) {     // the MX kernel: only where the plan runs it
+        delete net;
+        return fail(YOLO_ERR_ARG, "yolo_net_create: tile 24 (the MXFP8 3x3 kernel; yolo_net_options.force_tile = 25) needs dtype MXF8 and a "
+                                  "3x3 / stride-1 conv with Cin % 128 == 0 and W <= 100");
+    }
+    if (net->opt.force_tile > 0 && net->opt.force_tile != kMxTile + 1)        // test / tuning hook: one tile id on every conv that accepts it
         for (Kernel &k : net->kernels)
             if (k.kind == K_CONV && k.stem < 2 && conv_tile_valid(net, k, net->opt.force_tile - 1)) k.tile = net->opt.force_tile - 1;
     // the split-K slab is the last region of the workspace (plan.cpp reserves nothing for it): sized from the launches that can split
@@ -646,6 +678,10 @@ int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_d
             int rc = make_conv_params(net, k, P, batch, p);
             if (rc) return rc;
             if (k.head && p.obj_out) obj_rows_written += (long long)p.Ho * p.Wo * p.obj_na;
+            if (k.mx) {
+                e = launch_conv_mx(p, s);
+                break;
+            }
             {
                 const size_t slab = net->splitk_bytes / (size_t)net->arenas / 256 * 256;
                 fused2_done = conv_fuse2(net, ki, &P, batch, p, slab > kPairCounterBytes ? slab - kPairCounterBytes : 0);
@@ -934,6 +970,15 @@ int yolo_net_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out)
             }
             return YOLO_OK;
         }
+        if (k.mx) {         // e4m3 weights + one scale byte per 32 of them; fp16 activations in and out
+            ConvParams mp;
+            conv_shape_params(net, k, part_batch(net), mp);
+            out->variant = 8 + kMxTile;
+            out->weight_bytes = (double)k.cout * k.ksize * k.ksize * k.cin * (1.0 + 1.0 / 32) + 4.0 * k.cout;
+            snprintf(out->name, sizeof out->name, "conv_mx<mxf8,128x256>");
+            set_symbol(conv_mx_symbol(conv_fast_epilogue_ok(mp)));
+            return YOLO_OK;
+        }
         // which kernel runs at max_batch (bench.py runs at max_batch): the same decision the launch path takes
         ConvParams sp;
         const int per_arena = part_batch(net);
@@ -1086,7 +1131,7 @@ int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *strea
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     for (Kernel &k : net->kernels) {
-        if (k.kind != K_CONV || k.stem >= 2 || !dma_eligible(net, k)) continue;
+        if (k.kind != K_CONV || k.stem >= 2 || k.mx || !dma_eligible(net, k)) continue;      // (MX convs: one kernel, weights packed for it)
         ConvParams p;
         rc = make_conv_params(net, k, P, batch, p);
         if (rc) break;

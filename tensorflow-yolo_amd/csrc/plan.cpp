@@ -723,6 +723,78 @@ int plan_network(yolo_net *net, const yolo_layer_desc *layers, int n, std::strin
     return YOLO_OK;
 }
 
+// MXFP8 plans: the 3x3 / stride-1 convs conv_mx.hip takes -- 128-channel slices, the patch of a 256-position tile in LDS, 16-byte
+// aligned fp16 input views; its epilogue is conv_common.h's (any output view, fused residual) without the pooled, back-to-back 1x1,
+// stem and head-objectness forms, which stay on their fp16 kernels
+bool mx_eligible(const yolo_net *net, const Kernel &k) {
+    if (!net->mx || k.kind != K_CONV || k.ksize != 3 || k.stride != 1 || k.cin % 128 || k.cin_s != k.cin) return false;
+    if (k.stem || k.fuse2_next || k.fuse2_prev || k.head || k.outmode == OUT_POOL2 || k.in.f32) return false;
+    if (!conv_mx_fits(k.in.W) || k.in.H != k.out.H || k.in.W != k.out.W) return false;
+    return k.in.ld % 8 == 0 && k.in.coff % 8 == 0 && k.in.img_stride % 8 == 0 && k.in.coff + k.cin <= k.in.ld;
+}
+
+// float -> e4m3fn, round to nearest even; |x| <= 448 (the caller clamps)
+static unsigned char e4m3_rne(double x) {
+    const unsigned char sign = std::signbit(x) ? 0x80 : 0;
+    const double a = std::fabs(x);
+    if (a < 0.015625) return sign | (unsigned char)std::nearbyint(a * 512.0);      // subnormal m * 2^-9 (m = 8: the smallest normal)
+    int E;
+    const double fr = std::frexp(a, &E);        // a = fr 2^E, fr in [0.5, 1)
+    int e = E - 1, mant = (int)std::nearbyint((2.0 * fr - 1.0) * 8.0);
+    if (mant == 8) { ++e; mant = 0; }
+    return sign | (unsigned char)((e + 7) << 3) | (unsigned char)mant;
+}
+
+// the host twin of conv_mx.hip's mx_quant_block (OCP MX: e = floor(log2 amax) - 8, clamped to E8M0; elements RNE, saturated)
+unsigned char mx_quant_block_host(const float *v, unsigned char *q) {
+    float amax = 0.0f;
+    for (int i = 0; i < 32; ++i) amax = std::fmax(amax, std::fabs(v[i]));
+    if (amax == 0.0f) {
+        for (int i = 0; i < 32; ++i) q[i] = 0;
+        return 0;
+    }
+    int E;
+    (void)std::frexp(amax, &E);
+    int eb = (E - 1) - 8 + 127;
+    eb = eb < 0 ? 0 : eb > 254 ? 254 : eb;
+    const double mul = std::ldexp(1.0, 127 - eb);
+    for (int i = 0; i < 32; ++i) {
+        double x = (double)v[i] * mul;
+        x = x > 448.0 ? 448.0 : x < -448.0 ? -448.0 : x;
+        q[i] = e4m3_rne(x);
+    }
+    return (unsigned char)eb;
+}
+
+// conv_mx.hip weight image of one conv: for cout group G (32 couts), tap t, 128-channel slice s, cout tile a (0, 1) and lane l, the 32
+// e4m3 values of the MFMA A operand at ((((G * 9 + t) * S + s) * 2 + a) * 64 + l) * 32 -- row R = l & 15 = cout 32 G + 8 (R >> 2) +
+// 4 a + (R & 3); lane group g = l >> 4 holds channels 16 g .. 16 g + 15 and 64 + 16 g .. of the slice (conv_mx.hip: lane map) --, and
+// the scale byte of 32-channel block g of that row at the same fragment index behind all elements
+static void mx_pack(const Kernel &k, const float *kern, const std::vector<double> &scale, unsigned char *dst) {
+    const int S = k.cin / 128, cout_pad = (k.cout + 127) / 128 * 128;
+    unsigned char *sdst = dst + (size_t)cout_pad * 9 * k.cin;
+    float v[32];
+    unsigned char q[4][32], sc[4];
+    for (int G = 0; G < cout_pad / 32; ++G)
+        for (int t = 0; t < 9; ++t)
+            for (int s = 0; s < S; ++s)
+                for (int a = 0; a < 2; ++a)
+                    for (int R = 0; R < 16; ++R) {
+                        const int o = 32 * G + 8 * (R >> 2) + 4 * a + (R & 3);
+                        for (int b = 0; b < 4; ++b) {
+                            for (int j = 0; j < 32; ++j)
+                                v[j] = o < k.cout ? (float)((double)kern[((size_t)o * k.cin + s * 128 + 32 * b + j) * 9 + t] * scale[o]) : 0.0f;
+                            sc[b] = mx_quant_block_host(v, q[b]);
+                        }
+                        for (int g = 0; g < 4; ++g) {
+                            const size_t f = ((((size_t)G * 9 + t) * S + s) * 2 + a) * 64 + 16 * g + R;
+                            memcpy(dst + f * 32, q[g >> 1] + 16 * (g & 1), 16);
+                            memcpy(dst + f * 32 + 16, q[2 + (g >> 1)] + 16 * (g & 1), 16);
+                            sdst[f] = sc[g];
+                        }
+                    }
+}
+
 // Darknet stream -> device layout.  Order per conv (net/layers.py:53-63; net/base.py:26-46):
 // BN: beta, gamma, moving_mean, moving_variance, kernel[out][in][kh][kw]; else bias, kernel.
 // Fold: w' = w * gamma/sqrt(var+eps), b' = beta - mean*gamma/sqrt(var+eps), eps = 1e-5
@@ -769,6 +841,23 @@ int pack_weights(const yolo_net *net, const float *host, size_t n, std::vector<u
         const float *kern = p;      // [out][in][kh][kw]
         float *bdst = reinterpret_cast<float *>(blob.data() + k.b_off);
         const size_t wrow = (size_t)k.ktiles * 128;
+        if (k.mx) {     // folded bias as below; weights folded in float64, rounded to float32, quantized to MXFP8 once
+            std::vector<double> sc((size_t)k.cout, 1.0);
+            for (int o = 0; o < k.cout; ++o) {
+                if (k.batch_norm) {
+                    sc[o] = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
+                    bdst[o] = (float)((double)beta[o] - (double)mean[o] * sc[o]);
+                } else {
+                    bdst[o] = bias[o];
+                }
+            }
+            if ((size_t)(k.cout + 127) / 128 * 128 * 9 * k.cin * 33 / 32 > k.w_bytes) {
+                err = "MX weight image does not fit the conv's weight region";
+                return YOLO_ERR_PLAN;
+            }
+            mx_pack(k, kern, sc, blob.data() + k.w_off);
+            continue;
+        }
         for (int o = 0; o < k.cout; ++o) {
             double scale = 1.0;
             if (k.batch_norm) {
@@ -798,7 +887,7 @@ static const char *kind_name(int k) {
 
 std::string describe(const yolo_net *net) {
     std::ostringstream o;
-    o << "yolo_hip plan: dtype=" << (net->opt.dtype == YOLO_DTYPE_F16 ? "f16" : "f32") << " max_batch=" << net->opt.max_batch
+    o << "yolo_hip plan: dtype=" << (net->mx ? "mxf8" : net->opt.dtype == YOLO_DTYPE_F16 ? "f16" : "f32") << " max_batch=" << net->opt.max_batch
       << " layers=" << net->layers.size() << " kernels=" << net->kernels.size() << " buffers=" << net->buffers.size() << "\n";
     o << "  weights: " << net->weight_count << " floats -> " << net->weights_bytes << " B packed; activations "
       << net->act_bytes << " B; workspace " << net->workspace_bytes << " B; GFLOP/image " << net->flops_per_image * 1e-9 << "\n";
@@ -813,6 +902,7 @@ std::string describe(const yolo_net *net) {
         o << " out=b" << k.out.buf << "[" << k.out.H << "x" << k.out.W << "x" << k.out.C << " ld" << k.out.ld << "+" << k.out.coff
           << (k.out.f32 ? " f32" : "") << "]";
         if (!k.note.empty()) o << " " << k.note;
+        if (k.mx) o << " [mx: e4m3 x e4m3, block-scaled]";
         o << "\n";
     }
     return o.str();

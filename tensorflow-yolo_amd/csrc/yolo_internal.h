@@ -287,6 +287,15 @@ bool conv_tap_is2d(int variant);
 bool conv_tap_stride2(int variant);         // 3x3 / stride 2 over the input's parity planes (MODE 4)
 bool conv_tap_image_aligned(int variant);   // a tile = one whole image of the padded-linear grid (tile stride (H+1)(W+1))
 bool conv_tap_f32_ok(int variant);            // float32 instantiation usable (tiles with room for the second accumulator)
+// conv_mx.hip (MXFP8 plans): 3x3 / stride 1, Cin % 128 == 0, W <= kMxMaxW (the 128-channel patch of a 256-position tile in LDS, twice)
+constexpr int kMxMaxW = 100;
+constexpr int kMxTile = 24;           // its yolo_net_options.force_tile id (force_tile = 25)
+bool conv_mx_fits(int W);
+const char *conv_mx_symbol(bool fast);
+hipError_t launch_conv_mx(const ConvParams &p, hipStream_t s);
+hipError_t launch_mx_quantize(const void *src, int rows, int channels, unsigned char *q, unsigned char *sc, hipStream_t s);
+// host copy of the device quantizer (mx_quant_block): one block of 32 float values -> e4m3fn bytes, returns the E8M0 byte
+unsigned char mx_quant_block_host(const float *v, unsigned char *q);
 bool dma_cfg_f32_ok(int cfg);
 const char *dma_cfg_name(int cfg);
 // names exactly as rocprofv3's kernel trace prints them (yolo_kernel_info.symbol: joins bench.py's roofline to profiles/*.csv)
@@ -334,6 +343,7 @@ struct Kernel {
     int fuse2_next = 0;        // the NEXT kernel is a 1x1 128 -> 64 conv on this conv's output that the fused instantiation of this launch
                                // can compute (conv_common.h: conv_epilogue_fused_1x1); whether it does is decided per launch (api.cpp: conv_fuse2)
     int fuse2_prev = 0;        // ... and the mark on that 1x1: skipped when the conv in front of it has computed it
+    int mx = 0;                // MXFP8 plans: this conv runs conv3x3_mx_kernel (conv_mx.hip) on block-scaled e4m3 operands
     int side = 0;              // > 0: member of branch tail `side` (plan.cpp: side_chains): a run of kernels ending in a head conv whose
                                // results nothing else reads -- may run on a second stream beside the kernels that follow it in the list
     size_t w_off = 0, b_off = 0, w_bytes = 0;   // inside the device weight blob
@@ -356,7 +366,8 @@ struct LayerInfo {
 }  // namespace yolo
 
 struct yolo_net {
-    yolo_net_options opt;
+    yolo_net_options opt;          // (an MXFP8 plan keeps dtype = YOLO_DTYPE_F16 here: fp16 storage and kernels, `mx` set)
+    bool mx = false;               // created as YOLO_DTYPE_MXF8: the eligible 3x3 convs run conv_mx.hip (Kernel.mx)
     std::vector<yolo::LayerInfo> layers;
     std::vector<yolo::Kernel> kernels;
     std::vector<yolo::Buffer> buffers;
@@ -399,6 +410,7 @@ struct yolo_net {
 
 namespace yolo {
 int plan_network(yolo_net *net, const yolo_layer_desc *layers, int n, std::string &err);
+bool mx_eligible(const yolo_net *net, const Kernel &k);
 int pack_weights(const yolo_net *net, const float *host, size_t n, std::vector<unsigned char> &blob, std::string &err);
 std::string describe(const yolo_net *net);
 void set_error(const std::string &s);

@@ -77,9 +77,10 @@ class Plan(object):
         self.lib = _hip.lib()
         self.layers = list(net)
         known = {"fp16": _hip.DTYPE_F16, "f16": _hip.DTYPE_F16, "half": _hip.DTYPE_F16,
-                 "fp32": _hip.DTYPE_F32, "f32": _hip.DTYPE_F32, "float": _hip.DTYPE_F32}
+                 "fp32": _hip.DTYPE_F32, "f32": _hip.DTYPE_F32, "float": _hip.DTYPE_F32,
+                 "mxfp8": _hip.DTYPE_MXF8, "mxf8": _hip.DTYPE_MXF8}
         if str(dtype).lower() not in known:
-            raise ValueError("dtype must be fp16 or fp32, got %r" % (dtype,))
+            raise ValueError("dtype must be fp16, fp32 or mxfp8, got %r" % (dtype,))
         self.dtype = known[str(dtype).lower()]
         self.max_batch = int(max_batch)
         self.max_boxes = int(max_boxes)
