@@ -18,6 +18,9 @@
  *   yolo_net_detect         net/yolo.py:83-86 (forward + find_bounding_boxes in one enqueue)
  *   yolo_nms_host           net/base.py:195-209 non_maximum_suppression on a host box list
  *   yolo_preprocess_resize  net/base.py:115-155 preprocess_image (resize + colour order + /255) on the device
+ *   yolo_net_forward_u8, yolo_net_detect_u8, yolo_net_forward_timed_u8, yolo_net_tune_streams_u8, yolo_preprocess_resize_u8
+ *                           (ABI 7) the same call sites for a caller that holds the 8-bit pixels net/base.py:115-155 starts from:
+ *                           the / 255. of net/base.py:153 happens inside the first kernel instead of in a float32 tensor
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -29,8 +32,10 @@
 extern "C" {
 #endif
 
-#define YOLO_HIP_ABI_VERSION 6      /* 2: yolo_kernel_info.symbol; 3: yolo_net_num_streams, streams = 0 is the library's rule; 4: yolo_net_tune_streams; 5: yolo_net_set_streams;
-                                       6: YOLO_DTYPE_MXF8, yolo_mx_quantize, yolo_mx_quantize_host */
+#define YOLO_HIP_ABI_VERSION 7      /* 2: yolo_kernel_info.symbol; 3: yolo_net_num_streams, streams = 0 is the library's rule; 4: yolo_net_tune_streams; 5: yolo_net_set_streams;
+                                       6: YOLO_DTYPE_MXF8, yolo_mx_quantize, yolo_mx_quantize_host;
+                                       7: uint8 network input -- yolo_net_forward_u8, yolo_net_detect_u8, yolo_net_forward_timed_u8,
+                                          yolo_net_tune_streams_u8, yolo_preprocess_resize_u8, yolo_u8_unit_table */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -184,6 +189,24 @@ int yolo_net_bind_workspace(yolo_net *net, void *dev_workspace, size_t dev_bytes
  * out_dev: float32, reference layout -- v2 [B,h,w,A*(5+C)], v3 [B,sum(h*w*3),5+C] coarse->fine. */
 int yolo_net_forward(yolo_net *net, const float *in_dev, int batch, float *out_dev, void *stream);
 
+/* uint8 network input (ABI 7).  in_dev: uint8 NHWC [batch,h,w,c], values 0..255, RGB: the pixels net/base.py:115-155 has BEFORE its
+ * `/ 255.` (net/base.py:153), fed where net/yolo.py:83 feeds x_batch.  Dense (h*w*c bytes per image), any byte alignment.  The kernels
+ * that read the input -- the Darknet-53 stem, the first-layer kernels, the fallback input cast -- have uint8 twins that turn a byte u into
+ * float32(u / 255.) (division in float64 as NumPy does it = the correctly rounded float32 quotient; not u * float32(1 / 255), which differs
+ * for 126 of the 256 bytes) and go on as their float32 forms do; every later kernel is the same launch on the same operands.  So each
+ * *_u8 entry returns BIT-IDENTICAL results to its float32 twin fed float32(u / 255.), for every dtype and stream mode, with a quarter of
+ * the input bytes to produce, copy and read.  The input type is a property of the call: one net serves both.  Argument checks and
+ * messages as the float32 twins.  yolo_net_autotune stays float32-only (the tile choice does not depend on the input type), and
+ * yolo_net_kernel_info keeps describing the float32 plan: the uint8 twins carry the same names with `_u8_kernel` for `_kernel`
+ * (yolo::stem_v3_u8_kernel, yolo::first_pool_mfma_u8_kernel, yolo::first_pool_mfma_f32_u8_kernel<>, yolo::conv_first_u8_kernel<>,
+ * yolo::prep_u8_kernel<>). */
+int yolo_net_forward_u8(yolo_net *net, const uint8_t *in_dev, int batch, float *out_dev, void *stream);
+/* yolo_net_tune_streams on a uint8 batch (net/yolo.py:65-67 is one session: no reference call site) */
+int yolo_net_tune_streams_u8(yolo_net *net, const uint8_t *in_dev, int batch, void *stream);
+/* The conversion above for u = 0..255, computed on the host by the function the input kernels run on every byte: out256[u] = float32(u / 255.)
+ * (test hook; no reference call site beyond net/base.py:153). */
+int yolo_u8_unit_table(float *out256);
+
 /* Optional: time every valid tile configuration of each heavy conv on the device (synchronous, a few
  * hundred launches) and keep the fastest per layer for later forward/detect calls at this batch. */
 int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *stream);
@@ -196,7 +219,12 @@ int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *strea
 int yolo_net_detect(yolo_net *net, const float *in_dev, int batch, double threshold, double iou_threshold,
                     int nms_mode, yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev, void *stream);
 
-/* Per-kernel facts for roofline accounting (bench.py): algorithmic work of ONE image. */
+/* yolo_net_detect on a uint8 batch (net/yolo.py:83-86 with the pixels of net/base.py:115-155 before the / 255.): see yolo_net_forward_u8. */
+int yolo_net_detect_u8(yolo_net *net, const uint8_t *in_dev, int batch, double threshold, double iou_threshold,
+                       int nms_mode, yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev, void *stream);
+
+/* Per-kernel facts for roofline accounting (bench.py): algorithmic work of ONE image.  Always the plan of the float32 entry points
+ * (input bytes counted as float32, float32 kernel symbols), also for a net that is only ever fed uint8. */
 typedef struct yolo_kernel_info {
     int32_t kind;               /* 0 prep, 1 conv, 2 maxpool, 3 eltwise                         */
     int32_t layer;              /* reference layer index the kernel materialises                 */
@@ -216,6 +244,9 @@ int yolo_net_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out)
  * writes the device time of each kernel in milliseconds to ms_host[yolo_net_num_kernels()].
  * Measurement aid only (the events add bubbles): never used for throughput numbers. */
 int yolo_net_forward_timed(yolo_net *net, const float *in_dev, int batch, float *out_dev, void *stream, float *ms_host);
+
+/* yolo_net_forward_timed on a uint8 batch: ms_host[k] of an input kernel is the time of its uint8 twin (net/yolo.py:83). */
+int yolo_net_forward_timed_u8(yolo_net *net, const uint8_t *in_dev, int batch, float *out_dev, void *stream, float *ms_host);
 
 /* debug / parity: copy one layer's output to host as dense float32 NHWC (needs keep_all; synchronous) */
 int yolo_net_read_layer(yolo_net *net, int layer, int batch, float *host_out, size_t n);
@@ -243,6 +274,12 @@ int yolo_decode_nms(const yolo_head_desc *head, const float *logits_dev, int bat
  * Enqueued on `stream`. */
 int yolo_preprocess_resize(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, float *dst_dev, int dst_h, int dst_w,
                            int swap_rb, void *stream);
+
+/* The same resize with the 8-bit value itself as the result (net/base.py:115-155 up to, not including, the / 255. of :153):
+ * dst_dev receives uint8 [dst_h][dst_w][3], the image layout of yolo_net_forward_u8 / yolo_net_detect_u8.  yolo_preprocess_resize of the
+ * same source is float32(that / 255.) exactly. */
+int yolo_preprocess_resize_u8(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, uint8_t *dst_dev, int dst_h, int dst_w,
+                              int swap_rb, void *stream);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

@@ -235,14 +235,22 @@ int yolo_net_bind_workspace(yolo_net *net, void *ws, size_t bytes) {
 // ---- forward ------------------------------------------------------------------------------------
 namespace {
 
+// The network input of one call: the caller's float32 tensor, or (ABI 7: the *_u8 entries) its uint8 one.  Only the five kernels that
+// read the input look at the tag (K_PREP, K_FIRST, the stem); a byte u is to them float32(u / 255.) (yolo_internal.h: u8_unit).
+struct NetIn {
+    const void *ptr;
+    bool u8;
+    NetIn at(size_t elems) const { return NetIn{static_cast<const unsigned char *>(ptr) + elems * (u8 ? 1 : 4), u8}; }
+};
+
 struct Ptrs {
     yolo_net *net;
-    const float *in;            // already advanced to image `img0` by the caller
+    NetIn in;                   // already advanced to image `img0` by the caller
     float *out;                 // ditto
     int img0 = 0;               // first image of this pass in the batch (two-stream halves: compact per-image arrays)
     int arena = 0;              // activation arena of this pass
     unsigned char *buf_base(int b) const {
-        if (b == BUF_USER_IN) return reinterpret_cast<unsigned char *>(const_cast<float *>(in));
+        if (b == BUF_USER_IN) return static_cast<unsigned char *>(const_cast<void *>(in.ptr));
         if (b == BUF_USER_OUT) return reinterpret_cast<unsigned char *>(out);
         return net->dev_ws + (size_t)arena * net->arena_bytes + net->buffers[b].offset;
     }
@@ -602,9 +610,9 @@ int branch_streams(yolo_net *net, int arena) {
     return (size_t)arena < net->branch.size() ? YOLO_OK : fail(YOLO_ERR_STATE, "branch tail: arena out of range");
 }
 
-int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev, int img0, int arena,
+int run_forward_pass(yolo_net *net, const NetIn in, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev, int img0, int arena,
                      long long *obj_rows_out) {
-    Ptrs P{net, in_dev, out_dev, img0, arena};
+    Ptrs P{net, in, out_dev, img0, arena};
     const int dtype = net->opt.dtype;
     const int epc = net->epc;
     long long obj_rows_written = 0;          // rows of the compact objectness array the head convs of this pass fill
@@ -638,12 +646,12 @@ int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_d
         switch (k.kind) {
         case K_PREP: {
             PrepParams p;
-            p.in = in_dev;
+            p.in = in.ptr;
             p.out = P.view_ptr(k.out);
             p.pixels = (long long)batch * k.in.H * k.in.W;
             p.C = k.in.C;
             p.Cpad = k.out.ld;
-            e = launch_prep(p, dtype, s);
+            e = launch_prep(p, dtype, s, in.u8);
             break;
         }
         case K_CONV: {
@@ -651,7 +659,7 @@ int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_d
                 const Kernel &f = net->kernels[ki - 1];
                 StemParams p;
                 memset(&p, 0, sizeof p);
-                p.in = in_dev;
+                p.in = in.ptr;
                 p.w1 = reinterpret_cast<const float *>(net->dev_weights + f.w_off);
                 p.b1 = reinterpret_cast<const float *>(net->dev_weights + f.b_off);
                 p.w2 = net->dev_weights + k.w_off;
@@ -669,7 +677,7 @@ int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_d
                     p.out3 = P.view_ptr(t.out);
                     p.out3_ld = t.out.ld; p.out3_img_stride = t.out.img_stride;
                 }
-                e = launch_stem(p, batch, s, net->halves ? 512 / net->parts : 512);
+                e = launch_stem(p, batch, s, net->halves ? 512 / net->parts : 512, in.u8);
                 break;
             }
             if (k.stem == 3) break;     // computed by the stem kernel
@@ -692,7 +700,7 @@ int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_d
         case K_FIRST: {
             if (k.stem == 1) break;     // runs inside the next kernel (stem.hip)
             FirstParams p;
-            p.in = in_dev;
+            p.in = in.ptr;
             p.wgt = reinterpret_cast<const float *>(net->dev_weights + k.w_off);
             p.bias = reinterpret_cast<const float *>(net->dev_weights + k.b_off);
             p.out = P.view_ptr(k.out);
@@ -703,7 +711,7 @@ int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_d
             p.total = (long long)batch * k.in.H * k.in.W;
             if (k.out.ld % epc || (k.out.base + k.out.coff) % epc || k.out.img_stride % epc)
                 return fail(YOLO_ERR_PLAN, "first-layer kernel needs a 16-byte aligned output view");
-            e = launch_first(p, dtype, s);
+            e = launch_first(p, dtype, s, in.u8);
             break;
         }
         case K_POOL: {
@@ -754,7 +762,7 @@ int run_forward_pass(yolo_net *net, const float *in_dev, int batch, float *out_d
 // the bulk of the other parts' kernels instead of leaving CUs idle at each of the ~73 kernel boundaries.  Every part has
 // its own activation arena (plan.cpp: allocate).
 // every head conv of the plan fills the compact objectness array at this batch (what run_forward_impl finds out afterwards as obj_valid)
-bool all_heads_write_objectness(yolo_net *net, const float *in_dev, float *out_dev, int batch) {
+bool all_heads_write_objectness(yolo_net *net, const NetIn in_dev, float *out_dev, int batch) {
     if (!net->obj_bytes || net->head.n_classes <= 0) return false;
     const int per = net->parts >= 2 && batch > part_batch(net) ? part_batch(net) : batch;
     Ptrs P{net, in_dev, out_dev, 0, 0};
@@ -770,8 +778,8 @@ bool all_heads_write_objectness(yolo_net *net, const float *in_dev, float *out_d
     return any;
 }
 
-int run_forward_impl(yolo_net *net, const float *in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev);
-int run_forward(yolo_net *net, const float *in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev = nullptr) {
+int run_forward_impl(yolo_net *net, const NetIn in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev);
+int run_forward(yolo_net *net, const NetIn in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev = nullptr) {
     const int rc = run_forward_impl(net, in_dev, batch, out_dev, s, ev);
     if (rc != YOLO_OK) {        // leave the pair-split counters as every later launch expects them; keep the first error's message
         const std::string msg = get_error();
@@ -781,7 +789,7 @@ int run_forward(yolo_net *net, const float *in_dev, int batch, float *out_dev, h
     }
     return rc;
 }
-int run_forward_impl(yolo_net *net, const float *in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev) {
+int run_forward_impl(yolo_net *net, const NetIn in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev) {
     const long long rows = net->head.n_classes > 0 ? (long long)(net->out_count / (size_t)(5 + net->head.n_classes)) : -1;
     const int parts = net->parts;
     const int per = (net->opt.max_batch + parts - 1) / parts;       // images a part holds
@@ -808,7 +816,7 @@ int run_forward_impl(yolo_net *net, const float *in_dev, int batch, float *out_d
             hipStream_t st = part == 0 ? s : net->side[part - 1];
             if (part > 0) HIP_TRY(hipStreamWaitEvent(st, net->e_fork, 0));
             long long w = 0;
-            const int rc = run_forward_pass(net, in_dev + (size_t)img0 * in_img, nb, out_dev + (size_t)img0 * net->out_count, st, nullptr,
+            const int rc = run_forward_pass(net, in_dev.at((size_t)img0 * in_img), nb, out_dev + (size_t)img0 * net->out_count, st, nullptr,
                                             img0, part, &w);
             if (rc) return rc;
             all = all && w == rows;
@@ -889,17 +897,24 @@ int run_decode_nms(const yolo_head_desc &h, const float *logits, int batch, doub
 
 extern "C" {
 
-int yolo_net_forward(yolo_net *net, const float *in_dev, int batch, float *out_dev, void *stream) {
-    int rc = check_ready(net, in_dev, batch, "yolo_net_forward");
+// The float32 entries and their uint8 twins (ABI 7) are one implementation each, told apart by the NetIn tag and the name in messages.
+static int forward_any(yolo_net *net, const NetIn in, int batch, float *out_dev, void *stream, const char *who) {
+    int rc = check_ready(net, in.ptr, batch, who);
     if (rc) return rc;
-    if (!out_dev) return fail(YOLO_ERR_ARG, "yolo_net_forward: null output");
-    return run_forward(net, in_dev, batch, out_dev, static_cast<hipStream_t>(stream));
+    if (!out_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null output");
+    return run_forward(net, in, batch, out_dev, static_cast<hipStream_t>(stream));
+}
+int yolo_net_forward(yolo_net *net, const float *in_dev, int batch, float *out_dev, void *stream) {
+    return forward_any(net, NetIn{in_dev, false}, batch, out_dev, stream, "yolo_net_forward");
+}
+int yolo_net_forward_u8(yolo_net *net, const uint8_t *in_dev, int batch, float *out_dev, void *stream) {
+    return forward_any(net, NetIn{in_dev, true}, batch, out_dev, stream, "yolo_net_forward_u8");
 }
 
-int yolo_net_forward_timed(yolo_net *net, const float *in_dev, int batch, float *out_dev, void *stream, float *ms_host) {
-    int rc = check_ready(net, in_dev, batch, "yolo_net_forward_timed");
+static int forward_timed_any(yolo_net *net, const NetIn in_dev, int batch, float *out_dev, void *stream, float *ms_host, const char *who) {
+    int rc = check_ready(net, in_dev.ptr, batch, who);
     if (rc) return rc;
-    if (!out_dev || !ms_host) return fail(YOLO_ERR_ARG, "yolo_net_forward_timed: null output");
+    if (!out_dev || !ms_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null output");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nk = net->kernels.size();
     std::vector<hipEvent_t> ev(2 * nk, nullptr);
@@ -917,7 +932,7 @@ int yolo_net_forward_timed(yolo_net *net, const float *in_dev, int batch, float 
     for (int part = 0, img0 = 0; rc == YOLO_OK && img0 < batch; ++part, img0 += per) {
         const int nb = batch - img0 < per ? batch - img0 : per;
         long long w = 0;
-        rc = run_forward_pass(net, in_dev + (size_t)img0 * in_img, nb, out_dev + (size_t)img0 * net->out_count, s, ev.data(), img0, part, &w);
+        rc = run_forward_pass(net, in_dev.at((size_t)img0 * in_img), nb, out_dev + (size_t)img0 * net->out_count, s, ev.data(), img0, part, &w);
         rows_written += w;
         if (rc == YOLO_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(YOLO_ERR_HIP, "hipStreamSynchronize failed");
         for (size_t k = 0; rc == YOLO_OK && k < nk; ++k) {
@@ -931,6 +946,12 @@ int yolo_net_forward_timed(yolo_net *net, const float *in_dev, int batch, float 
     if (rc != YOLO_OK) { const std::string msg = get_error(); (void)hipGetLastError(); (void)zero_pair_counters(net); set_error(msg); }
     for (auto &e : ev) (void)hipEventDestroy(e);
     return rc;
+}
+int yolo_net_forward_timed(yolo_net *net, const float *in_dev, int batch, float *out_dev, void *stream, float *ms_host) {
+    return forward_timed_any(net, NetIn{in_dev, false}, batch, out_dev, stream, ms_host, "yolo_net_forward_timed");
+}
+int yolo_net_forward_timed_u8(yolo_net *net, const uint8_t *in_dev, int batch, float *out_dev, void *stream, float *ms_host) {
+    return forward_timed_any(net, NetIn{in_dev, true}, batch, out_dev, stream, ms_host, "yolo_net_forward_timed_u8");
 }
 
 int yolo_net_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
@@ -1068,8 +1089,8 @@ int yolo_net_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out)
     return YOLO_OK;
 }
 
-int yolo_net_tune_streams(yolo_net *net, const float *in_dev, int batch, void *stream) {
-    int rc = check_ready(net, in_dev, batch, "yolo_net_tune_streams");
+static int tune_streams_any(yolo_net *net, const NetIn in_dev, int batch, void *stream, const char *who) {
+    int rc = check_ready(net, in_dev.ptr, batch, who);
     if (rc) return rc;
     if (!net->arena_full || batch <= (net->opt.max_batch + 1) / 2) return YOLO_OK;       // nothing to choose (or not with this batch)
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1078,7 +1099,7 @@ int yolo_net_tune_streams(yolo_net *net, const float *in_dev, int batch, void *s
     HIP_TRY(hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) {
         (void)hipEventDestroy(e0);
-        return fail(YOLO_ERR_HIP, "yolo_net_tune_streams: hipEventCreate failed");
+        return fail(YOLO_ERR_HIP, std::string(who) + ": hipEventCreate failed");
     }
     // interleaved: one pass, two halves, one pass, ... -- three forward passes per sample, the first round of each only warms up,
     // the best of the other four counts (boxes differ: the same build gains 3-4 % from two halves on one MI355X and loses 1-2 % on
@@ -1087,10 +1108,10 @@ int yolo_net_tune_streams(yolo_net *net, const float *in_dev, int batch, void *s
     for (int rep = 0; rep < 5 && rc == YOLO_OK; ++rep)
         for (int parts = 1; parts <= 2 && rc == YOLO_OK; ++parts) {
             net->parts = parts;
-            if (hipEventRecord(e0, s) != hipSuccess) rc = fail(YOLO_ERR_HIP, "yolo_net_tune_streams: hipEventRecord failed");
+            if (hipEventRecord(e0, s) != hipSuccess) rc = fail(YOLO_ERR_HIP, std::string(who) + ": hipEventRecord failed");
             for (int k = 0; k < 3 && rc == YOLO_OK; ++k) rc = run_forward(net, in_dev, batch, logits, s);
             if (rc == YOLO_OK && (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess))
-                rc = fail(YOLO_ERR_HIP, "yolo_net_tune_streams: event failed");
+                rc = fail(YOLO_ERR_HIP, std::string(who) + ": event failed");
             float ms = 0.f;
             if (rc == YOLO_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && rep > 0 && ms < best[parts]) best[parts] = ms;
         }
@@ -1102,6 +1123,12 @@ int yolo_net_tune_streams(yolo_net *net, const float *in_dev, int batch, void *s
     net->parts_tuned = rc == YOLO_OK;
     net->obj_valid = false;
     return rc;
+}
+int yolo_net_tune_streams(yolo_net *net, const float *in_dev, int batch, void *stream) {
+    return tune_streams_any(net, NetIn{in_dev, false}, batch, stream, "yolo_net_tune_streams");
+}
+int yolo_net_tune_streams_u8(yolo_net *net, const uint8_t *in_dev, int batch, void *stream) {
+    return tune_streams_any(net, NetIn{in_dev, true}, batch, stream, "yolo_net_tune_streams_u8");
 }
 
 int yolo_net_set_streams(yolo_net *net, int parts) {
@@ -1124,9 +1151,9 @@ int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *strea
         const int per = part_batch(net);
         if (batch > per) batch = per;
     }
-    rc = run_forward(net, in_dev, batch, logits, s);      // real activations in every buffer
+    rc = run_forward(net, NetIn{in_dev, false}, batch, logits, s);      // real activations in every buffer
     if (rc) return rc;
-    Ptrs P{net, in_dev, logits};
+    Ptrs P{net, NetIn{in_dev, false}, logits};
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
@@ -1159,14 +1186,14 @@ int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *strea
     return rc;
 }
 
-int yolo_net_detect(yolo_net *net, const float *in_dev, int batch, double threshold, double iou_threshold, int nms_mode,
-                    yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev, void *stream) {
-    int rc = check_ready(net, in_dev, batch, "yolo_net_detect");
+static int detect_any(yolo_net *net, const NetIn in_dev, int batch, double threshold, double iou_threshold, int nms_mode,
+                      yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev, void *stream, const char *who) {
+    int rc = check_ready(net, in_dev.ptr, batch, who);
     if (rc) return rc;
-    if (!boxes_dev || !counts_dev || !status_dev) return fail(YOLO_ERR_ARG, "yolo_net_detect: null output");
+    if (!boxes_dev || !counts_dev || !status_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null output");
     std::string err;
     rc = check_head(&net->head, net->out_count, err);
-    if (rc) return fail(YOLO_ERR_STATE, "yolo_net_detect: head geometry not set (" + err + "); call yolo_net_set_head");
+    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
     hipStream_t s = static_cast<hipStream_t>(stream);
     float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
     // The logits of a detect call never leave the workspace, and the decode kernel reads the objectness of every row from the compact
@@ -1187,6 +1214,14 @@ int yolo_net_detect(yolo_net *net, const float *in_dev, int batch, double thresh
                           net->opt.max_boxes, net->dev_ws + net->cand_off, reinterpret_cast<int *>(net->dev_ws + net->count_off),
                           boxes_dev, counts_dev, status_dev, nullptr, s, net->dev_ws + net->nms_off,
                           net->obj_valid ? reinterpret_cast<const float *>(net->dev_ws + net->obj_off) : nullptr, &net->cand_clean);
+}
+int yolo_net_detect(yolo_net *net, const float *in_dev, int batch, double threshold, double iou_threshold, int nms_mode,
+                    yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev, void *stream) {
+    return detect_any(net, NetIn{in_dev, false}, batch, threshold, iou_threshold, nms_mode, boxes_dev, counts_dev, status_dev, stream, "yolo_net_detect");
+}
+int yolo_net_detect_u8(yolo_net *net, const uint8_t *in_dev, int batch, double threshold, double iou_threshold, int nms_mode,
+                       yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev, void *stream) {
+    return detect_any(net, NetIn{in_dev, true}, batch, threshold, iou_threshold, nms_mode, boxes_dev, counts_dev, status_dev, stream, "yolo_net_detect_u8");
 }
 
 int yolo_net_read_layer(yolo_net *net, int layer, int batch, float *host_out, size_t n) {
@@ -1242,14 +1277,28 @@ int yolo_decode_nms(const yolo_head_desc *head, const float *logits_dev, int bat
                           boxes_dev, counts_dev, status_dev, nullptr, static_cast<hipStream_t>(stream), slabs);
 }
 
-int yolo_preprocess_resize(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, float *dst_dev, int dst_h, int dst_w,
-                           int swap_rb, void *stream) {
+static int resize_any(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, void *dst_dev, bool dst_u8, int dst_h, int dst_w,
+                      int swap_rb, void *stream, const char *who) {
     if (!src_dev || !dst_dev || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0 || src_row_bytes < 3 * src_w)
-        return fail(YOLO_ERR_ARG, "yolo_preprocess_resize: bad argument");
+        return fail(YOLO_ERR_ARG, std::string(who) + ": bad argument");
     ResizeParams p;
     p.src = src_dev; p.dst = dst_dev;
     p.src_h = src_h; p.src_w = src_w; p.src_row_bytes = src_row_bytes; p.dst_h = dst_h; p.dst_w = dst_w; p.swap_rb = swap_rb ? 1 : 0;
-    HIP_TRY(launch_resize(p, static_cast<hipStream_t>(stream)));
+    HIP_TRY(launch_resize(p, static_cast<hipStream_t>(stream), dst_u8));
+    return YOLO_OK;
+}
+int yolo_preprocess_resize(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, float *dst_dev, int dst_h, int dst_w,
+                           int swap_rb, void *stream) {
+    return resize_any(src_dev, src_h, src_w, src_row_bytes, dst_dev, false, dst_h, dst_w, swap_rb, stream, "yolo_preprocess_resize");
+}
+int yolo_preprocess_resize_u8(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, uint8_t *dst_dev, int dst_h, int dst_w,
+                              int swap_rb, void *stream) {
+    return resize_any(src_dev, src_h, src_w, src_row_bytes, dst_dev, true, dst_h, dst_w, swap_rb, stream, "yolo_preprocess_resize_u8");
+}
+
+int yolo_u8_unit_table(float *out256) {
+    if (!out256) return fail(YOLO_ERR_ARG, "yolo_u8_unit_table: null argument");
+    for (unsigned u = 0; u < 256; ++u) out256[u] = u8_unit(u);     // the function the input kernels run on every byte
     return YOLO_OK;
 }
 

@@ -10,23 +10,33 @@ typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
 
 // feed point of the graph (net/layers.py:106-109): float32 NHWC -> T NHWC with the channel count
 // padded to one 16-byte chunk (zeros), so the first conv can run the chunked implicit GEMM.
-template <bool F32>
-__global__ void __launch_bounds__(256) prep_kernel(const PrepParams p) {
+// U8: the caller's tensor is uint8 (yolo_net_forward_u8), a byte u is float32(u / 255.) (u8_unit) where the float32 kernel has the float.
+template <bool F32, bool U8>
+__device__ __forceinline__ void prep_body(const PrepParams &p) {
     typedef typename std::conditional<F32, float, _Float16>::type T;
+    typedef typename std::conditional<U8, unsigned char, float>::type TIn;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long px = (long long)blockIdx.x * blockDim.x + threadIdx.x; px < p.pixels; px += stride) {
-        const float *src = p.in + px * p.C;
+        const TIn *src = reinterpret_cast<const TIn *>(p.in) + px * p.C;
         T *dst = reinterpret_cast<T *>(p.out) + px * p.Cpad;
         for (int c0 = 0; c0 < p.Cpad; c0 += 16 / (int)sizeof(T)) {
             T t[16 / sizeof(T)];
 #pragma unroll
-            for (int e = 0; e < 16 / (int)sizeof(T); ++e) t[e] = (c0 + e < p.C) ? (T)src[c0 + e] : (T)0.f;
+            for (int e = 0; e < 16 / (int)sizeof(T); ++e) {
+                if constexpr (U8) t[e] = (c0 + e < p.C) ? (T)u8_unit(src[c0 + e]) : (T)0.f;
+                else t[e] = (c0 + e < p.C) ? (T)src[c0 + e] : (T)0.f;
+            }
             uint4v u;
             __builtin_memcpy(&u, t, 16);
             *reinterpret_cast<uint4v *>(dst + c0) = u;
         }
     }
 }
+
+template <bool F32>
+__global__ void __launch_bounds__(256) prep_kernel(const PrepParams p) { prep_body<F32, false>(p); }
+template <bool F32>
+__global__ void __launch_bounds__(256) prep_u8_kernel(const PrepParams p) { prep_body<F32, true>(p); }
 
 // net/layers.py:70-81.  stride 2: zero pad (0 before, 1 after) then 2x2 VALID -- the pad row/col is
 // only read for odd H/W and then takes part in the max as 0.  stride 1: TF SAME, window clipped.
@@ -147,7 +157,9 @@ __device__ __forceinline__ void resize_coeff(int d, int src, int dst, int &s0, i
     s1 = s + 1 < src ? s + 1 : src - 1;
 }
 
-__global__ void __launch_bounds__(256) resize_u8_kernel(const ResizeParams p) {
+// OUT_U8: the 8-bit value itself goes to a uint8 destination (yolo_preprocess_resize_u8: the batch tensor of yolo_net_detect_u8)
+template <bool OUT_U8>
+__device__ __forceinline__ void resize_u8_body(const ResizeParams &p) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)p.dst_h * p.dst_w) return;
     const int dy = (int)(i / p.dst_w), dx = (int)(i - (long long)dy * p.dst_w);
@@ -168,19 +180,26 @@ __global__ void __launch_bounds__(256) resize_u8_kernel(const ResizeParams p) {
             v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
             v = v < 0 ? 0 : (v > 255 ? 255 : v);
         }
-        p.dst[i * 3 + c] = (float)((double)v / 255.);
+        if constexpr (OUT_U8) reinterpret_cast<unsigned char *>(p.dst)[i * 3 + c] = (unsigned char)v;
+        else reinterpret_cast<float *>(p.dst)[i * 3 + c] = (float)((double)v / 255.);
     }
 }
+__global__ void __launch_bounds__(256) resize_u8_kernel(const ResizeParams p) { resize_u8_body<false>(p); }
+__global__ void __launch_bounds__(256) resize_u8_to_u8_kernel(const ResizeParams p) { resize_u8_body<true>(p); }
 
-hipError_t launch_resize(const ResizeParams &p, hipStream_t s) {
+hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8) {
     const long long n = (long long)p.dst_h * p.dst_w;
     if (n <= 0 || p.src_h <= 0 || p.src_w <= 0 || (n + 255) / 256 > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(resize_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+    if (dst_u8) hipLaunchKernelGGL(resize_u8_to_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(resize_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
-hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s) {
-    if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(prep_kernel<false>, dim3(grid_for(p.pixels)), dim3(256), 0, s, p);
+hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s, bool in_u8) {
+    if (in_u8) {
+        if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(prep_u8_kernel<false>, dim3(grid_for(p.pixels)), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(prep_u8_kernel<true>, dim3(grid_for(p.pixels)), dim3(256), 0, s, p);
+    } else if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(prep_kernel<false>, dim3(grid_for(p.pixels)), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(prep_kernel<true>, dim3(grid_for(p.pixels)), dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -17,9 +17,12 @@ namespace yolo {
 // registers: a wave covers 32 x-positions of two adjacent rows (lane = 32 * row + x), the 2x2 window is a max over
 // lanes l ^ 1 and l ^ 32 of the raw accumulators (bias and leaky are monotone: pooling first is the same result with
 // a quarter of the activation work), and only the pooled pixel row (16 per wave) is written.  H and W even.
-template <bool F32, int COUT, bool POOL>
-__global__ void __launch_bounds__(256) conv_first_kernel(const FirstParams p) {
+// U8 (all three kernels of this file): the image is uint8 (yolo_net_forward_u8) -- byte loads, and a byte u is float32(u / 255.)
+// (u8_unit, yolo_internal.h) where the float32 kernel has the caller's float; everything behind the fetch is the same code.
+template <bool F32, int COUT, bool POOL, bool U8>
+__device__ __forceinline__ void conv_first_body(const FirstParams &p) {
     typedef typename std::conditional<F32, float, _Float16>::type T;
+    typedef typename std::conditional<U8, unsigned char, float>::type TIn;
     constexpr int EPC = 16 / (int)sizeof(T);
     constexpr int ROWB = COUT * (int)sizeof(T);     // bytes of one output pixel
     constexpr int NCH = ROWB / 16;                  // 16-byte chunks per pixel
@@ -68,18 +71,23 @@ __global__ void __launch_bounds__(256) conv_first_kernel(const FirstParams p) {
     for (int kh = 0; kh < 3; ++kh) {
         const int iy = oy - 1 + kh;                         // SAME padding: one zero row/col each side
         const bool rowok = (unsigned)iy < (unsigned)p.H;
-        const float *rowp = p.in + ((n * p.H + (rowok ? iy : 0)) * (long long)p.W) * 3;
+        const TIn *rowp = reinterpret_cast<const TIn *>(p.in) + ((n * p.H + (rowok ? iy : 0)) * (long long)p.W) * 3;
         float xin[3][3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const int ix = ox - 1 + c;
             const bool ok = rowok && (unsigned)ix < (unsigned)p.W;
             const int ixc = ix < 0 ? 0 : (ix >= p.W ? p.W - 1 : ix);    // always-valid address: load, then select
+            const unsigned okmask = ok ? 0xffu : 0u;                    // (U8: a VGPR mask instead of a lane mask held in SGPRs over the loads)
+            (void)okmask;
 #pragma unroll
             for (int ci = 0; ci < 3; ++ci) {
-                float v = rowp[ixc * 3 + ci];
+                float v;
+                if constexpr (U8) v = u8_unit(rowp[ixc * 3 + ci] & okmask);     // (the padding select on the byte: u8_unit(0) is 0.f)
+                else v = rowp[ixc * 3 + ci];
                 if (p.round_half) v = (float)(_Float16)v;
-                xin[c][ci] = ok ? v : 0.f;
+                if constexpr (U8) xin[c][ci] = v;
+                else xin[c][ci] = ok ? v : 0.f;
             }
         }
 #pragma unroll
@@ -151,6 +159,14 @@ __global__ void __launch_bounds__(256) conv_first_kernel(const FirstParams p) {
     }
 }
 
+template <bool F32, int COUT, bool POOL>
+__global__ void __launch_bounds__(256) conv_first_kernel(const FirstParams p) { conv_first_body<F32, COUT, POOL, false>(p); }
+// (fp16, 32 couts, no pool: left alone the register allocator takes 106 scalar registers where the float32-input form takes 94 and
+// ends one wave per SIMD short of it -- held to the twin's eight waves: no spilled VGPR, no scratch; tests/test_u8_cpu.py compares the twins)
+template <bool F32, int COUT, bool POOL>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((!F32 && COUT == 32 && !POOL) ? 8 : 1)))
+conv_first_u8_kernel(const FirstParams p) { conv_first_body<F32, COUT, POOL, true>(p); }
+
 // ---- fp16 nets, 32 couts, fused pool: the same layer on the MATRIX cores ------------------------------------------------------
 // The direct VALU kernel above runs Darknet-19's first layer + pool (416 x 416, batch 16) in 94 us = 10 % of the YOLOv2 step at
 // 0.8 TB/s: 864 FMAs per pixel make it VALU-bound.  This is the layer-1 phase of stem.hip on its own: a persistent workgroup (8 waves)
@@ -166,8 +182,10 @@ constexpr int FM_PX = 36;                            // pixels per LDS patch row
 constexpr int FM_LD = FM_PX * 4;                     // halfs per patch row
 }  // namespace
 
-__global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstParams p) {
+template <bool U8>
+__device__ __forceinline__ void first_pool_mfma_body(const FirstParams &p) {
     typedef _Float16 T;
+    typedef typename std::conditional<U8, unsigned char, float>::type TIn;
     __shared__ __attribute__((aligned(16))) unsigned char smem[FM_INY * FM_LD * 2];
     T *const sIn = reinterpret_cast<T *>(smem);
     const int tid = threadIdx.x;
@@ -203,7 +221,7 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstPara
 
     // input staging: four patch rows per pass, 128 threads per row (102 used)
     constexpr int NIN = (FM_INY + 3) / 4;
-    float in_r[NIN];
+    typename std::conditional<U8, unsigned, float>::type in_r[NIN];
     const int in_col = tid & 127, in_row0 = tid >> 7;
     const bool in_col_ok = in_col < FM_INX * 3;
     const int in_px = in_col / 3;
@@ -219,7 +237,7 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstPara
     auto fetch_input = [&](int tile) {
         int n, py0, px0;
         tile_origin(tile, n, py0, px0);
-        const float *img = p.in + (long long)n * p.H * p.W * 3;
+        const TIn *img = reinterpret_cast<const TIn *>(p.in) + (long long)n * p.H * p.W * 3;
         const int gy0 = 2 * py0 - 1 + in_row0, gx3 = (2 * px0 - 1) * 3 + in_col;
         const bool xok = in_col_ok && (unsigned)gx3 < (unsigned)(3 * p.W);
         const int w3 = 3 * p.W;
@@ -227,8 +245,8 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstPara
         for (int it = 0; it < NIN; ++it) {
             const int gy = gy0 + 4 * it;
             const bool ok = xok && (unsigned)gy < (unsigned)p.H && (4 * it + in_row0 < FM_INY);
-            const float v = img[ok ? gy * w3 + gx3 : 0];
-            in_r[it] = ok ? v : 0.f;
+            const TIn v = img[ok ? gy * w3 + gx3 : 0];        // always-valid address, then select
+            in_r[it] = ok ? v : (TIn)0;
         }
     };
 
@@ -240,7 +258,10 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstPara
         tile_origin(tile, n, py0, px0);
 #pragma unroll
         for (int it = 0; it < NIN; ++it)
-            if (in_col_ok && 4 * it + in_row0 < FM_INY) in_dst[4 * it * FM_LD] = (T)in_r[it];
+            if (in_col_ok && 4 * it + in_row0 < FM_INY) {
+                if constexpr (U8) in_dst[4 * it * FM_LD] = (T)u8_unit(in_r[it]);
+                else in_dst[4 * it * FM_LD] = (T)in_r[it];
+            }
         __syncthreads();        // input patch visible
         if (tile + (int)gridDim.x < p.n_tiles) fetch_input(tile + gridDim.x);
         const int oy = py0 + wave;
@@ -286,6 +307,9 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstPara
     }
 }
 
+__global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstParams p) { first_pool_mfma_body<false>(p); }
+__global__ void __launch_bounds__(512, 4) first_pool_mfma_u8_kernel(const FirstParams p) { first_pool_mfma_body<true>(p); }
+
 // ---- float32 nets, fused pool: the same on the float32 matrix instruction --------------------------------------------------------
 // tiny-YOLOv2-VOC's first layer (3 -> 16 + pool, 416 x 416, batch 64) ran 218 us on the VALU kernel: 1.4 TB/s where its 310 MB allow
 // ~70 us.  mfma_f32_16x16x4f32 takes ONE float per lane and operand: k = 4 s + (lane >> 4) for k-step s, so K = 27 is seven k-steps
@@ -293,8 +317,9 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_kernel(const FirstPara
 // are seven registers per 16 couts, and the bias is the C input.  Same tiling as above: persistent workgroups, 8 x 16 pooled outputs
 // per tile, wave w = pooled row w (conv rows 2 w, 2 w + 1 = two accumulators of a lane, columns = lanes fr, fr ^ 1), the input patch
 // as 16-byte (R G B 0) float32 pixels in LDS, fetched one tile ahead through registers.  NT = Cout / 16.
-template <int NT>
-__global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_kernel(const FirstParams p) {
+template <int NT, bool U8>
+__device__ __forceinline__ void first_pool_mfma_f32_body(const FirstParams &p) {
+    typedef typename std::conditional<U8, unsigned char, float>::type TIn;
     constexpr int LD = FM_PX * 4;               // floats per patch row
     __shared__ __attribute__((aligned(16))) float sIn[FM_INY * LD];
     const int tid = threadIdx.x;
@@ -324,7 +349,7 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_kernel(const First
     for (int i = tid; i < FM_INY * FM_PX; i += 512) *reinterpret_cast<float4v *>(sIn + i * 4) = float4v{0.f, 0.f, 0.f, 0.f};
 
     constexpr int NIN = (FM_INY + 3) / 4;
-    float in_r[NIN];
+    typename std::conditional<U8, unsigned, float>::type in_r[NIN];
     const int in_col = tid & 127, in_row0 = tid >> 7;
     const bool in_col_ok = in_col < FM_INX * 3;
     const int in_px = in_col / 3;
@@ -340,7 +365,7 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_kernel(const First
     auto fetch_input = [&](int tile) {
         int n, py0, px0;
         tile_origin(tile, n, py0, px0);
-        const float *img = p.in + (long long)n * p.H * p.W * 3;
+        const TIn *img = reinterpret_cast<const TIn *>(p.in) + (long long)n * p.H * p.W * 3;
         const int gy0 = 2 * py0 - 1 + in_row0, gx3 = (2 * px0 - 1) * 3 + in_col;
         const bool xok = in_col_ok && (unsigned)gx3 < (unsigned)(3 * p.W);
         const int w3 = 3 * p.W;
@@ -348,8 +373,8 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_kernel(const First
         for (int it = 0; it < NIN; ++it) {
             const int gy = gy0 + 4 * it;
             const bool ok = xok && (unsigned)gy < (unsigned)p.H && (4 * it + in_row0 < FM_INY);
-            const float v = img[ok ? gy * w3 + gx3 : 0];
-            in_r[it] = ok ? v : 0.f;
+            const TIn v = img[ok ? gy * w3 + gx3 : 0];        // always-valid address, then select
+            in_r[it] = ok ? v : (TIn)0;
         }
     };
 
@@ -361,7 +386,10 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_kernel(const First
         tile_origin(tile, n, py0, px0);
 #pragma unroll
         for (int it = 0; it < NIN; ++it)
-            if (in_col_ok && 4 * it + in_row0 < FM_INY) in_dst[4 * it * LD] = in_r[it];
+            if (in_col_ok && 4 * it + in_row0 < FM_INY) {
+                if constexpr (U8) in_dst[4 * it * LD] = u8_unit(in_r[it]);
+                else in_dst[4 * it * LD] = in_r[it];
+            }
         __syncthreads();        // input patch visible
         if (tile + (int)gridDim.x < p.n_tiles) fetch_input(tile + gridDim.x);
         const int oy = py0 + wave;
@@ -405,18 +433,28 @@ __global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_kernel(const First
     }
 }
 
+template <int NT>
+__global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_kernel(const FirstParams p) { first_pool_mfma_f32_body<NT, false>(p); }
+template <int NT>
+__global__ void __launch_bounds__(512, 4) first_pool_mfma_f32_u8_kernel(const FirstParams p) { first_pool_mfma_f32_body<NT, true>(p); }
+
 // the matrix-core forms of layer 1 + pool: fp16 nets with 32 couts, float32 nets with 16 or 32 (16-byte aligned float32 output view)
 static bool first_mfma_applies(int dtype, int cout, bool pool) {
     return pool && (dtype == YOLO_DTYPE_F16 ? cout == 32 : (cout == 16 || cout == 32));
 }
 
 template <bool T, int COUT>
-static void launch_first_t(const FirstParams &p, dim3 grid, hipStream_t s) {
+static void launch_first_t(const FirstParams &p, dim3 grid, hipStream_t s, bool in_u8) {
+    if (in_u8) {
+        if (p.pool) hipLaunchKernelGGL((conv_first_u8_kernel<T, COUT, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((conv_first_u8_kernel<T, COUT, false>), grid, dim3(256), 0, s, p);
+        return;
+    }
     if (p.pool) hipLaunchKernelGGL((conv_first_kernel<T, COUT, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv_first_kernel<T, COUT, false>), grid, dim3(256), 0, s, p);
 }
 
-hipError_t launch_first(const FirstParams &p0, int dtype, hipStream_t s) {
+hipError_t launch_first(const FirstParams &p0, int dtype, hipStream_t s, bool in_u8) {
     FirstParams p = p0;
     long long g = (p.total + 255) / 256;            // one workgroup per 256 output pixels
     if (g < 1 || p.total > 0x7fffffffLL) return hipErrorInvalidValue;   // 32-bit pixel indices (fdiv)
@@ -441,19 +479,23 @@ hipError_t launch_first(const FirstParams &p0, int dtype, hipStream_t s) {
         if (tiles < 1 || tiles > 0x7fffffffLL || (long long)p.H * p.W * 3 > 0x7fffffffLL) return hipErrorInvalidValue;
         p.n_tiles = (int)tiles;
         const dim3 mgrid((unsigned)(tiles < 1024 ? tiles : 1024));
-        if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(first_pool_mfma_kernel, mgrid, dim3(512), 0, s, p);
+        if (in_u8) {
+            if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(first_pool_mfma_u8_kernel, mgrid, dim3(512), 0, s, p);
+            else if (p.Cout == 16) hipLaunchKernelGGL(first_pool_mfma_f32_u8_kernel<1>, mgrid, dim3(512), 0, s, p);
+            else hipLaunchKernelGGL(first_pool_mfma_f32_u8_kernel<2>, mgrid, dim3(512), 0, s, p);
+        } else if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(first_pool_mfma_kernel, mgrid, dim3(512), 0, s, p);
         else if (p.Cout == 16) hipLaunchKernelGGL(first_pool_mfma_f32_kernel<1>, mgrid, dim3(512), 0, s, p);
         else hipLaunchKernelGGL(first_pool_mfma_f32_kernel<2>, mgrid, dim3(512), 0, s, p);
         return hipGetLastError();
     }
     const dim3 grid((unsigned)g);
     if (dtype == YOLO_DTYPE_F16) {
-        if (p.Cout == 32) launch_first_t<false, 32>(p, grid, s);
-        else if (p.Cout == 16) launch_first_t<false, 16>(p, grid, s);
+        if (p.Cout == 32) launch_first_t<false, 32>(p, grid, s, in_u8);
+        else if (p.Cout == 16) launch_first_t<false, 16>(p, grid, s, in_u8);
         else return hipErrorInvalidValue;
     } else {
-        if (p.Cout == 32) launch_first_t<true, 32>(p, grid, s);
-        else if (p.Cout == 16) launch_first_t<true, 16>(p, grid, s);
+        if (p.Cout == 32) launch_first_t<true, 32>(p, grid, s, in_u8);
+        else if (p.Cout == 16) launch_first_t<true, 16>(p, grid, s, in_u8);
         else return hipErrorInvalidValue;
     }
     return hipGetLastError();

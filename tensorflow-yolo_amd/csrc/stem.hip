@@ -24,6 +24,7 @@
 //            from the lane's own fp16 outputs as MFMA B operand (no LDS: the k order of an MFMA is free), saving the
 //            1x1 kernel its 378 MB re-read of the tensor just written.
 #include "conv_common.h"
+#include <type_traits>
 
 namespace yolo {
 
@@ -68,8 +69,12 @@ constexpr int BIAS_BYTES = (64 + 32) * 4;  // layer-2 and layer-3 biases (read p
 
 }  // namespace
 
-__global__ void __launch_bounds__(512, 4) stem_v3_kernel(const StemParams p) {
+// U8: the image is uint8 (yolo_net_forward_u8): only fetch_input / in_r[] differ -- byte loads, and the byte becomes float32(u / 255.)
+// (u8_unit) where the float32 kernel has the caller's float; LDS layout, MFMA phases and epilogues are the same code.
+template <bool U8>
+__device__ __forceinline__ void stem_v3_body(const StemParams &p) {
     typedef _Float16 T;
+    typedef typename std::conditional<U8, unsigned char, float>::type TIn;
     __shared__ __attribute__((aligned(16))) unsigned char smem[W2_BYTES + P_BYTES + IN_BYTES + BIAS_BYTES];
     unsigned char *const sW = smem;
     unsigned char *const sP = smem + W2_BYTES;
@@ -147,7 +152,7 @@ __global__ void __launch_bounds__(512, 4) stem_v3_kernel(const StemParams p) {
     // previous tile's two MFMA phases): four patch rows per pass, 128 threads per row (105 used), so a thread's column, pixel
     // and channel never change and its row advances by 4 -- no division, LDS offsets are immediates
     constexpr int NIN = (INY + 3) / 4;
-    float in_r[NIN];
+    typename std::conditional<U8, unsigned, float>::type in_r[NIN];
     const int in_col = tid & 127, in_row0 = tid >> 7;
     const bool in_col_ok = in_col < INX * 3;
     const int in_px = in_col / 3;
@@ -162,7 +167,7 @@ __global__ void __launch_bounds__(512, 4) stem_v3_kernel(const StemParams p) {
     auto fetch_input = [&](int tile) {
         int n, oy0, ox0;
         tile_origin(tile, n, oy0, ox0);
-        const float *img = p.in + (long long)n * p.in_img_stride;
+        const TIn *img = reinterpret_cast<const TIn *>(p.in) + (long long)n * p.in_img_stride;
         const int gy0 = 2 * oy0 - 2 + in_row0, gx3 = (2 * ox0 - 2) * 3 + in_col;
         const bool xok = in_col_ok && (unsigned)gx3 < (unsigned)(3 * p.W);
         const int w3 = 3 * p.W;
@@ -170,8 +175,8 @@ __global__ void __launch_bounds__(512, 4) stem_v3_kernel(const StemParams p) {
         for (int it = 0; it < NIN; ++it) {
             const int gy = gy0 + 4 * it;
             const bool ok = xok && (unsigned)gy < (unsigned)p.H && (4 * it + in_row0 < INY);
-            const float v = img[ok ? gy * w3 + gx3 : 0];      // always-valid address, then select (an image is < 2^31 floats)
-            in_r[it] = ok ? v : 0.f;
+            const TIn v = img[ok ? gy * w3 + gx3 : 0];        // always-valid address, then select (an image is < 2^31 elements)
+            in_r[it] = ok ? v : (TIn)0;
         }
     };
 
@@ -186,7 +191,10 @@ __global__ void __launch_bounds__(512, 4) stem_v3_kernel(const StemParams p) {
         // float32 -> fp16 (same operand rounding as the unfused first-layer kernel)
 #pragma unroll
         for (int it = 0; it < NIN; ++it)
-            if (in_col_ok && 4 * it + in_row0 < INY) in_dst[4 * it * IN_LD] = (T)in_r[it];
+            if (in_col_ok && 4 * it + in_row0 < INY) {
+                if constexpr (U8) in_dst[4 * it * IN_LD] = (T)u8_unit(in_r[it]);
+                else in_dst[4 * it * IN_LD] = (T)in_r[it];
+            }
         __syncthreads();    // input patch visible; every wave is past phase 2 of the previous tile (patch P is free)
         if (tile + (int)gridDim.x < p.n_tiles) fetch_input(tile + gridDim.x);
 
@@ -294,7 +302,10 @@ __global__ void __launch_bounds__(512, 4) stem_v3_kernel(const StemParams p) {
     }
 }
 
-hipError_t launch_stem(const StemParams &p0, int batch, hipStream_t s, int max_grid) {
+__global__ void __launch_bounds__(512, 4) stem_v3_kernel(const StemParams p) { stem_v3_body<false>(p); }
+__global__ void __launch_bounds__(512, 4) stem_v3_u8_kernel(const StemParams p) { stem_v3_body<true>(p); }
+
+hipError_t launch_stem(const StemParams &p0, int batch, hipStream_t s, int max_grid, bool in_u8) {
     StemParams p = p0;
     if ((p.H & 1) || (p.W & 1) || p.Ho != p.H / 2 || p.Wo != p.W / 2) return hipErrorInvalidValue;
     p.tiles_x = (p.Wo + TX - 1) / TX;
@@ -306,7 +317,8 @@ hipError_t launch_stem(const StemParams &p0, int batch, hipStream_t s, int max_g
     p.n_tiles = (int)tiles;
     // persistent workgroups: two per CU (78 KB of LDS each), every one walks tiles blockIdx, blockIdx + grid, ...
     const unsigned grid = (unsigned)(tiles < max_grid ? tiles : max_grid);
-    hipLaunchKernelGGL(stem_v3_kernel, dim3(grid), dim3(512), 0, s, p);
+    if (in_u8) hipLaunchKernelGGL(stem_v3_u8_kernel, dim3(grid), dim3(512), 0, s, p);
+    else hipLaunchKernelGGL(stem_v3_kernel, dim3(grid), dim3(512), 0, s, p);
     return hipGetLastError();
 }
 

@@ -82,6 +82,20 @@ __host__ __device__ __forceinline__ float leaky01(float x) {
 #endif
 }
 
+// uint8 network input (yolo_net_forward_u8 and friends): a pixel byte u enters the first conv as float32(u / 255.), the value the
+// float32 entry points are handed (net/base.py:153 divides in float64, the placeholder casts to float32: net/layers.py:108).  That is
+// the correctly rounded IEEE float32 quotient u / 255 -- NOT u * float32(1 / 255), which differs for 126 of the 256 bytes.  Computed
+// as a quotient estimate plus one correction on its exact remainder: r = u - 255 q is exact in an FMA (q is within one ulp), and
+// q + r / 255 rounds to the quotient (checked against float64 division for all 256 bytes: tests/test_u8_cpu.py, through
+// yolo_u8_unit_table).  Three dependent VALU instructions, no division sequence, nothing a fast-math flag can rewrite.
+__host__ __device__ __forceinline__ float u8_unit(unsigned u) {
+#pragma clang fp contract(off)
+    const float a = (float)u;
+    const float rcp = 0x1.010102p-8f;       // float32(1 / 255.)
+    const float q = a * rcp;
+    return __builtin_fmaf(__builtin_fmaf(-255.f, q, a), rcp, q);
+}
+
 // The per-image candidate counters of the decode live one per 128-byte line: with the 32 counters of a batch in ONE line every
 // candidate's atomicAdd of the whole batch went through one L2 channel (YOLOv3-608 b32: 2 900 atomics, decode_kernel 31 us, 5 us with
 // no candidate at all).
@@ -155,15 +169,15 @@ inline void conv_set_divisors(ConvParams &p, int stages_per_tap) {
     p.dtiles_n = make_fastdiv((uint32_t)(p.n_tiles_n > 0 ? p.n_tiles_n : 1));
 }
 
-struct PrepParams {            // float32 NHWC [B,H,W,C] -> T NHWC [B,H,W,Cpad], zero fill
-    const float *in;
+struct PrepParams {            // float32 (or uint8: launch_prep's in_u8, prep_u8_kernel) NHWC [B,H,W,C] -> T NHWC [B,H,W,Cpad], zero fill
+    const void *in;
     void *out;
     long long pixels;
     int C, Cpad;
 };
 
 struct FirstParams {           // first layer: 3x3/1 conv on the float32 NHWC3 input, Cout 16|32
-    const float *in;           // [B,H,W,3] float32 (the caller's tensor)
+    const void *in;            // [B,H,W,3] float32 (the caller's tensor), or uint8 for the *_u8_kernel twins (launch_first: in_u8)
     const float *wgt;          // [27][Cout] float32, BN folded (rounded through fp16 for fp16 nets)
     const float *bias;         // [Cout]
     void *out;                 // T NHWC view
@@ -178,7 +192,7 @@ struct FirstParams {           // first layer: 3x3/1 conv on the float32 NHWC3 i
 };
 
 struct StemParams {            // stem.hip: fused conv 3x3/1 3->32 + conv 3x3/2 32->64 (both BN + leaky), fp16 nets
-    const float *in;           // [B,H,W,3] float32 (the caller's tensor)
+    const void *in;            // [B,H,W,3] float32 (the caller's tensor), or uint8 for stem_v3_u8_kernel (launch_stem: in_u8)
     const float *w1;           // first layer [27][32] float32 (K_FIRST packing)
     const float *b1;           // [32]
     const void *w2;            // second layer, K_CONV packing: [Cout_pad][wrow2 bytes] fp16, K = (kh, kw, 32 cin)
@@ -191,14 +205,14 @@ struct StemParams {            // stem.hip: fused conv 3x3/1 3->32 + conv 3x3/2 
     long long out3_img_stride;
     uint32_t w2_bytes, wrow2;
     int H, W, Ho, Wo, out_ld;
-    long long in_img_stride, out_img_stride;
+    long long in_img_stride, out_img_stride;     // in ELEMENTS of the input type (floats, or bytes for a uint8 input)
     int tiles_x, tiles_y, n_tiles;   // set by launch_stem
     FastDiv dtx, dty;
 };
 
-struct ResizeParams {          // uint8 HWC3 image -> float32 [dst_h][dst_w][3] in [0,1] (aux.hip: resize_u8_kernel)
+struct ResizeParams {          // uint8 HWC3 image -> float32 [dst_h][dst_w][3] in [0,1] (aux.hip: resize_u8_kernel), or the 8-bit value itself
     const unsigned char *src;
-    float *dst;
+    void *dst;                 // float32, or uint8 for resize_u8_to_u8_kernel (launch_resize: dst_u8)
     int src_h, src_w, src_row_bytes, dst_h, dst_w, swap_rb;
 };
 
@@ -315,10 +329,11 @@ bool dma_cfg_splitk_ok(int cfg);        // the kernel behind this tile id takes 
 hipError_t launch_splitk_reduce(const ReduceParams &p, hipStream_t s);
 bool conv_tap_splitk_ok(int variant);
 bool conv_tap_pair_ok(int variant, bool f32);
-hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s);
-hipError_t launch_resize(const ResizeParams &p, hipStream_t s);
-hipError_t launch_first(const FirstParams &p, int dtype, hipStream_t s);
-hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = 512);     // stem.hip
+// in_u8 / dst_u8: the kernel's uint8 twin runs -- `in` (`dst`) holds bytes, dense, any alignment (the parameter blocks are the same)
+hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s, bool in_u8 = false);
+hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8 = false);
+hipError_t launch_first(const FirstParams &p, int dtype, hipStream_t s, bool in_u8 = false);
+hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = 512, bool in_u8 = false);     // stem.hip
 hipError_t launch_pool(const PoolParams &p, int dtype, hipStream_t s);
 hipError_t launch_eltwise(const EltParams &p, int dtype, hipStream_t s);
 hipError_t launch_decode(const DecodeParams &p, int batch, hipStream_t s, bool zero_counts = true);

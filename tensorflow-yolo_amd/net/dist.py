@@ -71,11 +71,12 @@ def gather_records(flat, group=None, always=False):
     return out.view(w, flat.numel())
 
 
-def detect_sharded(engine, x_local, threshold, iou_threshold, nms_mode=0, group=None):
+def detect_sharded(engine, x_local, threshold, iou_threshold, nms_mode=0, group=None, u8=False):
     """One step of the sharded hot path on this rank: forward + decode + NMS of the local shard (one C call,
     `engine.detect`) and the all-gather of the record buffer.  x_local may be None / empty when the global batch
     leaves this rank without images (its counts are then zero).  `engine` needs `.records` (int32
     [record_words]), `.max_batch`, `.max_boxes` and `.detect()`; the gloo tests pass a CPU stand-in.
+    u8: x_local is a uint8 batch (0..255) and goes through `engine.detect_u8` (same records as float32(x / 255.) through `detect`).
     Returns (boxes [W, B, K, 6], counts [W, B], status [W, B]) as views of the gathered buffer."""
     n_local = 0 if x_local is None else int(x_local.shape[0])
     B = engine.max_batch
@@ -85,9 +86,14 @@ def detect_sharded(engine, x_local, threshold, iou_threshold, nms_mode=0, group=
         # instead of each rank's own tuner answer (engine.agree_streams; stand-in engines of the CPU tests have none)
         agree = getattr(engine, "agree_streams", None)
         if agree is not None:
-            agree(x_local if n_local else None, group)
+            if u8:
+                agree(x_local if n_local else None, group, u8=True)
+            else:
+                agree(x_local if n_local else None, group)
         engine._streams_agreed = True
-    if n_local:
+    if n_local and u8:
+        engine.detect_u8(x_local, threshold, iou_threshold, nms_mode)
+    elif n_local:
         engine.detect(x_local, threshold, iou_threshold, nms_mode)
     if n_local < B:         # records of images this rank did not run: count 0, status 0
         engine.records[n_local:B].zero_()

@@ -101,6 +101,7 @@ class Plan(object):
         self.num_kernels = self.lib.yolo_net_num_kernels(handle)
         self._auto_streams = int(streams) <= 0                          # streams = 0: the library's rule, re-measured on the device
         self._streams_tuned = False                                     # (HipNetwork: at the first full batch)
+        self.u8_calls = 0                                               # diagnostic: calls that went through a uint8 entry point (forward_u8 / detect_u8 / forward_timed_u8)
         self.input_hwc = self.layers[0].out.hwc
         last = self.layers[-1]
         if isinstance(last, L.detection_layer):
@@ -192,6 +193,29 @@ class HipNetwork(Plan):
             raise ValueError("batch %d outside 1..%d (max_batch)" % (x.shape[0], self.max_batch))
         return x
 
+    def check_u8(self, x_batch):
+        """Shape / dtype rule of the uint8 entry points (no GPU needed): a uint8 NumPy array or torch tensor [B,H,W,C] of the net's input
+        shape with 1 <= B <= max_batch; anything else raises ValueError (a float array is NOT scaled or cast here: use forward / detect)."""
+        dt = str(getattr(x_batch, "dtype", None)).replace("torch.", "")
+        if dt != "uint8":
+            raise ValueError("the uint8 entry points take a uint8 array or tensor, got %s (%s)" % (type(x_batch).__name__, dt))
+        h, w, c = self.input_hwc
+        shape = tuple(int(v) for v in x_batch.shape)
+        if len(shape) != 4 or shape[1:] != (h, w, c):
+            raise ValueError("expected uint8 input [B,%d,%d,%d], got %s" % (h, w, c, shape))
+        if not 1 <= shape[0] <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d (max_batch)" % (shape[0], self.max_batch))
+        return shape[0]
+
+    def to_device_u8(self, x_batch):
+        """uint8 [B,H,W,C] (host NumPy / torch, or already on the device) -> dense uint8 device tensor: one copy of B*H*W*C bytes, no
+        arithmetic (the / 255. of net/base.py:153 happens inside the first kernel).  A contiguous device view is passed as it is,
+        whatever its byte alignment."""
+        torch = self.torch
+        self.check_u8(x_batch)
+        x = x_batch if isinstance(x_batch, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x_batch))
+        return x.to(self.device).contiguous()
+
     def _tune_streams(self, x):
         """streams = 0 and the rule said two halves: time one pass against two halves on THIS device, once, with the first batch
         that is large enough, and keep the faster (yolo_net_tune_streams: the gain is board-dependent, +4 % to -1.5 %)."""
@@ -200,17 +224,18 @@ class HipNetwork(Plan):
         if self.lib.yolo_net_num_streams(self.handle) < 2 or 2 * x.shape[0] <= self.max_batch:
             self._streams_tuned = self.lib.yolo_net_num_streams(self.handle) < 2
             return
+        name = "yolo_net_tune_streams_u8" if x.dtype == self.torch.uint8 else "yolo_net_tune_streams"
         with self.torch.cuda.device(self.device):
-            _hip.check(self.lib.yolo_net_tune_streams(self.handle, x.data_ptr(), x.shape[0], self._stream()), "yolo_net_tune_streams")
+            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), x.shape[0], self._stream()), name)
         self._streams_tuned = True
 
-    def agree_streams(self, x, group=None):
+    def agree_streams(self, x, group=None, u8=False):
         """Ranks of a sharded batch must run the SAME plan: each rank measures for itself where it can, then rank
         0's answer is broadcast and taken by everyone -- one pass and two halves differ in fp16 summation order, and the job's step
         time is the slowest rank's.  A collective: every rank calls it once (net/dist.py does, at its first sharded detect)."""
         torch = self.torch
         if x is not None and x.shape[0] > 0:
-            self._tune_streams(self.to_device(x))
+            self._tune_streams(self.to_device_u8(x) if u8 else self.to_device(x))
         import torch.distributed as dist
         from . import dist as ydist
         want = ydist.broadcast_rank0_int(self.num_streams, group, self.device if dist.get_backend(group) == "nccl" else "cpu")
@@ -244,6 +269,46 @@ class HipNetwork(Plan):
                                                 int(nms_mode), self._boxes.data_ptr(), self._counts.data_ptr(),
                                                 self._status.data_ptr(), self._stream()), "yolo_net_detect")
         return self._boxes[:b], self._counts[:b], self._status[:b]
+
+    # -- uint8 input (ABI 7): bit-identical to forward / detect / forward_timed fed float32(x / 255.) -----------------------------
+    def forward_u8(self, x, out=None):
+        """forward() for a uint8 batch [B,H,W,C] (0..255, RGB): the bytes go to the device as they are."""
+        torch = self.torch
+        x = self.to_device_u8(x)
+        self._tune_streams(x)
+        b = x.shape[0]
+        if out is None:
+            out = torch.empty((b,) + tuple(self.output_shape), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_forward_u8(self.handle, x.data_ptr(), b, out.data_ptr(), self._stream()), "yolo_net_forward_u8")
+        self.u8_calls += 1
+        return out
+
+    def detect_u8(self, x, threshold, iou_threshold, nms_mode=_hip.NMS_AGNOSTIC):
+        """detect() for a uint8 batch [B,H,W,C] (0..255, RGB)."""
+        x = self.to_device_u8(x)
+        self._tune_streams(x)
+        b = x.shape[0]
+        with self.torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_detect_u8(self.handle, x.data_ptr(), b, float(threshold), float(iou_threshold),
+                                                   int(nms_mode), self._boxes.data_ptr(), self._counts.data_ptr(),
+                                                   self._status.data_ptr(), self._stream()), "yolo_net_detect_u8")
+        self.u8_calls += 1
+        return self._boxes[:b], self._counts[:b], self._status[:b]
+
+    def forward_timed_u8(self, x, out=None):
+        """forward_timed() for a uint8 batch: the input kernel's entry is the time of its uint8 twin."""
+        torch = self.torch
+        x = self.to_device_u8(x)
+        b = x.shape[0]
+        if out is None:
+            out = torch.empty((b,) + tuple(self.output_shape), dtype=torch.float32, device=self.device)
+        ms = np.zeros(self.num_kernels, dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_forward_timed_u8(self.handle, x.data_ptr(), b, out.data_ptr(), self._stream(),
+                                                          ms.ctypes.data), "yolo_net_forward_timed_u8")
+        self.u8_calls += 1
+        return ms
 
     def autotune(self, x):
         """Pick the fastest conv tile per layer by timing them on the device (optional, synchronous)."""

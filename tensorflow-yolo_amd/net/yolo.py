@@ -73,10 +73,20 @@ class Yolo(object):
             return self.predict_shard(x_batch[lo:hi] if hi > lo else None, len(x_batch), threshold, iou_threshold, nms_mode, group)
         return self.predict_shard(x_batch, len(x_batch), threshold, iou_threshold, nms_mode, group)
 
-    def predict_shard(self, x_local, n_global, threshold=0.5, iou_threshold=0.6, nms_mode=_hip.NMS_AGNOSTIC, group=None):
+    def predict_u8(self, x_batch_u8, threshold=0.5, iou_threshold=0.6, nms_mode=_hip.NMS_AGNOSTIC, group=None):
+        """predict() for a uint8 batch [B,H,W,C] with values 0..255, RGB -- the pixels net/base.py:115-155 has before its `/ 255.`:
+        the bytes go to the device as they are (a quarter of the float32 batch) and the first kernel converts.  Returns exactly
+        what predict() returns for float32(x_batch_u8 / 255.); sharding as in predict()."""
+        rank, world = ydist.world(group)
+        if world > 1:
+            lo, hi = ydist.shard_range(len(x_batch_u8), rank, world)
+            return self.predict_shard(x_batch_u8[lo:hi] if hi > lo else None, len(x_batch_u8), threshold, iou_threshold, nms_mode, group, u8=True)
+        return self.predict_shard(x_batch_u8, len(x_batch_u8), threshold, iou_threshold, nms_mode, group, u8=True)
+
+    def predict_shard(self, x_local, n_global, threshold=0.5, iou_threshold=0.6, nms_mode=_hip.NMS_AGNOSTIC, group=None, u8=False):
         """predict() for a caller that holds only ITS images of the global batch (Yolo.test under torch.distributed
         preprocesses just the rank's shard): x_local = images shard_range(n_global, rank, world) of the batch, or None
-        when the shard is empty.  Returns the list for all n_global images on every rank."""
+        when the shard is empty.  u8: x_local is uint8 0..255 (predict_u8).  Returns the list for all n_global images on every rank."""
         eng = self.net.engine
         if not eng.weights_loaded:
             raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
@@ -90,20 +100,27 @@ class Yolo(object):
             n_local = 0 if x_local is None else len(x_local)
             if n_local != hi - lo:
                 raise ValueError("rank %d holds %d images of a global batch of %d, its shard is [%d, %d)" % (rank, n_local, n, lo, hi))
-            boxes, counts, status = ydist.detect_sharded(eng, x_local if n_local else None, threshold, iou_threshold, nms_mode, group)
+            if u8:
+                boxes, counts, status = ydist.detect_sharded(eng, x_local if n_local else None, threshold, iou_threshold, nms_mode, group, u8=True)
+            else:
+                boxes, counts, status = ydist.detect_sharded(eng, x_local if n_local else None, threshold, iou_threshold, nms_mode, group)
             keep = [r * eng.max_batch + i for r in range(world) for i in range(per)][:n]     # slot of global image g
             status = status.cpu().numpy().reshape(-1)[keep]
             self.last_status = status
             engine.check_status(status)
             lists = ydist.records_to_lists(boxes, counts)
             return base.boxes_from_records([lists[k] for k in keep])
-        boxes, counts, status = eng.detect(x_local, threshold, iou_threshold, nms_mode)
+        boxes, counts, status = (eng.detect_u8 if u8 else eng.detect)(x_local, threshold, iou_threshold, nms_mode)
         records, self.last_status = engine.records_to_host(boxes, counts, status)
         return base.boxes_from_records(records)
 
     def forward(self, x_batch):
         """Head logits as a NumPy float32 array in the reference's layout (what sess.run returns)."""
         return self.net.engine.forward(x_batch).cpu().numpy()
+
+    def forward_u8(self, x_batch_u8):
+        """forward() for a uint8 batch (0..255): the same array as forward(float32(x_batch_u8 / 255.))."""
+        return self.net.engine.forward_u8(x_batch_u8).cpu().numpy()
 
     # ---- TEST mode --------------------------------------------------------------------------------
     def test(self, params):
@@ -162,8 +179,11 @@ class Yolo(object):
         self.timing = {"images": len(image_paths), "batch_size": batch_size}      # (seconds per stage of the loop: tools/e2e_launcher.py)
         if world == 1 and not pillow and str(params.get("pipeline", "true")).lower() == "true":
             self.timing["mode"] = "pipelined"
+            # (new optional key `staging`: "u8" keeps the resized batch as 8-bit pixels on the device and runs yolo_net_detect_u8 -- same
+            # files, a quarter of the staging memory; "f32", the default until tools/e2e_launcher.py has timed both, the float32 batch)
             self._test_pipelined(image_paths, out_dir, batch_size, input_shape, threshold, iou_threshold, nms_mode, class_names,
-                                 workers=int(params.get("workers", 0)), timings=self.timing)
+                                 workers=int(params.get("workers", 0)), timings=self.timing,
+                                 staging=str(params.get("staging", "f32")).lower())
             self.timing["loop_s"] = time.perf_counter() - t_loop
             print("Done")
             return
@@ -194,12 +214,13 @@ class Yolo(object):
             print("Done")
 
     def _test_pipelined(self, image_paths, out_dir, batch_size, input_shape, threshold, iou_threshold, nms_mode, class_names, workers=0,
-                        timings=None):
+                        timings=None, staging="f32"):
         """The body of the reference's test loop (net/yolo.py:80-95) as a pipeline over batches:
 
             worker threads   decode_image() of the files of batch i + 1 (Pillow releases the GIL inside its codecs)
             this thread      batch i: uint8 pixels -> pinned staging -> device (async), yolo_preprocess_resize of every image
-                             straight into the batch tensor, yolo_net_detect, async copy of the record buffer
+                             straight into the batch tensor, yolo_net_detect (staging = "u8": a uint8 batch tensor through
+                             yolo_preprocess_resize_u8 / yolo_net_detect_u8, same records), async copy of the record buffer
                              [counts | status | boxes] to pinned memory + an event -- nothing here waits for the GPU
             worker PROCESSES batch i - 1, once its event has fired: records -> BoundingBox lists, draw_boxes on the pixels
                              already decoded (no second read of the file), encode + write `<stem>_out<ext>`
@@ -234,7 +255,13 @@ class Yolo(object):
         decode = lambda paths: [pool.submit(base.decode_image, p) for p in paths]
         stream = torch.cuda.current_stream(torch_dev)
         # two sets of per-batch resources, used alternately: batch i + 1 is prepared while batch i's records are still in flight
-        x_dev = [torch.empty((batch_size, h, w, c), dtype=torch.float32, device=torch_dev) for _ in range(2)]
+        if staging not in ("u8", "f32"):
+            raise ValueError("staging must be u8 or f32, got %r" % (staging,))
+        u8 = staging == "u8"
+        t["staging"] = staging
+        resize = lib.yolo_preprocess_resize_u8 if u8 else lib.yolo_preprocess_resize
+        resize_name = "yolo_preprocess_resize_u8" if u8 else "yolo_preprocess_resize"
+        x_dev = [torch.empty((batch_size, h, w, c), dtype=torch.uint8 if u8 else torch.float32, device=torch_dev) for _ in range(2)]
         rec_host = [torch.empty(ydist.record_words(eng.max_batch, eng.max_boxes), dtype=torch.int32).pin_memory() for _ in range(2)]
         stage_host, stage_dev = [None, None], [None, None]
         events = [torch.cuda.Event() for _ in range(2)]
@@ -297,11 +324,10 @@ class Yolo(object):
             stage_dev[slot][:off].copy_(stage_host[slot][:off], non_blocking=True)
             x = x_dev[slot][:len(paths)]
             for i, (o, ih, iw) in enumerate(spans):
-                _hip.check(lib.yolo_preprocess_resize(stage_dev[slot].data_ptr() + o, ih, iw, iw * 3, x[i].data_ptr(), h, w, 0,
-                                                      stream.cuda_stream), "yolo_preprocess_resize")
+                _hip.check(resize(stage_dev[slot].data_ptr() + o, ih, iw, iw * 3, x[i].data_ptr(), h, w, 0, stream.cuda_stream), resize_name)
             t["upload_resize_enqueue"] += time.perf_counter() - t0
             t0 = time.perf_counter()
-            eng.detect(x, threshold, iou_threshold, nms_mode)
+            (eng.detect_u8 if u8 else eng.detect)(x, threshold, iou_threshold, nms_mode)
             rec_host[slot].copy_(eng.records, non_blocking=True)
             events[slot].record(stream)
             t["detect_enqueue"] += time.perf_counter() - t0

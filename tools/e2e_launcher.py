@@ -65,11 +65,13 @@ def main():
             wpath = os.path.join(tmp, "%s.weights" % kind)
             base.write_darknet_weights(wpath, w, kind)
             for ext in ("jpg", "png"):
-                for pipeline in (False, True):
-                    out_dir = os.path.join(tmp, "out_%s_%s_%s_%d" % (kind, dtype, ext, pipeline))
+                for pipeline, staging in ((False, None), (True, "f32"), (True, "u8")):      # the pipeline with float32 and with uint8 batch tensors
+                    out_dir = os.path.join(tmp, "out_%s_%s_%s_%d_%s" % (kind, dtype, ext, pipeline, staging))
                     params = dict(image_dir=dirs[ext], out_dir=out_dir, batch_size=batch, threshold=0.5, iou_threshold=0.6, anchors=anchors,
                                   class_names=names, input_h=size, input_w=size, input_c=3, checkpoint_path="",
                                   pretrained_weights_path=wpath, cpu_only="False", dtype=dtype, pipeline=str(pipeline), version=kind)
+                    if staging:
+                        params["staging"] = staging
                     yolo = launcher.pick_model(kind)
                     buf = io.StringIO()
                     t0 = time.perf_counter()
@@ -79,7 +81,7 @@ def main():
                     lines = [l for l in buf.getvalue().splitlines() if ": Found " in l]
                     assert len(lines) == args.images and len(os.listdir(out_dir)) == args.images
                     t = dict(yolo.timing)
-                    row = {"net": "%s-%d-%s-b%d" % (kind, size, dtype, batch), "files": ext, "pipeline": pipeline, "images": args.images,
+                    row = {"net": "%s-%d-%s-b%d" % (kind, size, dtype, batch), "files": ext, "pipeline": pipeline, "staging": staging, "images": args.images,
                            "loop_s": round(t.pop("loop_s"), 3), "images_per_s": round(args.images / yolo.timing["loop_s"], 1),
                            "boxes_found": sum(int(l.split("Found ")[1].split(" ")[0]) for l in lines),
                            "wall_incl_build_s": round(wall, 2), "lines_digest": hash(tuple(sorted(l.split(" Saved to ")[0] for l in lines))) & 0xffffffff,
