@@ -51,7 +51,7 @@ enum yolo_status {
 enum yolo_op {
     YOLO_OP_INPUT = 0,      /* layers.py:106-109 input_layer     (h, w, c)                       */
     YOLO_OP_CONV = 1,       /* layers.py:17-67   conv2d_bn_act   (filters,ksize,stride,bn,leaky) */
-    YOLO_OP_MAXPOOL = 2,    /* layers.py:70-81   max_pool2d      (ksize, stride)                 */
+    YOLO_OP_MAXPOOL = 2,    /* layers.py:70-81   max_pool2d      (ksize 2, stride 1|2; or odd ksize 3..13, stride 1: SAME) */
     YOLO_OP_ROUTE = 3,      /* layers.py:84-87   route           (src[0..n_src))                 */
     YOLO_OP_REORG = 4,      /* layers.py:90-97   reorg           (stride)                        */
     YOLO_OP_SHORTCUT = 5,   /* layers.py:100-103 shortcut        (src[0] = prev, src[1] = skip)  */
@@ -226,7 +226,7 @@ int yolo_net_detect_u8(yolo_net *net, const uint8_t *in_dev, int batch, double t
 /* Per-kernel facts for roofline accounting (bench.py): algorithmic work of ONE image.  Always the plan of the float32 entry points
  * (input bytes counted as float32, float32 kernel symbols), also for a net that is only ever fed uint8. */
 typedef struct yolo_kernel_info {
-    int32_t kind;               /* 0 prep, 1 conv, 2 maxpool, 3 eltwise                         */
+    int32_t kind;               /* 0 prep, 1 conv, 2 maxpool (incl. the fused SPP block: one read, three writes), 3 eltwise */
     int32_t layer;              /* reference layer index the kernel materialises                 */
     int32_t variant;            /* conv: cout-tile config (0 N128, 1 N64, 2 N32) + 4*perchunk    */
     int32_t ksize, stride, cin, cout, out_h, out_w;

@@ -715,6 +715,20 @@ int run_forward_pass(yolo_net *net, const NetIn in, int batch, float *out_dev, h
             break;
         }
         case K_POOL: {
+            if (k.spp) {        // the three pools of an SPP block in one launch
+                SppParams p;
+                memset(&p, 0, sizeof p);
+                p.in = P.view_ptr(k.in);
+                p.H = k.in.H; p.W = k.in.W; p.chunks = k.in.C / 8;
+                p.in_ld = k.in.ld; p.in_img_stride = k.in.img_stride;
+                const View *ov[3] = {&k.out, &k.out2, &k.out3};
+                for (int l = 0; l < 3; ++l) {
+                    p.out[l] = P.view_ptr(*ov[l]);
+                    p.out_ld[l] = ov[l]->ld; p.out_img_stride[l] = ov[l]->img_stride;
+                }
+                e = launch_spp(p, (k.pool_k - 1) / 2, batch, s);
+                break;
+            }
             PoolParams p;
             p.in = P.view_ptr(k.in);
             p.out = P.view_ptr(k.out);
@@ -722,7 +736,8 @@ int run_forward_pass(yolo_net *net, const NetIn in, int batch, float *out_dev, h
             p.Ho = k.out.H; p.Wo = k.out.W; p.out_ld = k.out.ld; p.stride = k.pool_stride;
             p.in_img_stride = k.in.img_stride; p.out_img_stride = k.out.img_stride;
             p.total = (long long)batch * k.out.H * k.out.W;
-            e = launch_pool(p, dtype, s);
+            p.ksize = k.pool_k;
+            e = k.pool_k == 2 ? launch_pool(p, dtype, s) : launch_pool_same(p, dtype, s);
             break;
         }
         case K_ELTWISE: {
@@ -1085,6 +1100,16 @@ int yolo_net_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out)
         const bool vec = k.kind == K_POOL && k.in.C % epc == 0 && k.in.ld % epc == 0 && k.out.ld % epc == 0 && (k.in.base + k.in.coff) % epc == 0 &&
                          (k.out.base + k.out.coff) % epc == 0 && k.in.img_stride % epc == 0 && k.out.img_stride % epc == 0;
         set_symbol(aux_symbol(k.kind, net->opt.dtype, vec));
+        if (k.kind == K_POOL && k.spp) {        // one read, three writes
+            out->ksize = k.pool_k; out->stride = 1;
+            out->bytes += elems(k.out2) * esz(k.out2) + elems(k.out3) * esz(k.out3);
+            snprintf(out->name, sizeof out->name, "spp_pool<%s,%d-%d-%d>", t, k.pool_k, 2 * k.pool_k - 1, 3 * k.pool_k - 2);
+            set_symbol(spp_pool_symbol((k.pool_k - 1) / 2));
+        } else if (k.kind == K_POOL && k.pool_k != 2) {
+            out->ksize = k.pool_k; out->stride = 1;
+            snprintf(out->name, sizeof out->name, "pool_same<%s,%dx%d>", t, k.pool_k, k.pool_k);
+            set_symbol(pool_same_symbol(net->opt.dtype, vec));
+        }
     }
     return YOLO_OK;
 }

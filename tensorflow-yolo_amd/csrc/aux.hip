@@ -1,4 +1,4 @@
-// Bandwidth kernels around the conv stack: input cast/pad, max-pool, and the generic strided
+// Bandwidth kernels around the conv stack: input cast/pad, max-pool (2x2, general stride-1 SAME, fused SPP block), and the generic strided
 // element-wise fallback (standalone shortcut / upsample / reorg / concat-copy / f32 convert) the
 // planner uses when a fusion into a conv epilogue is not possible.
 #include "yolo_internal.h"
@@ -90,6 +90,130 @@ __global__ void __launch_bounds__(256) pool_kernel(const PoolParams p) {
         } else {
             o[0] = (T)best[0];
         }
+    }
+}
+
+// net/layers.py:70-81 at stride 1 with an ODD window (tf.layers.max_pooling2d, padding="SAME"): the window [i - r, i + r], r = (k - 1) / 2,
+// clipped to the map -- padding never takes part, an all-negative map stays negative.  The plain form: one thread per (pixel, 16-byte
+// channel chunk), k x k loads each; any view, scalar when a stride is not chunk-aligned.  The SPP block of YOLOv3-SPP runs spp_pool_kernel
+// below where it applies and three launches of this one where it does not (float32 nets, maps above 32 x 32, unaligned views).
+template <bool F32, bool VEC>
+__global__ void __launch_bounds__(256) pool_same_kernel(const PoolParams p) {
+    typedef typename std::conditional<F32, float, _Float16>::type T;
+    constexpr int EPC = 16 / (int)sizeof(T);
+    constexpr int STEP = VEC ? EPC : 1;
+    const int cchunks = (p.C + STEP - 1) / STEP;
+    const int r = p.ksize >> 1;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < p.total; w += stride) {
+        const int cc = (int)(w % cchunks);
+        long long t = w / cchunks;
+        const int ox = (int)(t % p.W); t /= p.W;
+        const int oy = (int)(t % p.H);
+        const long long n = t / p.H;
+        const int y0 = oy - r < 0 ? 0 : oy - r, y1 = oy + r > p.H - 1 ? p.H - 1 : oy + r;
+        const int x0 = ox - r < 0 ? 0 : ox - r, x1 = ox + r > p.W - 1 ? p.W - 1 : ox + r;
+        float best[STEP];
+#pragma unroll
+        for (int e = 0; e < STEP; ++e) best[e] = -INFINITY;
+        const T *base = reinterpret_cast<const T *>(p.in) + n * p.in_img_stride + cc * STEP;
+        for (int y = y0; y <= y1; ++y)
+            for (int x = x0; x <= x1; ++x) {
+                const T *q = base + ((long long)y * p.W + x) * p.in_ld;
+                if (VEC) {
+                    const uint4v u = *reinterpret_cast<const uint4v *>(q);
+                    T tv[EPC];
+                    __builtin_memcpy(tv, &u, 16);
+#pragma unroll
+                    for (int e = 0; e < STEP; ++e) best[e] = fmaxf(best[e], (float)tv[e]);
+                } else {
+                    best[0] = fmaxf(best[0], (float)q[0]);
+                }
+            }
+        T *o = reinterpret_cast<T *>(p.out) + n * p.out_img_stride + ((long long)oy * p.W + ox) * p.out_ld + cc * STEP;
+        if (VEC) {
+            T tv[EPC];
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) tv[e] = (T)best[e];
+            uint4v u;
+            __builtin_memcpy(&u, tv, 16);
+            *reinterpret_cast<uint4v *>(o) = u;
+        } else {
+            o[0] = (T)best[0];
+        }
+    }
+}
+
+// max of eight fp16 values at a time: four packed instructions (max never rounds: the result is bit-exact whatever the order)
+__device__ __forceinline__ uint4v pk_max8(const uint4v a, const uint4v b) {
+    uint4v r;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_pk_max_f16 %0, %1, %2" : "=v"(r.x) : "v"(a.x), "v"(b.x));
+    asm("v_pk_max_f16 %0, %1, %2" : "=v"(r.y) : "v"(a.y), "v"(b.y));
+    asm("v_pk_max_f16 %0, %1, %2" : "=v"(r.z) : "v"(a.z), "v"(b.z));
+    asm("v_pk_max_f16 %0, %1, %2" : "=v"(r.w) : "v"(a.w), "v"(b.w));
+#else
+    r = a; (void)b;
+#endif
+    return r;
+}
+
+// The SPP block of YOLOv3-SPP (Darknet yolov3-spp.cfg: max-pools 5, 9 and 13 at stride 1 of one 512-channel tensor x, concatenated with x)
+// as ONE launch: x is read once, the three pooled tensors are written once -- 4 tensor passes over HBM where three pool launches make 6.
+//   * a workgroup owns one image x `slab` 16-byte channel chunks and keeps the H x W plane of each in LDS, twice (A, B): item i = pixel *
+//     slab + chunk, 16 bytes each, consecutive lanes on consecutive 16-byte words in every pass (ds_read_b128 / ds_write_b128 without
+//     bank conflicts: a shifted window is the same contiguous run of words);
+//   * pools are separable (a row pass A -> B, a column pass B -> A) and they cascade: with windows clipped to the map and no padding
+//     value, pool(4r+1) = pool(2r+1) o pool(2r+1) and pool(6r+1) = pool(2r+1) o pool(4r+1) exactly, because max is associative and idempotent
+//     (the clipped window of a clipped window is the clipped wider window) -- so each level is 2 x (2r+1) LDS reads per item, 12r + 6 in all
+//     against (6r+1)^2 + ... loads of the plain form;
+//   * every level's column pass also stores the level's tensor: 16-byte stores into its own view (ld / coff / image stride: a channel
+//     slice of the concat buffer or a tensor of its own).  Lanes whose chunk lies beyond C (last slab) load and store nothing.
+// LDS: 2 x H W slab x 16 bytes <= 64 KiB (launch_spp picks slab); maps up to kSppMaxSide square.
+template <int RAD>
+__global__ void __launch_bounds__(256) spp_pool_kernel(const SppParams p) {
+    extern __shared__ uint4v spp_lds[];
+    const int n = blockIdx.y;
+    const int sh = p.slab_shift;
+    const int chunk0 = (int)blockIdx.x << sh;
+    const int items = (p.H * p.W) << sh;
+    const int row = p.W << sh;              // items per map row
+    uint4v *A = spp_lds, *B = spp_lds + items;
+    const _Float16 *in = reinterpret_cast<const _Float16 *>(p.in) + (long long)n * p.in_img_stride + chunk0 * 8;
+    for (int i = threadIdx.x; i < items; i += 256) {
+        const int s = i & (p.slab - 1), px = i >> sh;
+        if (chunk0 + s < p.chunks) A[i] = *reinterpret_cast<const uint4v *>(in + (long long)px * p.in_ld + s * 8);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int lvl = 0; lvl < 3; ++lvl) {
+        for (int i = threadIdx.x; i < items; i += 256) {        // row pass
+            const int px = i >> sh;
+            const int x = px - (int)fdiv((uint32_t)px, p.dW) * p.W;
+            uint4v v = A[i];
+#pragma unroll
+            for (int d = 1; d <= RAD; ++d) {
+                if (x - d >= 0) v = pk_max8(v, A[i - (d << sh)]);
+                if (x + d < p.W) v = pk_max8(v, A[i + (d << sh)]);
+            }
+            B[i] = v;
+        }
+        __syncthreads();
+        _Float16 *out = reinterpret_cast<_Float16 *>(p.out[lvl]) + (long long)n * p.out_img_stride[lvl] + chunk0 * 8;
+        const int out_ld = p.out_ld[lvl];
+        for (int i = threadIdx.x; i < items; i += 256) {        // column pass + the level's tensor
+            const int s = i & (p.slab - 1), px = i >> sh;
+            const int y = (int)fdiv((uint32_t)px, p.dW);
+            uint4v v = B[i];
+#pragma unroll
+            for (int d = 1; d <= RAD; ++d) {
+                if (y - d >= 0) v = pk_max8(v, B[i - d * row]);
+                if (y + d < p.H) v = pk_max8(v, B[i + d * row]);
+            }
+            if (lvl < 2) A[i] = v;
+            if (chunk0 + s < p.chunks) *reinterpret_cast<uint4v *>(out + (long long)px * out_ld + s * 8) = v;
+        }
+        if (lvl < 2) __syncthreads();
     }
 }
 
@@ -223,6 +347,55 @@ hipError_t launch_pool(const PoolParams &p0, int dtype, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_pool_same(const PoolParams &p0, int dtype, hipStream_t s) {
+    PoolParams p = p0;
+    if (p.ksize < 3 || p.ksize > 13 || !(p.ksize & 1) || p.Ho != p.H || p.Wo != p.W) return hipErrorInvalidValue;
+    const int epc = dtype == YOLO_DTYPE_F16 ? 8 : 4;
+    const bool vec = (p.C % epc == 0) && (p.in_ld % epc == 0) && (p.out_ld % epc == 0) &&
+                     ((uintptr_t)p.in % 16 == 0) && ((uintptr_t)p.out % 16 == 0) &&
+                     (p.in_img_stride % epc == 0) && (p.out_img_stride % epc == 0);
+    const long long pix = p.total;      // caller passes B*H*W
+    p.total = pix * (vec ? p.C / epc : p.C);
+    const dim3 g(grid_for(p.total)), b(256);
+    if (dtype == YOLO_DTYPE_F16) {
+        if (vec) hipLaunchKernelGGL((pool_same_kernel<false, true>), g, b, 0, s, p);
+        else hipLaunchKernelGGL((pool_same_kernel<false, false>), g, b, 0, s, p);
+    } else {
+        if (vec) hipLaunchKernelGGL((pool_same_kernel<true, true>), g, b, 0, s, p);
+        else hipLaunchKernelGGL((pool_same_kernel<true, false>), g, b, 0, s, p);
+    }
+    return hipGetLastError();
+}
+
+// 16-byte channel chunks per workgroup of spp_pool_kernel: as many as two copies of their planes fit 64 KiB of LDS, up to 8 (a 128-byte
+// line per pixel), fewer while the launch would leave most CUs without a workgroup
+int spp_slab(int H, int W, int chunks, int batch) {
+    int slab = 8;
+    while (slab > 1 && (long long)H * W * slab * 32 > 65536) slab >>= 1;
+    while (slab > 1 && slab / 2 >= chunks) slab >>= 1;
+    while (slab > 1 && (long long)batch * ((chunks + slab - 1) / slab) < 256) slab >>= 1;
+    return slab;
+}
+
+hipError_t launch_spp(const SppParams &p0, int rad, int batch, hipStream_t s) {
+    SppParams p = p0;
+    if (p.H < 1 || p.W < 1 || p.H > kSppMaxSide || p.W > kSppMaxSide || p.chunks < 1 || batch < 1 || batch > 65535 || (rad != 1 && rad != 2))
+        return hipErrorInvalidValue;
+    if (p.in_ld % 8 || p.in_img_stride % 8 || (uintptr_t)p.in % 16) return hipErrorInvalidValue;
+    for (int l = 0; l < 3; ++l)
+        if (!p.out[l] || p.out_ld[l] % 8 || p.out_img_stride[l] % 8 || (uintptr_t)p.out[l] % 16) return hipErrorInvalidValue;
+    p.slab = spp_slab(p.H, p.W, p.chunks, batch);
+    p.slab_shift = p.slab == 8 ? 3 : p.slab == 4 ? 2 : p.slab == 2 ? 1 : 0;
+    p.slabs = (p.chunks + p.slab - 1) / p.slab;
+    p.dW = make_fastdiv((uint32_t)p.W);
+    const size_t lds = (size_t)p.H * p.W * p.slab * 32;
+    if (lds > 65536) return hipErrorInvalidValue;
+    const dim3 g((unsigned)p.slabs, (unsigned)batch), b(256);
+    if (rad == 1) hipLaunchKernelGGL(spp_pool_kernel<1>, g, b, lds, s, p);
+    else hipLaunchKernelGGL(spp_pool_kernel<2>, g, b, lds, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_eltwise(const EltParams &p, int dtype, hipStream_t s) {
     const dim3 g(grid_for(p.total)), b(256);
     if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(eltwise_kernel<false>, g, b, 0, s, p);
@@ -306,5 +479,9 @@ std::string aux_symbol(int kind, int dtype, bool vec) {
     if (kind == K_POOL) return std::string("void yolo::pool_kernel<") + f + ", " + (vec ? "true" : "false") + ">(yolo::PoolParams)";
     return std::string("void yolo::eltwise_kernel<") + f + ">(yolo::EltParams)";
 }
+std::string pool_same_symbol(int dtype, bool vec) {
+    return std::string("void yolo::pool_same_kernel<") + (dtype == YOLO_DTYPE_F16 ? "false" : "true") + ", " + (vec ? "true" : "false") + ">(yolo::PoolParams)";
+}
+std::string spp_pool_symbol(int rad) { return "void yolo::spp_pool_kernel<" + std::to_string(rad) + ">(yolo::SppParams)"; }
 
 }  // namespace yolo

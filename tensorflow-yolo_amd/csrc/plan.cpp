@@ -105,8 +105,10 @@ struct Planner {
                 L[i].C = d.filters;
                 break;
             case YOLO_OP_MAXPOOL:
-                if (d.n_src != 1 || d.ksize != 2 || (d.stride != 1 && d.stride != 2))
-                    return fail(std::string(nm) + "maxpool supports ksize 2, stride 1|2");
+                // ksize 2 (stride 1 | 2), or an odd window 3..13 at stride 1 (SAME, clipped: the SPP pools)
+                if (d.n_src != 1 || !((d.ksize == 2 && (d.stride == 1 || d.stride == 2)) ||
+                                      (d.stride == 1 && (d.ksize & 1) && d.ksize >= 3 && d.ksize <= 13)))
+                    return fail(std::string(nm) + "maxpool supports ksize 2 with stride 1|2, or an odd ksize 3..13 with stride 1");
                 L[i].H = d.stride == 1 ? S(0).H : (S(0).H - 1) / 2 + 1;
                 L[i].W = d.stride == 1 ? S(0).W : (S(0).W - 1) / 2 + 1;
                 L[i].C = S(0).C;
@@ -256,6 +258,45 @@ struct Planner {
                 off += L[r].C;
             }
         }
+    }
+
+    bool chunk_aligned(const View &v) const {
+        return !v.f32 && v.C % epc == 0 && v.ld % epc == 0 && (v.base + v.coff) % epc == 0 && v.img_stride % epc == 0;
+    }
+
+    // The Darknet SPP block (yolov3-spp.cfg): three stride-1 pools of odd sizes k1 < k2 < k3 over the same tensor with k2 - 1 = 2 (k1 - 1)
+    // and k3 - 1 = 3 (k1 - 1) -- 5 / 9 / 13 -- become ONE kernel that reads the tensor once and writes all three (aux.hip:
+    // spp_pool_kernel).  Layer i is the k1 pool, k its half-made kernel (in, out set); the two wider pools are later layers of the list.
+    // Nothing is elided, so keep_all does not matter.  fp16 tensors, maps up to 32 x 32, every view 16-byte aligned; else (and under
+    // YOLO_NO_SPP_FUSE) each pool is a pool_same_kernel launch of its own.
+    bool spp_block(int i, int s, Kernel &k) {
+        const yolo_layer_desc &d = L[i].d;
+        const int r = (d.ksize - 1) / 2;
+        if (net->opt.dtype != YOLO_DTYPE_F16 || (r != 1 && r != 2) || getenv("YOLO_NO_SPP_FUSE")) return false;
+        if (L[i].H > kSppMaxSide || L[i].W > kSppMaxSide || !chunk_aligned(k.in) || !chunk_aligned(k.out)) return false;
+        int wide[2] = {-1, -1};
+        for (int j = i + 1; j < n; ++j) {
+            const yolo_layer_desc &e = L[j].d;
+            if (e.op != YOLO_OP_MAXPOOL || e.stride != 1 || resolve(e.src[0]) != s || L[j].materialised) continue;
+            for (int t = 0; t < 2; ++t)
+                if (wide[t] < 0 && e.ksize - 1 == (t + 2) * (d.ksize - 1)) wide[t] = j;
+        }
+        if (wide[0] < 0 || wide[1] < 0) return false;
+        for (int t = 0; t < 2; ++t)         // (a tensor of its own is dense, so aligned like the input; a concat slice may not be)
+            if (wide[t] == n - 1 || (has_claim[wide[t]] && !chunk_aligned(claim[wide[t]]))) return false;
+        const View v2 = out_view_for(wide[0]), v3 = out_view_for(wide[1]);
+        k.spp = 1;
+        k.out2 = v2; k.out3 = v3;
+        k.spp_layer[0] = wide[0]; k.spp_layer[1] = wide[1];
+        k.note = "fused SPP block: pools " + std::to_string(d.ksize) + " / " + std::to_string(L[wide[0]].d.ksize) + " / " +
+                 std::to_string(L[wide[1]].d.ksize) + " of one read (layers " + std::to_string(i) + ", " + std::to_string(wide[0]) + ", " +
+                 std::to_string(wide[1]) + ")";
+        if (has_claim[i] || has_claim[wide[0]] || has_claim[wide[1]]) k.note += " -> concat slices";
+        for (int t = 0; t < 2; ++t) {
+            L[wide[t]].view = t ? v3 : v2;
+            L[wide[t]].materialised = true;
+        }
+        return true;
     }
 
     View out_view_for(int key) {
@@ -473,10 +514,17 @@ struct Planner {
                         }
                     }
                 }
+                if (L[i].materialised) break;       // a wider pool of an SPP block: written by the block's fused kernel
                 Kernel k;
-                k.kind = K_POOL; k.layer = i; k.in = L[s].view; k.pool_stride = d.stride;
+                k.kind = K_POOL; k.layer = i; k.in = L[s].view; k.pool_stride = d.stride; k.pool_k = d.ksize;
                 if (k.in.f32) return fail(std::string(nm) + "maxpool cannot read a float32 head tensor");
                 k.out = out_view_for(i);
+                if (d.ksize != 2 && spp_block(i, s, k)) {
+                    net->kernels.push_back(k);
+                    L[i].view = k.out; L[i].materialised = true;
+                    break;
+                }
+                if (d.ksize != 2) k.note = "SAME max-pool " + std::to_string(d.ksize) + "x" + std::to_string(d.ksize) + "/1" + (has_claim[i] ? " -> concat slice" : "");
                 if (k.out.f32) {    // final layer: pool into T, then convert
                     View t = alloc_view(L[i].H, L[i].W, L[i].C);
                     View fin = k.out;
@@ -587,7 +635,7 @@ struct Planner {
         std::vector<Kernel> &K = net->kernels;
         const int n = (int)K.size();
         auto readers = [&](int buf) { int c = 0; for (const Kernel &k : K) c += (k.in.buf == buf) + (k.has_res && k.in2.buf == buf); return c; };
-        auto writers = [&](int buf) { int c = 0; for (const Kernel &k : K) c += k.out.buf == buf; return c; };
+        auto writers = [&](int buf) { int c = 0; for (const Kernel &k : K) c += (k.out.buf == buf) + (k.spp && k.out2.buf == buf) + (k.spp && k.out3.buf == buf); return c; };
         int id = 0;
         for (int h = 0; h + 1 < n && id < 4; ++h) {
             if (K[h].kind != K_CONV || !K[h].head || K[h].side) continue;
@@ -612,7 +660,7 @@ struct Planner {
         std::vector<Buffer> &B = net->buffers;
         std::vector<Kernel> &K = net->kernels;
         for (int k = 0; k < (int)K.size(); ++k) {
-            for (const View *v : {&K[k].in, &K[k].in2, &K[k].out}) {
+            for (const View *v : {&K[k].in, &K[k].in2, &K[k].out, &K[k].out2, &K[k].out3}) {
                 if (v->buf < 0) continue;
                 B[v->buf].first = std::min(B[v->buf].first, k);
                 B[v->buf].last = std::max(B[v->buf].last, K[k].side ? (int)K.size() - 1 : k);      // (a branch tail's tensors: to the end of the pass)
@@ -893,7 +941,8 @@ std::string describe(const yolo_net *net) {
       << net->act_bytes << " B; workspace " << net->workspace_bytes << " B; GFLOP/image " << net->flops_per_image * 1e-9 << "\n";
     int idx = 0;
     for (const Kernel &k : net->kernels) {
-        o << "  [" << idx++ << "] " << kind_name(k.kind) << " layer " << k.layer;
+        o << "  [" << idx++ << "] " << (k.kind == K_POOL && k.spp ? "spp_pool" : k.kind == K_POOL && k.pool_k != 2 ? "pool_same" : kind_name(k.kind))
+          << " layer " << k.layer;
         if (k.kind == K_CONV)
             o << " (conv@" << k.src_layer << ") " << k.ksize << "x" << k.ksize << "/" << k.stride << " " << k.cin << "->" << k.cout
               << " cfg=N" << (k.cfg == CFG_N128 ? 128 : k.cfg == CFG_N64 ? 64 : 32) << (k.perchunk ? " perchunk" : "")
@@ -901,6 +950,9 @@ std::string describe(const yolo_net *net) {
         o << " in=b" << k.in.buf << "[" << k.in.H << "x" << k.in.W << "x" << k.in.C << " ld" << k.in.ld << "+" << k.in.coff << "]";
         o << " out=b" << k.out.buf << "[" << k.out.H << "x" << k.out.W << "x" << k.out.C << " ld" << k.out.ld << "+" << k.out.coff
           << (k.out.f32 ? " f32" : "") << "]";
+        if (k.spp)
+            for (const View *v : {&k.out2, &k.out3})
+                o << " out=b" << v->buf << "[" << v->H << "x" << v->W << "x" << v->C << " ld" << v->ld << "+" << v->coff << "]";
         if (!k.note.empty()) o << " " << k.note;
         if (k.mx) o << " [mx: e4m3 x e4m3, block-scaled]";
         o << "\n";

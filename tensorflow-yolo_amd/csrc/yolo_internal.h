@@ -222,6 +222,18 @@ struct PoolParams {            // net/layers.py:70-81
     int H, W, C, in_ld, Ho, Wo, out_ld, stride;
     long long in_img_stride, out_img_stride;
     long long total;           // B*Ho*Wo*(C/EPC) work items
+    int ksize = 2;             // pool_same_kernel: odd window size (stride 1, SAME); pool_kernel is the 2x2 window whatever this says
+};
+
+struct SppParams {             // aux.hip: spp_pool_kernel -- the three stride-1 SAME pools of an SPP block (windows 2r+1, 4r+1, 6r+1) of one fp16 tensor
+    const void *in;            // element pointers incl. view base / coff; every stride a multiple of the 16-byte chunk
+    void *out[3];              // smallest window first
+    int H, W, chunks;          // chunks = C / 8
+    int in_ld, out_ld[3];
+    long long in_img_stride, out_img_stride[3];
+    int slab, slab_shift;      // 16-byte channel chunks a workgroup owns (power of two) and its log2 (set by launch_spp)
+    int slabs;                 // workgroups per image
+    FastDiv dW;
 };
 
 struct EltParams {             // generic fallback: out[map(p)] = a[p] (+ b[p]); scalar, any view
@@ -322,6 +334,8 @@ std::string conv_symbol(int dtype, int cfg, bool perchunk, bool f32_emu = false)
 bool conv_f32_emu_rule(int f32_products, int dtype, const ConvParams &p, int cfg, bool perchunk, int ksplit);
 std::string first_symbol(int dtype, int cout, bool pool);
 std::string aux_symbol(int kind, int dtype, bool vec);
+std::string pool_same_symbol(int dtype, bool vec);
+std::string spp_pool_symbol(int rad);
 int dma_num_cfgs();
 int dma_cfg_na(int cfg);
 int dma_cfg_nb(int cfg);
@@ -335,6 +349,10 @@ hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8 = fal
 hipError_t launch_first(const FirstParams &p, int dtype, hipStream_t s, bool in_u8 = false);
 hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = 512, bool in_u8 = false);     // stem.hip
 hipError_t launch_pool(const PoolParams &p, int dtype, hipStream_t s);
+hipError_t launch_pool_same(const PoolParams &p, int dtype, hipStream_t s);     // stride 1, SAME, odd window PoolParams.ksize
+constexpr int kSppMaxSide = 32;         // spp_pool_kernel: the H x W plane of a chunk lives in LDS twice (2 x 16 KiB at 32 x 32)
+hipError_t launch_spp(const SppParams &p, int rad, int batch, hipStream_t s);   // p.H, p.W <= kSppMaxSide; windows 2 rad + 1, 4 rad + 1, 6 rad + 1 (rad 1 | 2)
+int spp_slab(int H, int W, int chunks, int batch);                              // chunks per workgroup launch_spp picks
 hipError_t launch_eltwise(const EltParams &p, int dtype, hipStream_t s);
 hipError_t launch_decode(const DecodeParams &p, int batch, hipStream_t s, bool zero_counts = true);
 hipError_t launch_nms(const NmsParams &p, int batch, hipStream_t s);
@@ -366,6 +384,10 @@ struct Kernel {
     int batch_norm = 0;
     // pool
     int pool_stride = 0;
+    int pool_k = 2;            // window: 2 = pool_kernel; odd 3..13 (stride 1, SAME) = pool_same_kernel, or with `spp` the smallest window of the block
+    int spp = 0;               // 1: spp_pool_kernel -- this launch also writes the two wider pools of the SPP block into out2 / out3
+    int spp_layer[2] = {-1, -1};   // ... which materialise these layers
+    View out2, out3;
     std::string note;
 };
 

@@ -6,7 +6,7 @@ COMMON / ANCHOR / TRAIN / TEST merged as {**section, **COMMON}, relative `*_dir`
 resolved against the .ini's directory, `anchors` / `class_names` parsed as Python literals, and the
 network picked by COMMON.version.  Only `test` runs on this backend; `train` and `anchor` end with a
 clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up);
-version additionally accepts `v2-tiny`.  `--section` selects another TEST-like section (the
+version additionally accepts `v2-tiny`, `v3-tiny` and `v3-spp`.  `--section` selects another TEST-like section (the
 reference's yolo_2.ini keeps its COCO settings in [TEST_COCO], which no mode reaches there).
 """
 import argparse
@@ -42,8 +42,8 @@ def read_config(ini_path):
 
 
 def pick_model(version):
-    from .net.yolo import YoloV2, YoloV2Tiny, YoloV3
-    table = {"v2": YoloV2, "v3": YoloV3, "v2-tiny": YoloV2Tiny}
+    from .net.yolo import YoloV2, YoloV2Tiny, YoloV3, YoloV3SPP, YoloV3Tiny
+    table = {"v2": YoloV2, "v3": YoloV3, "v2-tiny": YoloV2Tiny, "v3-tiny": YoloV3Tiny, "v3-spp": YoloV3SPP}
     if version not in table:
         raise ValueError("Unsupported version: {}".format(version))
     return table[version]()

@@ -91,7 +91,9 @@ class conv2d_bn_act(_Layer):
 
 
 class max_pool2d(_Layer):
-    """Reference: net/layers.py:70-81."""
+    """Reference: net/layers.py:70-81.  The library takes kernel_size 2 (stride 1 or 2) and, at stride 1, an odd kernel_size 3..13
+    (tf.layers.max_pooling2d padding="SAME": the window clipped to the map, shape kept -- the SPP pools); anything else is refused
+    when the net is planned."""
     op = _hip.OP_MAXPOOL
 
     def __init__(self, prev, kernel_size, stride=2):

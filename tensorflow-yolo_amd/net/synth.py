@@ -21,7 +21,8 @@ from .layers import conv2d_bn_act, shortcut
 
 # per network: (head_gain, fraction of cells per anchor that pass sigmoid(obj) >= 0.5 after
 # calibrate_model) -- a realistic few dozen candidates per image (see DESIGN.md "Synthetic weights")
-HEAD_DEFAULTS = {"v3": (0.6, 0.004), "v2": (4.0, 0.08), "v2-tiny": (2.0, 0.15)}
+HEAD_DEFAULTS = {"v3": (0.6, 0.004), "v2": (4.0, 0.08), "v2-tiny": (2.0, 0.15),
+                 "v3-spp": (0.6, 0.004), "v3-tiny": (2.0, 0.02)}       # (the v3 family scores sigmoid(obj) alone: a small fraction per anchor)
 
 
 def calibrate_model(model, x_calib, fraction):

@@ -48,7 +48,7 @@ class Yolo(object):
         self.anchors, self.class_names = anchors, list(class_names)
         net = type(self).create_network(anchors, class_names, False, input_shape=tuple(input_shape))
         net.engine = engine.HipNetwork(net, dtype=dtype, max_batch=max_batch, **engine_kw)
-        if self.version != "v3":
+        if not self.version.startswith("v3"):
             h, w, _ = net[-1].out.hwc
             net.engine.set_head(engine.head_desc_v2(h, w, anchors, len(class_names)))
         if weights is not None:
@@ -362,5 +362,21 @@ class YoloV2Tiny(Yolo):
 class YoloV3(Yolo):
     version = "v3"
     create_network = staticmethod(v3.create_network)
+    load_weights = staticmethod(v3.load_weights)
+    find_bounding_boxes = staticmethod(v3.find_bounding_boxes)
+
+
+class YoloV3Tiny(Yolo):
+    """Not in the reference: upstream Darknet's yolov3-tiny.cfg (two scales); same plug points."""
+    version = "v3-tiny"
+    create_network = staticmethod(v3.create_tiny_network)
+    load_weights = staticmethod(v3.load_weights)
+    find_bounding_boxes = staticmethod(v3.find_bounding_boxes)
+
+
+class YoloV3SPP(Yolo):
+    """Not in the reference: upstream Darknet's yolov3-spp.cfg (Darknet-53 + SPP block in the coarse head); same plug points."""
+    version = "v3-spp"
+    create_network = staticmethod(v3.create_spp_network)
     load_weights = staticmethod(v3.load_weights)
     find_bounding_boxes = staticmethod(v3.find_bounding_boxes)
