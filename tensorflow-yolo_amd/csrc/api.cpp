@@ -26,15 +26,9 @@ static int fail(int code, const std::string &msg) {
 }
 
 namespace {
-// images one part of a full batch holds (what every launch of a forward pass sees at most)
-inline int part_batch(const yolo_net *net) { return (net->opt.max_batch + net->parts - 1) / net->parts; }
-const size_t kPairCounterBytes = 65536;            // in-launch pair / split-K (conv_tap.hip): one ticket per tile, a 128-byte line each (512 tiles), in front of the slabs
-
 // packed weights of a kernel; nullptr while no weights are bound (yolo_net_kernel_info / describe build launch parameters of a plan that
 // has none yet: no offset is applied to a null pointer -- found by the sanitizer build, tests/test_sanitizer.py)
 static inline const unsigned char *weights_at(const yolo_net *net, size_t off) { return net->dev_weights ? net->dev_weights + off : nullptr; }
-bool conv_tile_valid(const yolo_net *net, const Kernel &k, int tile);
-size_t splitk_slab_bytes(const yolo_net *net);
 
 // Ticket counters of the in-launch pair split: every launch returns them to zero, so they are cleared when the workspace is bound
 // and again after any failed forward (a launch that did not run may leave the forward half-way).  The memset goes to the null
@@ -43,7 +37,7 @@ int zero_pair_counters(yolo_net *net) {
     if (!net->splitk_bytes || !net->dev_ws) return YOLO_OK;
     const size_t per = net->splitk_bytes / (size_t)net->arenas;
     for (int a = 0; a < net->arenas; ++a)
-        HIP_TRY(hipMemset(net->dev_ws + net->splitk_off + (size_t)a * (per / 256 * 256), 0, per < kPairCounterBytes ? per : kPairCounterBytes));
+        HIP_TRY(hipMemset(net->dev_ws + net->splitk_off + (size_t)a * arena_slab_bytes(net), 0, per < kPairCounterBytes ? per : kPairCounterBytes));
     HIP_TRY(hipDeviceSynchronize());
     return YOLO_OK;
 }
@@ -259,56 +253,21 @@ struct Ptrs {
     unsigned char *view_ptr(const View &v) const { return buf_base(v.buf) + (size_t)(v.base + v.coff) * esz(v); }
 };
 
-// 16-byte epilogue accesses are possible when every stride of the view is chunk-aligned (planned buffers start 4096-byte aligned
-// inside a 256-byte aligned workspace; a caller-owned tensor is checked at launch)
-void conv_vec_flags(const yolo_net *net, const Kernel &k, bool out_f32, int &vec_out, int &vec_res) {
-    const int epc = net->epc;
-    const int ch = k.cfg == CFG_N32 ? 8 : 16;
-    const int oepc = out_f32 ? 4 : epc;
-    vec_out = (k.cout % ch == 0) && (k.out.ld % oepc == 0) && ((k.out.base + k.out.coff) % oepc == 0) && (k.out.img_stride % oepc == 0);
-    vec_res = k.has_res && (k.cout % ch == 0) && (k.in2.ld % epc == 0) && (k.in2.coff % epc == 0) && (k.in2.img_stride % epc == 0);
-}
-
-// conv launch parameters for one planned kernel at the given batch
+// conv launch parameters for one planned kernel at the given batch: the shape half (conv_dispatch.cpp) + pointers, the byte-limit
+// checks and the objectness block
 int make_conv_params(yolo_net *net, const Kernel &k, const Ptrs &P, int batch, ConvParams &p) {
-    const int dtype = net->opt.dtype;
-    memset(&p, 0, sizeof p);
-    const View &in = k.in;
-    const long long in_bytes = (long long)batch * in.img_stride * net->esize;
+    const long long in_bytes = (long long)batch * k.in.img_stride * net->esize;
     if (in_bytes > 0x7ffffff0LL)
         return fail(YOLO_ERR_ARG, "conv input tensor exceeds 2 GiB (32-bit buffer addressing): lower the batch");
-    p.in = P.buf_base(in.buf);
+    if ((long long)batch * net->layers[k.src_layer].H * net->layers[k.src_layer].W > 0x7fffffffLL)
+        return fail(YOLO_ERR_ARG, "too many output pixels for one launch");
+    conv_shape_params(net, k, batch, p);
+    p.in = P.buf_base(k.in.buf);
     p.in_bytes = (uint32_t)in_bytes;
     p.wgt = weights_at(net, k.w_off);
-    p.wgt_bytes = (uint32_t)k.w_bytes;
     p.bias = reinterpret_cast<const float *>(weights_at(net, k.b_off));
-    p.H = in.H; p.W = in.W; p.in_ld = in.ld; p.in_coff = in.coff; p.in_img_stride = in.img_stride;
-    const yolo_layer_desc &d = net->layers[k.src_layer].d;
-    const int Ho = net->layers[k.src_layer].H, Wo = net->layers[k.src_layer].W;
-    p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo;
-    const long long M = (long long)batch * Ho * Wo;
-    if (M > 0x7fffffffLL) return fail(YOLO_ERR_ARG, "too many output pixels for one launch");
-    p.M = (int)M;
-    p.Cout = k.cout;
     p.out = P.view_ptr(k.out);
-    p.out_ld = k.out.ld;
-    p.out_img_stride = k.out.img_stride;
-    p.out_f32 = k.out.f32 || dtype == YOLO_DTYPE_F32;
-    {   // extents for buffer-addressed epilogues (conv_tap.hip stream kernel): 0 when a tensor is not below 2 GiB
-        const long long ob = (long long)batch * k.out.img_stride * (p.out_f32 ? 4 : net->esize);
-        p.out_bytes = ob > 0 && ob <= 0x7ffffff0LL ? (uint32_t)ob : 0u;
-    }
-    p.ksize = d.ksize; p.stride = d.stride; p.pad = (d.ksize - 1) / 2; p.taps = d.ksize * d.ksize;
-    p.ktiles = k.ktiles;
-    p.tiles_per_tap = k.perchunk ? 1 : k.cpt / 8;
-    p.cin_chunks = k.cpt;
-    p.cpt_shift = k.cpt == 1 ? 0 : k.cpt == 2 ? 1 : 2;
-    p.wrow_bytes = (uint32_t)k.ktiles * 128;
-    p.leaky = k.leaky; p.outmode = k.outmode; p.has_res = k.has_res;
-    p.f32 = dtype == YOLO_DTYPE_F32;
-    int vo = 0, vr = 0;
-    conv_vec_flags(net, k, p.out_f32 != 0, vo, vr);
-    p.vec_out = vo && ((uintptr_t)P.buf_base(k.out.buf) % 16 == 0);
+    p.vec_out = p.vec_out && ((uintptr_t)P.buf_base(k.out.buf) % 16 == 0);
     if (k.head && net->obj_bytes && net->head.n_classes > 0 && !p.vec_out && p.out_f32 && k.outmode == OUT_NORMAL && !k.has_res) {
         const int width = 5 + net->head.n_classes;
         const long long base = k.out.base + k.out.coff;
@@ -319,243 +278,35 @@ int make_conv_params(yolo_net *net, const Kernel &k, const Ptrs &P, int batch, C
             p.obj_min = net->obj_min_logit;     // -inf outside yolo_net_detect: every row is written
         }
     }
-    if (k.has_res) {
-        p.res = P.view_ptr(k.in2);
-        p.res_ld = k.in2.ld;
-        p.res_img_stride = k.in2.img_stride;
-        const long long rbytes = (long long)batch * k.in2.img_stride * net->esize;
-        p.res_bytes = rbytes > 0 && rbytes <= 0x7ffffff0LL ? (uint32_t)rbytes : 0u;
-        p.vec_res = vr;
-    }
+    if (k.has_res) p.res = P.view_ptr(k.in2);
     return YOLO_OK;
 }
 
-// the LDS-DMA kernels take fp16 convs whose Cin is a multiple of 4 chunks (32 channels)
-// float32 nets: only the tap-reuse kernel (3x3/1) has a float32 instantiation besides the 4-wave kernel
-bool dma_eligible(const yolo_net *net, const Kernel &k) {
-    if (k.cpt % 4) return false;
-    return net->opt.dtype == YOLO_DTYPE_F16 || (k.ksize == 3 && k.stride == 1);
-}
-// tile 0 = the 4-wave kernel of conv.hip with the planner's cfg (always available)
-bool conv_tile_valid(const yolo_net *net, const Kernel &k, int tile) {
-    if (k.outmode == OUT_POOL2 && tile != 12 && tile != 13 && tile != 17) return false;      // the fused max-pool lives in the 16 x 16 2-D tap tiles
-    if (tile == 0) return true;
-    if (net->opt.dtype == YOLO_DTYPE_F32 && !dma_cfg_f32_ok(tile)) return false;
-    if ((tile == 18 || tile == 21 || tile == 22) && k.in.H != k.in.W) return false;     // the image-aligned tap tiles: square maps (the rules price tiles by W alone)
-    if ((tile == 20 || tile == 21 || tile == 23) && ((k.in.H & 1) || net->opt.dtype != YOLO_DTYPE_F16)) return false;      // stride 2 over parity planes: even maps, fp16
-    return dma_eligible(net, k) && dma_cfg_valid(tile, k.cout, k.cpt, true, k.ksize, k.stride, k.in.W);
-}
-
-// Split-K decision for one conv launch (0 = the 4-wave kernel with the planner's cfg, else a tap-reuse tile): when the launch
-// would leave most of the chip idle (<= 128 workgroups) and K is long, the K range is cut into `ks` splits of `ku` units
-// (conv_tap.hip: channel slices, conv.hip: K tiles) so that ~384 workgroups exist; their float32 partial sums meet in
-// splitk_reduce_kernel.  Returns 1 when the launch stays whole.
-int choose_ksplit(const Kernel &k, const ConvParams &p, int tile, size_t slab_bytes, int &ku) {
-    ku = 0;
-    if (!slab_bytes || p.M <= 0) return 1;
-    long long blocks;
-    int units, min_units;
-    if (tile == 0) {
-        const int na = k.cfg == CFG_N128 ? 128 : k.cfg == CFG_N64 ? 64 : 32, nb = k.cfg == CFG_N128 ? 128 : 256;
-        blocks = ((long long)p.M + nb - 1) / nb * ((p.Cout + na - 1) / na);
-        units = p.ktiles;
-        min_units = 2;                  // >= 64 (float32) / 128 (fp16) k per split: these launches are latency-bound, not MFMA-bound
-    } else if (dma_cfg_is_tap(tile) && dma_cfg_splitk_ok(tile)) {
-        const long long mq = (long long)(p.M / p.HoWo) * (p.H + 1) * (p.W + 1);        // padded-linear positions
-        blocks = (mq + dma_cfg_nb(tile) - 1) / dma_cfg_nb(tile) * ((p.Cout + dma_cfg_na(tile) - 1) / dma_cfg_na(tile));
-        units = p.cin_chunks >> 2;
-        min_units = 2;                  // >= 288 (float32) / 576 (fp16) k per split
-    } else {
-        return 1;
-    }
-    if (blocks > 128 || units < 2 * min_units) return 1;
-    // workgroups = blocks x ks: 512 (two per CU) when K is long enough for that many splits, else 256, else whatever K allows --
-    // a count between the two leaves some CUs with two workgroups and the rest with one, and the pairs set the time
-    const long long kmax = units / min_units < 32 ? units / min_units : 32;
-    long long ks = 512 / blocks;
-    if (ks > kmax) ks = 256 / blocks;
-    if (ks > kmax) ks = kmax;
-    const size_t cout_pad = ((size_t)p.Cout + 127) / 128 * 128;
-    // the partial sums are written and read back once: worth it while that traffic stays in the order of the weight stream the
-    // launch reads anyway (measured: YOLOv2 13x13 at batch 1, 22 MB of partials beside 38 MB of weights, 553 -> 70 us; YOLOv3 19x19
-    // at batch 8, 47 MB beside 9 MB, slower than unsplit); a few MB are always fine (L2-resident, ~2 us)
-    const size_t wbytes = (size_t)p.Cout * (size_t)p.taps * (size_t)p.cin_chunks * 16;
-    // (1x1 layers: up to 24 MB -- tiny-YOLOv2's head 1024 -> 125 at 13x13, batch 64, is 85 workgroups walking K = 1024 alone: 85 us whole,
-    // 53 us as four splits with 22 MB of partial sums)
-    // 3x3: 8 MB; 16 MB where a split still walks a long K loop -- float32 (MFMA 16x slower: YOLOv2-416 b1 104 x 104 64 -> 128 43 -> 33 us,
-    // 52 x 52 and 26 x 26 layers 40 -> 33 us, step 0.815 -> 0.757 ms) or >= 8 channel slices (YOLOv3-608 b1 38 x 38: 2 -> 4 splits, 19.6 -> 18 us);
-    // a short-K fp16 layer loses with it (76 x 76 128 -> 256 at batch 1: 15.7 -> 18.8 us)
-    const size_t small_cap = (size_t)(p.taps == 1 ? 24 : (p.f32 || units >= 8) ? 16 : 8) << 20;
-    while (ks >= 2 && ((size_t)ks * (size_t)p.M * cout_pad * 4 > slab_bytes || (size_t)ks * (size_t)p.M * cout_pad * 4 > (2 * wbytes > small_cap ? 2 * wbytes : small_cap))) --ks;
-    if (ks < 2) return 1;
-    ku = (int)((units + ks - 1) / ks);
-    return (units + ku - 1) / ku;       // every split owns at least one unit
-}
-
-// What one conv launch runs: the tile (0 = the 4-wave kernel of conv.hip with the planner's cfg, > 0 = conv_dma.hip tile id) and
-// the K split (ks = 1: whole K).  tile_req < 0: the rules of choose_dma_cfg.  One function for the launch path, the workspace
-// sizing (split-K slab) and yolo_net_kernel_info, so what is reported is what runs.
-struct ConvPick { int tile, ks, ku, pair; };
-const size_t kSplitkSlabMax = (size_t)64 << 20;     // per arena
-
-ConvPick pick_conv(const yolo_net *net, const Kernel &k, const ConvParams &p, int tile_req, size_t slab_bytes) {
-    int tile = tile_req;
-    if (!dma_eligible(net, k) || (tile > 0 && !conv_tile_valid(net, k, tile))) tile = 0;
-    else if (tile < 0) {
-        tile = choose_dma_cfg(p.M, k.cout, k.cpt, p.taps, k.has_res, true, k.stride, k.in.W, net->opt.dtype == YOLO_DTYPE_F32);
-        if (tile == 18 && !conv_tile_valid(net, k, 18)) tile = conv_tile_valid(net, k, 15) ? 15 : 8;
-        if (tile == 22 && !conv_tile_valid(net, k, 22)) tile = conv_tile_valid(net, k, 10) ? 10 : 8;
-        if ((tile == 20 || tile == 21) && !conv_tile_valid(net, k, tile)) tile = conv_tile_valid(net, k, 20) ? 20 : conv_tile_valid(net, k, 5) ? 5 : 0;
-        if (tile == 23 && !conv_tile_valid(net, k, 23)) tile = conv_tile_valid(net, k, 6) ? 6 : 0;
-    }
-    // A launch for the in-launch pair on a WIDE tile (64-128 tiles of 128 x 256, or of the image-aligned 128 x 192: half the weight
-    // bytes per flop of the 128 x 128 tile) is not split any other way.
-    static const bool no_pair_w = getenv("YOLO_NO_PAIR_SPLIT") != nullptr;
-    bool wide_pair = false;
-    if (tile > 0 && dma_cfg_is_tap(tile) && !no_pair_w && tile_req <= 0 && !p.f32 && (p.cin_chunks >> 2) >= 8 && p.HoWo > 0) {
-        const long long mq = (long long)(p.M / p.HoWo) * (p.H + 1) * (p.W + 1);
-        const long long ct = (p.Cout + 127) / 128;
-        const long long b8 = (mq + 255) / 256 * ct, b22 = (long long)(p.M / p.HoWo) * ct;
-        wide_pair = (conv_tile_valid(net, k, 22) && b22 >= 64 && b22 <= 128 && (size_t)b22 * 2 * 98304 <= slab_bytes) ||
-                    (conv_tile_valid(net, k, 8) && b8 >= 64 && b8 <= 128 && (size_t)b8 * 2 * 131072 <= slab_bytes);
-    }
-    int ku = 0;
-    int ks = wide_pair ? 1 : choose_ksplit(k, p, tile, slab_bytes, ku);
-    // a 3x3/1 layer small enough for split-K runs it on the 128 x 128 tap tile (the one with the split-K instantiation), whatever
-    // tile the cost model would pick for the whole-K launch
-    // (an explicitly requested tile -- force_tile, an autotune candidate -- runs as requested)
-    if (ks <= 1 && !wide_pair && tile_req <= 0 && tile > 0 && dma_cfg_is_tap(tile) && tile != 11 && conv_tile_valid(net, k, 11)) {
-        int ku11 = 0;
-        const int ks11 = choose_ksplit(k, p, 11, slab_bytes, ku11);
-        if (ks11 > 1) { tile = 11; ks = ks11; ku = ku11; }
-    }
-    // 129-256 tiles of 128 x 128 (13 x 13 / 19 x 19 maps at batch 8-32) with a long K: every workgroup would run ALONE on its CU at
-    // 0.6 of the rate a pair reaches (block trace, profiles/r03_ablation.md).  K in two halves inside ONE launch (conv_tap.hip):
-    // two co-resident half-K workgroups per tile, the second arriver sums -- no reduce kernel, 2 x 64 KiB of slab per tile.
-    int pair = 0;
-    static const bool no_pair = getenv("YOLO_NO_PAIR_SPLIT") != nullptr;       // A/B switch (read once; results unchanged up to summation order)
-    // (an explicitly requested tile -- force_tile, an autotune candidate -- runs as requested: the hook must time and test the tile it names)
-    if (ks <= 1 && tile > 0 && dma_cfg_is_tap(tile) && !no_pair && tile_req <= 0) {
-        const long long mq = (long long)(p.M / p.HoWo) * (p.H + 1) * (p.W + 1);
-        const int units = p.cin_chunks >> 2;
-        const long long ct = (p.Cout + 127) / 128;
-        // the 128 x 256 tile first (fp16): per CU the K loop of the 128 x 128 tile is bound by the LDS-DMA path (8 KiB of weights
-        // per tap for 1 MFLOP: two half-K workgroups on a CU were measured no faster than one whole-K one), the wider tile halves
-        // the weight bytes per flop
-        const long long b8 = (mq + 255) / 256 * ct, b11 = (mq + 127) / 128 * ct;
-        const long long b22 = (long long)(p.M / p.HoWo) * ct;        // image-aligned 128 x 192 tile: a tile per image and cout tile
-        // (that instantiation is built for ONE workgroup per CU -- it needs 180 registers --, so at most 128 tiles = 256 half-K workgroups:
-        // 26 x 26 at batch 16 = 184 tiles ran 48 us as 368 halves against 33 us whole)
-        // (12 x 12 / 13 x 13 maps: one image per 192-position tile -- 5 % padding where 256-position tiles of the padded-linear grid
-        // compute 23 %, and 16 images x 8 cout tiles x 2 halves are exactly 256 workgroups: YOLOv2-416 b16 13 x 13 layers -25 %)
-        if (units >= 8 && !p.f32 && conv_tile_valid(net, k, 22) && b22 >= 64 && b22 <= 128 && (size_t)b22 * 2 * 98304 <= slab_bytes) {
-            tile = 22; ks = 2; ku = (units + 1) / 2; pair = 1;
-        } else if (units >= 8 && !p.f32 && conv_tile_valid(net, k, 8) && b8 >= 64 && b8 <= 128 && (size_t)b8 * 2 * 131072 <= slab_bytes) {
-            tile = 8; ks = 2; ku = (units + 1) / 2; pair = 1;
-        } else if (units >= 8 && conv_tile_valid(net, k, 11) && b11 > 128 && b11 <= 256 && (size_t)b11 * 2 * 65536 <= slab_bytes) {
-            tile = 11; ks = 2; ku = (units + 1) / 2; pair = 1;
-        }
-    }
-    // Split-K on the 128 x 128 tap tile (small maps at batch 1-4: a handful of tiles, K in up to 32 splits): the splits meet INSIDE the
-    // launch -- ticket per tile, the last arriver sums every split's slab in split order and runs the fused epilogue (conv_tap.hip) --
-    // instead of in a splitk_reduce_kernel launch of its own (YOLOv3-608 at batch 1: 20 of 95 launches).
-    static const bool no_inl = getenv("YOLO_NO_INLAUNCH_SPLITK") != nullptr;      // A/B switch (same results up to the fp32 summation order of the splits)
-    // (up to eight splits: ONE workgroup reads them all -- 38 x 38 at batch 1, 2 splits: 23 -> 20 us; 19 x 19, 8 splits: 25.5 -> 24; beyond
-    // that the reduce launch, which spreads the sum over the chip, wins: 13 x 13 float32 with 16 / 32 splits 38 -> 40.5 / 61 -> 67 us)
-    if (ks > 1 && ks <= 8 && !pair && tile == 11 && !no_inl) {
-        const long long mq = (long long)(p.M / p.HoWo) * (p.H + 1) * (p.W + 1);
-        const long long nb11 = (mq + 127) / 128 * ((p.Cout + 127) / 128);
-        if (nb11 * 128 <= (long long)kPairCounterBytes && (size_t)nb11 * (size_t)ks * 65536 <= slab_bytes) pair = 1;
-    }
-    return ConvPick{tile, ks, ku, pair};
-}
-
-// the shape fields pick_conv reads, for a batch, without device pointers (workspace sizing, kernel_info)
-void conv_shape_params(const yolo_net *net, const Kernel &k, int batch, ConvParams &p) {
-    memset(&p, 0, sizeof p);
-    const yolo_layer_desc &d = net->layers[k.src_layer].d;
-    p.H = k.in.H; p.W = k.in.W;
-    p.Ho = net->layers[k.src_layer].H; p.Wo = net->layers[k.src_layer].W; p.HoWo = p.Ho * p.Wo;
-    p.M = (int)((long long)batch * p.HoWo);
-    p.Cout = k.cout;
-    p.ksize = d.ksize; p.stride = d.stride; p.taps = d.ksize * d.ksize;
-    p.ktiles = k.ktiles; p.cin_chunks = k.cpt;
-    p.f32 = net->opt.dtype == YOLO_DTYPE_F32;
-    p.out_f32 = k.out.f32 || p.f32;
-    p.outmode = k.outmode; p.has_res = k.has_res;
-    conv_vec_flags(net, k, p.out_f32 != 0, p.vec_out, p.vec_res);
-    const long long ob = (long long)batch * k.out.img_stride * (p.out_f32 ? 4 : net->esize);
-    p.out_bytes = ob > 0 && ob <= 0x7ffffff0LL ? (uint32_t)ob : 0u;
-    const long long rb = k.has_res ? (long long)batch * k.in2.img_stride * net->esize : 0;
-    p.res_bytes = rb > 0 && rb <= 0x7ffffff0LL ? (uint32_t)rb : 0u;
-}
-
-// float32 partial-sum slab one arena needs for ANY batch up to its share of max_batch (a net built for batch 32 also runs
-// the short last batch of a TEST directory, where the small maps do split): 0 when no launch ever splits
-size_t splitk_slab_bytes(const yolo_net *net) {
-    const int per = net->arena_full ? net->opt.max_batch : (net->opt.max_batch + net->arenas - 1) / net->arenas;
-    size_t need = 0;
-    for (const Kernel &k : net->kernels) {
-        if (k.kind != K_CONV || k.stem >= 2) continue;
-        for (int b = 1; b <= per; ++b) {
-            ConvParams p;
-            conv_shape_params(net, k, b, p);
-            const ConvPick pk = pick_conv(net, k, p, k.tile, kSplitkSlabMax);
-            if (pk.pair) {
-                const long long mq = (long long)(p.M / p.HoWo) * (p.H + 1) * (p.W + 1);
-                const int nb = dma_cfg_nb(pk.tile);
-                const long long ptiles = pk.tile == 22 ? (long long)(p.M / p.HoWo) : (mq + nb - 1) / nb;      // (22: a tile per image)
-                const size_t bytes = (size_t)(ptiles * ((p.Cout + 127) / 128)) * (size_t)pk.ks * 128 * (size_t)nb * 4;
-                if (bytes > need) need = bytes;
-            } else if (pk.ks > 1) {
-                const size_t bytes = (size_t)pk.ks * (size_t)p.M * (size_t)((p.Cout + 127) / 128 * 128) * 4;
-                if (bytes > need) need = bytes;
-            }
-        }
-    }
-    // layout of an arena's slab: [ticket counters of the in-launch pair split, kPairCounterBytes | partial sums]: the counters must
-    // never be written by anything but the pair kernels (they rely on finding them at zero)
-    return need ? kPairCounterBytes + (need + 4095) / 4096 * 4096 : 0;
-}
-
-// Back-to-back 1x1: does the launch of conv `ki` at this batch also compute the 1x1 conv `ki + 1` (plan.cpp marked the pair)?
-// Yes when the tile the batch picks holds all 128 couts of 256 positions per workgroup and has the fused instantiation: the 2-D
-// 128 x 256 tap tile (12) or the 128 x 256 K32 LDS-DMA tile (6), whole K, lean epilogue.  On success `p` (the 3x3's launch
-// parameters) carries the 1x1's weights, bias and output view.
-bool conv_fuse2(const yolo_net *net, size_t ki, const Ptrs *P, int batch, ConvParams &p, size_t slab_bytes) {
-    const Kernel &k = net->kernels[ki];
-    if (!k.fuse2_next || ki + 1 >= net->kernels.size() || !net->kernels[ki + 1].fuse2_prev) return false;
-    const ConvPick pk = pick_conv(net, k, p, k.tile, slab_bytes);
-    if ((pk.tile != 12 && pk.tile != 6 && pk.tile != 23) || pk.ks > 1 || pk.pair || !conv_fast_epilogue_ok(p)) return false;
-    if ((pk.tile == 12) != (p.has_res != 0)) return false;      // the instantiations built: 2-D tap tile + residual; LDS-DMA tile / stride-2 tap tile without
-    const Kernel &b = net->kernels[ki + 1];
-    const long long ob = (long long)batch * b.out.img_stride * net->esize;
-    if (ob <= 0 || ob > 0x7ffffff0LL) return false;
+// Back-to-back 1x1 (ConvLaunch.fuse2): `p`, the 3x3's launch parameters, takes the weights, bias and output view of the 1x1 `b` behind it
+void attach_fuse2(const yolo_net *net, const Kernel &b, const Ptrs &P, int batch, ConvParams &p) {
     p.fuse2 = 1;
     p.w2 = weights_at(net, b.w_off);
     p.w2_bytes = (uint32_t)b.w_bytes;
     p.wrow2_bytes = (uint32_t)b.ktiles * 128;
     p.b2 = reinterpret_cast<const float *>(weights_at(net, b.b_off));
-    p.out2 = P ? P->view_ptr(b.out) : nullptr;
-    p.out2_bytes = (uint32_t)ob;
+    p.out2 = P.view_ptr(b.out);
+    p.out2_bytes = (uint32_t)((long long)batch * b.out.img_stride * net->esize);       // (below 2 GiB: resolve_conv)
     p.out2_ld = b.out.ld;
     p.out2_img_stride = b.out.img_stride;
     p.leaky2 = b.leaky;
-    return true;
 }
 
-hipError_t launch_conv_any(const yolo_net *net, const Kernel &k, const ConvParams &p0, int tile_req, hipStream_t s, int arena = 0) {
-    const size_t slab = net->splitk_bytes / (size_t)net->arenas / 256 * 256;      // concurrent parts (streams) must not share a slab
-    const size_t data_bytes = slab > kPairCounterBytes ? slab - kPairCounterBytes : 0;
-    const ConvPick pk = pick_conv(net, k, p0, tile_req, data_bytes);
-    const int tile = pk.tile, ks = pk.ks, ku = pk.ku;
+// one conv launch as its record says (the split fields are set here, after the record was built from the whole-K parameters)
+hipError_t launch_conv_any(const yolo_net *net, const Kernel &k, const ConvParams &p0, const ConvLaunch &L, hipStream_t s, int arena = 0) {
+    const int tile = L.tile, ks = L.ks;
     ConvParams p = p0;
     if (ks > 1) {
-        p.ksplit = ks; p.kunits = ku;
+        p.ksplit = ks; p.kunits = L.ku;
         p.cout_pad = (p.Cout + 127) / 128 * 128;
-        unsigned char *base = net->dev_ws + net->splitk_off + (size_t)arena * slab;
+        unsigned char *base = net->dev_ws + net->splitk_off + (size_t)arena * arena_slab_bytes(net);
         p.part = reinterpret_cast<float *>(base + kPairCounterBytes);
-        if (pk.pair) {      // counters (zeroed at bind, returned to zero by every launch) in front of the partial sums
+        if (L.pair) {       // counters (zeroed at bind, returned to zero by every launch) in front of the partial sums
+            const size_t data_bytes = arena_slab_data_bytes(net);
             p.pair = 1;
             p.pair_cnt = reinterpret_cast<int *>(base);
             p.part_bytes = (uint32_t)(data_bytes < 0x7ffffff0u ? data_bytes : 0x7ffffff0u);
@@ -563,7 +314,7 @@ hipError_t launch_conv_any(const yolo_net *net, const Kernel &k, const ConvParam
     }
     if (tile <= 0) p.f32_emu = conv_f32_emu_rule(net->opt.f32_products, net->opt.dtype, p, k.cfg, k.perchunk != 0, ks) ? 1 : 0;
     hipError_t e = tile > 0 ? launch_conv_dma(p, tile, s) : launch_conv(p, net->opt.dtype, k.cfg, k.perchunk != 0, s);
-    if (e != hipSuccess || ks <= 1 || pk.pair) return e;
+    if (e != hipSuccess || ks <= 1 || L.pair) return e;
     ReduceParams r;
     memset(&r, 0, sizeof r);
     r.part = p.part; r.bias = p.bias; r.res = p.has_res ? p.res : nullptr; r.out = p.out;
@@ -580,17 +331,7 @@ bool branch_tails_ok(yolo_net *net, int batch) {
     if (off || net->side_chains <= 0 || net->opt.keep_all || batch <= 0 || batch > net->opt.max_batch) return false;
     if (net->side_ok.size() != (size_t)net->opt.max_batch + 1) net->side_ok.assign((size_t)net->opt.max_batch + 1, -1);
     signed char &memo = net->side_ok[(size_t)batch];
-    if (memo < 0) {
-        const size_t slab = net->splitk_bytes / (size_t)net->arenas / 256 * 256;
-        const size_t data_bytes = slab > kPairCounterBytes ? slab - kPairCounterBytes : 0;
-        memo = 1;
-        for (const Kernel &k : net->kernels) {
-            if (k.kind != K_CONV || k.stem >= 2) continue;
-            ConvParams p;
-            conv_shape_params(net, k, batch, p);
-            if (pick_conv(net, k, p, k.tile, data_bytes).ks > 1) { memo = 0; break; }
-        }
-    }
+    if (memo < 0) memo = pass_splits_k(net, batch) ? 0 : 1;
     return memo == 1;
 }
 int branch_streams(yolo_net *net, int arena) {
@@ -690,11 +431,10 @@ int run_forward_pass(yolo_net *net, const NetIn in, int batch, float *out_dev, h
                 e = launch_conv_mx(p, s);
                 break;
             }
-            {
-                const size_t slab = net->splitk_bytes / (size_t)net->arenas / 256 * 256;
-                fused2_done = conv_fuse2(net, ki, &P, batch, p, slab > kPairCounterBytes ? slab - kPairCounterBytes : 0);
-            }
-            e = launch_conv_any(net, k, p, k.tile, s, P.arena);
+            const ConvLaunch L = resolve_conv(net, ki, p, k.tile, arena_slab_data_bytes(net));
+            if (L.fuse2) attach_fuse2(net, net->kernels[ki + 1], P, batch, p);
+            fused2_done = L.fuse2 != 0;
+            e = launch_conv_any(net, k, p, L, s, P.arena);
             break;
         }
         case K_FIRST: {
@@ -979,106 +719,7 @@ int yolo_net_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out)
     auto elems = [](const View &v) { return (double)v.H * v.W * v.C; };
     auto esz = [&](const View &v) { return v.f32 ? 4.0 : (double)net->esize; };
     if (k.kind == K_CONV) {
-        const LayerInfo &li = net->layers[k.src_layer];
-        out->variant = k.cfg + 4 * k.perchunk;
-        out->ksize = k.ksize; out->stride = k.stride; out->cin = k.cin; out->cout = k.cout; out->out_h = li.H; out->out_w = li.W;
-        out->flops = 2.0 * li.H * li.W * k.cout * k.ksize * k.ksize * k.cin;
-        out->bytes = (double)k.in.H * k.in.W * k.cin * net->esize + elems(k.out) * esz(k.out) + (k.has_res ? elems(k.in2) * net->esize : 0.0);
-        out->weight_bytes = (double)k.cout * k.ksize * k.ksize * k.cin * net->esize + 4.0 * k.cout;
-        if (k.stem == 3) {          // no launch of its own
-            out->flops = 0; out->bytes = 0; out->weight_bytes = 0;
-            snprintf(out->name, sizeof out->name, "conv_igemm<fused into conv_stem>");
-            return YOLO_OK;
-        }
-        if (k.stem == 2) {
-            const Kernel &f = net->kernels[kernel - 1];
-            out->flops += 2.0 * f.out.H * f.out.W * f.cout * 27;
-            out->bytes = (double)f.in.H * f.in.W * 3 * 4 + elems(k.out) * esz(k.out);
-            out->weight_bytes += 28.0 * f.cout * 4;
-            snprintf(out->name, sizeof out->name, "conv_stem<f16,3-32-64>");
-            set_symbol("yolo::stem_v3_kernel(yolo::StemParams)");
-            if (kernel + 1 < (int)net->kernels.size() && net->kernels[kernel + 1].stem == 3) {
-                const Kernel &t3 = net->kernels[kernel + 1];
-                out->flops += 2.0 * li.H * li.W * t3.cout * t3.cin;
-                out->bytes += elems(t3.out) * esz(t3.out);
-                out->weight_bytes += (double)t3.cout * t3.cin * net->esize + 4.0 * t3.cout;
-                snprintf(out->name, sizeof out->name, "conv_stem<f16,3-32-64-32>");
-            }
-            return YOLO_OK;
-        }
-        if (k.mx) {         // e4m3 weights + one scale byte per 32 of them; fp16 activations in and out
-            ConvParams mp;
-            conv_shape_params(net, k, part_batch(net), mp);
-            out->variant = 8 + kMxTile;
-            out->weight_bytes = (double)k.cout * k.ksize * k.ksize * k.cin * (1.0 + 1.0 / 32) + 4.0 * k.cout;
-            snprintf(out->name, sizeof out->name, "conv_mx<mxf8,128x256>");
-            set_symbol(conv_mx_symbol(conv_fast_epilogue_ok(mp)));
-            return YOLO_OK;
-        }
-        // which kernel runs at max_batch (bench.py runs at max_batch): the same decision the launch path takes
-        ConvParams sp;
-        const int per_arena = part_batch(net);
-        conv_shape_params(net, k, per_arena, sp);
-        const size_t slab_i = net->splitk_bytes / (size_t)net->arenas / 256 * 256;
-        const size_t slab_d = slab_i > kPairCounterBytes ? slab_i - kPairCounterBytes : 0;
-        if (k.fuse2_prev && kernel > 0) {       // computed by the conv in front of it at this batch?
-            ConvParams pp;
-            conv_shape_params(net, net->kernels[kernel - 1], per_arena, pp);
-            if (conv_fuse2(net, (size_t)kernel - 1, nullptr, per_arena, pp, slab_d)) {
-                out->flops = 0; out->bytes = 0; out->weight_bytes = 0;
-                snprintf(out->name, sizeof out->name, "conv_igemm<fused into the conv in front>");
-                return YOLO_OK;
-            }
-        }
-        const bool fused2 = conv_fuse2(net, (size_t)kernel, nullptr, per_arena, sp, slab_d);
-        if (fused2) {       // this launch also computes the 1x1 behind it: its work and its output belong here
-            const Kernel &b2 = net->kernels[kernel + 1];
-            out->flops += 2.0 * li.H * li.W * b2.cout * b2.cin;
-            out->bytes += elems(b2.out) * esz(b2.out);
-            out->weight_bytes += (double)b2.cout * b2.cin * net->esize + 4.0 * b2.cout;
-        }
-        const ConvPick pk = pick_conv(net, k, sp, k.tile, slab_d);
-        const int tile = pk.tile;
-        const bool f32net = net->opt.dtype == YOLO_DTYPE_F32;
-        if (tile > 0) {
-            out->variant = 8 + tile;
-            snprintf(out->name, sizeof out->name, "conv_igemm_dma<%s,%s>", t, dma_cfg_name(tile));
-            sp.ksplit = pk.ks;
-            std::string sym = dma_cfg_symbol_for(tile, f32net, sp);      // (the persistent form of the tap kernel where it takes the launch)
-            if (pk.ks > 1) {        // the split-K instantiation of the tap kernel (its last template argument)
-                const size_t at = sym.rfind(", false, false, false>(");
-                if (at != std::string::npos) sym.replace(at, 23, ", true, false, false>(");
-                const size_t occ = sym.find("26, 4, 1, true, false, false>(");       // the in-launch pair on the 128 x 256 tile is built for one workgroup per CU
-                if (pk.pair && occ != std::string::npos) sym.replace(occ, 30, "26, 2, 1, true, false, false>(");
-                const size_t occ22 = sym.find("14, 4, 1, true, false, false>(");     // ... and on the image-aligned 128 x 192 tile
-                if (pk.pair && occ22 != std::string::npos) sym.replace(occ22, 30, "14, 2, 1, true, false, false>(");
-            }
-            set_symbol(sym);
-        } else {
-            const bool emu = conv_f32_emu_rule(net->opt.f32_products, net->opt.dtype, sp, k.cfg, k.perchunk != 0, pk.ks);
-            set_symbol(conv_symbol(net->opt.dtype, k.cfg, k.perchunk != 0, emu));
-            if (emu) snprintf(out->name, sizeof out->name, "conv_igemm_emu<f32 as 9 x bf16,N128>");
-            else snprintf(out->name, sizeof out->name, "conv_igemm<%s,N%d,%s>", t, k.cfg == CFG_N128 ? 128 : k.cfg == CFG_N64 ? 64 : 32,
-                          k.perchunk ? "perchunk" : "uniform");
-        }
-        if (k.outmode == OUT_POOL2) {
-            const size_t n = strlen(out->name);
-            snprintf(out->name + n, sizeof out->name - n, "+pool");
-        }
-        if (fused2) {
-            const size_t n = strlen(out->name);
-            snprintf(out->name + n, sizeof out->name - n, "+1x1");
-        }
-        if (pk.pair) {              // K in two halves (or pk.ks splits) inside the launch
-            const size_t n = strlen(out->name);
-            if (pk.ks == 2) snprintf(out->name + n, sizeof out->name - n, "+pairK");
-            else snprintf(out->name + n, sizeof out->name - n, "+splitK%d,1launch", pk.ks);
-            out->bytes += (double)pk.ks * (double)li.H * li.W * ((k.cout + 127) / 128 * 128) * 4.0;
-        } else if (pk.ks > 1) {     // two launches: K splits into the float32 slab, then splitk_reduce_kernel (sum + fused epilogue)
-            const size_t n = strlen(out->name);
-            snprintf(out->name + n, sizeof out->name - n, "+splitK%d", pk.ks);
-            out->bytes += 2.0 * pk.ks * (double)li.H * li.W * ((k.cout + 127) / 128 * 128) * 4.0;      // partial sums written + read once
-        }
+        conv_kernel_info(net, kernel, out);
     } else if (k.kind == K_FIRST) {
         out->ksize = 3; out->stride = 1; out->cin = 3; out->cout = k.cout; out->out_h = k.out.H; out->out_w = k.out.W;
         out->flops = 2.0 * k.out.H * k.out.W * k.cout * 27;
@@ -1182,7 +823,8 @@ int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *strea
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
-    for (Kernel &k : net->kernels) {
+    for (size_t ki = 0; ki < net->kernels.size(); ++ki) {
+        Kernel &k = net->kernels[ki];
         if (k.kind != K_CONV || k.stem >= 2 || k.mx || !dma_eligible(net, k)) continue;      // (MX convs: one kernel, weights packed for it)
         ConvParams p;
         rc = make_conv_params(net, k, P, batch, p);
@@ -1191,10 +833,11 @@ int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *strea
         int best_tile = -1;
         for (int tile = 0; tile < dma_num_cfgs(); ++tile) {
             if (!conv_tile_valid(net, k, tile)) continue;
+            const ConvLaunch L = resolve_conv(net, ki, p, tile, arena_slab_data_bytes(net));       // (timed without the 1x1 behind it: L.fuse2 is not attached)
             float ms = 1e30f;
             bool ok = true;
             for (int rep = 0; rep < 4 && ok; ++rep) {       // first launch warms caches; keep the best of the rest
-                ok = hipEventRecord(e0, s) == hipSuccess && launch_conv_any(net, k, p, tile, s) == hipSuccess &&
+                ok = hipEventRecord(e0, s) == hipSuccess && launch_conv_any(net, k, p, L, s) == hipSuccess &&
                      hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
                 float t = 0.f;
                 if (ok && rep > 0 && hipEventElapsedTime(&t, e0, e1) == hipSuccess && t < ms) ms = t;

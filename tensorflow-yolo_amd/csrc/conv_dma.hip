@@ -549,6 +549,7 @@ std::string dma_cfg_symbol_for(int cfg, bool f32, const ConvParams &p) {
     if (p.fuse2) return cfg == 6 ? "void yolo::conv_igemm_dma_kernel<2, 4, 4, 4, 3, 4, 4, true, 0>(yolo::ConvParams)"
                        : cfg == 23 ? "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 4, 4, false, true, true>(yolo::ConvParams)"
                                    : "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 4, 27, 4, 2, false, true, true>(yolo::ConvParams)";
+    if (is_tap_cfg(cfg) && p.ksplit > 1) return conv_tap_splitk_symbol(tap_variant(cfg), f32);
     if (is_tap_cfg(cfg) && conv_tap_stream_ok(p, tap_variant(cfg))) return conv_tap_stream_symbol(tap_variant(cfg));
     if (!is_tap_cfg(cfg)) {     // the LDS-DMA kernel: last template argument = the epilogue kind of this launch
         std::string sym = dma_cfg_symbol(cfg, f32, false);

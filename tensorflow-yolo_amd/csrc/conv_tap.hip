@@ -1064,6 +1064,15 @@ const char *conv_tap_stream_symbol(int variant) {
     }
 }
 
+// the split-K instantiations (launch_conv_tap, p.ksplit > 1): the 128 x 128 tile, and for the in-launch pair the fp16 128 x 256 and
+// image-aligned 128 x 192 tiles built for one workgroup per CU (OCC 2)
+const char *conv_tap_splitk_symbol(int variant, bool f32) {
+    if (variant == 0) return "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 2, 1, true, false, false>(yolo::ConvParams)";
+    if (variant == 12) return "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 3, 14, 2, 1, true, false, false>(yolo::ConvParams)";
+    return f32 ? "void yolo::conv3x3_tap_kernel<true, 2, 4, 4, 2, 28, 4, 1, true, false, false>(yolo::ConvParams)"
+               : "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 2, 28, 4, 1, true, false, false>(yolo::ConvParams)";
+}
+
 bool conv_tap_stream_ok(const ConvParams &p, int variant) {
     if (variant != 5) return false;
     if (p.f32 || p.out_f32 || p.ksplit > 1 || p.outmode != OUT_NORMAL || !p.vec_out || (p.has_res && (!p.vec_res || !p.res_bytes)) || !p.out_bytes) return false;

@@ -451,7 +451,7 @@ struct Planner {
                 // conv in front of it writes, where that conv's workgroups hold all 128 couts of their positions (Darknet-53 at
                 // 152 x 152: the stride-2 conv into the stage and the first residual block's 3x3, each followed by the next block's
                 // 1x1).  Structural conditions here; whether a launch takes the fused instantiation depends on the tile its batch
-                // picks (api.cpp: conv_fuse2), else the 1x1 runs as a launch of its own.
+                // picks (conv_dispatch.cpp: resolve_conv), else the 1x1 runs as a launch of its own.
                 if (!net->kernels.empty() && net->opt.dtype == YOLO_DTYPE_F16 && !net->opt.keep_all && !getenv("YOLO_NO_FUSE2") &&
                     d.ksize == 1 && d.stride == 1 && d.filters == 64 && cin == 128 && f.kind == 0 && !has_head[i] && !k.out.f32 &&
                     k.out.ld % epc == 0 && (k.out.base + k.out.coff) % epc == 0 && k.out.img_stride % epc == 0) {
@@ -764,7 +764,7 @@ int plan_network(yolo_net *net, const yolo_layer_desc *layers, int n, std::strin
     net->obj_bytes = net->head.n_classes > 0 ? (size_t)net->opt.max_batch * (net->out_count / (size_t)(5 + net->head.n_classes)) * 4 : 0;
     off += roundup_sz(net->obj_bytes, 4096);
     // split-K slabs (float32 partial sums of the convs whose launch would leave the chip idle): last region of the workspace,
-    // sized by yolo_net_create from the launches that can actually split (api.cpp: splitk_slab_bytes) -- 0 for most big-batch nets
+    // sized by yolo_net_create from the launches that can actually split (conv_dispatch.cpp: splitk_slab_bytes) -- 0 for most big-batch nets
     net->splitk_off = off;
     net->splitk_bytes = 0;
     net->workspace_bytes = off;

@@ -327,8 +327,9 @@ const char *dma_cfg_name(int cfg);
 // names exactly as rocprofv3's kernel trace prints them (yolo_kernel_info.symbol: joins bench.py's roofline to profiles/*.csv)
 const char *dma_cfg_symbol(int cfg, bool f32, bool fast = false);      // fast: the lean-epilogue instantiation of a tap tile
 const char *conv_tap_symbol(int variant, bool f32, bool fast = false);
-std::string dma_cfg_symbol_for(int cfg, bool f32, const ConvParams &p);      // the kernel that runs THIS launch (stream form included)
+std::string dma_cfg_symbol_for(int cfg, bool f32, const ConvParams &p);      // the kernel that runs THIS launch (stream form, split-K and pair forms included: p.ksplit, p.pair, p.fuse2 as launched)
 const char *conv_tap_stream_symbol(int variant);
+const char *conv_tap_splitk_symbol(int variant, bool f32);      // the instantiation launch_conv_tap runs when p.ksplit > 1
 std::string conv_symbol(int dtype, int cfg, bool perchunk, bool f32_emu = false);
 // float32 nets: does this launch of the 4-wave kernel run its products as nine bf16 products (yolo_net_options.f32_products)?
 bool conv_f32_emu_rule(int f32_products, int dtype, const ConvParams &p, int cfg, bool perchunk, int ksplit);
@@ -374,7 +375,7 @@ struct Kernel {
     int stem = 0;              // 1: first-layer kernel fused away into the next conv; 2: this conv runs as stem.hip with it;
                                // 3: this 1x1 conv is computed by the stem kernel in front of it (no launch)
     int fuse2_next = 0;        // the NEXT kernel is a 1x1 128 -> 64 conv on this conv's output that the fused instantiation of this launch
-                               // can compute (conv_common.h: conv_epilogue_fused_1x1); whether it does is decided per launch (api.cpp: conv_fuse2)
+                               // can compute (conv_common.h: conv_epilogue_fused_1x1); whether it does is decided per launch (conv_dispatch.cpp: resolve_conv)
     int fuse2_prev = 0;        // ... and the mark on that 1x1: skipped when the conv in front of it has computed it
     int mx = 0;                // MXFP8 plans: this conv runs conv3x3_mx_kernel (conv_mx.hip) on block-scaled e4m3 operands
     int side = 0;              // > 0: member of branch tail `side` (plan.cpp: side_chains): a run of kernels ending in a head conv whose
@@ -451,4 +452,31 @@ bool mx_eligible(const yolo_net *net, const Kernel &k);
 int pack_weights(const yolo_net *net, const float *host, size_t n, std::vector<unsigned char> &blob, std::string &err);
 std::string describe(const yolo_net *net);
 void set_error(const std::string &s);
+
+// ---- conv dispatch (conv_dispatch.cpp) ------------------------------------------------------
+// images one part of a full batch holds (what every launch of a forward pass sees at most)
+inline int part_batch(const yolo_net *net) { return (net->opt.max_batch + net->parts - 1) / net->parts; }
+// An arena's share of the split-K region: [ticket counters of the in-launch splits, kPairCounterBytes | float32 partial sums]
+// (conv_tap.hip: one ticket per tile, a 128-byte line each, 512 tiles).  Concurrent parts (streams) must not share a slab.
+constexpr size_t kPairCounterBytes = 65536;
+constexpr size_t kSplitkSlabMax = (size_t)64 << 20;     // partial sums per arena, at most
+inline size_t arena_slab_bytes(const yolo_net *net) { return net->splitk_bytes / (size_t)net->arenas / 256 * 256; }
+inline size_t arena_slab_data_bytes(const yolo_net *net) {
+    const size_t slab = arena_slab_bytes(net);
+    return slab > kPairCounterBytes ? slab - kPairCounterBytes : 0;
+}
+// What one conv launch runs: the tile (0 = the 4-wave kernel of conv.hip with the planner's cfg, > 0 = conv_dma.hip tile id), the K
+// split (ks = 1: whole K; else ks splits of ku units), whether the splits meet inside the launch (pair), whether the launch also
+// computes the 1x1 conv behind it (fuse2), and the bytes of partial sums it writes (0 if none).
+struct ConvLaunch {
+    int tile, ks, ku, pair, fuse2;
+    size_t slab_need;
+};
+void conv_shape_params(const yolo_net *net, const Kernel &k, int batch, ConvParams &p);
+ConvLaunch resolve_conv(const yolo_net *net, size_t ki, const ConvParams &p, int tile_req, size_t slab_bytes);
+bool dma_eligible(const yolo_net *net, const Kernel &k);
+bool conv_tile_valid(const yolo_net *net, const Kernel &k, int tile);
+size_t splitk_slab_bytes(const yolo_net *net);          // per arena, tickets included
+bool pass_splits_k(const yolo_net *net, int batch);     // any conv launch of a forward pass at this batch splits K
+void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out);
 }  // namespace yolo

@@ -1,4 +1,4 @@
-"""CPU: the host code of the planner and the C ABI (plan.cpp, api.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer
+"""CPU: the host code of the planner and the C ABI (plan.cpp, conv_dispatch.cpp, api.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer
 (VERDICT r4 #4 ii).  `make SAN=1` builds a second library (host side instrumented, device code as usual: GPU ASan is not
 available on this pool and is not asked for); the planning / ABI tests of tests/test_abi.py and tests/test_host_logic.py and the
 weight-packing probe run against it in child processes with the ASan runtime preloaded.  Any report aborts the child.
