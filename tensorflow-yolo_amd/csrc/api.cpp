@@ -4,6 +4,7 @@
 #include <new>
 
 #include <cmath>
+#include "conv_tiles.h"
 #include "yolo_internal.h"
 
 namespace yolo {
@@ -831,7 +832,7 @@ int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *strea
         if (rc) break;
         float best = 1e30f;
         int best_tile = -1;
-        for (int tile = 0; tile < dma_num_cfgs(); ++tile) {
+        for (int tile = 0; tile < kNumTiles; ++tile) {
             if (!conv_tile_valid(net, k, tile)) continue;
             const ConvLaunch L = resolve_conv(net, ki, p, tile, arena_slab_data_bytes(net));       // (timed without the 1x1 behind it: L.fuse2 is not attached)
             float ms = 1e30f;

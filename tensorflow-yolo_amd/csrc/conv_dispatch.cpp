@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "conv_tiles.h"
 #include "yolo_internal.h"
 
 namespace yolo {
@@ -61,25 +62,27 @@ bool dma_eligible(const yolo_net *net, const Kernel &k) {
 }
 // tile 0 = the 4-wave kernel of conv.hip with the planner's cfg (always available)
 bool conv_tile_valid(const yolo_net *net, const Kernel &k, int tile) {
-    if (k.outmode == OUT_POOL2 && tile != 12 && tile != 13 && tile != 17) return false;      // the fused max-pool lives in the 16 x 16 2-D tap tiles
-    if (tile == 0) return true;
-    if (net->opt.dtype == YOLO_DTYPE_F32 && !dma_cfg_f32_ok(tile)) return false;
-    if ((tile == 18 || tile == 21 || tile == 22) && k.in.H != k.in.W) return false;     // the image-aligned tap tiles: square maps (the rules price tiles by W alone)
-    if ((tile == 20 || tile == 21 || tile == 23) && ((k.in.H & 1) || net->opt.dtype != YOLO_DTYPE_F16)) return false;      // stride 2 over parity planes: even maps, fp16
+    if (tile < 0 || tile >= kNumTiles) return false;
+    const ConvTile &t = conv_tile(tile);
+    if (k.outmode == OUT_POOL2 && !t.has(CAP_POOL)) return false;      // the fused max-pool lives in the 16 x 16 2-D tap tiles
+    if (tile == TILE_4WAVE) return true;
+    if (net->opt.dtype == YOLO_DTYPE_F32 && !t.f32_ok()) return false;
+    if (t.image_aligned() && k.in.H != k.in.W) return false;     // the image-aligned tap tiles: square maps (the rules price tiles by W alone)
+    if (t.stride2() && ((k.in.H & 1) || net->opt.dtype != YOLO_DTYPE_F16)) return false;      // stride 2 over parity planes: even maps, fp16
     return dma_eligible(net, k) && dma_cfg_valid(tile, k.cout, k.cpt, true, k.ksize, k.stride, k.in.W);
 }
 
 namespace {
 
-// Tile geometry.  Workgroups a tap tile launches (p.HoWo > 0): position tiles of the padded-linear grid -- the image-aligned 128 x 192
-// tile (22): a tile per image -- times cout tiles.
+// Tile geometry.  Workgroups a stride-1 tap tile of the padded-linear grid launches (p.HoWo > 0; the tiles that split K are such): position
+// tiles -- image-aligned: a tile per image -- times cout tiles.
 long long tap_blocks(const ConvParams &p, int tile) {
+    const ConvTile &t = conv_tile(tile);
     const long long images = p.M / p.HoWo, mq = images * (p.H + 1) * (p.W + 1);         // mq: padded-linear positions
-    const int na = dma_cfg_na(tile), nb = dma_cfg_nb(tile);
-    return (tile == 22 ? images : (mq + nb - 1) / nb) * ((p.Cout + na - 1) / na);
+    return (t.image_aligned() ? images : (mq + t.nb() - 1) / t.nb()) * ((p.Cout + t.na() - 1) / t.na());
 }
 // Partial sums of a launch whose splits meet inside it (conv_tap.hip): every split of every tile owns a float32 slab of the whole tile
-size_t pair_slab_bytes(int tile, long long tiles, int ks) { return (size_t)tiles * (size_t)ks * 128 * (size_t)dma_cfg_nb(tile) * 4; }
+size_t pair_slab_bytes(int tile, long long tiles, int ks) { return (size_t)tiles * (size_t)ks * 128 * (size_t)conv_tile(tile).nb() * 4; }
 // ... and of one whose splits meet in splitk_reduce_kernel: part[ks][M][cout_pad]
 size_t reduce_slab_bytes(const ConvParams &p, long long ks) { return (size_t)ks * (size_t)p.M * (size_t)((p.Cout + 127) / 128 * 128) * 4; }
 
@@ -92,12 +95,12 @@ int choose_ksplit(const Kernel &k, const ConvParams &p, int tile, size_t slab_by
     if (!slab_bytes || p.M <= 0) return 1;
     long long blocks;
     int units, min_units;
-    if (tile == 0) {
+    if (tile == TILE_4WAVE) {
         const int na = k.cfg == CFG_N128 ? 128 : k.cfg == CFG_N64 ? 64 : 32, nb = k.cfg == CFG_N128 ? 128 : 256;
         blocks = ((long long)p.M + nb - 1) / nb * ((p.Cout + na - 1) / na);
         units = p.ktiles;
         min_units = 2;                  // >= 64 (float32) / 128 (fp16) k per split: these launches are latency-bound, not MFMA-bound
-    } else if (dma_cfg_is_tap(tile) && dma_cfg_splitk_ok(tile)) {
+    } else if (conv_tile(tile).has(CAP_SPLITK)) {
         blocks = tap_blocks(p, tile);
         units = p.cin_chunks >> 2;
         min_units = 2;                  // >= 288 (float32) / 576 (fp16) k per split
@@ -139,13 +142,14 @@ ConvLaunch resolve_conv(const yolo_net *net, size_t ki, const ConvParams &p, int
     if (!dma_eligible(net, k) || (tile > 0 && !conv_tile_valid(net, k, tile))) tile = 0;
     else if (tile < 0) {
         tile = choose_dma_cfg(p.M, k.cout, k.cpt, p.taps, k.has_res, true, k.stride, k.in.W, net->opt.dtype == YOLO_DTYPE_F32);
-        if (tile == 18 && !conv_tile_valid(net, k, 18)) tile = conv_tile_valid(net, k, 15) ? 15 : 8;
-        if (tile == 22 && !conv_tile_valid(net, k, 22)) tile = conv_tile_valid(net, k, 10) ? 10 : 8;
-        if ((tile == 20 || tile == 21) && !conv_tile_valid(net, k, tile)) tile = conv_tile_valid(net, k, 20) ? 20 : conv_tile_valid(net, k, 5) ? 5 : 0;
-        if (tile == 23 && !conv_tile_valid(net, k, 23)) tile = conv_tile_valid(net, k, 6) ? 6 : 0;
+        auto or_else = [&](int a, int b) { return conv_tile_valid(net, k, a) ? a : b; };
+        if (tile == TILE_TAPIMG_128x384 && !conv_tile_valid(net, k, tile)) tile = or_else(TILE_TAP_256x224, TILE_TAP_128x256);
+        if (tile == TILE_TAPIMG_128x192 && !conv_tile_valid(net, k, tile)) tile = or_else(TILE_TAP_128x192, TILE_TAP_128x256);
+        if ((tile == TILE_TAPS2_128x256 || tile == TILE_TAPS2IMG_128x384) && !conv_tile_valid(net, k, tile)) tile = or_else(TILE_TAPS2_128x256, or_else(TILE_DMA_256x128_K32, TILE_4WAVE));
+        if (tile == TILE_TAPS2_128x256_WIDE && !conv_tile_valid(net, k, tile)) tile = or_else(TILE_DMA_128x256_K32, TILE_4WAVE);
     }
     ConvLaunch r{tile, 1, 0, 0, 0, 0};
-    const bool tap_by_rule = tile > 0 && dma_cfg_is_tap(tile) && tile_req <= 0;     // (an explicitly requested tile -- force_tile, an autotune candidate -- runs as requested: the hook must time and test the tile it names)
+    const bool tap_by_rule = conv_tile(tile).is_tap() && tile_req <= 0;     // (an explicitly requested tile -- force_tile, an autotune candidate -- runs as requested: the hook must time and test the tile it names)
     const int units = p.cin_chunks >> 2;        // channel slices
     // K in two halves inside ONE launch (conv_tap.hip): two co-resident half-K workgroups per tile, the second arriver sums -- no reduce
     // kernel, two slabs per tile.  For a long K on a tap tile by rule; `lo`..`hi` tiles of tile `t`.
@@ -165,37 +169,38 @@ ConvLaunch resolve_conv(const yolo_net *net, size_t ki, const ConvParams &p, int
     // 26 x 26 at batch 16 = 184 tiles ran 48 us as 368 halves against 33 us whole)
     // (12 x 12 / 13 x 13 maps: one image per 192-position tile -- 5 % padding where 256-position tiles of the padded-linear grid
     // compute 23 %, and 16 images x 8 cout tiles x 2 halves are exactly 256 workgroups: YOLOv2-416 b16 13 x 13 layers -25 %)
-    const bool wide_pair = !p.f32 && (pair_on(22, 64, 128) || pair_on(8, 64, 128));
+    const bool wide_pair = !p.f32 && (pair_on(TILE_TAPIMG_128x192, 64, 128) || pair_on(TILE_TAP_128x256, 64, 128));
     if (!wide_pair) {
         r.ks = choose_ksplit(k, p, tile, slab_bytes, r.ku);
         // a 3x3/1 layer small enough for split-K runs it on the 128 x 128 tap tile (the one with the split-K instantiation), whatever
         // tile the cost model would pick for the whole-K launch
-        if (r.ks <= 1 && tap_by_rule && tile != 11 && conv_tile_valid(net, k, 11)) {
+        if (r.ks <= 1 && tap_by_rule && tile != TILE_TAP_128x128 && conv_tile_valid(net, k, TILE_TAP_128x128)) {
             int ku11 = 0;
-            const int ks11 = choose_ksplit(k, p, 11, slab_bytes, ku11);
-            if (ks11 > 1) { r.tile = 11; r.ks = ks11; r.ku = ku11; }
+            const int ks11 = choose_ksplit(k, p, TILE_TAP_128x128, slab_bytes, ku11);
+            if (ks11 > 1) { r.tile = TILE_TAP_128x128; r.ks = ks11; r.ku = ku11; }
         }
         // still whole: 129-256 tiles of 128 x 128 (13 x 13 / 19 x 19 maps at batch 8-32, any dtype) -- every workgroup would run ALONE on
         // its CU at 0.6 of the rate a pair reaches (block trace, profiles/r03_ablation.md)
-        if (r.ks <= 1) pair_on(11, 129, 256);
+        if (r.ks <= 1) pair_on(TILE_TAP_128x128, 129, 256);
         // Split-K on the 128 x 128 tap tile (small maps at batch 1-4: a handful of tiles, K in up to 32 splits): the splits meet INSIDE the
         // launch -- ticket per tile, the last arriver sums every split's slab in split order and runs the fused epilogue (conv_tap.hip) --
         // instead of in a splitk_reduce_kernel launch of its own (YOLOv3-608 at batch 1: 20 of 95 launches).
         // (up to eight splits: ONE workgroup reads them all -- 38 x 38 at batch 1, 2 splits: 23 -> 20 us; 19 x 19, 8 splits: 25.5 -> 24; beyond
         // that the reduce launch, which spreads the sum over the chip, wins: 13 x 13 float32 with 16 / 32 splits 38 -> 40.5 / 61 -> 67 us)
         static const bool no_inl = getenv("YOLO_NO_INLAUNCH_SPLITK") != nullptr;      // A/B switch (same results up to the fp32 summation order of the splits)
-        if (r.ks > 1 && r.ks <= 8 && !r.pair && r.tile == 11 && !no_inl) {
-            const long long tiles = tap_blocks(p, 11);
-            if (tiles * 128 <= (long long)kPairCounterBytes && pair_slab_bytes(11, tiles, r.ks) <= slab_bytes) r.pair = 1;
+        if (r.ks > 1 && r.ks <= 8 && !r.pair && r.tile == TILE_TAP_128x128 && !no_inl) {
+            const long long tiles = tap_blocks(p, r.tile);
+            if (tiles * 128 <= (long long)kPairCounterBytes && pair_slab_bytes(r.tile, tiles, r.ks) <= slab_bytes) r.pair = 1;
         }
     }
     if (r.pair) r.slab_need = pair_slab_bytes(r.tile, tap_blocks(p, r.tile), r.ks);
     else if (r.ks > 1) r.slab_need = reduce_slab_bytes(p, r.ks);
     // Back-to-back 1x1: does this launch also compute the 1x1 conv `ki + 1` (plan.cpp marked the pair)?  Yes when the tile holds all 128
-    // couts of 256 positions per workgroup and has the fused instantiation -- the 2-D 128 x 256 tap tile (12, with a residual), the
-    // 128 x 256 K32 LDS-DMA tile (6) or the wide stride-2 tap tile (23), both without --, whole K, lean epilogue.
-    if (k.fuse2_next && ki + 1 < net->kernels.size() && net->kernels[ki + 1].fuse2_prev && (r.tile == 12 || r.tile == 6 || r.tile == 23) &&
-        r.ks <= 1 && conv_fast_epilogue_ok(p) && (r.tile == 12) == (p.has_res != 0) && p.HoWo > 0) {
+    // couts of 256 positions per workgroup and has the fused instantiation (CAP_FUSE2) -- the 2-D 128 x 256 tap tile with a residual, the
+    // 128 x 256 K32 LDS-DMA tile or the wide stride-2 tap tile, both without --, whole K, lean epilogue.
+    const ConvTile &rt = conv_tile(r.tile);
+    if (k.fuse2_next && ki + 1 < net->kernels.size() && net->kernels[ki + 1].fuse2_prev && rt.has(CAP_FUSE2) &&
+        r.ks <= 1 && conv_fast_epilogue_ok(p) && rt.has(CAP_FUSE2_RES) == (p.has_res != 0) && p.HoWo > 0) {
         const long long ob = (long long)(p.M / p.HoWo) * net->kernels[ki + 1].out.img_stride * net->esize;       // the 1x1's output: buffer-addressed
         r.fuse2 = ob > 0 && ob <= 0x7ffffff0LL;
     }
@@ -300,9 +305,9 @@ void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
     const int tile = pk.tile;
     if (tile > 0) {
         out->variant = 8 + tile;
-        snprintf(out->name, sizeof out->name, "conv_igemm_dma<%s,%s>", t, dma_cfg_name(tile));
+        snprintf(out->name, sizeof out->name, "conv_igemm_dma<%s,%s>", t, conv_tile(tile).name);
         sp.ksplit = pk.ks; sp.pair = pk.pair; sp.fuse2 = pk.fuse2;       // as launched
-        set_symbol(dma_cfg_symbol_for(tile, net->opt.dtype == YOLO_DTYPE_F32, sp));
+        set_symbol(conv_tile_symbol(tile, sp));
     } else {
         const bool emu = conv_f32_emu_rule(net->opt.f32_products, net->opt.dtype, sp, k.cfg, k.perchunk != 0, pk.ks);
         set_symbol(conv_symbol(net->opt.dtype, k.cfg, k.perchunk != 0, emu));

@@ -15,7 +15,9 @@
 // Per K tile: wait(tile kt landed) -> barrier -> issue DMA of tile kt+S-1 into the stage read at
 // kt-1 -> ds_read fragments + MFMAs of tile kt.
 #include "conv_common.h"
+#include "conv_tiles.h"
 #include <cstdio>
+#include <utility>
 #include <vector>
 
 namespace yolo {
@@ -250,56 +252,17 @@ __global__ void __launch_bounds__(512, OCC) conv_igemm_dma_kernel(const ConvPara
 #endif
 }
 
-struct DmaCfg {
-    int na, nb, slots_per_cu;
-    float rate;     // relative per-CU throughput while busy (measured ordering, refined by profiling)
-    const char *name;
-    int bkc;        // K chunks per stage: Cin must be a multiple of it
-};
-static const DmaCfg kCfgs[] = {
-    {128, 128, 2, 0.55f, "", 8},                   // 0: conv.hip 4-wave register-staged kernel (two workgroups per CU)
-    {256, 256, 1, 0.80f, "256x256,K64,S2", 8},     // 1
-    {256, 128, 1, 0.85f, "256x128,K64,S3", 8},     // 2: 256 couts x 128 pixels
-    {128, 256, 1, 0.85f, "128x256,K64,S3", 8},     // 3: 128 couts x 256 pixels
-    {256, 256, 1, 1.00f, "256x256,K32,S4", 4},     // 4: 96 KiB in flight instead of 64
-    {256, 128, 2, 1.30f, "256x128,K32,S3,x2", 4},  // 5: 72 KiB LDS, <=128 VGPRs: two workgroups per CU
-    {128, 256, 2, 1.30f, "128x256,K32,S3,x2", 4},  // 6
-    {64, 512, 2, 1.00f, "64x512,K32,S2,x2", 4},    // 7: narrow early layers (Cout <= 64), bandwidth-bound
-    {128, 256, 2, 1.00f, "128x256,tap9,x2", 4},        // 8: conv_tap.hip, 3x3/1 only: input patch loaded once for the 9 taps
-    {256, 256, 1, 1.00f, "256x256,tap9", 4},           // 9
-    {128, 192, 2, 1.00f, "128x192,tap9,x2", 4},        // 10: smaller position tiles for small feature maps
-    {128, 128, 2, 1.00f, "128x128,tap9,x2", 4},        // 11
-    {128, 256, 2, 1.00f, "128x256,tap9,2d,x2", 4},     // 12: 2-D 16x16 tiles for maps wider than 78
-    {64, 256, 2, 1.00f, "64x256,tap9,2d,x2", 4},       // 13: ... and Cout <= 64
-    {128, 128, 3, 1.00f, "128x128,K32,S3,x3", 4},      // 14: conv_dma again: 48 KiB LDS, <= 80 VGPRs: three workgroups per CU (short-K 1x1 layers)
-    {256, 224, 1, 1.00f, "256x224,tap9", 4},           // 15: conv_tap.hip variant 6 (see there)
-    {128, 128, 3, 1.00f, "128x128,tap9,2d,x3", 4},     // 16: conv_tap.hip variant 7: 8 x 16 2-D tile, three workgroups per CU
-    {32, 256, 2, 1.00f, "32x256,tap9,2d,x2", 4},       // 17: conv_tap.hip variant 8: 32 couts x (16 x 16)
-    {128, 384, 1, 1.00f, "128x384,tap9,img", 4},       // 18: conv_tap.hip variant 9: one whole image (19 x 19) per tile
-    {128, 192, 1, 1.00f, "128x192,K64,S4", 8},         // 19: conv_dma again: the whole LDS as a four-stage ring (120 KiB in flight), for one-round 1x1 layers on small maps
-    {128, 256, 2, 1.00f, "128x256,tap9,s2,x2", 4},     // 20: conv_tap.hip variant 10: 3x3 / stride 2 with tap reuse over the input's parity planes
-    {128, 384, 1, 1.00f, "128x384,tap9,s2,img", 4},    // 21: conv_tap.hip variant 11: ... one whole (19 x 19) output image per tile
-    {128, 192, 2, 1.00f, "128x192,tap9,img,x2", 4},    // 22: conv_tap.hip variant 12: one whole 12 x 12 / 13 x 13 image per tile (stride 1)
-    {128, 256, 2, 1.00f, "128x256,tap9,s2,wide,x2", 4},   // 23: conv_tap.hip variant 13: tile 20 for output maps up to 158 wide; hosts the back-to-back 1x1
-};
-static const int kNumCfgs = 24;
-static const int kFirstTapCfg = 8, kLastTapCfg = 13;
-static inline bool is_tap_cfg(int cfg) { return (cfg >= kFirstTapCfg && cfg <= kLastTapCfg) || (cfg >= 15 && cfg <= 18) || (cfg >= 20 && cfg <= 23); }
-static inline int tap_variant(int cfg) { return cfg >= 20 ? cfg - 10 : cfg >= 15 ? cfg - 9 : cfg - kFirstTapCfg; }     // conv_tap.hip variant of a tap cfg
-bool dma_cfg_is_tap(int cfg) { return is_tap_cfg(cfg); }
-bool dma_cfg_f32_ok(int cfg) { return is_tap_cfg(cfg) && conv_tap_f32_ok(tap_variant(cfg)); }
-
 // Pick the block tile that minimises rounds x tile time on 256 CUs (tail quantisation matters:
 // e.g. 38x38x512 at batch 32 is 362 tiles of 256x256 = 2 rounds at 71 % but 722 of 256x128 = 3 at 94 %).
 bool dma_cfg_valid(int cfg, int cout, int cin_chunks, bool v1_ok, int ksize, int stride, int W) {
-    if (cfg == 0) return v1_ok;
-    if (cfg < 0 || cfg >= kNumCfgs) return false;
-    const DmaCfg &k = kCfgs[cfg];
+    if (cfg < 0 || cfg >= kNumTiles) return false;
+    const ConvTile &k = conv_tile(cfg);
+    if (k.family == FAM_4WAVE) return v1_ok;
     if (cin_chunks % k.bkc) return false;
-    if (is_tap_cfg(cfg) && (ksize != 3 || stride != (conv_tap_stride2(tap_variant(cfg)) ? 2 : 1) || !conv_tap_fits(tap_variant(cfg), W))) return false;
-    if (k.na == 32) return cout <= 32 && cout > 16;
-    if (k.na == 64) return cout <= 64 && (!is_tap_cfg(cfg) || cout > 32);
-    return k.na <= (cout + 127) / 128 * 128 && cout > 64;
+    if (k.is_tap() && (ksize != 3 || stride != (k.stride2() ? 2 : 1) || !conv_tap_fits(k, W))) return false;
+    if (k.na() == 32) return cout <= 32 && cout > 16;
+    if (k.na() == 64) return cout <= 64 && (!k.is_tap() || cout > 32);
+    return k.na() <= (cout + 127) / 128 * 128 && cout > 64;
 }
 
 // Default tile per layer: a cost model calibrated on MI355X (profiles/r01_ablation.md).  A launch runs
@@ -310,162 +273,139 @@ bool dma_cfg_valid(int cfg, int cout, int cin_chunks, bool v1_ok, int ksize, int
 // workgroups on 256 CUs) vs 71 us on 256x128,K64 (75 measured).  yolo_net_autotune replaces the model by
 // on-device timing when asked.
 // Two-per-CU tiles have three regimes: more workgroups than the 512 slots (back-filled rounds, `a_shared`), between
-// 257 and 512 (one round, most CUs shared and in lockstep: `a_mid`), at most 256 (a workgroup has its CU alone).
-struct TileCost { float a_shared, a_mid, a_alone, f; };   // us per K64 tile, fixed us per round
-static const TileCost kCost[] = {
-    {1.14f, 1.14f, 0.82f, 9.0f},        // 0: 4-wave 128x128, two per CU
-    {1.45f, 1.45f, 1.45f, 20.0f},       // 1: 256x256 K64 S2
-    {0.82f, 0.82f, 0.82f, 12.0f},       // 2: 256x128 K64 S3
-    {0.82f, 0.82f, 0.82f, 12.0f},       // 3: 128x256 K64 S3
-    {1.47f, 1.47f, 1.47f, 20.0f},       // 4: 256x256 K32 S4
-    {1.75f, 1.75f, 1.30f, 8.0f},        // 5: 256x128 K32 S3, two per CU
-    {1.75f, 1.75f, 1.30f, 8.0f},        // 6: 128x256 K32 S3, two per CU
-    {0.0f, 0.0f, 0.0f, 0.0f},           // 7: 64x512 (bandwidth-bound narrow layers: chosen by rule)
-    {1.20f, 1.45f, 0.76f, 7.9f},        // 8: 128x256 tap reuse, two per CU   (fitted on the sweep of tools/gpu_tile_sweep.sh:
-    {1.20f, 1.20f, 1.20f, 20.0f},       // 9: 256x256 tap reuse                v3-608-b32, v3-416-b32, v2-416-b16, within ~8 %)
-    {0.94f, 1.32f, 0.68f, 8.5f},        // 10: 128x192 tap reuse, two per CU
-    {0.76f, 0.90f, 0.63f, 6.9f},        // 11: 128x128 tap reuse, two per CU
-    {0.90f, 1.10f, 0.60f, 17.0f},       // 12: 128x256 tap reuse, 2-D tiles (152x152 64->128: 175 us, 76x76: 117, 38x38: 138)
-    {1.00f, 1.00f, 0.60f, 5.8f},        // 13: 64x256 tap reuse, 2-D tiles (chosen by rule below)
-    {1.10f, 1.50f, 0.70f, 8.0f},        // 14: 128x128 K32 S3, three per CU: 1x1 layers only (short K, memory / latency bound)
-    {1.05f, 1.05f, 1.05f, 18.0f},       // 15: 256x224 tap reuse (7/8 of the 256x256 tile's loop)
-    {0.0f, 0.0f, 0.0f, 0.0f},           // 16: 128x128 2-D tap reuse, three per CU (chosen by rule)
-    {0.0f, 0.0f, 0.0f, 0.0f},           // 17: 32x256 2-D tap reuse (chosen by rule)
-    {0.90f, 0.90f, 0.90f, 18.0f},       // 18: 128x384 image-aligned tap reuse (6/7 of the 256x224 tile's loop)
-    {0.60f, 0.60f, 0.60f, 12.0f},       // 19: 128x192 K64 S4
-    {1.20f, 1.45f, 0.76f, 7.9f},        // 20: 128x256 stride-2 tap reuse, two per CU (as tile 8)
-    {0.90f, 0.90f, 0.90f, 18.0f},       // 21: 128x384 image-aligned stride-2 tap reuse (as tile 18)
-    {0.94f, 1.32f, 0.68f, 8.5f},        // 22: 128x192 image-aligned tap reuse, two per CU (as tile 10)
-    {0.0f, 0.0f, 0.0f, 0.0f},           // 23: wide stride-2 tap reuse (chosen by rule)
-};
-
+// 257 and 512 (one round, most CUs shared and in lockstep: `a_mid`), at most 256 (a workgroup has its CU alone): ConvTile.cost.
 int choose_dma_cfg(int M, int cout, int cin_chunks, int taps, int has_res, bool v1_ok, int stride, int W, bool tap_only) {
     const int ksize = taps == 9 ? 3 : 1;
+    auto valid = [&](int c) { return dma_cfg_valid(c, cout, cin_chunks, v1_ok, ksize, stride, W); };
 #ifdef YOLO_EXPERIMENT      // tools/gpu_tile_sweep.sh: force one tile id on every layer that accepts it
     const char *force = getenv("YOLO_CONV_TILE");
-    if (force && *force && dma_cfg_valid(atoi(force), cout, cin_chunks, v1_ok, ksize, stride, W) && (!tap_only || atoi(force) == 0 || is_tap_cfg(atoi(force))))
+    if (force && *force && valid(atoi(force)) && (!tap_only || conv_tile(atoi(force)).family != FAM_DMA))
         return atoi(force);
 #endif
-    const int fallback = v1_ok ? 0 : -1;
-    if (cout <= 32 && M >= 8192 && dma_cfg_valid(17, cout, cin_chunks, v1_ok, ksize, stride, W)) return 17;     // (tiny-YOLOv2 16 -> 32 at 208 x 208)
+    const int fallback = v1_ok ? TILE_4WAVE : -1;
+    if (cout <= 32 && M >= 8192 && valid(TILE_TAP2D_32x256)) return TILE_TAP2D_32x256;     // (tiny-YOLOv2 16 -> 32 at 208 x 208)
     if (cout <= 64) {   // narrow, bandwidth-bound layers: 3x3/1 with tap reuse (304x304 32->64: 239 us vs 273 on the 64x512 tile)
-        if (M >= 8192 && dma_cfg_valid(13, cout, cin_chunks, v1_ok, ksize, stride, W)) return 13;
-        return !tap_only && dma_cfg_valid(7, cout, cin_chunks, v1_ok, ksize, stride, W) && M >= 8192 ? 7 : fallback;
+        if (M >= 8192 && valid(TILE_TAP2D_64x256)) return TILE_TAP2D_64x256;
+        return !tap_only && valid(TILE_DMA_64x512) && M >= 8192 ? TILE_DMA_64x512 : fallback;
     }
     // wide maps with a short K (152x152 64 -> 128 at batch 32, round 3, after the bias moved into the accumulators and the 2-D
     // tile lost its 36 spilled registers: 155 us on the 128 x 256 2-D tap tile, 161 on the 128 x 128 2-D tile at three
     // workgroups per CU, 175 on the padded-linear 128 x 128 tile, 181 on the per-tap LDS-DMA tile the model picks)
-    if (!tap_only && taps == 9 && stride == 1 && W > 110 && cout <= 128 && cin_chunks <= 8 && M >= 262144 &&
-        dma_cfg_valid(12, cout, cin_chunks, v1_ok, ksize, stride, W))
-        return 12;
+    if (!tap_only && taps == 9 && stride == 1 && W > 110 && cout <= 128 && cin_chunks <= 8 && M >= 262144 && valid(TILE_TAP2D_128x256))
+        return TILE_TAP2D_128x256;
     // ... and at a quarter of that batch the 8 x 16 tile at three workgroups per CU (152x152 64->128 at batch 8: 40 us vs 47.5 on
     // the per-tap LDS-DMA tile the model picks; at batch 32 it is the slower of the two 2-D tiles, 161 vs 155)
-    if (!tap_only && taps == 9 && stride == 1 && W > 110 && cout <= 128 && cin_chunks <= 8 && M >= 65536 && M < 262144 &&
-        dma_cfg_valid(16, cout, cin_chunks, v1_ok, ksize, stride, W))
-        return 16;
+    if (!tap_only && taps == 9 && stride == 1 && W > 110 && cout <= 128 && cin_chunks <= 8 && M >= 65536 && M < 262144 && valid(TILE_TAP2D_128x128_X3))
+        return TILE_TAP2D_128x128_X3;
     // float32, MFMA-bound (fp32 matrix peak is 1/16 of fp16's): long K on a 13x13 map over more than one round of workgroups.  There
     // the padded-linear grid's (14/13)^2 = 16 % of computed-and-dropped positions are the whole difference: tiny-YOLOv2 b64
     // 1024->1024 2.09 ms on the tap tile (97 TFLOP/s) vs 1.81 ms on the 4-wave kernel (113 TFLOP/s = 72 % of the fp32 MFMA peak),
     // 512->1024 1.06 vs 0.91 ms; 256->512 (one round, K 2304) and every 26x26 / 52x52 layer stay faster on the tap tile.
     if (tap_only && v1_ok && taps == 9 && stride == 1 && W <= 14 && taps * cin_chunks * 4 >= 4608 &&
         ((long long)M * (W + 1) * (W + 1) / ((long long)W * W) + 127) / 128 * ((cout + 127) / 128) > 512)
-        return 0;
+        return TILE_4WAVE;
     // (tile 23, the parity-plane tap tile with the back-to-back 1x1 for the stride-2 conv 64 -> 128 into a wide stage, is NOT chosen by
     // rule: at 304 -> 152, batch 32, it measures 211 us against 208 for LDS-DMA tile 6 with the same fusion -- two channel slices are
     // too short a K loop for tap reuse to matter, the launch is the 660 MB it moves)
     const double k64 = taps * cin_chunks / 8.0;         // 64-deep K tiles
     int best = fallback;
     double best_t = 1e300;
-    for (int c = 0; c < kNumCfgs; ++c) {
+    for (int c = 0; c < kNumTiles; ++c) {
+        const ConvTile &k = conv_tile(c);
         // float32 nets: only conv_tap.hip has a float32 instantiation, and it beats the 4-wave kernel by ~10 % on every 3x3/1
         // layer measured (tiny-YOLOv2 b64: 1024->1024 at 13x13 2.26 -> 2.06 ms), so the 4-wave kernel is only the fallback
-        if (tap_only && !dma_cfg_f32_ok(c)) continue;
-        if (c == 12 && W <= 110) continue;      // the padded-linear tiles fit and measured faster (104x104: 70 vs 84 us)
+        if (tap_only && !k.f32_ok()) continue;
+        if (c == TILE_TAP2D_128x256 && W <= 110) continue;      // the padded-linear tiles fit and measured faster (104x104: 70 vs 84 us)
         // the three-per-CU tile: 1x1 layers; measured 10-20 % slower than the larger tiles on every 3x3 layer that fills the chip, but
         // the best tile for a stride-2 layer of 129-256 workgroups (19x19 512->1024 at batch 8: 57 us vs 72 on the 4-wave kernel)
         // (with <= 128 workgroups the 4-wave kernel's split-K wins: 25 vs 49 us at batch 1)
         const long long wg128 = (long long)((M + 127) / 128) * ((cout + 127) / 128);
-        if (c == 14 && taps != 1 && !(stride == 2 && wg128 > 128 && wg128 <= 256)) continue;
-        if (c == 19 && taps != 1) continue;     // (measured on 1x1 layers only)
-        if (c == 7 || c == 13 || c == 16 || c == 17 || c == 23 || !dma_cfg_valid(c, cout, cin_chunks, v1_ok, ksize, stride, W)) continue;
-        const DmaCfg &k = kCfgs[c];
+        if (c == TILE_DMA_128x128_X3 && taps != 1 && !(stride == 2 && wg128 > 128 && wg128 <= 256)) continue;
+        if (c == TILE_DMA_128x192_S4 && taps != 1) continue;     // (measured on 1x1 layers only)
+        if (k.has(CAP_RULE_ONLY) || !valid(c)) continue;
+        const int na = k.na(), nb = k.nb();
         // tap-reuse tiles walk the padded position grid: (H+1)(W+1) positions per image (square maps assumed here)
         long long Meff = M;
-        const int Wq = is_tap_cfg(c) && conv_tap_stride2(tap_variant(c)) ? W / 2 : W;      // width of the map the tap tiles walk
-        if (is_tap_cfg(c) && conv_tap_stride2(tap_variant(c))) {
+        const int Wq = k.stride2() ? W / 2 : W;      // width of the map the tap tiles walk
+        if (k.stride2()) {
             if (cin_chunks <= 8) continue;      // (Cin <= 64, two slices: the LDS-DMA tile that also computes the 1x1 behind it is the better launch)
             Meff = (long long)M * (Wq + 1) * (Wq + 1) / ((long long)Wq * Wq);
-        } else if (is_tap_cfg(c)) {
-            if (conv_tap_is2d(tap_variant(c))) { const long long th = k.nb / 16, tx = (W + 15) / 16, ty = (W + th - 1) / th; Meff = (long long)M * tx * ty * k.nb / ((long long)W * W); }
+        } else if (k.is_tap()) {
+            if (k.is2d()) { const long long th = nb / 16, tx = (W + 15) / 16, ty = (W + th - 1) / th; Meff = (long long)M * tx * ty * nb / ((long long)W * W); }
             else Meff = (long long)M * (W + 1) * (W + 1) / ((long long)W * W);
         }
-        long long blocks = (Meff + k.nb - 1) / k.nb * ((cout + k.na - 1) / k.na);
-        if (is_tap_cfg(c) && conv_tap_image_aligned(tap_variant(c))) blocks = (long long)(M / (Wq * Wq)) * ((cout + k.na - 1) / k.na);    // a tile per image
+        long long blocks = (Meff + nb - 1) / nb * ((cout + na - 1) / na);
+        if (k.image_aligned()) blocks = (long long)(M / (Wq * Wq)) * ((cout + na - 1) / na);    // a tile per image
         // (a stride-2 launch of a handful of tiles belongs to the 4-wave kernel, which splits K: 38 -> 19 at batch 1 25 us there, 58 us here)
-        if (is_tap_cfg(c) && conv_tap_stride2(tap_variant(c)) && blocks <= 128) continue;
-        const long long slots = 256LL * k.slots_per_cu;     // resident workgroups on the chip
+        if (k.stride2() && blocks <= 128) continue;
+        const long long slots = 256LL * k.per_cu();     // resident workgroups on the chip
         // one workgroup per CU: whole rounds; two per CU: the dispatcher back-fills, the tail costs ~half a round
         double rounds, a;
-        if (k.slots_per_cu == 1) {
+        if (k.per_cu() == 1) {
             rounds = (double)((blocks + slots - 1) / slots);
-            a = kCost[c].a_shared;
+            a = k.cost.a_shared;
         } else if (blocks > slots) {
             rounds = (double)blocks / slots + 0.5;
-            a = kCost[c].a_shared;
+            a = k.cost.a_shared;
         } else {
             rounds = 1.0;
-            a = blocks <= 256 ? kCost[c].a_alone : kCost[c].a_mid;
+            a = blocks <= 256 ? k.cost.a_alone : k.cost.a_mid;
         }
-        const double t = rounds * (k64 * a + kCost[c].f * (has_res ? 1.0 : 0.7));
+        const double t = rounds * (k64 * a + k.cost.f * (has_res ? 1.0 : 0.7));
         if (t < best_t) { best_t = t; best = c; }
     }
     return best;
 }
 
-int dma_num_cfgs() { return kNumCfgs; }
-int dma_cfg_na(int cfg) { return cfg > 0 && cfg < kNumCfgs ? kCfgs[cfg].na : 128; }
-int dma_cfg_nb(int cfg) { return cfg > 0 && cfg < kNumCfgs ? kCfgs[cfg].nb : 128; }
-bool dma_cfg_splitk_ok(int cfg) { return is_tap_cfg(cfg) && conv_tap_splitk_ok(tap_variant(cfg)); }
-int dma_cfg_bkc(int cfg) { return cfg > 0 && cfg < kNumCfgs ? kCfgs[cfg].bkc : 8; }
-const char *dma_cfg_name(int cfg) { return cfg > 0 && cfg < kNumCfgs ? kCfgs[cfg].name : ""; }
-
-// tile id, then the template arguments WM, WN, TM, TP, S, BKC, OCC (", "-separated: the stringified list equals the demangled symbol)
-#define YOLO_DMA_VARIANTS(X) \
-    X(1, 2, 4, 8, 4, 2, 8, 2) \
-    X(2, 4, 2, 4, 4, 3, 8, 2) \
-    X(3, 2, 4, 4, 4, 3, 8, 2) \
-    X(4, 2, 4, 8, 4, 4, 4, 2) \
-    X(5, 4, 2, 4, 4, 3, 4, 4) \
-    X(6, 2, 4, 4, 4, 3, 4, 4) \
-    X(7, 1, 8, 4, 4, 2, 4, 4) \
-    X(14, 2, 4, 4, 2, 3, 4, 6) \
-    X(19, 2, 4, 4, 3, 4, 8, 2)
-
-// the epilogue instantiation a launch runs (see the kernel's EPI): 2 = float32 head rows, 1 = lean fp16, 0 = generic
-static inline int dma_epilogue_kind(const ConvParams &p) {
-    if (p.out_f32 && !p.vec_out && p.outmode == OUT_NORMAL && !p.has_res) return 2;
+// Which instantiation of conv_igemm_dma_kernel a launch runs (see its EPI): launch_dma_tile launches it, conv_tile_symbol names it
+static ConvForm dma_form(const ConvTile &t, const ConvParams &p) {
+    if (t.family != FAM_DMA) return FORM_INVALID;
+    if (p.fuse2) return t.has(CAP_FUSE2) && conv_fast_epilogue_ok(p) ? FORM_FUSED : FORM_INVALID;
+    if (p.out_f32 && !p.vec_out && p.outmode == OUT_NORMAL && !p.has_res) return FORM_HEAD_F32;
     static const bool no_fast_epi = getenv("YOLO_NO_FAST_EPI") != nullptr;        // A/B switch, read once (same results either way)
-    return !no_fast_epi && conv_fast_epilogue_ok(p) ? 1 : 0;
+    return !no_fast_epi && conv_fast_epilogue_ok(p) ? FORM_LEAN : FORM_GENERIC;
+}
+static constexpr int dma_epi(ConvForm f) { return f == FORM_HEAD_F32 ? 2 : f == FORM_LEAN ? 1 : 0; }       // the template argument EPI of a form
+
+template <int ID, ConvForm F>
+static hipError_t launch_dma_inst(const ConvParams &p, hipStream_t s) {
+    constexpr ConvTile t = kTiles[ID];
+    hipLaunchKernelGGL((conv_igemm_dma_kernel<t.wm, t.wn, t.tm, t.tp, t.s, t.bkc, t.occ, F == FORM_FUSED, dma_epi(F)>), dim3((unsigned)p.n_blocks), dim3(512), 0, s, p);
+    return hipGetLastError();
+}
+template <int ID>
+static hipError_t launch_dma_tile_id(ConvForm f, const ConvParams &p, hipStream_t s) {
+    constexpr ConvTile t = kTiles[ID];
+    if constexpr (t.family == FAM_DMA) {
+        switch (f) {
+        case FORM_GENERIC: return launch_dma_inst<ID, FORM_GENERIC>(p, s);
+        case FORM_LEAN: return launch_dma_inst<ID, FORM_LEAN>(p, s);
+        case FORM_HEAD_F32: return launch_dma_inst<ID, FORM_HEAD_F32>(p, s);
+        case FORM_FUSED: if constexpr (t.has(CAP_FUSE2)) return launch_dma_inst<ID, FORM_FUSED>(p, s); break;
+        default: break;
+        }
+    }
+    return hipErrorInvalidValue;
+}
+template <int... ID>
+static hipError_t launch_dma_by_id(int id, ConvForm f, const ConvParams &p, hipStream_t s, std::integer_sequence<int, ID...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((id == ID && ((e = launch_dma_tile_id<ID>(f, p, s)), true)) || ...);
+    return e;
 }
 
 static hipError_t launch_dma_tile(const ConvParams &p, int cfg, hipStream_t s) {
-    const dim3 grid((unsigned)p.n_blocks), block(512);
-    if (p.fuse2) {          // back-to-back 1x1: the 128 x 256 K32 tile
-        if (cfg != 6 || !conv_fast_epilogue_ok(p) || p.has_res || p.n_tiles_n != 1 || p.Cout != 128 || !p.w2 || !p.b2 || !p.out2 || !p.out2_bytes) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((conv_igemm_dma_kernel<2, 4, 4, 4, 3, 4, 4, true>), grid, block, 0, s, p);
-        return hipGetLastError();
-    }
-    switch (cfg) {
-#define X(id, ...) case id: \
-        if (dma_epilogue_kind(p) == 2) hipLaunchKernelGGL((conv_igemm_dma_kernel<__VA_ARGS__, false, 2>), grid, block, 0, s, p); \
-        else if (dma_epilogue_kind(p) == 1) hipLaunchKernelGGL((conv_igemm_dma_kernel<__VA_ARGS__, false, 1>), grid, block, 0, s, p); \
-        else hipLaunchKernelGGL((conv_igemm_dma_kernel<__VA_ARGS__, false, 0>), grid, block, 0, s, p); \
-        break;
-        YOLO_DMA_VARIANTS(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const ConvForm f = dma_form(conv_tile(cfg), p);
+    // back-to-back 1x1: the 128 x 256 K32 tile
+    if (f == FORM_FUSED && (p.has_res || p.n_tiles_n != 1 || p.Cout != 128 || !p.w2 || !p.b2 || !p.out2 || !p.out2_bytes)) return hipErrorInvalidValue;
+    return launch_dma_by_id(cfg, f, p, s, std::make_integer_sequence<int, kNumTiles>());
+}
+
+static int tap_stream_wanted() {      // ConvParams.stream of a tap launch: the persistent form where it exists and applies (conv_tap.hip: tap_stream_ok)
+#ifdef YOLO_EXPERIMENT
+    if (getenv("YOLO_NO_TAP_STREAM")) return 0;
+#endif
+    return 1;
 }
 
 #ifdef YOLO_EXPERIMENT
@@ -478,7 +418,7 @@ static hipError_t launch_traced(ConvParams p, int cfg, hipStream_t s) {
     if (hipMalloc((void **)&dev, bytes) != hipSuccess) return hipErrorOutOfMemory;
     (void)hipMemset(dev, 0, bytes);
     p.trace = dev;
-    hipError_t e = is_tap_cfg(cfg) ? launch_conv_tap(p, tap_variant(cfg), s) : launch_dma_tile(p, cfg, s);
+    hipError_t e = conv_tile(cfg).is_tap() ? launch_conv_tap(p, cfg, s) : launch_dma_tile(p, cfg, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     std::vector<unsigned long long> host((size_t)p.n_blocks * 8);
     if (e == hipSuccess) e = hipMemcpy(host.data(), dev, bytes, hipMemcpyDeviceToHost);
@@ -498,34 +438,35 @@ static hipError_t launch_traced(ConvParams p, int cfg, hipStream_t s) {
 #endif
 
 hipError_t launch_conv_dma(const ConvParams &p0, int cfg, hipStream_t s) {
-    if (cfg <= 0 || cfg >= kNumCfgs) return hipErrorInvalidValue;
+    if (cfg <= 0 || cfg >= kNumTiles) return hipErrorInvalidValue;
     ConvParams p = p0;
-    const DmaCfg &k = kCfgs[cfg];
+    const ConvTile &k = conv_tile(cfg);
+    const int na = k.na(), nb = k.nb();
 #ifdef YOLO_EXPERIMENT
     { const char *d = getenv("YOLO_CONV_DBG"); p.dbg = d ? atoi(d) : 0; }
 #endif
-    p.n_tiles_n = (p.Cout + k.na - 1) / k.na;
-    const long long blocks = ((long long)p.M + k.nb - 1) / k.nb * p.n_tiles_n;
+    p.n_tiles_n = (p.Cout + na - 1) / na;
+    const long long blocks = ((long long)p.M + nb - 1) / nb * p.n_tiles_n;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     p.n_blocks = (int)blocks;
     conv_set_divisors(p, p.cin_chunks / k.bkc);
-    if (is_tap_cfg(cfg)) {          // padded-linear position grid: one shared pad column per row, one pad row per image
+    if (k.is_tap()) {          // padded-linear position grid: one shared pad column per row, one pad row per image
         long long mq;
-        if (conv_tap_is2d(tap_variant(cfg))) {     // TH x 16 tiles (TH = positions per block / 16): qW = tiles per tile row, qHW = tiles per image
-            const int th = k.nb / 16;
+        if (k.is2d()) {     // TH x 16 tiles (TH = positions per block / 16): qW = tiles per tile row, qHW = tiles per image
+            const int th = nb / 16;
             p.t2_shift = th == 16 ? 8 : 7;
             if (th != 16 && th != 8) return hipErrorInvalidValue;
             p.qW = (p.W + 15) / 16;
             p.qHW = p.qW * ((p.H + th - 1) / th);
-            mq = (long long)(p.M / p.HoWo) * p.qHW * k.nb;
+            mq = (long long)(p.M / p.HoWo) * p.qHW * nb;
         } else {
             p.qW = p.Wo + 1;          // (stride 1: Ho = H, Wo = W; the stride-2 tiles walk the OUTPUT map)
             p.qHW = (p.Ho + 1) * (p.Wo + 1);
             mq = (long long)(p.M / p.HoWo) * p.qHW;
         }
-        const bool img = conv_tap_image_aligned(tap_variant(cfg));
-        p.q_stride = img ? p.qHW : k.nb;
-        const long long qblocks = img ? (long long)(p.M / p.HoWo) * p.n_tiles_n : (mq + k.nb - 1) / k.nb * p.n_tiles_n;
+        const bool img = k.image_aligned();
+        p.q_stride = img ? p.qHW : nb;
+        const long long qblocks = img ? (long long)(p.M / p.HoWo) * p.n_tiles_n : (mq + nb - 1) / nb * p.n_tiles_n;
         if (qblocks <= 0 || qblocks > 0x7fffffffLL) return hipErrorInvalidValue;
         p.Mq = (int)mq;
         p.n_blocks = (int)qblocks;
@@ -533,11 +474,8 @@ hipError_t launch_conv_dma(const ConvParams &p0, int cfg, hipStream_t s) {
 #ifdef YOLO_EXPERIMENT
         if (getenv("YOLO_CONV_TRACE")) return launch_traced(p, cfg, s);
 #endif
-        p.stream = 1;       // the persistent form of the tap kernel where it exists and applies (conv_tap.hip: conv_tap_stream_ok)
-#ifdef YOLO_EXPERIMENT
-        if (getenv("YOLO_NO_TAP_STREAM")) p.stream = 0;
-#endif
-        return launch_conv_tap(p, tap_variant(cfg), s);
+        p.stream = tap_stream_wanted();
+        return launch_conv_tap(p, cfg, s);
     }
 #ifdef YOLO_EXPERIMENT
     if (getenv("YOLO_CONV_TRACE")) return launch_traced(p, cfg, s);
@@ -545,36 +483,20 @@ hipError_t launch_conv_dma(const ConvParams &p0, int cfg, hipStream_t s) {
     return launch_dma_tile(p, cfg, s);
 }
 
-std::string dma_cfg_symbol_for(int cfg, bool f32, const ConvParams &p) {
-    if (p.fuse2) return cfg == 6 ? "void yolo::conv_igemm_dma_kernel<2, 4, 4, 4, 3, 4, 4, true, 0>(yolo::ConvParams)"
-                       : cfg == 23 ? "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 4, 4, false, true, true>(yolo::ConvParams)"
-                                   : "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 4, 27, 4, 2, false, true, true>(yolo::ConvParams)";
-    if (is_tap_cfg(cfg) && p.ksplit > 1) return conv_tap_splitk_symbol(tap_variant(cfg), f32);
-    if (is_tap_cfg(cfg) && conv_tap_stream_ok(p, tap_variant(cfg))) return conv_tap_stream_symbol(tap_variant(cfg));
-    if (!is_tap_cfg(cfg)) {     // the LDS-DMA kernel: last template argument = the epilogue kind of this launch
-        std::string sym = dma_cfg_symbol(cfg, f32, false);
-        const size_t at = sym.rfind(", false, 0>(");
-        if (at != std::string::npos) sym[at + 9] = (char)('0' + dma_epilogue_kind(p));
-        return sym;
+// the name rocprofv3's kernel trace prints for the kernel that runs THIS launch of a tile (yolo_kernel_info.symbol: joins bench.py's
+// roofline to profiles/*.csv); p as launched: ksplit, pair, fuse2 set
+std::string conv_tile_symbol(int cfg, ConvParams p) {
+    const ConvTile &t = conv_tile(cfg);
+    if (t.is_tap()) {
+        p.stream = tap_stream_wanted();
+        return conv_tap_symbol(t, p);
     }
-    std::string sym = dma_cfg_symbol(cfg, f32, !f32 && conv_fast_epilogue_ok(p) && cfg != 20 && cfg != 23);
-    if (is_tap_cfg(cfg) && p.outmode == OUT_POOL2) {        // the fused-pool instantiation: template argument MODE 3 instead of 2
-        const size_t at = sym.rfind(", 2, false, false, false>(");
-        if (at != std::string::npos) sym.replace(at, 26, ", 3, false, false, false>(");
-    }
-    return sym;
-}
-
-// the name rocprofv3's kernel trace prints for the kernel a tile id runs (yolo_kernel_info.symbol)
-const char *dma_cfg_symbol(int cfg, bool f32, bool fast) {
-    if (is_tap_cfg(cfg)) return conv_tap_symbol(tap_variant(cfg), f32, fast);
-    switch (cfg) {
-#define X(id, ...) case id: return fast ? "void yolo::conv_igemm_dma_kernel<" #__VA_ARGS__ ", false, 1>(yolo::ConvParams)" \
-                                          : "void yolo::conv_igemm_dma_kernel<" #__VA_ARGS__ ", false, 0>(yolo::ConvParams)";
-        YOLO_DMA_VARIANTS(X)
-#undef X
-    default: return "";
-    }
+    const ConvForm f = dma_form(t, p);
+    if (f == FORM_INVALID) return "";
+    char b[160];
+    snprintf(b, sizeof b, "void yolo::conv_igemm_dma_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %d>(yolo::ConvParams)", t.wm, t.wn, t.tm, t.tp, t.s, t.bkc, t.occ,
+             f == FORM_FUSED ? "true" : "false", dma_epi(f));
+    return b;
 }
 
 }  // namespace yolo

@@ -25,7 +25,10 @@
 // LDS-DMA ring (slot = tap % 3), the patch of slice c+1 is fetched into the other patch buffer during the taps
 // of slice c.  One barrier per tap; vmcnt waits are counted so that the patch may stay in flight for three taps.
 #include "conv_common.h"
+#include "conv_tiles.h"
+#include <cstdio>
 #include <type_traits>
+#include <utility>
 
 #ifndef YOLO_TAP_ASM_MFMA
 #define YOLO_TAP_ASM_MFMA 1
@@ -202,7 +205,7 @@ __global__ void __launch_bounds__(WM * WN * 64, OCC) conv3x3_tap_kernel(const Co
     const int mt = (int)fdiv((uint32_t)bid, p.dtiles_n);
     const int nt = bid - mt * p.n_tiles_n;
     const int n0 = nt * NA;
-    const int q0 = mt * p.q_stride;    // NB, or (H+1)(W+1) for the image-aligned tile (variant 9)
+    const int q0 = mt * p.q_stride;    // NB, or (H+1)(W+1) for an image-aligned tile
     const bool has_a = JA_TOT % NW == 0 || wave < JA_TOT;   // wave-uniform
 
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.in), 0, p.in_bytes, 0x00020000);
@@ -967,192 +970,146 @@ __global__ void __launch_bounds__(512, OCC) conv3x3_tap_stream_kernel(const Conv
     }
 }
 
-// (6 = 256 couts x 224 positions, one workgroup per CU: 19 x 19 maps at batch 32 are 12 800 padded positions -> 58 x 4 = 232
-// tiles on 256 CUs, where the 256-position tiles leave 200 or 400 workgroups on 256 / 512 slots)
-// variants: 0 = 128 couts x 256 positions, 1 = 256 x 256 (one workgroup per CU), 2 = 128 x 192, 3 = 128 x 128 (smaller
-// position tiles fill the 512 workgroup slots of the chip better on small feature maps), all padded-linear;
-// 4 = 128 x (16 x 16) and 5 = 64 x (16 x 16) 2-D tiles for maps wider than 78 (any width)
-// 7 = 128 couts x (8 x 16) 2-D tile at THREE workgroups per CU (48 KiB LDS, <= 80 VGPRs) for wide maps with a short K, where
-// a workgroup spends as long in setup + epilogue as in its K loop (152 x 152 64 -> 128: block trace in profiles/r03_ablation.md)
-// 8 = 32 couts x (16 x 16): the one 3x3 layer with 32 filters behind the first conv (tiny-YOLOv2 16 -> 32 at 208 x 208; float32 MFMA is 1/16 of
-// fp16's, so the 64-cout tile's idle half would double a launch that is MFMA-bound)
-// 9 = 128 couts x 384 positions, IMAGE-ALIGNED, one workgroup per CU: a tile is one whole image of a map with H (W+1) <= 384 (19 x 19:
-// 380), tile m starts at position m (H+1)(W+1) -- the shared pad row behind every image is never computed (6 % of the positions are
-// padding instead of 10.8 %) and 19 x 19 at batch 32 is 32 x 8 = 256 tiles: every CU busy, 14 % less work per CU than the 232 tiles
-// of variant 6
-// 10 = 128 x 256 and 11 = 128 x 384 image-aligned for 3x3 / STRIDE 2 (MODE 4: parity planes of the input, see the kernel): fp16 only
-// 12 = 128 x 192 image-aligned: one 12 x 12 or 13 x 13 image per tile (YOLOv2-416 / YOLOv3-416 tails: 13 x 14 = 182 of 192 positions
-// real, where 256-position tiles of the padded-linear grid compute 23 % padding); with the in-launch pair split 16 images x 8 cout
-// tiles x 2 K halves = 256 workgroups
-// 13 = variant 10 with a patch of 26 row groups (output maps up to 158 wide): the stride-2 conv into the 152 x 152 stage, whose
-// workgroups hold all 128 couts of 256 positions -- the one stride-2 tile with the back-to-back 1x1 instantiation (FUSE2)
-// (round 5, measured and NOT kept -- profiles/r05_ablation.md, source in commit 57e38ee: variant 0's block tile as four fat waves of 64 couts x 128
-// positions with the position fragments prefetched across the barrier, +0.5 ... +2.5 % slower; variant 9's 128 x 384 tile on the padded-linear grid
-// for 38 x 38 maps -- 508 tiles on 256 CUs -- +4.3 % slower than the 764 workgroups of variant 0; position fragments of the taps kw = 1, 2 by DPP lane
+// The tiles are rows of kTiles (conv_tiles.h; what each is for is said there): the launchers below instantiate from the row.
+// (round 5, measured and NOT kept -- profiles/r05_ablation.md, source in commit 57e38ee: tile 8's block tile as four fat waves of 64 couts x 128
+// positions with the position fragments prefetched across the barrier, +0.5 ... +2.5 % slower; tile 18's 128 x 384 tile on the padded-linear grid
+// for 38 x 38 maps -- 508 tiles on 256 CUs -- +4.3 % slower than the 764 workgroups of tile 8; position fragments of the taps kw = 1, 2 by DPP lane
 // shifts instead of LDS reads, correct and +5 ... +9 % slower)
-static const int kTapNB[] = {256, 256, 192, 128, 256, 256, 224, 128, 256, 384, 256, 384, 192, 256};
-static const int kTapPRG[] = {26, 26, 26, 28, 27, 27, 17, 12, 27, 27, 21, 26, 14, 26};
-static const int kTapTP[] = {4, 4, 3, 2, 4, 2, 7, 2, 2, 6, 4, 6, 3, 4};        // TP of the variant (YOLO_TAP_VARIANTS below): position fragments per wave
-static const int kTapVariants = 14;
-static const bool kTapF32[] = {false, false, false, true, false, true, false, false, true, false, false, false, false, false};      // float32 tiles: TP <= 2 (second-level accumulator)
-bool conv_tap_image_aligned(int variant) { return variant == 9 || variant == 11 || variant == 12; }
-bool conv_tap_stride2(int variant) { return variant == 10 || variant == 11 || variant == 13; }
-bool conv_tap_splitk_ok(int variant) { return variant == 3; }      // the 128 x 128 tile has the (two-pass) split-K instantiation
-bool conv_tap_pair_ok(int variant, bool f32) { return variant == 3 || ((variant == 0 || variant == 12) && !f32); }   // in-launch pair split: also the fp16 128 x 256 and image-aligned 128 x 192 tiles
-bool conv_tap_is2d(int variant) { return variant == 4 || variant == 5 || variant == 7 || variant == 8; }
-bool conv_tap_f32_ok(int variant) { return variant >= 0 && variant < kTapVariants && kTapF32[variant]; }
-bool conv_tap_fits(int variant, int W) {
-    if (variant < 0 || variant >= kTapVariants) return false;
-    if (conv_tap_is2d(variant)) return true;
-    if (conv_tap_stride2(variant)) {        // W = the INPUT's width (even); the position grid is the output's
+bool conv_tap_fits(const ConvTile &t, int W) {
+    if (!t.is_tap()) return false;
+    if (t.is2d()) return true;
+    if (t.stride2()) {        // W = the INPUT's width (even); the position grid is the output's
         if (W & 1) return false;
         W >>= 1;
     }
     // (the image-aligned tile: square maps of 17 .. 19 -- a whole image per tile with at least 80 % of the positions real)
-    if (conv_tap_image_aligned(variant) && (W * (W + 1) > kTapNB[variant] || W * (W + 1) * 5 < kTapNB[variant] * 4)) return false;
-    if (conv_tap_stride2(variant)) return kTapNB[variant] + W + 2 <= kTapPRG[variant] * 16;
+    if (t.image_aligned() && (W * (W + 1) > t.nb() || W * (W + 1) * 5 < t.nb() * 4)) return false;
+    if (t.stride2()) return t.nb() + W + 2 <= t.prg * 16;
     // (position-interleaved fragments: the patch buffer holds TP planes of PRG * 16 / TP whole rows)
-    const int tp = kTapTP[variant], rows = YOLO_TAP_PIL ? kTapPRG[variant] * 16 / tp * tp : kTapPRG[variant] * 16;
-    return kTapNB[variant] + 2 * W + 4 <= rows;
+    const int rows = YOLO_TAP_PIL ? t.prg * 16 / t.tp * t.tp : t.prg * 16;
+    return t.nb() + 2 * W + 4 <= rows;
 }
 
-// variant id, then the template arguments after F32: WM, WN, TM, TP, PRG, OCC, MODE (written with ", " so that the
-// stringified list equals the demangled symbol)
-#define YOLO_TAP_VARIANTS(X) \
-    X(0, 2, 4, 4, 4, 26, 4, 1) \
-    X(1, 2, 4, 8, 4, 26, 2, 1) \
-    X(2, 2, 4, 4, 3, 26, 4, 1) \
-    X(3, 2, 4, 4, 2, 28, 4, 1) \
-    X(4, 2, 4, 4, 4, 27, 4, 2) \
-    X(5, 1, 8, 4, 2, 27, 4, 2) \
-    X(6, 4, 2, 4, 7, 17, 2, 1) \
-    X(7, 2, 4, 4, 2, 12, 6, 2) \
-    X(8, 1, 8, 2, 2, 27, 4, 2) \
-    X(9, 2, 4, 4, 6, 27, 2, 1) \
-    X(10, 2, 4, 4, 4, 21, 4, 4) \
-    X(11, 2, 4, 4, 6, 26, 2, 4) \
-    X(12, 2, 4, 4, 3, 14, 4, 1) \
-    X(13, 2, 4, 4, 4, 26, 4, 4)
-
-const char *conv_tap_symbol(int variant, bool f32, bool fast) {
-    switch (variant) {
-#define X(id, ...) case id: return f32 ? "void yolo::conv3x3_tap_kernel<true, " #__VA_ARGS__ ", false, false, false>(yolo::ConvParams)" \
-                                       : fast ? "void yolo::conv3x3_tap_kernel<false, " #__VA_ARGS__ ", false, true, false>(yolo::ConvParams)" \
-                                              : "void yolo::conv3x3_tap_kernel<false, " #__VA_ARGS__ ", false, false, false>(yolo::ConvParams)";
-        YOLO_TAP_VARIANTS(X)
-#undef X
-    default: return "";
-    }
-}
-
-// the persistent form (conv3x3_tap_stream_kernel) is instantiated for variant 5 only (64 couts x 16 x 16 pixels, 93 VGPRs, no spill:
-// 304 x 304 32 -> 64 at batch 32 0.242 -> 0.225 ms).  The TP = 4 tiles (variants 0 and 4) sit at the 128-register limit of two
+// The persistent form (conv3x3_tap_stream_kernel, CAP_STREAM) exists for the 64 couts x 16 x 16 tile only (93 VGPRs, no spill:
+// 304 x 304 32 -> 64 at batch 32 0.242 -> 0.225 ms).  The TP = 4 tiles (8 and 12) sit at the 128-register limit of two
 // workgroups per CU: with the loop state of the stream they spill (19-23 VGPRs with all four residual fragments in flight, 5-17 with
 // the two-deep residual pipeline the epilogue has for them), reloads land inside the K loop (each a `s_waitcnt vmcnt(0)` that drains
 // the DMA pipeline) and the launches got SLOWER both times: 76 x 76 +15 % / +3 %, 152 x 152 +6.5 % / +13 % (profiles/r03_ablation.md).
 // (round 5: with the MFMAs in place the 128 x 256 tile compiles in this form without a spill -- 123 registers -- and is still slower than the
 // plain kernel: 76 x 76 +3 ... +5 %, 38 x 38 +-0, profiles/r05_ablation.md section 6; so it stays the 64-cout tile's alone)
-#define YOLO_TAP_STREAM_VARIANTS(X) \
-    X(5, 1, 8, 4, 2, 27, 4, 2)
-
-const char *conv_tap_stream_symbol(int variant) {
-    switch (variant) {
-#define X(id, ...) case id: return "void yolo::conv3x3_tap_stream_kernel<" #__VA_ARGS__ ">(yolo::ConvParams)";
-        YOLO_TAP_STREAM_VARIANTS(X)
-#undef X
-    default: return "";
-    }
-}
-
-// the split-K instantiations (launch_conv_tap, p.ksplit > 1): the 128 x 128 tile, and for the in-launch pair the fp16 128 x 256 and
-// image-aligned 128 x 192 tiles built for one workgroup per CU (OCC 2)
-const char *conv_tap_splitk_symbol(int variant, bool f32) {
-    if (variant == 0) return "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 2, 1, true, false, false>(yolo::ConvParams)";
-    if (variant == 12) return "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 3, 14, 2, 1, true, false, false>(yolo::ConvParams)";
-    return f32 ? "void yolo::conv3x3_tap_kernel<true, 2, 4, 4, 2, 28, 4, 1, true, false, false>(yolo::ConvParams)"
-               : "void yolo::conv3x3_tap_kernel<false, 2, 4, 4, 2, 28, 4, 1, true, false, false>(yolo::ConvParams)";
-}
-
-bool conv_tap_stream_ok(const ConvParams &p, int variant) {
-    if (variant != 5) return false;
+static bool tap_stream_ok(const ConvTile &t, const ConvParams &p) {
+    if (!t.has(CAP_STREAM)) return false;
     if (p.f32 || p.out_f32 || p.ksplit > 1 || p.outmode != OUT_NORMAL || !p.vec_out || (p.has_res && (!p.vec_res || !p.res_bytes)) || !p.out_bytes) return false;
-    if (p.Cout % 16 || (p.Cout + 127) / 128 * 128 > kTapStreamBiasFloats) return false;
-    return true;
+    return p.Cout % 16 == 0 && (p.Cout + 127) / 128 * 128 <= kTapStreamBiasFloats;
 }
 
-static hipError_t launch_conv_tap_stream(const ConvParams &p0, int variant, hipStream_t s) {
-    ConvParams p = p0;
-    p.cout_pad = (p.Cout + 127) / 128 * 128;
-    const int slots = 512;              // two workgroups per CU (every stream variant is OCC 4)
-    const dim3 grid((unsigned)(p.n_blocks < slots ? p.n_blocks : slots));
-    switch (variant) {
-#define X(id, ...) case id: hipLaunchKernelGGL((conv3x3_tap_stream_kernel<__VA_ARGS__>), grid, dim3(512), 0, s, p); break;
-        YOLO_TAP_STREAM_VARIANTS(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
+// ConvParams.fast_epi of a launch: the lean epilogue applies and the tile runs it (the fused pair exists in the lean form only)
+static bool tap_lean(const ConvTile &t, const ConvParams &p) {
+    static const bool no_fast_epi = getenv("YOLO_NO_FAST_EPI") != nullptr;        // A/B switch, read once (same results either way)
+    return (!no_fast_epi || p.fuse2) && conv_fast_epilogue_ok(p) && (!t.has(CAP_NO_LEAN) || p.fuse2);
+}
+
+// Which instantiation a launch runs (p as launched: stream, ksplit, pair, outmode, fuse2): launch_conv_tap launches it, conv_tap_symbol names it
+static ConvForm tap_form(const ConvTile &t, const ConvParams &p) {
+    if (!t.is_tap() || (p.f32 && !t.f32_ok())) return FORM_INVALID;
+    if (p.stream && tap_stream_ok(t, p)) return FORM_STREAM;
+    if (p.ksplit > 1) return (p.pair ? t.split_occ != 0 : t.has(CAP_SPLITK)) ? FORM_SPLITK : FORM_INVALID;
+    if (p.outmode == OUT_POOL2) return t.has(CAP_POOL) ? FORM_POOL : FORM_INVALID;
+    if (p.fuse2) return t.has(CAP_FUSE2) && tap_lean(t, p) ? FORM_FUSED : FORM_INVALID;
+    return !p.f32 && tap_lean(t, p) ? FORM_LEAN : FORM_GENERIC;
+}
+
+// the template arguments of conv3x3_tap_kernel that a form changes or adds: split-K runs the build for split_occ, the pool is MODE 3
+struct TapInst { bool f32; int occ, mode; bool splitk, fast, fuse2; };
+static constexpr TapInst tap_inst(const ConvTile &t, ConvForm f, bool f32) {
+    return {f32, f == FORM_SPLITK ? t.split_occ : t.occ, f == FORM_POOL ? 3 : t.mode, f == FORM_SPLITK, f == FORM_LEAN || f == FORM_FUSED, f == FORM_FUSED};
+}
+
+// the name rocprofv3's kernel trace prints for the kernel this launch runs (yolo_kernel_info.symbol)
+std::string conv_tap_symbol(const ConvTile &t, const ConvParams &p) {
+    const ConvForm f = tap_form(t, p);
+    if (f == FORM_INVALID) return "";
+    char b[192];
+    auto tf = [](bool v) { return v ? "true" : "false"; };
+    const TapInst i = tap_inst(t, f, p.f32 != 0);
+    if (f == FORM_STREAM) snprintf(b, sizeof b, "void yolo::conv3x3_tap_stream_kernel<%d, %d, %d, %d, %d, %d, %d>(yolo::ConvParams)", t.wm, t.wn, t.tm, t.tp, t.prg, t.occ, t.mode);
+    else snprintf(b, sizeof b, "void yolo::conv3x3_tap_kernel<%s, %d, %d, %d, %d, %d, %d, %d, %s, %s, %s>(yolo::ConvParams)", tf(i.f32), t.wm, t.wn, t.tm, t.tp, t.prg,
+                  i.occ, i.mode, tf(i.splitk), tf(i.fast), tf(i.fuse2));
+    return b;
+}
+
+template <int ID, ConvForm F, bool F32>
+static hipError_t launch_tap_inst(const ConvParams &p, dim3 grid, hipStream_t s) {
+    constexpr ConvTile t = kTiles[ID];
+    constexpr TapInst i = tap_inst(t, F, F32);
+    hipLaunchKernelGGL((conv3x3_tap_kernel<i.f32, t.wm, t.wn, t.tm, t.tp, t.prg, i.occ, i.mode, i.splitk, i.fast, i.fuse2>), grid, dim3(512), 0, s, p);
     return hipGetLastError();
 }
+// ... in fp16, and in float32 where the form has that build
+template <int ID, ConvForm F, bool HAS_F32>
+static hipError_t launch_tap_dtype(const ConvParams &p, dim3 grid, hipStream_t s) {
+    if constexpr (HAS_F32) if (p.f32) return launch_tap_inst<ID, F, true>(p, grid, s);
+    return launch_tap_inst<ID, F, false>(p, grid, s);
+}
 
-hipError_t launch_conv_tap(const ConvParams &p0, int variant, hipStream_t s) {
+template <int ID>
+static hipError_t launch_tap_tile(ConvForm f, const ConvParams &p0, dim3 grid, hipStream_t s) {
+    constexpr ConvTile t = kTiles[ID];
+    if constexpr (t.is_tap()) {
+        switch (f) {
+        case FORM_GENERIC: return launch_tap_dtype<ID, FORM_GENERIC, true>(p0, grid, s);      // (the float32 build exists for every tile; tap_form lets only CAP_F32 tiles reach it)
+        case FORM_LEAN: return launch_tap_inst<ID, FORM_LEAN, false>(p0, grid, s);
+        case FORM_SPLITK: if constexpr (t.split_occ != 0) return launch_tap_dtype<ID, FORM_SPLITK, t.f32_ok()>(p0, grid, s); break;
+        case FORM_POOL: if constexpr (t.has(CAP_POOL)) return launch_tap_dtype<ID, FORM_POOL, t.f32_ok()>(p0, grid, s); break;
+        case FORM_FUSED: if constexpr (t.has(CAP_FUSE2)) return launch_tap_inst<ID, FORM_FUSED, false>(p0, grid, s); break;
+        case FORM_STREAM:
+            if constexpr (t.has(CAP_STREAM)) {
+                ConvParams p = p0;
+                p.cout_pad = (p.Cout + 127) / 128 * 128;
+                const int slots = 256 * t.per_cu();
+                hipLaunchKernelGGL((conv3x3_tap_stream_kernel<t.wm, t.wn, t.tm, t.tp, t.prg, t.occ, t.mode>), dim3((unsigned)(p.n_blocks < slots ? p.n_blocks : slots)), dim3(512), 0, s, p);
+                return hipGetLastError();
+            }
+            break;
+        default: break;
+        }
+    }
+    return hipErrorInvalidValue;
+}
+template <int... ID>
+static hipError_t launch_tap_by_id(int id, ConvForm f, const ConvParams &p, dim3 grid, hipStream_t s, std::integer_sequence<int, ID...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((id == ID && ((e = launch_tap_tile<ID>(f, p, grid, s)), true)) || ...);
+    return e;
+}
+
+hipError_t launch_conv_tap(const ConvParams &p0, int tile, hipStream_t s) {
+    if (tile < 0 || tile >= kNumTiles) return hipErrorInvalidValue;
+    const ConvTile &t = conv_tile(tile);
     ConvParams p = p0;
-    static const bool no_fast_epi = getenv("YOLO_NO_FAST_EPI") != nullptr;        // A/B switch, read once (same results either way)
-    // (variant 10, the two-per-CU stride-2 tile: its lean instantiation spills 13 registers at the 128-register limit; the generic one does not)
-    p.fast_epi = (!no_fast_epi || p.fuse2) && conv_fast_epilogue_ok(p) && variant != 10 && (variant != 13 || p.fuse2) ? 1 : 0;      // (the fused pair exists in the lean form only)
-    const bool s2 = conv_tap_stride2(variant);
-    if (p.ksize != 3 || p.stride != (s2 ? 2 : 1) || p.pad != 1 || (p.cin_chunks & 3) || !conv_tap_fits(variant, p.W) || (p.f32 && !conv_tap_f32_ok(variant)))
+    p.fast_epi = tap_lean(t, p) ? 1 : 0;
+    const bool s2 = t.stride2();
+    if (p.ksize != 3 || p.stride != (s2 ? 2 : 1) || p.pad != 1 || (p.cin_chunks & 3) || !conv_tap_fits(t, p.W) || (p.f32 && !t.f32_ok()))
         return hipErrorInvalidValue;
-    if (s2 ? ((p.H & 1) || (p.W & 1) || p.Ho * 2 != p.H || p.Wo * 2 != p.W || p.f32 || p.ksplit > 1 || (p.fuse2 && variant != 13) || p.outmode == OUT_POOL2 || p.qW != p.Wo + 1)
+    if (s2 ? ((p.H & 1) || (p.W & 1) || p.Ho * 2 != p.H || p.Wo * 2 != p.W || p.f32 || p.ksplit > 1 || (p.fuse2 && !t.has(CAP_FUSE2)) || p.outmode == OUT_POOL2 || p.qW != p.Wo + 1)
            : (p.Ho != p.H || p.Wo != p.W))
         return hipErrorInvalidValue;
-    if (conv_tap_image_aligned(variant) ? (p.q_stride != p.qHW || p.Ho * (p.Wo + 1) > kTapNB[variant]) : (!conv_tap_is2d(variant) && p.q_stride != kTapNB[variant]))
+    if (t.image_aligned() ? (p.q_stride != p.qHW || p.Ho * (p.Wo + 1) > t.nb()) : (!t.is2d() && p.q_stride != t.nb()))
         return hipErrorInvalidValue;
-    if (p.outmode == OUT_POOL2 && ((variant != 4 && variant != 5 && variant != 8) || (p.H & 1) || (p.W & 1) || p.has_res || p.ksplit > 1 || !p.vec_out || p.Cout % 16))
-        return hipErrorInvalidValue;        // the fused pool lives in the 2-D tiles' epilogue only (plan.cpp asks for it accordingly)
-    if (p.stream && conv_tap_stream_ok(p, variant)) return launch_conv_tap_stream(p, variant, s);
+    if (p.outmode == OUT_POOL2 && (!t.has(CAP_POOL) || (p.H & 1) || (p.W & 1) || p.has_res || p.ksplit > 1 || !p.vec_out || p.Cout % 16))
+        return hipErrorInvalidValue;        // the fused pool lives in the 16 x 16 2-D tiles' epilogue only (plan.cpp asks for it accordingly)
+    const ConvForm f = tap_form(t, p);
+    if (f == FORM_SPLITK) {
+        if (!p.part || p.kunits < 1 || (long long)p.ksplit * p.kunits < (p.cin_chunks >> 2)) return hipErrorInvalidValue;
+        if (p.pair && (p.ksplit < 2 || (p.ksplit > 2 && !t.has(CAP_SPLITK)) || !p.pair_cnt || p.n_blocks > 512 ||        // (512 padded tickets: api.cpp kPairCounterBytes)
+                       (unsigned long long)p.n_blocks * (unsigned long long)p.ksplit * 128ull * t.nb() * 4ull > p.part_bytes))
+            return hipErrorInvalidValue;
+    }
+    // back-to-back 1x1: the 2-D 128 x 256 tile (residual block's 3x3) or the wide stride-2 tile (no residual)
+    if (f == FORM_FUSED && (t.has(CAP_FUSE2_RES) != (p.has_res != 0) || p.n_tiles_n != 1 || p.Cout != 128 || !p.w2 || !p.b2 || !p.out2 || !p.out2_bytes))
+        return hipErrorInvalidValue;
     const dim3 grid((unsigned)p.n_blocks, (unsigned)(p.ksplit > 1 ? p.ksplit : 1));
-    if (p.ksplit > 1) {     // split-K instantiation (128 x 128 tile)
-        if (!(p.pair ? conv_tap_pair_ok(variant, p.f32 != 0) : conv_tap_splitk_ok(variant)) || !p.part || p.kunits < 1 ||
-            (long long)p.ksplit * p.kunits < (p.cin_chunks >> 2))
-            return hipErrorInvalidValue;
-        if (p.pair && (p.ksplit < 2 || (p.ksplit > 2 && variant != 3) || !p.pair_cnt || p.n_blocks > 512 ||        // (512 padded tickets: api.cpp kPairCounterBytes)
-                       (unsigned long long)p.n_blocks * (unsigned long long)p.ksplit * 128ull * kTapNB[variant] * 4ull > p.part_bytes))
-            return hipErrorInvalidValue;
-        // (OCC 2 = up to 256 registers: the pair launches are <= 512 workgroups of half K on 256 CUs, and the 128 x 256 tile + the
-        // hand-off state spills at the 128 registers of two-per-CU residency)
-        if (variant == 0) hipLaunchKernelGGL((conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 2, 1, true>), grid, dim3(512), 0, s, p);
-        else if (variant == 12) hipLaunchKernelGGL((conv3x3_tap_kernel<false, 2, 4, 4, 3, 14, 2, 1, true>), grid, dim3(512), 0, s, p);
-        else if (p.f32) hipLaunchKernelGGL((conv3x3_tap_kernel<true, 2, 4, 4, 2, 28, 4, 1, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((conv3x3_tap_kernel<false, 2, 4, 4, 2, 28, 4, 1, true>), grid, dim3(512), 0, s, p);
-        return hipGetLastError();
-    }
-    if (p.outmode == OUT_POOL2) {       // MODE 3 = the 2-D tile + the max-pool in the epilogue: variants 4 (fp16) and 5 (fp16, float32)
-        if (variant == 4 && !p.f32) hipLaunchKernelGGL((conv3x3_tap_kernel<false, 2, 4, 4, 4, 27, 4, 3, false>), grid, dim3(512), 0, s, p);
-        else if (variant == 5 && !p.f32) hipLaunchKernelGGL((conv3x3_tap_kernel<false, 1, 8, 4, 2, 27, 4, 3, false>), grid, dim3(512), 0, s, p);
-        else if (variant == 5) hipLaunchKernelGGL((conv3x3_tap_kernel<true, 1, 8, 4, 2, 27, 4, 3, false>), grid, dim3(512), 0, s, p);
-        else if (variant == 8 && !p.f32) hipLaunchKernelGGL((conv3x3_tap_kernel<false, 1, 8, 2, 2, 27, 4, 3, false>), grid, dim3(512), 0, s, p);
-        else if (variant == 8) hipLaunchKernelGGL((conv3x3_tap_kernel<true, 1, 8, 2, 2, 27, 4, 3, false>), grid, dim3(512), 0, s, p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (p.fuse2) {          // back-to-back 1x1: the 2-D 128 x 256 tile (residual block's 3x3) or the wide stride-2 tile (no residual), lean epilogue
-        if ((variant != 4 && variant != 13) || !p.fast_epi || (variant == 4) != (p.has_res != 0) || p.n_tiles_n != 1 || p.Cout != 128 || !p.w2 || !p.b2 || !p.out2 || !p.out2_bytes)
-            return hipErrorInvalidValue;
-        if (variant == 4) hipLaunchKernelGGL((conv3x3_tap_kernel<false, 2, 4, 4, 4, 27, 4, 2, false, true, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 4, 4, false, true, true>), grid, dim3(512), 0, s, p);
-        return hipGetLastError();
-    }
-    switch (variant) {
-#define X(id, ...) case id: \
-        if (p.f32) hipLaunchKernelGGL((conv3x3_tap_kernel<true, __VA_ARGS__, false>), grid, dim3(512), 0, s, p); \
-        else if (p.fast_epi) hipLaunchKernelGGL((conv3x3_tap_kernel<false, __VA_ARGS__, false, true>), grid, dim3(512), 0, s, p); \
-        else hipLaunchKernelGGL((conv3x3_tap_kernel<false, __VA_ARGS__, false>), grid, dim3(512), 0, s, p); \
-        break;
-        YOLO_TAP_VARIANTS(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_tap_by_id(tile, f, p, grid, s, std::make_integer_sequence<int, kNumTiles>());
 }
 
 }  // namespace yolo

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <sstream>
 
+#include "conv_tiles.h"
 #include "yolo_internal.h"
 
 namespace yolo {
@@ -489,7 +490,7 @@ struct Planner {
                     }
                 }
                 // conv 3x3/1 -> max-pool 2x2/2 on a wide map: the pool is taken in the conv's epilogue (conv_common.h:
-                // conv_epilogue_pool2, 2-D tap tiles only, so the conv is pinned to one: 13 = 64 couts, 12 = 128-cout tiles) and the
+                // conv_epilogue_pool2, the CAP_POOL 2-D tap tiles only, so the conv is pinned to the one of its width) and the
                 // full-resolution tensor is never written.  Wide maps only: below ~96 columns the padded-linear tiles beat the 2-D
                 // ones by more than the pool kernel costs (r03 sweep: 52 x 52 128 -> 256 +9 us vs a 9 us pool)
                 if (!net->kernels.empty() && net->kernels.back().kind == K_CONV && net->kernels.back().layer == s &&
@@ -497,15 +498,15 @@ struct Planner {
                     L[s].W % 2 == 0 && L[s].W >= 96 && !getenv("YOLO_NO_CONV_POOL")) {
                     Kernel &c = net->kernels.back();
                     const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-                    const bool tile13 = c.cout == 64, tile17 = c.cout == 32, tile12 = c.cout > 64 && f16;       // (the float32 2-D tiles: 64 and 32 couts)
+                    const int pool_tile = c.cout == 64 ? TILE_TAP2D_64x256 : c.cout == 32 ? TILE_TAP2D_32x256 : c.cout > 64 ? TILE_TAP2D_128x256 : -1;
                     if (c.ksize == 3 && c.stride == 1 && c.outmode == OUT_NORMAL && !c.has_res && !c.head && !c.stem && !has_claim[s] &&
-                        c.cpt % 4 == 0 && c.cout % 16 == 0 && (tile13 || tile12 || tile17)) {
+                        c.cpt % 4 == 0 && c.cout % 16 == 0 && pool_tile >= 0 && (f16 || conv_tile(pool_tile).f32_ok())) {
                         View pv = out_view_for(i);
                         if (!pv.f32 && pv.ld % epc == 0 && (pv.base + pv.coff) % epc == 0 && pv.img_stride % epc == 0) {
                             c.outmode = OUT_POOL2;
                             c.out = pv;
                             c.layer = i;
-                            c.tile = tile13 ? 13 : tile17 ? 17 : 12;
+                            c.tile = pool_tile;
                             c.note += " + fused 2x2/2 max-pool (layer " + std::to_string(i) + ")";
                             if (has_claim[i]) c.note += " -> concat slice";
                             L[i].view = pv; L[i].materialised = true;

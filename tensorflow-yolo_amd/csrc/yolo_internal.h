@@ -299,20 +299,17 @@ struct NmsParams {
 
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);
-// conv_dma.hip: 8-wave LDS-DMA kernel for the heavy fp16 layers.  choose_dma_cfg returns 0 when the
-// 4-wave kernel of conv.hip should run, else the tile id for launch_conv_dma.
+// conv_dma.hip: 8-wave LDS-DMA kernel for the heavy fp16 layers; conv_tap.hip: 3x3 with tap reuse.  What a tile id is: conv_tiles.h.
+// choose_dma_cfg returns 0 when the 4-wave kernel of conv.hip should run, else the tile id for launch_conv_dma.
+struct ConvTile;
 int choose_dma_cfg(int M, int cout, int cin_chunks, int taps, int has_res, bool v1_ok, int stride, int W, bool tap_only = false);   // -1: no DMA tile and no 4-wave kernel fits
 bool dma_cfg_valid(int cfg, int cout, int cin_chunks, bool v1_ok, int ksize, int stride, int W);
-bool dma_cfg_is_tap(int cfg);
-int dma_cfg_bkc(int cfg);
-hipError_t launch_conv_dma(const ConvParams &p, int cfg, hipStream_t s);
-hipError_t launch_conv_tap(const ConvParams &p, int variant, hipStream_t s);       // conv_tap.hip: 3x3/1 with tap reuse
-bool conv_tap_stream_ok(const ConvParams &p, int variant);                         // the persistent form takes this launch
-bool conv_tap_fits(int variant, int W);
-bool conv_tap_is2d(int variant);
-bool conv_tap_stride2(int variant);         // 3x3 / stride 2 over the input's parity planes (MODE 4)
-bool conv_tap_image_aligned(int variant);   // a tile = one whole image of the padded-linear grid (tile stride (H+1)(W+1))
-bool conv_tap_f32_ok(int variant);            // float32 instantiation usable (tiles with room for the second accumulator)
+hipError_t launch_conv_dma(const ConvParams &p, int cfg, hipStream_t s);           // any tile id > 0: sets up the grid, then launch_conv_tap for a tap tile
+hipError_t launch_conv_tap(const ConvParams &p, int tile, hipStream_t s);
+bool conv_tap_fits(const ConvTile &t, int W);
+// the kernel that runs THIS launch (p.ksplit, p.pair, p.fuse2 as launched), named as rocprofv3's kernel trace prints it (yolo_kernel_info.symbol)
+std::string conv_tile_symbol(int tile, ConvParams p);
+std::string conv_tap_symbol(const ConvTile &t, const ConvParams &p);
 // conv_mx.hip (MXFP8 plans): 3x3 / stride 1, Cin % 128 == 0, W <= kMxMaxW (the 128-channel patch of a 256-position tile in LDS, twice)
 constexpr int kMxMaxW = 100;
 constexpr int kMxTile = 24;           // its yolo_net_options.force_tile id (force_tile = 25)
@@ -322,14 +319,6 @@ hipError_t launch_conv_mx(const ConvParams &p, hipStream_t s);
 hipError_t launch_mx_quantize(const void *src, int rows, int channels, unsigned char *q, unsigned char *sc, hipStream_t s);
 // host copy of the device quantizer (mx_quant_block): one block of 32 float values -> e4m3fn bytes, returns the E8M0 byte
 unsigned char mx_quant_block_host(const float *v, unsigned char *q);
-bool dma_cfg_f32_ok(int cfg);
-const char *dma_cfg_name(int cfg);
-// names exactly as rocprofv3's kernel trace prints them (yolo_kernel_info.symbol: joins bench.py's roofline to profiles/*.csv)
-const char *dma_cfg_symbol(int cfg, bool f32, bool fast = false);      // fast: the lean-epilogue instantiation of a tap tile
-const char *conv_tap_symbol(int variant, bool f32, bool fast = false);
-std::string dma_cfg_symbol_for(int cfg, bool f32, const ConvParams &p);      // the kernel that runs THIS launch (stream form, split-K and pair forms included: p.ksplit, p.pair, p.fuse2 as launched)
-const char *conv_tap_stream_symbol(int variant);
-const char *conv_tap_splitk_symbol(int variant, bool f32);      // the instantiation launch_conv_tap runs when p.ksplit > 1
 std::string conv_symbol(int dtype, int cfg, bool perchunk, bool f32_emu = false);
 // float32 nets: does this launch of the 4-wave kernel run its products as nine bf16 products (yolo_net_options.f32_products)?
 bool conv_f32_emu_rule(int f32_products, int dtype, const ConvParams &p, int cfg, bool perchunk, int ksplit);
@@ -337,13 +326,7 @@ std::string first_symbol(int dtype, int cout, bool pool);
 std::string aux_symbol(int kind, int dtype, bool vec);
 std::string pool_same_symbol(int dtype, bool vec);
 std::string spp_pool_symbol(int rad);
-int dma_num_cfgs();
-int dma_cfg_na(int cfg);
-int dma_cfg_nb(int cfg);
-bool dma_cfg_splitk_ok(int cfg);        // the kernel behind this tile id takes ConvParams.ksplit
 hipError_t launch_splitk_reduce(const ReduceParams &p, hipStream_t s);
-bool conv_tap_splitk_ok(int variant);
-bool conv_tap_pair_ok(int variant, bool f32);
 // in_u8 / dst_u8: the kernel's uint8 twin runs -- `in` (`dst`) holds bytes, dense, any alignment (the parameter blocks are the same)
 hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s, bool in_u8 = false);
 hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8 = false);
@@ -465,7 +448,7 @@ inline size_t arena_slab_data_bytes(const yolo_net *net) {
     const size_t slab = arena_slab_bytes(net);
     return slab > kPairCounterBytes ? slab - kPairCounterBytes : 0;
 }
-// What one conv launch runs: the tile (0 = the 4-wave kernel of conv.hip with the planner's cfg, > 0 = conv_dma.hip tile id), the K
+// What one conv launch runs: the tile (conv_tiles.h: 0 = the 4-wave kernel of conv.hip with the planner's cfg), the K
 // split (ks = 1: whole K; else ks splits of ku units), whether the splits meet inside the launch (pair), whether the launch also
 // computes the 1x1 conv behind it (fuse2), and the bytes of partial sums it writes (0 if none).
 struct ConvLaunch {

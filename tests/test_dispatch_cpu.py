@@ -4,7 +4,10 @@ What a conv launch runs -- tile, K split, in-launch pair, back-to-back 1x1 fusio
 partial sums is decided on the host (csrc/conv_dispatch.cpp) and reported by yolo_net_kernel_info / yolo_net_workspace_regions without
 a GPU.  For every plan of PLANS the record holds, per kernel, name, variant, symbol and the exact reprs of flops / bytes /
 weight_bytes; the workspace size; offset, used and region bytes of the "split-K tickets + slabs" region; and the stream count.  The
-comparison is exact equality.  test_grid_reaches_every_arm asserts that the recorded names cover every arm of the decision.
+comparison is exact equality.  test_grid_reaches_every_arm asserts that the recorded names cover every arm of the decision,
+test_every_instantiation_is_reachable_and_every_report_is_real that the recorded symbols and the library's conv kernels are the same set
+(up to a listed remainder).  The plans of FORCED are recorded once per tile id: what a tile id accepts, what a forced tile falls back
+to and the symbol of every form it runs.
 
 The record is a statement about behaviour, not about this code: a refactor of the dispatch must leave it untouched.
 `python tests/test_dispatch_cpu.py` rewrites it after a DELIBERATE change of the rules (with YOLO_HIP_LIB pointing at another build of
@@ -44,6 +47,11 @@ NETS = {
 PAIR_GRAPHS = [("fp16", (24, 13, 13, 256, 512)), ("fp16", (20, 19, 19, 512, 256)), ("fp32", (24, 13, 13, 128, 512)), ("fp32", (24, 19, 19, 128, 256))]
 
 
+# (net, dtype, batch) of the plans that are recorded once per forced tile id
+FORCED = [("v3-608", "fp16", 8), ("v3-608", "fp16", 32), ("v3-416", "fp16", 32), ("v2-416", "fp16", 16), ("v2-416", "fp32", 1), ("v2-416", "fp32", 16),
+          ("tinyv2voc-416", "fp32", 64)]
+
+
 def _pair_graph(shape):
     _, H, W, cin, cout = shape
     g = new_graph(H, W, cin)
@@ -64,8 +72,9 @@ def _plans():
         for s in (1, 2):
             out.append(("v3-608/fp16/b%d/streams%d" % (b, s), "v3-608", dict(dtype="fp16", max_batch=b, streams=s)))
     out.append(("v3-608/fp16/b2/keep_all", "v3-608", dict(dtype="fp16", max_batch=2, keep_all=True)))
-    for tile in (0, 8, 11, 12, 22):         # (0: the 4-wave kernel)
-        out.append(("v3-608/fp16/b8/tile%d" % tile, "v3-608", dict(dtype="fp16", max_batch=8, force_tile=tile)))
+    for net, dtype, b in FORCED:
+        for tile in range(24):      # every tile id (0: the 4-wave kernel): validity, the fall-backs of a forced tile, the symbol of every form
+            out.append(("%s/%s/b%d/tile%d" % (net, dtype, b, tile), net, dict(dtype=dtype, max_batch=b, force_tile=tile)))
     # (the MXFP8 kernel by name: yolo_net_options.force_tile = 25, which engine.Plan spells force_tile=24)
     out.append(("v3-608/mxfp8/b8/tile24", "v3-608", dict(dtype="mxfp8", max_batch=8, force_tile=24)))
     for f in (1, 2):
@@ -180,6 +189,60 @@ def test_grid_reaches_every_arm():
     }
     missing = [what for what, hit in arms.items() if not any(hit(n) for n in names)]
     assert not missing, missing
+
+
+CONV_KERNEL = re.compile(r"void yolo::(?:conv3x3_tap_kernel|conv3x3_tap_stream_kernel|conv_igemm_dma_kernel)<[^>]*>\(yolo::ConvParams\)")
+_G = "generic-epilogue fp16 form: every pinned fp16 launch of this tile has the plain, aligned output map the lean form takes"
+_F = "float32 form of a tile without float32 support (built with every tile, refused by the launcher)"
+# instantiations in the library that no recorded plan runs, with the reason (from the record itself: a new or a lost instantiation shows up here)
+UNREACHED = {
+    "conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 4, 1, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 8, 4, 26, 2, 1, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 4, 3, 26, 4, 1, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 4, 2, 28, 4, 1, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 4, 4, 27, 4, 2, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 4, 2, 4, 7, 17, 2, 1, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 4, 2, 12, 6, 2, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 4, 6, 27, 2, 1, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 4, 6, 26, 2, 4, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 2, 4, 4, 3, 14, 4, 1, false, false, false>": _G,
+    "conv3x3_tap_kernel<false, 1, 8, 4, 2, 27, 4, 2, false, false, false>": "fp16 64-cout 2-D tile, generic: the pinned launches take its persistent form",
+    "conv3x3_tap_kernel<false, 1, 8, 4, 2, 27, 4, 2, false, true, false>": "fp16 64-cout 2-D tile, lean: the pinned launches take its persistent form",
+    "conv3x3_tap_kernel<false, 1, 8, 2, 2, 27, 4, 2, false, false, false>": "fp16 form of the 32-cout tile: no pinned fp16 net has a 3x3 conv of 17-32 filters on 32+ channels",
+    "conv3x3_tap_kernel<false, 1, 8, 2, 2, 27, 4, 2, false, true, false>": "fp16 form of the 32-cout tile (lean)",
+    "conv3x3_tap_kernel<false, 1, 8, 2, 2, 27, 4, 3, false, false, false>": "fp16 form of the 32-cout tile (fused pool)",
+    "conv3x3_tap_kernel<true, 1, 8, 2, 2, 27, 4, 2, false, false, false>": "float32 32-cout tile without the pool: its one pinned layer (tiny-YOLOv2 16 -> 32) runs the fused-pool form",
+    "conv3x3_tap_kernel<false, 2, 4, 4, 4, 21, 4, 4, false, true, false>": "lean form of the two-per-CU stride-2 tile: spills, the launcher runs the generic one",
+    "conv3x3_tap_kernel<false, 2, 4, 4, 4, 26, 4, 4, false, true, false>": "lean form of the wide stride-2 tile without the 1x1: the launcher runs the generic one",
+    "conv3x3_tap_kernel<true, 2, 4, 4, 4, 26, 4, 1, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 8, 4, 26, 2, 1, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 3, 26, 4, 1, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 4, 27, 4, 2, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 4, 2, 4, 7, 17, 2, 1, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 2, 12, 6, 2, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 6, 27, 2, 1, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 4, 21, 4, 4, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 6, 26, 2, 4, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 3, 14, 4, 1, false, false, false>": _F,
+    "conv3x3_tap_kernel<true, 2, 4, 4, 4, 26, 4, 4, false, false, false>": _F,
+    "conv_igemm_dma_kernel<1, 8, 4, 4, 2, 4, 4, false, 2>": "float32 head rows on the 64 x 512 tile: no head conv has 64 filters or fewer",
+}
+
+
+def test_every_instantiation_is_reachable_and_every_report_is_real():
+    """The conv kernels the library exports (nm -DC) against the symbols of the recorded plans: a reported symbol is a kernel that
+    exists, and every kernel that exists runs in some recorded plan or is listed in UNREACHED with its reason."""
+    import subprocess
+    nm = subprocess.run(["nm", "-DC", _hip.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    built = {m.group(0) for line in nm.splitlines() if "__device_stub__" not in line for m in [CONV_KERNEL.search(line)] if m}
+    assert len(built) > 50, "no conv kernels found in nm -DC of %s" % _hip.LIB_PATH
+    with open(PLANS_JSON) as f:
+        recorded = {s for s in json.load(f)["symbols"] if CONV_KERNEL.fullmatch(s)}
+    assert recorded <= {k[2] for rec in got_plans().values() for k in rec["kernels"]}
+    assert not recorded - built, "reported, but not in the library: %s" % sorted(recorded - built)
+    listed = {"void yolo::%s(yolo::ConvParams)" % k for k in UNREACHED}
+    assert built - recorded == listed, ("in the library, in no recorded plan and not listed: %s; listed but recorded or not built: %s"
+                                        % (sorted(built - recorded - listed), sorted(listed - (built - recorded))))
 
 
 if __name__ == "__main__":      # rewrite the record (no GPU needed)
