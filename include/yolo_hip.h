@@ -21,6 +21,14 @@
  *   yolo_net_forward_u8, yolo_net_detect_u8, yolo_net_forward_timed_u8, yolo_net_tune_streams_u8, yolo_preprocess_resize_u8
  *                           (ABI 7) the same call sites for a caller that holds the 8-bit pixels net/base.py:115-155 starts from:
  *                           the / 255. of net/base.py:153 happens inside the first kernel instead of in a float32 tensor
+ *   yolo_preprocess_frames, yolo_preprocess_frames_u8
+ *                           net/base.py:158-168 generate_test_batch's loop over net/base.py:115-155 preprocess_image: every frame of a batch,
+ *                           whatever its size, in one launch (stretch as there, or Darknet's letterbox, which the reference does not have)
+ *   yolo_net_detect_frames_u8
+ *                           net/yolo.py:80-86: that loop, the forward pass and find_bounding_boxes in one enqueue
+ *   yolo_letterbox_geometry, yolo_boxes_to_frames
+ *                           no reference call site: net/base.py:121 only stretches, so its boxes are normalised to the frame as they are
+ *                           (net/base.py:212-226 draw_boxes scales them by the frame size)
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -35,7 +43,10 @@ extern "C" {
 #define YOLO_HIP_ABI_VERSION 7      /* 2: yolo_kernel_info.symbol; 3: yolo_net_num_streams, streams = 0 is the library's rule; 4: yolo_net_tune_streams; 5: yolo_net_set_streams;
                                        6: YOLO_DTYPE_MXF8, yolo_mx_quantize, yolo_mx_quantize_host;
                                        7: uint8 network input -- yolo_net_forward_u8, yolo_net_detect_u8, yolo_net_forward_timed_u8,
-                                          yolo_net_tune_streams_u8, yolo_preprocess_resize_u8, yolo_u8_unit_table */
+                                          yolo_net_tune_streams_u8, yolo_preprocess_resize_u8, yolo_u8_unit_table;
+                                          added WITHIN ABI 7 (new exports, struct yolo_frame and enum yolo_resize_mode only: no existing struct or
+                                          entry changed) -- the frame entries yolo_letterbox_geometry, yolo_preprocess_frames,
+                                          yolo_preprocess_frames_u8, yolo_boxes_to_frames, yolo_net_detect_frames_u8 */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -280,6 +291,59 @@ int yolo_preprocess_resize(const uint8_t *src_dev, int src_h, int src_w, int src
  * same source is float32(that / 255.) exactly. */
 int yolo_preprocess_resize_u8(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, uint8_t *dst_dev, int dst_h, int dst_w,
                               int swap_rb, void *stream);
+
+/* ---- frames of any size: batched resize, letterbox, boxes in frame coordinates (added within ABI 7) ------------------------------
+ * One decoded frame on the device: uint8 HWC, 3 channels, row_bytes >= 3 * w, any byte alignment.  swap_rb != 0: channels 0 and 2 change
+ * places on the way (a BGR frame for an RGB network, net/base.py:152). */
+typedef struct yolo_frame {
+    const uint8_t *pixels_dev;
+    int32_t h, w, row_bytes, swap_rb;
+} yolo_frame;
+
+enum yolo_resize_mode {
+    YOLO_RESIZE_STRETCH = 0,    /* the reference: cv2.resize to the network input, aspect ratio not kept (net/base.py:121)  */
+    YOLO_RESIZE_LETTERBOX = 1   /* Darknet's `detector test`: aspect ratio kept, the rest of the canvas is the byte 128     */
+};
+
+/* Where a src_h x src_w frame lands in a dst_h x dst_w network input, in integers (pure host function, no device).  Stretch: new = dst,
+ * offsets 0.  Letterbox (Darknet's letterbox_image with its float comparison replaced by the exact cross-multiplied one): if
+ * dst_w * src_h < dst_h * src_w the width binds -- new_w = dst_w, new_h = max(1, src_h * dst_w / src_w) -- else new_h = dst_h,
+ * new_w = max(1, src_w * dst_h / src_h) (integer division); off_x = (dst_w - new_w) / 2, off_y = (dst_h - new_h) / 2.  Small frames are
+ * enlarged, as Darknet does.  All sizes >= 1 (and below 2^31: the products are taken in 64 bits). */
+int yolo_letterbox_geometry(int src_h, int src_w, int dst_h, int dst_w, int mode, int32_t *new_h, int32_t *new_w, int32_t *off_y,
+                            int32_t *off_x);
+
+/* The resize of a whole batch: frames_host[0..n) (a HOST array; the descriptors travel in the kernel arguments, at most 64 frames per
+ * launch, larger n as consecutive launches -- no device table, no copy, nothing in the workspace) -> dst_dev, the dense batch tensor
+ * uint8 [n][dst_h][dst_w][3] of yolo_net_forward_u8 / yolo_net_detect_u8.  Frames may differ in size, pitch and alignment.  Inside the
+ * new_h x new_w region of yolo_letterbox_geometry every pixel is what yolo_preprocess_resize_u8 gives for that frame resized to
+ * (new_h, new_w) -- the project's one resize arithmetic, OpenCV's 8-bit INTER_LINEAR, not Darknet's bilinear; outside it the byte 128
+ * (written without touching the source).  Every byte of the n images is written by each call.  A thread produces 4 consecutive pixels
+ * of a row and stores them as dwords: dst_w must be a multiple of 4 (every network width is: YOLO_ERR_ARG otherwise); a dst_dev that is
+ * not 4-byte aligned (16 for the float32 twin) is served by narrower stores.  Enqueued on `stream`. */
+int yolo_preprocess_frames_u8(const yolo_frame *frames_host, int n, int mode, uint8_t *dst_dev, int dst_h, int dst_w, void *stream);
+/* The same with float32 [n][dst_h][dst_w][3] results, the batch tensor of yolo_net_forward / yolo_net_detect: float32(u / 255.) of the
+ * uint8 result by the conversion of the uint8 input kernels (yolo_u8_unit_table); the canvas is float32(128 / 255.). */
+int yolo_preprocess_frames(const yolo_frame *frames_host, int n, int mode, float *dst_dev, int dst_h, int dst_w, void *stream);
+
+/* Box records of a detect call on such a batch (normalised to the net_h x net_w network input) -> normalised to each frame, in place:
+ * the first counts_dev[i] (at most max_boxes) records of image i, with (new_h, new_w, off_y, off_x) = yolo_letterbox_geometry of frame i,
+ *     x' = float32((double(x) * net_w - off_x) / new_w)      w' = float32(double(w) * net_w / new_w)
+ *     y' = float32((double(y) * net_h - off_y) / new_h)      h' = float32(double(h) * net_h / new_h)
+ * (the products are exact in float64, then one IEEE division and one narrowing: NumPy's float64 gives the same bits).  prob and class_idx
+ * stay; nothing is clipped (net/base.py:212-226 draw_boxes clamps).  Records behind the count are not touched.  NMS has run in network
+ * coordinates before: set and order of the boxes are those of the detect call.  YOLO_RESIZE_STRETCH changes nothing and launches
+ * nothing.  Only h and w of the frame descriptors are read; the geometry travels in the kernel arguments, 64 images per launch. */
+int yolo_boxes_to_frames(yolo_box *boxes_dev, const int32_t *counts_dev, int batch, int max_boxes, const yolo_frame *frames_host, int mode,
+                         int net_h, int net_w, void *stream);
+
+/* One enqueue for a whole step: yolo_preprocess_frames_u8 of frames_host[0..batch) into the caller's batch_dev (uint8
+ * [batch][H][W][3], H x W the network input, which must have 3 channels), yolo_net_detect_u8 on it, yolo_boxes_to_frames on the
+ * survivors.  Records, counts and status are those of yolo_net_detect_u8 on that batch tensor, boxes normalised to each frame.
+ * Argument checks and messages as yolo_net_detect_u8, plus the frames' (h, w >= 1, row_bytes >= 3 w). */
+int yolo_net_detect_frames_u8(yolo_net *net, const yolo_frame *frames_host, int batch, int mode, uint8_t *batch_dev, double threshold,
+                              double iou_threshold, int nms_mode, yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev,
+                              void *stream);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

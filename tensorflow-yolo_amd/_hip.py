@@ -16,6 +16,9 @@ ABI_VERSION = 7
 OP_INPUT, OP_CONV, OP_MAXPOOL, OP_ROUTE, OP_REORG, OP_SHORTCUT, OP_UPSAMPLE, OP_YOLO, OP_DETECTION = range(9)
 DTYPE_F32, DTYPE_F16, DTYPE_MXF8 = 0, 1, 2
 NMS_AGNOSTIC, NMS_PER_CLASS = 0, 1
+RESIZE_STRETCH, RESIZE_LETTERBOX = 0, 1         # enum yolo_resize_mode
+RESIZE_MODES = {"stretch": RESIZE_STRETCH, "letterbox": RESIZE_LETTERBOX}
+FRAMES_PER_LAUNCH = 64                          # frames one launch of the batched resize covers (larger batches: consecutive launches)
 MAX_SRC, MAX_ANCHORS, MAX_SCALES = 4, 8, 4
 # Records per image every Python entry point asks for unless told otherwise.  The reference's lists are unbounded
 # (net/base.py:195-209); 1024 covers every YOLOv2 head (845 rows) and exceeding it raises (engine.check_status).
@@ -44,6 +47,11 @@ class HeadDesc(C.Structure):
     _fields_ = [("version", C.c_int32), ("n_classes", C.c_int32), ("n_scales", C.c_int32),
                 ("h", C.c_int32 * MAX_SCALES), ("w", C.c_int32 * MAX_SCALES), ("n_anchors", C.c_int32 * MAX_SCALES),
                 ("anchors", (C.c_double * (2 * MAX_ANCHORS)) * MAX_SCALES)]
+
+
+class Frame(C.Structure):
+    """yolo_frame: one decoded uint8 HWC3 frame on the device"""
+    _fields_ = [("pixels_dev", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("row_bytes", C.c_int32), ("swap_rb", C.c_int32)]
 
 
 class WsRegion(C.Structure):
@@ -100,6 +108,14 @@ SIGNATURES = {
                                   C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     "yolo_preprocess_resize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # frames of any size (added within ABI 7): batched resize / letterbox, boxes back in frame coordinates, the whole step
+    "yolo_letterbox_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "yolo_preprocess_frames_u8": (C.c_int, [C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "yolo_preprocess_frames": (C.c_int, [C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "yolo_boxes_to_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Frame), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "yolo_net_detect_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yolo_nms_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int,
                                 C.c_void_p, C.POINTER(C.c_int32)]),
 }
@@ -135,6 +151,22 @@ def lib():
         raise ImportError("libyolo_hip.so ABI version %d, binding expects %d: rebuild the library" % (v, ABI_VERSION))
     _lib = handle
     return _lib
+
+
+def resize_mode(name):
+    """'stretch' | 'letterbox' (the .ini key `resize`, the `resize` argument of predict_frames) -> enum yolo_resize_mode; else ValueError"""
+    key = str(name).strip().lower()
+    if key not in RESIZE_MODES:
+        raise ValueError("resize must be stretch or letterbox, got %r" % (name,))
+    return RESIZE_MODES[key]
+
+
+def letterbox_geometry(src_h, src_w, dst_h, dst_w, mode):
+    """(new_h, new_w, off_y, off_x) of a src_h x src_w frame in a dst_h x dst_w network input (yolo_letterbox_geometry: host only)"""
+    out = [C.c_int32() for _ in range(4)]
+    check(lib().yolo_letterbox_geometry(int(src_h), int(src_w), int(dst_h), int(dst_w), int(mode), *[C.byref(v) for v in out]),
+          "yolo_letterbox_geometry")
+    return tuple(int(v.value) for v in out)
 
 
 def check(rc, what=""):

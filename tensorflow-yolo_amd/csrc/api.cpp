@@ -965,6 +965,122 @@ int yolo_preprocess_resize_u8(const uint8_t *src_dev, int src_h, int src_w, int 
     return resize_any(src_dev, src_h, src_w, src_row_bytes, dst_dev, true, dst_h, dst_w, swap_rb, stream, "yolo_preprocess_resize_u8");
 }
 
+// ---- frames of any size (yolo_hip.h: added within ABI 7) -------------------------------------------------------------------------
+static bool frame_geometry(int src_h, int src_w, int dst_h, int dst_w, int mode, int &new_h, int &new_w, int &off_y, int &off_x) {
+    if (src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || (mode != YOLO_RESIZE_STRETCH && mode != YOLO_RESIZE_LETTERBOX)) return false;
+    new_h = dst_h; new_w = dst_w;
+    if (mode == YOLO_RESIZE_LETTERBOX) {
+        if ((long long)dst_w * src_h < (long long)dst_h * src_w) {      // the width binds (Darknet: net_w / w < net_h / h, cross-multiplied)
+            const long long v = (long long)src_h * dst_w / src_w;
+            new_h = v < 1 ? 1 : (int)v;
+        } else {
+            const long long v = (long long)src_w * dst_h / src_h;
+            new_w = v < 1 ? 1 : (int)v;
+        }
+    }
+    off_y = (dst_h - new_h) / 2;
+    off_x = (dst_w - new_w) / 2;
+    return true;
+}
+
+int yolo_letterbox_geometry(int src_h, int src_w, int dst_h, int dst_w, int mode, int32_t *new_h, int32_t *new_w, int32_t *off_y, int32_t *off_x) {
+    if (!new_h || !new_w || !off_y || !off_x) return fail(YOLO_ERR_ARG, "yolo_letterbox_geometry: null argument");
+    if (mode != YOLO_RESIZE_STRETCH && mode != YOLO_RESIZE_LETTERBOX) return fail(YOLO_ERR_ARG, "yolo_letterbox_geometry: mode must be YOLO_RESIZE_STRETCH or YOLO_RESIZE_LETTERBOX");
+    int nh, nw, oy, ox;
+    if (!frame_geometry(src_h, src_w, dst_h, dst_w, mode, nh, nw, oy, ox)) return fail(YOLO_ERR_ARG, "yolo_letterbox_geometry: sizes must be at least 1");
+    *new_h = nh; *new_w = nw; *off_y = oy; *off_x = ox;
+    return YOLO_OK;
+}
+
+// the checks every frame entry makes of its descriptors and mode
+static int check_frames(const yolo_frame *frames, int n, int mode, bool need_pixels, const char *who) {
+    if (!frames) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (n < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": frame count must be at least 1");
+    if (mode != YOLO_RESIZE_STRETCH && mode != YOLO_RESIZE_LETTERBOX) return fail(YOLO_ERR_ARG, std::string(who) + ": mode must be YOLO_RESIZE_STRETCH or YOLO_RESIZE_LETTERBOX");
+    for (int i = 0; i < n; ++i) {
+        const yolo_frame &f = frames[i];
+        if (f.h < 1 || f.w < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": frame " + std::to_string(i) + " has h or w below 1");
+        if (need_pixels && !f.pixels_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": frame " + std::to_string(i) + " has no pixels");
+        if (need_pixels && (long long)f.row_bytes < 3LL * f.w) return fail(YOLO_ERR_ARG, std::string(who) + ": frame " + std::to_string(i) + " has row_bytes below 3 * w");
+    }
+    return YOLO_OK;
+}
+
+static int frames_any(const yolo_frame *frames, int n, int mode, void *dst_dev, bool dst_u8, int dst_h, int dst_w, void *stream, const char *who) {
+    int rc = check_frames(frames, n, mode, true, who);
+    if (rc) return rc;
+    if (!dst_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (dst_h < 1 || dst_w < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": dst_h and dst_w must be at least 1");
+    if (dst_w % 4) return fail(YOLO_ERR_ARG, std::string(who) + ": dst_w must be a multiple of 4");
+    const size_t esize = dst_u8 ? 1 : 4;
+    const size_t img_bytes = (size_t)dst_h * dst_w * 3 * esize;
+    FramesParams p;
+    p.dst_h = dst_h; p.dst_w = dst_w;
+    p.wide = (uintptr_t)dst_dev % (dst_u8 ? 4 : 16) == 0;
+    for (int i0 = 0; i0 < n; i0 += kFramesPerLaunch) {
+        const int m = n - i0 < kFramesPerLaunch ? n - i0 : kFramesPerLaunch;
+        for (int i = 0; i < m; ++i) {
+            const yolo_frame &f = frames[i0 + i];
+            FrameGeom &g = p.f[i];
+            g.src = f.pixels_dev; g.src_h = f.h; g.src_w = f.w; g.src_row_bytes = f.row_bytes; g.swap_rb = f.swap_rb ? 1 : 0;
+            frame_geometry(f.h, f.w, dst_h, dst_w, mode, g.new_h, g.new_w, g.off_y, g.off_x);
+        }
+        for (int i = m; i < kFramesPerLaunch; ++i) p.f[i] = FrameGeom{nullptr, 1, 1, 3, 0, 1, 1, 0, 0};
+        p.dst = static_cast<unsigned char *>(dst_dev) + (size_t)i0 * img_bytes;     // (a multiple of 12 / 48 bytes per image: alignment stays)
+        HIP_TRY(launch_frames_resize(p, m, static_cast<hipStream_t>(stream), dst_u8));
+    }
+    return YOLO_OK;
+}
+int yolo_preprocess_frames_u8(const yolo_frame *frames_host, int n, int mode, uint8_t *dst_dev, int dst_h, int dst_w, void *stream) {
+    return frames_any(frames_host, n, mode, dst_dev, true, dst_h, dst_w, stream, "yolo_preprocess_frames_u8");
+}
+int yolo_preprocess_frames(const yolo_frame *frames_host, int n, int mode, float *dst_dev, int dst_h, int dst_w, void *stream) {
+    return frames_any(frames_host, n, mode, dst_dev, false, dst_h, dst_w, stream, "yolo_preprocess_frames");
+}
+
+static int boxes_to_frames_any(yolo_box *boxes_dev, const int32_t *counts_dev, int batch, int max_boxes, const yolo_frame *frames, int mode,
+                               int net_h, int net_w, void *stream, const char *who) {
+    int rc = check_frames(frames, batch, mode, false, who);
+    if (rc) return rc;
+    if (!boxes_dev || !counts_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (max_boxes < 1 || net_h < 1 || net_w < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": max_boxes, net_h and net_w must be at least 1");
+    if (mode == YOLO_RESIZE_STRETCH) return YOLO_OK;        // new = net, offsets 0: x * W / W is x -- nothing to launch
+    RemapParams p;
+    p.max_boxes = max_boxes; p.net_h = net_h; p.net_w = net_w;
+    for (int i0 = 0; i0 < batch; i0 += kFramesPerLaunch) {
+        const int m = batch - i0 < kFramesPerLaunch ? batch - i0 : kFramesPerLaunch;
+        for (int i = 0; i < kFramesPerLaunch; ++i) {
+            BoxGeom &g = p.g[i];
+            g = BoxGeom{1, 1, 0, 0};
+            if (i < m) frame_geometry(frames[i0 + i].h, frames[i0 + i].w, net_h, net_w, mode, g.new_h, g.new_w, g.off_y, g.off_x);
+        }
+        p.boxes = boxes_dev + (size_t)i0 * max_boxes;
+        p.counts = counts_dev + i0;
+        HIP_TRY(launch_boxes_to_frames(p, m, static_cast<hipStream_t>(stream)));
+    }
+    return YOLO_OK;
+}
+int yolo_boxes_to_frames(yolo_box *boxes_dev, const int32_t *counts_dev, int batch, int max_boxes, const yolo_frame *frames_host, int mode,
+                         int net_h, int net_w, void *stream) {
+    return boxes_to_frames_any(boxes_dev, counts_dev, batch, max_boxes, frames_host, mode, net_h, net_w, stream, "yolo_boxes_to_frames");
+}
+
+int yolo_net_detect_frames_u8(yolo_net *net, const yolo_frame *frames_host, int batch, int mode, uint8_t *batch_dev, double threshold,
+                              double iou_threshold, int nms_mode, yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev, void *stream) {
+    const char *who = "yolo_net_detect_frames_u8";
+    if (!frames_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    int rc = check_ready(net, batch_dev, batch, who);
+    if (rc) return rc;
+    if (!boxes_dev || !counts_dev || !status_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null output");
+    const LayerInfo &in = net->layers[0];
+    if (in.C != 3) return fail(YOLO_ERR_ARG, std::string(who) + ": the network input must have 3 channels");
+    rc = frames_any(frames_host, batch, mode, batch_dev, true, in.H, in.W, stream, who);
+    if (rc) return rc;
+    rc = detect_any(net, NetIn{batch_dev, true}, batch, threshold, iou_threshold, nms_mode, boxes_dev, counts_dev, status_dev, stream, who);
+    if (rc) return rc;
+    return boxes_to_frames_any(boxes_dev, counts_dev, batch, net->opt.max_boxes, frames_host, mode, in.H, in.W, stream, who);
+}
+
 int yolo_u8_unit_table(float *out256) {
     if (!out256) return fail(YOLO_ERR_ARG, "yolo_u8_unit_table: null argument");
     for (unsigned u = 0; u < 256; ++u) out256[u] = u8_unit(u);     // the function the input kernels run on every byte

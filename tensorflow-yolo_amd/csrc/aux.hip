@@ -1,4 +1,5 @@
-// Bandwidth kernels around the conv stack: input cast/pad, max-pool (2x2, general stride-1 SAME, fused SPP block), and the generic strided
+// Bandwidth kernels around the conv stack: input cast/pad, image resize (per image, and a batch of frames of any size in one launch) with the
+// map of box records back to frame coordinates, max-pool (2x2, general stride-1 SAME, fused SPP block), and the generic strided
 // element-wise fallback (standalone shortcut / upsample / reorg / concat-copy / f32 convert) the
 // planner uses when a fusion into a conv epilogue is not possible.
 #include "yolo_internal.h"
@@ -267,9 +268,9 @@ static inline unsigned grid_for(long long work) {
 // one thread per destination pixel.  8-bit INTER_LINEAR as OpenCV defines it (imgproc/resize.cpp): half-pixel centres,
 // weights rounded to 11-bit fixed point, horizontal pass in int32, vertical pass
 // ((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2; then float32(v / 255.) (division in float64 like NumPy).
-__device__ __forceinline__ void resize_coeff(int d, int src, int dst, int &s0, int &s1, int &w0, int &w1) {
+// (resize_coeff_at: the same with the caller's scale = (double)src / (double)dst -- frames_resize_kernel divides once for its four pixels)
+__device__ __forceinline__ void resize_coeff_at(int d, int src, double scale, int &s0, int &s1, int &w0, int &w1) {
 #pragma clang fp contract(off)
-    const double scale = (double)src / (double)dst;
     float f = (float)(((double)d + 0.5) * scale - 0.5);
     int s = (int)floorf(f);
     f -= (float)s;
@@ -279,6 +280,9 @@ __device__ __forceinline__ void resize_coeff(int d, int src, int dst, int &s0, i
     w1 = __float2int_rn(f * 2048.f);
     s0 = s;
     s1 = s + 1 < src ? s + 1 : src - 1;
+}
+__device__ __forceinline__ void resize_coeff(int d, int src, int dst, int &s0, int &s1, int &w0, int &w1) {
+    resize_coeff_at(d, src, (double)src / (double)dst, s0, s1, w0, w1);
 }
 
 // OUT_U8: the 8-bit value itself goes to a uint8 destination (yolo_preprocess_resize_u8: the batch tensor of yolo_net_detect_u8)
@@ -316,6 +320,116 @@ hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8) {
     if (n <= 0 || p.src_h <= 0 || p.src_w <= 0 || (n + 255) / 256 > 0x7fffffffLL) return hipErrorInvalidValue;
     if (dst_u8) hipLaunchKernelGGL(resize_u8_to_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(resize_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// The resize of a whole batch in one launch (yolo_preprocess_frames[_u8]): grid row y is frame y of the launch, whatever its size, pitch
+// and alignment (FramesParams.f[y], read with scalar loads: the index is the workgroup's).  A thread produces a run of 4 consecutive
+// destination pixels of one row -- 12 bytes, three dword stores, or 48 bytes of float32, three dwordx4 stores -- where resize_u8_kernel
+// stores single bytes; dst_w % 4 == 0 keeps every run inside its row and aligned.  Inside the frame's new_h x new_w region at
+// (off_y, off_x) a pixel is resize_u8_kernel's for the frame resized to (new_h, new_w): the same resize_coeff, the same integer passes
+// (the row coefficients once per thread, the double division of the column scale once for the four pixels).  Outside it (letterbox) the
+// byte 128, written without a read.  Stretch is new = dst, offsets 0.
+template <bool OUT_U8>
+__global__ void __launch_bounds__(256) frames_resize_kernel(const FramesParams p) {
+    const int runs_per_row = p.dst_w >> 2;
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= (long long)p.dst_h * runs_per_row) return;
+    const FrameGeom &g = p.f[blockIdx.y];
+    const int dy = (int)(r / runs_per_row), dx0 = (int)(r - (long long)dy * runs_per_row) * 4;
+    const int iy = dy - g.off_y;
+    const bool row_in = iy >= 0 && iy < g.new_h;
+    const bool same = g.src_h == g.new_h && g.src_w == g.new_w;
+    int y0 = 0, y1 = 0, b0 = 0, b1 = 0;
+    if (row_in) resize_coeff(iy, g.src_h, g.new_h, y0, y1, b0, b1);
+    const unsigned char *r0 = g.src + (long long)y0 * g.src_row_bytes, *r1 = g.src + (long long)y1 * g.src_row_bytes;
+    const double scale_x = (double)g.src_w / (double)g.new_w;
+    unsigned v[12];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int ix = dx0 + q - g.off_x;
+        if (row_in && ix >= 0 && ix < g.new_w) {
+            int x0, x1, a0, a1;
+            resize_coeff_at(ix, g.src_w, scale_x, x0, x1, a0, a1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int cs = g.swap_rb ? 2 - c : c;
+                int t;
+                if (same) {
+                    t = r0[x0 * 3 + cs];
+                } else {
+                    const int h0 = (int)r0[x0 * 3 + cs] * a0 + (int)r0[x1 * 3 + cs] * a1;
+                    const int h1 = (int)r1[x0 * 3 + cs] * a0 + (int)r1[x1 * 3 + cs] * a1;
+                    t = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                    t = t < 0 ? 0 : (t > 255 ? 255 : t);
+                }
+                v[q * 3 + c] = (unsigned)t;
+            }
+        } else {
+            v[q * 3] = v[q * 3 + 1] = v[q * 3 + 2] = 128u;
+        }
+    }
+    // element offset of the run: image blockIdx.y, row dy, pixel dx0
+    const long long e = (((long long)blockIdx.y * p.dst_h + dy) * p.dst_w + dx0) * 3;
+    if constexpr (OUT_U8) {
+        unsigned char *o = reinterpret_cast<unsigned char *>(p.dst) + e;
+        if (p.wide) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                reinterpret_cast<unsigned *>(o)[k] = v[4 * k] | (v[4 * k + 1] << 8) | (v[4 * k + 2] << 16) | (v[4 * k + 3] << 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) o[k] = (unsigned char)v[k];
+        }
+    } else {
+        typedef float float4v __attribute__((ext_vector_type(4)));
+        float *o = reinterpret_cast<float *>(p.dst) + e;
+        if (p.wide) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float4v f;
+                f.x = u8_unit(v[4 * k]); f.y = u8_unit(v[4 * k + 1]); f.z = u8_unit(v[4 * k + 2]); f.w = u8_unit(v[4 * k + 3]);
+                reinterpret_cast<float4v *>(o)[k] = f;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) o[k] = u8_unit(v[k]);
+        }
+    }
+}
+
+hipError_t launch_frames_resize(const FramesParams &p, int n, hipStream_t s, bool dst_u8) {
+    const long long runs = (long long)p.dst_h * (p.dst_w >> 2);
+    if (n < 1 || n > kFramesPerLaunch || p.dst_h < 1 || p.dst_w < 4 || (p.dst_w & 3) || (runs + 255) / 256 > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 g((unsigned)((runs + 255) / 256), (unsigned)n), b(256);
+    if (dst_u8) hipLaunchKernelGGL(frames_resize_kernel<true>, g, b, 0, s, p);
+    else hipLaunchKernelGGL(frames_resize_kernel<false>, g, b, 0, s, p);
+    return hipGetLastError();
+}
+
+// Box records of a detect call on a letterboxed batch, from network-input to frame coordinates, in place (yolo_boxes_to_frames): one
+// workgroup per image, a thread per valid record.  float64 with one rounding to float32 each -- x * W is exact in float64 (24 + 12 bits),
+// so contracting it into an FMA could not change a bit; it is switched off all the same.  One IEEE division, one narrowing: this file is
+// compiled without fast-math, NumPy's float64 gives the same bits.  prob and class_idx are not touched, records behind the count neither.
+__global__ void __launch_bounds__(256) boxes_to_frames_kernel(const RemapParams p) {
+#pragma clang fp contract(off)
+    const int img = blockIdx.x;
+    const BoxGeom &g = p.g[img];
+    int n = p.counts[img];
+    n = n < 0 ? 0 : (n > p.max_boxes ? p.max_boxes : n);
+    yolo_box *b = p.boxes + (long long)img * p.max_boxes;
+    for (int k = threadIdx.x; k < n; k += 256) {
+        const double x = b[k].x, y = b[k].y, w = b[k].w, h = b[k].h;
+        b[k].x = (float)((x * (double)p.net_w - (double)g.off_x) / (double)g.new_w);
+        b[k].y = (float)((y * (double)p.net_h - (double)g.off_y) / (double)g.new_h);
+        b[k].w = (float)(w * (double)p.net_w / (double)g.new_w);
+        b[k].h = (float)(h * (double)p.net_h / (double)g.new_h);
+    }
+}
+
+hipError_t launch_boxes_to_frames(const RemapParams &p, int n, hipStream_t s) {
+    if (n < 1 || n > kFramesPerLaunch || p.max_boxes < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(boxes_to_frames_kernel, dim3((unsigned)n), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

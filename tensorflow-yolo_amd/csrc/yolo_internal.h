@@ -216,6 +216,28 @@ struct ResizeParams {          // uint8 HWC3 image -> float32 [dst_h][dst_w][3] 
     int src_h, src_w, src_row_bytes, dst_h, dst_w, swap_rb;
 };
 
+// aux.hip: frames_resize_kernel -- up to kFramesPerLaunch frames of any size into one dense batch tensor, one launch.  The descriptors
+// travel by value in the kernel argument (64 x 40 bytes: no device table, no copy); workgroups of grid row y read entry y through scalar loads.
+constexpr int kFramesPerLaunch = 64;
+struct FrameGeom {             // one frame and where it lands in the network input (yolo_letterbox_geometry)
+    const unsigned char *src;
+    int src_h, src_w, src_row_bytes, swap_rb;
+    int new_h, new_w, off_y, off_x;
+};
+struct FramesParams {
+    FrameGeom f[kFramesPerLaunch];
+    void *dst;                 // image 0 of this launch: uint8 or float32 [n][dst_h][dst_w][3]
+    int dst_h, dst_w;          // dst_w % 4 == 0
+    int wide;                  // dst is aligned for the wide stores (4 bytes for uint8, 16 for float32); else element stores
+};
+struct BoxGeom { int new_h, new_w, off_y, off_x; };
+struct RemapParams {           // aux.hip: boxes_to_frames_kernel -- box records from network to frame coordinates, in place
+    BoxGeom g[kFramesPerLaunch];
+    yolo_box *boxes;           // image 0 of this launch
+    const int *counts;
+    int max_boxes, net_h, net_w;
+};
+
 struct PoolParams {            // net/layers.py:70-81
     const void *in;
     void *out;
@@ -330,6 +352,8 @@ hipError_t launch_splitk_reduce(const ReduceParams &p, hipStream_t s);
 // in_u8 / dst_u8: the kernel's uint8 twin runs -- `in` (`dst`) holds bytes, dense, any alignment (the parameter blocks are the same)
 hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s, bool in_u8 = false);
 hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8 = false);
+hipError_t launch_frames_resize(const FramesParams &p, int n, hipStream_t s, bool dst_u8);     // n <= kFramesPerLaunch frames
+hipError_t launch_boxes_to_frames(const RemapParams &p, int n, hipStream_t s);                 // n <= kFramesPerLaunch images
 hipError_t launch_first(const FirstParams &p, int dtype, hipStream_t s, bool in_u8 = false);
 hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = 512, bool in_u8 = false);     // stem.hip
 hipError_t launch_pool(const PoolParams &p, int dtype, hipStream_t s);

@@ -5,7 +5,8 @@ Keeps the reference launcher's surface (reference launcher.py:15-60): the two fl
 COMMON / ANCHOR / TRAIN / TEST merged as {**section, **COMMON}, relative `*_dir` / `*_path` values
 resolved against the .ini's directory, `anchors` / `class_names` parsed as Python literals, and the
 network picked by COMMON.version.  Only `test` runs on this backend; `train` and `anchor` end with a
-clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up);
+clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up),
+`resize` (stretch, the reference's geometry and the default | letterbox, Darknet's: aspect ratio kept, grey canvas, boxes mapped back to the frame);
 version additionally accepts `v2-tiny`, `v3-tiny` and `v3-spp`.  `--section` selects another TEST-like section (the
 reference's yolo_2.ini keeps its COCO settings in [TEST_COCO], which no mode reaches there).
 """
@@ -49,11 +50,19 @@ def pick_model(version):
     return table[version]()
 
 
+def test_options(params):
+    """The optional TEST keys with a closed set of values, checked before a network is built: `resize` (stretch | letterbox).
+    Returns them parsed; anything else raises ValueError."""
+    from . import _hip
+    return {"resize": _hip.resize_mode(params.get("resize", "stretch"))}
+
+
 def run(cfg, mode, section=None):
     yolo = pick_model(cfg["COMMON"]["version"])
     if mode == "test":
         params = dict(cfg[section or "TEST"])
         params.update(cfg["COMMON"])
+        test_options(params)
         yolo.test(params)
     elif mode in ("train", "anchor"):
         raise SystemExit("mode '{}' is not supported by the HIP inference backend (TEST mode only)".format(mode))

@@ -121,6 +121,18 @@ def decode_image(image_path):
     return np.array(img.convert("RGB"), dtype=np.uint8)         # a writable, contiguous copy
 
 
+def decode_frames(image_paths):
+    """decode_image of every path (RGB uint8 [h, w, 3], sizes as they come): the frames of one batch for the batched device-side resize
+    (HipNetwork.frame_descs / preprocess_frames).  Raises IOError for a file that cannot be read, as generate_test_batch does."""
+    frames = []
+    for p in image_paths:
+        rgb = decode_image(p)
+        if rgb is None:
+            raise IOError("cannot read image {}".format(p))
+        frames.append(rgb)
+    return frames
+
+
 def preprocess_image_gpu(image_path, new_shape, device=None, stream=None):
     """preprocess_image with the resize / colour order / /255 on the device (yolo_preprocess_resize): OpenCV's 8-bit
     INTER_LINEAR arithmetic (what the reference's cv2.resize computes, restated in oracle/preprocess_ref.py) instead of

@@ -71,12 +71,14 @@ def gather_records(flat, group=None, always=False):
     return out.view(w, flat.numel())
 
 
-def detect_sharded(engine, x_local, threshold, iou_threshold, nms_mode=0, group=None, u8=False):
+def detect_sharded(engine, x_local, threshold, iou_threshold, nms_mode=0, group=None, u8=False, after_detect=None):
     """One step of the sharded hot path on this rank: forward + decode + NMS of the local shard (one C call,
     `engine.detect`) and the all-gather of the record buffer.  x_local may be None / empty when the global batch
     leaves this rank without images (its counts are then zero).  `engine` needs `.records` (int32
     [record_words]), `.max_batch`, `.max_boxes` and `.detect()`; the gloo tests pass a CPU stand-in.
     u8: x_local is a uint8 batch (0..255) and goes through `engine.detect_u8` (same records as float32(x / 255.) through `detect`).
+    after_detect: called behind this rank's detect, before the all-gather, when the rank ran images (Yolo.predict_frames: the rank maps
+    the boxes of its own shard to frame coordinates on the device, so the record exchange stays what it is).
     Returns (boxes [W, B, K, 6], counts [W, B], status [W, B]) as views of the gathered buffer."""
     n_local = 0 if x_local is None else int(x_local.shape[0])
     B = engine.max_batch
@@ -95,6 +97,8 @@ def detect_sharded(engine, x_local, threshold, iou_threshold, nms_mode=0, group=
         engine.detect_u8(x_local, threshold, iou_threshold, nms_mode)
     elif n_local:
         engine.detect(x_local, threshold, iou_threshold, nms_mode)
+    if n_local and after_detect is not None:
+        after_detect()
     if n_local < B:         # records of images this rank did not run: count 0, status 0
         engine.records[n_local:B].zero_()
         engine.records[B + n_local:2 * B].zero_()

@@ -296,6 +296,87 @@ class HipNetwork(Plan):
         self.u8_calls += 1
         return self._boxes[:b], self._counts[:b], self._status[:b]
 
+    # -- frames of any size: batched resize / letterbox, boxes in frame coordinates -----------------------------------------------
+    def frame_descs(self, frames):
+        """list of uint8 [h, w, 3] frames of any sizes (NumPy arrays, or torch tensors on any device) -> (yolo_frame array, the device
+        tensors it points into).  Host frames travel in ONE copy, each starting on a 256-byte boundary; a device tensor whose pixels are
+        dense within a row is described where it lies (any pitch, any alignment)."""
+        torch = self.torch
+        n = len(frames)
+        descs = (_hip.Frame * max(n, 1))()
+        keep, host, spans, total = [], [], [], 0
+        for i, f in enumerate(frames):
+            dt = str(getattr(f, "dtype", None)).replace("torch.", "")
+            shape = tuple(int(v) for v in getattr(f, "shape", ()))
+            if dt != "uint8" or len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+                raise ValueError("frame %d: expected a uint8 array or tensor [h, w, 3], got %s %s" % (i, dt, shape))
+            if isinstance(f, torch.Tensor) and f.device.type != "cpu":
+                t = f.to(self.device)
+                if t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * shape[1]:
+                    t = t.contiguous()
+                keep.append(t)
+                descs[i] = _hip.Frame(t.data_ptr(), shape[0], shape[1], t.stride(0), 0)
+            else:
+                a = f.numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
+                host.append((i, np.ascontiguousarray(a).reshape(-1)))
+                spans.append((i, total, shape))
+                total += (a.size + 255) // 256 * 256
+        if host:
+            stage = np.empty(total, dtype=np.uint8)
+            for (i, flat), (_, off, _) in zip(host, spans):
+                stage[off:off + flat.size] = flat
+            dev = torch.from_numpy(stage).to(self.device)
+            keep.append(dev)
+            for i, off, shape in spans:
+                descs[i] = _hip.Frame(dev.data_ptr() + off, shape[0], shape[1], 3 * shape[1], 0)
+        return descs, keep
+
+    def _frames_batch(self, n, u8=True):
+        """the batch tensor the frame entries resize into: [max_batch, H, W, 3], allocated once per type"""
+        h, w, c = self.input_hwc
+        if c != 3:
+            raise ValueError("the frame entries need a network input of 3 channels, this one has %d" % c)
+        if not 1 <= n <= self.max_batch:
+            raise ValueError("batch %d outside 1..%d (max_batch)" % (n, self.max_batch))
+        key = "_frames_u8" if u8 else "_frames_f32"
+        if getattr(self, key, None) is None:
+            setattr(self, key, self.torch.empty((self.max_batch, h, w, 3), dtype=self.torch.uint8 if u8 else self.torch.float32, device=self.device))
+        return getattr(self, key)[:n]
+
+    def preprocess_frames(self, descs, n, resize=_hip.RESIZE_STRETCH, u8=True, out=None):
+        """yolo_preprocess_frames[_u8]: the n frames of `descs` (frame_descs) -> the batch tensor [n, H, W, 3] (uint8, or float32 in
+        [0, 1]), stretched or letterboxed, one launch per 64 frames.  Enqueued; returns the tensor."""
+        x = self._frames_batch(n, u8) if out is None else out
+        h, w, _ = self.input_hwc
+        name = "yolo_preprocess_frames_u8" if u8 else "yolo_preprocess_frames"
+        with self.torch.cuda.device(self.device):
+            _hip.check(getattr(self.lib, name)(descs, n, int(resize), x.data_ptr(), h, w, self._stream()), name)
+        return x
+
+    def boxes_to_frames(self, descs, n, resize):
+        """yolo_boxes_to_frames on the engine's own record buffer: the records of the last detect call, normalised to the network input,
+        become normalised to each frame (in place, on the device; nothing happens for stretch)."""
+        h, w, _ = self.input_hwc
+        with self.torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_boxes_to_frames(self._boxes.data_ptr(), self._counts.data_ptr(), n, self.max_boxes, descs, int(resize),
+                                                     h, w, self._stream()), "yolo_boxes_to_frames")
+
+    def detect_frames(self, frames, threshold, iou_threshold, nms_mode=_hip.NMS_AGNOSTIC, resize=_hip.RESIZE_STRETCH):
+        """One enqueue for a whole step (yolo_net_detect_frames_u8): frames of any sizes -> batched resize (stretch | letterbox) into a
+        uint8 batch -> forward + decode + NMS -> boxes normalised to each frame.  Returns what detect() returns."""
+        n = len(frames)
+        x = self._frames_batch(n, True)
+        descs, keep = self.frame_descs(frames)
+        if self._auto_streams and not self._streams_tuned:         # (the one-off stream measurement wants the batch it would run)
+            self._tune_streams(self.preprocess_frames(descs, n, resize, True))
+        with self.torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_detect_frames_u8(self.handle, descs, n, int(resize), x.data_ptr(), float(threshold), float(iou_threshold),
+                                                          int(nms_mode), self._boxes.data_ptr(), self._counts.data_ptr(),
+                                                          self._status.data_ptr(), self._stream()), "yolo_net_detect_frames_u8")
+        self.u8_calls += 1
+        self._frames_keep = keep        # (the frames stay allocated until the next call: the work is only enqueued)
+        return self._boxes[:n], self._counts[:n], self._status[:n]
+
     def forward_timed_u8(self, x, out=None):
         """forward_timed() for a uint8 batch: the input kernel's entry is the time of its uint8 twin."""
         torch = self.torch

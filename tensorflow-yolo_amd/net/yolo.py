@@ -83,10 +83,38 @@ class Yolo(object):
             return self.predict_shard(x_batch_u8[lo:hi] if hi > lo else None, len(x_batch_u8), threshold, iou_threshold, nms_mode, group, u8=True)
         return self.predict_shard(x_batch_u8, len(x_batch_u8), threshold, iou_threshold, nms_mode, group, u8=True)
 
-    def predict_shard(self, x_local, n_global, threshold=0.5, iou_threshold=0.6, nms_mode=_hip.NMS_AGNOSTIC, group=None, u8=False):
+    def predict_frames(self, frames, threshold=0.5, iou_threshold=0.6, nms_mode=_hip.NMS_AGNOSTIC, resize="stretch", group=None):
+        """predict() for frames of ANY sizes: a list of uint8 [h, w, 3] RGB arrays or device tensors.  The whole batch is resized on the
+        device in one launch -- resize = "stretch" (the reference, net/base.py:121) or "letterbox" (Darknet's `detector test`: aspect
+        ratio kept, grey canvas) -- and the boxes come back normalised to each FRAME, so draw_boxes and every other consumer of
+        BoundingBox work as they are.  Stretch returns exactly what predict_u8 returns for the frames resized one by one.  Sharding as
+        in predict_u8: each rank resizes, runs and maps back its own shard before the one all-gather."""
+        mode = _hip.resize_mode(resize)
+        eng = self.net.engine
+        if not eng.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
+        frames = list(frames)
+        rank, world = ydist.world(group)
+        if world > 1:
+            lo, hi = ydist.shard_range(len(frames), rank, world)
+            local = frames[lo:hi]
+            if not local:
+                return self.predict_shard(None, len(frames), threshold, iou_threshold, nms_mode, group, u8=True)
+            descs, keep = eng.frame_descs(local)
+            x_local = eng.preprocess_frames(descs, len(local), mode, True)
+            return self.predict_shard(x_local, len(frames), threshold, iou_threshold, nms_mode, group, u8=True,
+                                      after_detect=lambda: eng.boxes_to_frames(descs, len(local), mode))
+        boxes, counts, status = eng.detect_frames(frames, threshold, iou_threshold, nms_mode, mode)
+        records, self.last_status = engine.records_to_host(boxes, counts, status)
+        return base.boxes_from_records(records)
+
+    def predict_shard(self, x_local, n_global, threshold=0.5, iou_threshold=0.6, nms_mode=_hip.NMS_AGNOSTIC, group=None, u8=False,
+                      after_detect=None):
         """predict() for a caller that holds only ITS images of the global batch (Yolo.test under torch.distributed
         preprocesses just the rank's shard): x_local = images shard_range(n_global, rank, world) of the batch, or None
-        when the shard is empty.  u8: x_local is uint8 0..255 (predict_u8).  Returns the list for all n_global images on every rank."""
+        when the shard is empty.  u8: x_local is uint8 0..255 (predict_u8).  after_detect: called behind the local detect, before the
+        records leave the device (predict_frames / Yolo.test: boxes to frame coordinates).  Returns the list for all n_global images on
+        every rank."""
         eng = self.net.engine
         if not eng.weights_loaded:
             raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
@@ -100,10 +128,11 @@ class Yolo(object):
             n_local = 0 if x_local is None else len(x_local)
             if n_local != hi - lo:
                 raise ValueError("rank %d holds %d images of a global batch of %d, its shard is [%d, %d)" % (rank, n_local, n, lo, hi))
+            extra = {"after_detect": after_detect} if after_detect is not None else {}
             if u8:
-                boxes, counts, status = ydist.detect_sharded(eng, x_local if n_local else None, threshold, iou_threshold, nms_mode, group, u8=True)
+                boxes, counts, status = ydist.detect_sharded(eng, x_local if n_local else None, threshold, iou_threshold, nms_mode, group, u8=True, **extra)
             else:
-                boxes, counts, status = ydist.detect_sharded(eng, x_local if n_local else None, threshold, iou_threshold, nms_mode, group)
+                boxes, counts, status = ydist.detect_sharded(eng, x_local if n_local else None, threshold, iou_threshold, nms_mode, group, **extra)
             keep = [r * eng.max_batch + i for r in range(world) for i in range(per)][:n]     # slot of global image g
             status = status.cpu().numpy().reshape(-1)[keep]
             self.last_status = status
@@ -111,6 +140,8 @@ class Yolo(object):
             lists = ydist.records_to_lists(boxes, counts)
             return base.boxes_from_records([lists[k] for k in keep])
         boxes, counts, status = (eng.detect_u8 if u8 else eng.detect)(x_local, threshold, iou_threshold, nms_mode)
+        if after_detect is not None:
+            after_detect()
         records, self.last_status = engine.records_to_host(boxes, counts, status)
         return base.boxes_from_records(records)
 
@@ -171,6 +202,11 @@ class Yolo(object):
         # resize / colour order / /255 run on the device with OpenCV's INTER_LINEAR arithmetic (base.preprocess_image_gpu);
         # `preprocess = pillow` (new optional key) keeps the host-side Pillow resampler
         pillow = str(params.get("preprocess", "gpu")).lower() == "pillow"
+        # `resize` (new optional key): "stretch", the default, is the reference's geometry (net/base.py:121); "letterbox" is Darknet's
+        # `detector test` -- aspect ratio kept, grey canvas, boxes mapped back to the frame on the device (yolo_boxes_to_frames)
+        resize = _hip.resize_mode(params.get("resize", "stretch"))
+        if pillow and resize != _hip.RESIZE_STRETCH:
+            raise ValueError("resize = letterbox needs the device-side preprocessing (preprocess = gpu)")
         # One process: the loop is a three-stage pipeline (new optional key `pipeline`, default True): worker threads decode the files
         # of batch i + 1 and draw / encode / write the images of batch i - 1 while the GPU runs batch i; the box records come back by
         # an asynchronous copy into pinned memory.  Same files, same console lines in the same order as the serial loop.
@@ -183,20 +219,30 @@ class Yolo(object):
             # files, a quarter of the staging memory; "f32", the default until tools/e2e_launcher.py has timed both, the float32 batch)
             self._test_pipelined(image_paths, out_dir, batch_size, input_shape, threshold, iou_threshold, nms_mode, class_names,
                                  workers=int(params.get("workers", 0)), timings=self.timing,
-                                 staging=str(params.get("staging", "f32")).lower())
+                                 staging=str(params.get("staging", "f32")).lower(), resize=resize)
             self.timing["loop_s"] = time.perf_counter() - t_loop
             print("Done")
             return
         self.timing.update(mode="serial", decode_preprocess=0.0, predict=0.0, draw_save=0.0)
-        batches = base.generate_test_batch if pillow else base.generate_test_batch_gpu
+        eng = self.net.engine
         for start in range(0, len(image_paths), batch_size):
             paths = image_paths[start:start + batch_size]
             # every rank decodes / resizes only ITS shard of the batch (one process per GPU)
             lo, hi = ydist.shard_range(len(paths), rank, world)
             t0 = time.perf_counter()
-            x_local = next(iter(batches(paths[lo:hi], batch_size, input_shape)))[0] if hi > lo else None
+            after = None
+            if hi <= lo:
+                x_local = None
+            elif pillow:
+                x_local = next(iter(base.generate_test_batch(paths[lo:hi], batch_size, input_shape)))[0]
+            else:
+                # the shard's frames in one copy and ONE resize launch (yolo_preprocess_frames) where a launch per image used to be
+                descs, keep = eng.frame_descs(base.decode_frames(paths[lo:hi]))
+                x_local = eng.preprocess_frames(descs, hi - lo, resize, u8=False)
+                if resize != _hip.RESIZE_STRETCH:
+                    after = lambda d=descs, n=hi - lo: eng.boxes_to_frames(d, n, resize)
             t1 = time.perf_counter()
-            net_boxes = self.predict_shard(x_local, len(paths), threshold, iou_threshold, nms_mode)
+            net_boxes = self.predict_shard(x_local, len(paths), threshold, iou_threshold, nms_mode, after_detect=after)
             t2 = time.perf_counter()
             self.timing["decode_preprocess"] += t1 - t0
             self.timing["predict"] += t2 - t1
@@ -214,13 +260,14 @@ class Yolo(object):
             print("Done")
 
     def _test_pipelined(self, image_paths, out_dir, batch_size, input_shape, threshold, iou_threshold, nms_mode, class_names, workers=0,
-                        timings=None, staging="f32"):
+                        timings=None, staging="f32", resize=_hip.RESIZE_STRETCH):
         """The body of the reference's test loop (net/yolo.py:80-95) as a pipeline over batches:
 
             worker threads   decode_image() of the files of batch i + 1 (Pillow releases the GIL inside its codecs)
-            this thread      batch i: uint8 pixels -> pinned staging -> device (async), yolo_preprocess_resize of every image
-                             straight into the batch tensor, yolo_net_detect (staging = "u8": a uint8 batch tensor through
-                             yolo_preprocess_resize_u8 / yolo_net_detect_u8, same records), async copy of the record buffer
+            this thread      batch i: uint8 pixels -> pinned staging -> device (async), ONE yolo_preprocess_frames of all its images
+                             (stretch or letterbox) straight into the batch tensor, yolo_net_detect (staging = "u8": a uint8 batch
+                             tensor through yolo_preprocess_frames_u8 / yolo_net_detect_u8, same records), for letterbox
+                             yolo_boxes_to_frames on the survivors, async copy of the record buffer
                              [counts | status | boxes] to pinned memory + an event -- nothing here waits for the GPU
             worker PROCESSES batch i - 1, once its event has fired: records -> BoundingBox lists, draw_boxes on the pixels
                              already decoded (no second read of the file), encode + write `<stem>_out<ext>`
@@ -259,8 +306,9 @@ class Yolo(object):
             raise ValueError("staging must be u8 or f32, got %r" % (staging,))
         u8 = staging == "u8"
         t["staging"] = staging
-        resize = lib.yolo_preprocess_resize_u8 if u8 else lib.yolo_preprocess_resize
-        resize_name = "yolo_preprocess_resize_u8" if u8 else "yolo_preprocess_resize"
+        resize_name = "yolo_preprocess_frames_u8" if u8 else "yolo_preprocess_frames"
+        resize_frames = getattr(lib, resize_name)
+        descs = (_hip.Frame * batch_size)()
         x_dev = [torch.empty((batch_size, h, w, c), dtype=torch.uint8 if u8 else torch.float32, device=torch_dev) for _ in range(2)]
         rec_host = [torch.empty(ydist.record_words(eng.max_batch, eng.max_boxes), dtype=torch.int32).pin_memory() for _ in range(2)]
         stage_host, stage_dev = [None, None], [None, None]
@@ -323,11 +371,14 @@ class Yolo(object):
                 off += (n + 255) // 256 * 256
             stage_dev[slot][:off].copy_(stage_host[slot][:off], non_blocking=True)
             x = x_dev[slot][:len(paths)]
+            base_ptr = stage_dev[slot].data_ptr()
             for i, (o, ih, iw) in enumerate(spans):
-                _hip.check(resize(stage_dev[slot].data_ptr() + o, ih, iw, iw * 3, x[i].data_ptr(), h, w, 0, stream.cuda_stream), resize_name)
+                descs[i] = _hip.Frame(base_ptr + o, ih, iw, iw * 3, 0)
+            _hip.check(resize_frames(descs, len(spans), resize, x.data_ptr(), h, w, stream.cuda_stream), resize_name)
             t["upload_resize_enqueue"] += time.perf_counter() - t0
             t0 = time.perf_counter()
             (eng.detect_u8 if u8 else eng.detect)(x, threshold, iou_threshold, nms_mode)
+            eng.boxes_to_frames(descs, len(spans), resize)        # (stretch: returns at once, nothing is launched)
             rec_host[slot].copy_(eng.records, non_blocking=True)
             events[slot].record(stream)
             t["detect_enqueue"] += time.perf_counter() - t0
