@@ -56,8 +56,9 @@ def iou_score(b1, b2):                       # base.py:180-192
     imax = np.minimum(b1_max, b2_max)
     iwh = np.maximum(imax - imin, 0)
     inter = iwh[0] * iwh[1]
-    union = np.maximum(a1 + a2 - inter, 1e-8)
-    return inter / union
+    with np.errstate(invalid="ignore"):      # two infinite boxes: inf + inf - inf = NaN, np.maximum propagates it, NaN >= thr is False
+        union = np.maximum(a1 + a2 - inter, 1e-8)
+        return inter / union
 
 
 def non_maximum_suppression(boxes, iou_threshold):   # base.py:195-209

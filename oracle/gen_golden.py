@@ -58,10 +58,11 @@ def fake_v3_net(c):
     anc = np.reshape(anchors, [3, -1, 2])[::-1, :, :]               # net/v3.py:11
     det = _Obj()
     det.yolos = []
+    H, W = cases.input_hw(c)
     for i, s in enumerate((32, 16, 8)):
         y = _Obj()
-        y.h = y.w = c["input"] // s
-        stride = (c["input"] / y.h, c["input"] / y.w)
+        y.h, y.w = H // s, W // s
+        stride = (H / y.h, W / y.w)
         y.anchors = [(a[0] / stride[0], a[1] / stride[1]) for a in anc[i]]
         y.b = len(y.anchors)
         det.yolos.append(y)
@@ -119,7 +120,7 @@ def main():
         if c["version"] == 2:
             mine = decode_ref.find_bounding_boxes_v2(head, c["threshold"], c["iou"], c["anchors"], c["classes"])
         else:
-            sc = decode_ref.v3_scales(c["anchors"], (c["input"], c["input"]))
+            sc = decode_ref.v3_scales(c["anchors"], cases.input_hw(c))
             mine = decode_ref.find_bounding_boxes_v3(head, c["threshold"], c["iou"], sc)
         g = np.load(os.path.join(out_dir, "decode_%s.npz" % name))
         for i in range(c["batch"]):

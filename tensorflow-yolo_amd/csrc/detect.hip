@@ -154,6 +154,10 @@ __device__ __forceinline__ unsigned orderable(float f) {        // monotone floa
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// base.py:190 np.maximum(union, 1e-8): NaN-propagating, unlike fmax.  Two infinite boxes (expf overflow of a w/h logit above 88.7)
+// give inf + inf - inf = NaN, their IoU is NaN, NaN >= thr is false and the reference keeps both.
+__device__ __forceinline__ double union_floor(double u) { return u < 1e-8 ? 1e-8 : u; }
+
 // bytes of the union region { sort keys | sorted boxes (+ suppression bit matrix of the <= 512-candidate path) }
 __host__ __device__ inline size_t nms_union_bytes(size_t cap2) {
     const size_t u = (cap2 * 29 + 15) & ~(size_t)15;            // max(key 8 B, boxes 8+8+4+4+4+1 = 29 B) per entry
@@ -284,7 +288,7 @@ __global__ void __launch_bounds__(1024) nms_kernel(const NmsParams p) {
                 const double iw = fmax(fmin(ax2, bx2) - fmax(ax1, bx1), 0.);
                 const double ih = fmax(fmin(ay2, by2) - fmax(ay1, by1), 0.);
                 const double inter = iw * ih;
-                const double uni = fmax(a1 + w2 * h2 - inter, 1e-8);                // base.py:190
+                const double uni = union_floor(a1 + w2 * h2 - inter);               // base.py:190
                 hit = inter / uni >= thr;                                           // base.py:204
             }
             const unsigned long long bits = __ballot(hit);
@@ -332,7 +336,7 @@ __global__ void __launch_bounds__(1024) nms_kernel(const NmsParams p) {
             const double iw = fmax(fmin(ax2, bx2) - fmax(ax1, bx1), 0.);
             const double ih = fmax(fmin(ay2, by2) - fmax(ay1, by1), 0.);
             const double inter = iw * ih;
-            const double uni = fmax(a1 + w2 * h2 - inter, 1e-8);                // base.py:190
+            const double uni = union_floor(a1 + w2 * h2 - inter);               // base.py:190
             if (inter / uni >= thr) alive[j] = 0;                               // base.py:204
         }
         __syncthreads();

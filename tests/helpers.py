@@ -73,12 +73,18 @@ def match_boxes(got, want, atol_xy=2e-5, atol_p=2e-6):
     """got/want: lists of (x,y,w,h,cls,prob) in output order.  Exact order, class and count; coordinates/prob to float32
     rounding.  Order: up to boxes whose scores tie within 4 float32 ulps -- the reference's score is float32 arithmetic on
     NumPy's float32 exp (net/base.py:171-172), a few ulp accurate and not the same function as the GPU's expf, so two rows
-    whose exact scores are closer than that may be sorted either way (oracle/parity.py: kTieUlps)."""
+    whose exact scores are closer than that may be sorted either way (oracle/parity.py: kTieUlps).  A non-finite value
+    (an infinite box: expf overflow) matches only its exact equal."""
     assert len(got) == len(want), "count %d vs %d" % (len(got), len(want))
 
+    def close(g, w, atol):
+        if not (np.isfinite(g) and np.isfinite(w)):
+            return g == w
+        return abs(g - w) <= atol
+
     def same(g, w):
-        return (int(g[4]) == int(w[4]) and abs(g[5] - w[5]) <= atol_p and
-                all(abs(g[i] - w[i]) <= atol_xy * max(1.0, abs(w[i])) for i in range(4)))
+        return (int(g[4]) == int(w[4]) and close(g[5], w[5], atol_p) and
+                all(close(g[i], w[i], atol_xy * max(1.0, abs(w[i]))) for i in range(4)))
 
     tie = 4 * 2.0 ** -24
     used = [False] * len(want)
@@ -96,3 +102,47 @@ def match_boxes(got, want, atol_xy=2e-5, atol_p=2e-6):
         w = want[k]
         assert j is not None, "box %d: %r vs %r (no box of the tied-score run %d..%d matches)" % (k, tuple(g), tuple(w), lo, hi)
         used[j] = True
+
+
+def guarded_run(net, w, x, dtype, tile=None, keep_all=True, detect=False, guard=4096):
+    """Plan with `guard` never-used bytes behind every tensor, fill the WHOLE workspace with a pattern, run, and require every byte no
+    plan region claims as payload to still hold the pattern: the slack + guard behind each tensor / candidate list / counter block /
+    scratch slab (yolo_net_workspace_regions).  With keep_all no two tensors share bytes; without it (the fused production plan:
+    lifetime-packed arenas) only slack that no other region's payload overlaps can be checked."""
+    import torch
+    from tensorflow_yolo_amd import _hip
+    eng = engine.HipNetwork(net, dtype=dtype, max_batch=x.shape[0], keep_all=keep_all, force_tile=tile, guard_bytes=guard)
+    eng.load_weights(w)
+    ws = eng._workspace
+    ws.fill_(0xA5)
+    _hip.check(eng.lib.yolo_net_bind_workspace(eng.handle, ws.data_ptr(), ws.numel()), "yolo_net_bind_workspace")   # (zeroes the tickets)
+    eng.forward(x)
+    if detect:
+        eng.detect(x, 0.3, 0.6)
+    torch.cuda.synchronize()
+    regions = eng.workspace_regions()
+    payload = sorted((off, off + used) for _, off, used, _ in regions if used)
+    checked = 0
+    for name, off, used, region in regions:
+        lo, hi = off + used, off + region
+        if hi <= lo:
+            continue
+        # cut out what another region's payload covers (lifetime-packed arenas)
+        spans, cur = [], lo
+        for a, b in payload:
+            if b <= cur or a >= hi:
+                continue
+            if a > cur:
+                spans.append((cur, a))
+            cur = max(cur, b)
+            if cur >= hi:
+                break
+        if cur < hi:
+            spans.append((cur, hi))
+        for a, b in spans:
+            bad = (ws[a:b] != 0xA5).nonzero()
+            assert bad.numel() == 0, "%s (tile %s, %s): byte %d behind the payload of a %d-byte region was written\n%s" % (
+                name, tile, dtype, int(bad[0]) + a - lo, used, eng.describe())
+            checked += b - a
+    assert checked >= guard, "nothing to check"
+    return eng, checked

@@ -129,10 +129,10 @@ def test_whole_net_mxfp8_against_the_fp32_oracle(kind):
 
 
 def test_mx_launches_write_only_their_tensors():
-    from test_gpu_ops import _guarded_run
+    from helpers import guarded_run
     g = new_graph(19, 21, 256)
     g.append(PL.conv2d_bn_act(g[-1].out, 256, 3, 1))
     g.append(PL.shortcut(g[-1].out, g[0].out))           # MX conv + fused residual add
     g.append(PL.conv2d_bn_act(g[-1].out, 128, 3, 1))      # a second MX conv
     g.append(PL.conv2d_bn_act(g[-1].out, 16, 1, 1))
-    _guarded_run(g, synth.darknet_stream(g, seed=2), synth.synthetic_input(3, 19, 21, 256, seed=2), "mxfp8")
+    guarded_run(g, synth.darknet_stream(g, seed=2), synth.synthetic_input(3, 19, 21, 256, seed=2), "mxfp8")

@@ -11,7 +11,7 @@ import zlib
 import numpy as np
 import pytest
 
-from helpers import new_graph, rel_err, run_hip, to_oracle
+from helpers import guarded_run, new_graph, rel_err, run_hip, to_oracle
 from oracle import forward_ref as FR, topology as T
 from tensorflow_yolo_amd.net import layers as PL, synth
 
@@ -578,51 +578,6 @@ def test_split_k_small_maps(dtype, batch):
 
 
 # ---- guard-band canaries -----------------------------------------------------------------------------
-def _guarded_run(net, w, x, dtype, tile=None, keep_all=True, detect=False, guard=4096):
-    """Plan with `guard` never-used bytes behind every tensor, fill the WHOLE workspace with a pattern, run, and require every byte no
-    plan region claims as payload to still hold the pattern: the slack + guard behind each tensor / candidate list / counter block /
-    scratch slab (yolo_net_workspace_regions).  With keep_all no two tensors share bytes; without it (the fused production plan:
-    lifetime-packed arenas) only slack that no other region's payload overlaps can be checked."""
-    import torch
-    from tensorflow_yolo_amd import _hip
-    from tensorflow_yolo_amd.net import engine
-    eng = engine.HipNetwork(net, dtype=dtype, max_batch=x.shape[0], keep_all=keep_all, force_tile=tile, guard_bytes=guard)
-    eng.load_weights(w)
-    ws = eng._workspace
-    ws.fill_(0xA5)
-    _hip.check(eng.lib.yolo_net_bind_workspace(eng.handle, ws.data_ptr(), ws.numel()), "yolo_net_bind_workspace")   # (zeroes the tickets)
-    eng.forward(x)
-    if detect:
-        eng.detect(x, 0.3, 0.6)
-    torch.cuda.synchronize()
-    regions = eng.workspace_regions()
-    payload = sorted((off, off + used) for _, off, used, _ in regions if used)
-    checked = 0
-    for name, off, used, region in regions:
-        lo, hi = off + used, off + region
-        if hi <= lo:
-            continue
-        # cut out what another region's payload covers (lifetime-packed arenas)
-        spans, cur = [], lo
-        for a, b in payload:
-            if b <= cur or a >= hi:
-                continue
-            if a > cur:
-                spans.append((cur, a))
-            cur = max(cur, b)
-            if cur >= hi:
-                break
-        if cur < hi:
-            spans.append((cur, hi))
-        for a, b in spans:
-            bad = (ws[a:b] != 0xA5).nonzero()
-            assert bad.numel() == 0, "%s (tile %s, %s): byte %d behind the payload of a %d-byte region was written\n%s" % (
-                name, tile, dtype, int(bad[0]) + a - lo, used, eng.describe())
-            checked += b - a
-    assert checked >= guard, "nothing to check"
-    return eng, checked
-
-
 @pytest.mark.parametrize("dtype", ["fp16", "fp32"])
 @pytest.mark.parametrize("which", ["v2-416", "v3-160", "tiny-v2-416"])
 def test_no_kernel_writes_outside_its_tensor_whole_nets(which, dtype):
@@ -645,7 +600,7 @@ def test_no_kernel_writes_outside_its_tensor_whole_nets(which, dtype):
     x = synth.synthetic_input(batch, size, size, 3, seed=32)
     total = 0
     for keep_all in (True, False):
-        eng, checked = _guarded_run(net, w, x, dtype, keep_all=keep_all, detect=(which == "v3-160"))
+        eng, checked = guarded_run(net, w, x, dtype, keep_all=keep_all, detect=(which == "v3-160"))
         total += checked
     print("%s %s: %d guard / slack bytes intact" % (which, dtype, total))
 
@@ -676,6 +631,6 @@ def test_no_kernel_writes_outside_its_tensor_every_tile(tile):
         w = synth.darknet_stream(g, seed=41)
         x = synth.synthetic_input(B, H, W, 3, seed=42)
         for dtype in ("fp16", "fp32"):
-            _, checked = _guarded_run(g, w, x, dtype, tile=tile, keep_all=True)
+            _, checked = guarded_run(g, w, x, dtype, tile=tile, keep_all=True)
             total += checked
     print("tile %d: %d guard / slack bytes intact" % (tile, total))

@@ -112,7 +112,7 @@ def test_spp_block_bit_exact(hw, C, monkeypatch):
 def test_spp_block_writes_only_its_tensors(fuse, monkeypatch):
     """guard bytes behind every tensor and a pattern-filled workspace: every byte outside the regions' payloads stays intact (19 x 19 with a
     ragged last slab of chunks, and a 2 x 2 map whose windows all exceed it)"""
-    from test_gpu_ops import _guarded_run
+    from helpers import guarded_run
     if fuse:
         monkeypatch.delenv("YOLO_NO_SPP_FUSE", raising=False)
     else:
@@ -121,7 +121,7 @@ def test_spp_block_writes_only_its_tensors(fuse, monkeypatch):
     for H, W, C in ((19, 19, 264), (2, 2, 24), (32, 32, 8)):
         g, w = spp_graph(H, W, C, "fp16", False)
         for keep_all in (True, False):
-            eng, checked = _guarded_run(g, w, synth.synthetic_input(3, H, W, 3, seed=5), "fp16", keep_all=keep_all)
+            eng, checked = guarded_run(g, w, synth.synthetic_input(3, H, W, 3, seed=5), "fp16", keep_all=keep_all)
             syms = [ki.symbol.decode() for ki in eng.kernel_infos() if ki.kind == 2]
             assert syms == ([SPP_SYMBOL] if fuse else [same_symbol(False, True)] * 3), syms
             total += checked

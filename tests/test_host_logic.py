@@ -380,3 +380,19 @@ def test_tap_variant_tables_agree_with_the_instantiation_list():
         assert wm * wn == 8 and na == wm * tm * 16 and nb == wn * tp * 16, m.group(0)
         seen[fam] += 1
     assert seen == {"tap": 14, "dma": 9}
+
+
+def test_vector_nms_equals_the_pinned_restatements():
+    """tests/nms_ref.py (the vectorised float64 NMS the GPU tests use at sizes the pure-Python restatement is too slow for) against
+    oracle/decode_ref.py, which is pinned to the reference: both modes, 400 boxes of three classes with rounded -- tied -- probabilities"""
+    from nms_ref import random_boxes, vector_nms
+    from oracle import decode_ref
+    xy, wh, prob, cls = random_boxes(np.random.RandomState(3), 400)
+    cls = cls % 3
+    assert len(np.unique(prob)) < 400
+    boxes = [decode_ref.Box(xy[i, 0], xy[i, 1], wh[i, 0], wh[i, 1], int(cls[i]), prob[i], scan=i) for i in range(400)]
+    kept = {}
+    for per_class, ref in ((False, decode_ref.non_maximum_suppression), (True, decode_ref.non_maximum_suppression_per_class)):
+        kept[per_class] = [b.scan for b in ref(boxes, 0.45)]
+        assert kept[per_class] == [int(i) for i in vector_nms(xy[:, 0], xy[:, 1], wh[:, 0], wh[:, 1], prob, 0.45, cls=cls, per_class=per_class)]
+    assert 10 < len(kept[False]) < len(kept[True]) < 400

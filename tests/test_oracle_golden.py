@@ -22,7 +22,7 @@ def test_decode_matches_reference(name, full_scan):
     """full_scan: the per-cell Python scan exactly as the reference's triple loop walks it (what bench.py times as the CPU
     decode baseline) instead of the vectorised pre-filter -- both against the reference's own outputs"""
     c = cases.CASES[name]
-    if full_scan and c["input"] >= 608 and c["batch"] > 1:
+    if full_scan and max(cases.input_hw(c)) >= 608 and c["batch"] > 1:
         pytest.skip("the full scan of the large multi-image case takes tens of seconds; the single-image 608 case covers it")
     g, meta = _load(name)
     assert meta["source"] == "reference functions"
@@ -31,7 +31,7 @@ def test_decode_matches_reference(name, full_scan):
         if c["version"] == 2:
             mine = decode_ref.find_bounding_boxes_v2(head, c["threshold"], c["iou"], c["anchors"], c["classes"], nms=nms, full_scan=full_scan)
         else:
-            sc = decode_ref.v3_scales(c["anchors"], (c["input"], c["input"]))
+            sc = decode_ref.v3_scales(c["anchors"], cases.input_hw(c))
             mine = decode_ref.find_bounding_boxes_v3(head, c["threshold"], c["iou"], sc, nms=nms, full_scan=full_scan)
         for i in range(c["batch"]):
             want = g[("post%d" if nms else "pre%d") % i]
@@ -51,6 +51,50 @@ def test_fixture_margins():
             pre = g["pre%d" % i]
             if len(pre):
                 assert np.min(np.abs(pre[:, 5] - c["threshold"])) > 1e-5, name
+
+
+def _pre_with_rows(name):
+    """per image: the reference's own pre-NMS array and the head row of each of its entries (the restatement walks the
+    same scan order and agrees entry for entry: test_decode_matches_reference)"""
+    c = cases.CASES[name]
+    g, _ = _load(name)
+    head = cases.make_head(name)
+    if c["version"] == 2:
+        mine = decode_ref.find_bounding_boxes_v2(head, c["threshold"], c["iou"], c["anchors"], c["classes"], nms=False)
+    else:
+        mine = decode_ref.find_bounding_boxes_v3(head, c["threshold"], c["iou"], decode_ref.v3_scales(c["anchors"], cases.input_hw(c)), nms=False)
+    out = []
+    for i in range(c["batch"]):
+        pre = g["pre%d" % i]
+        assert len(pre) == len(mine[i])
+        out.append((pre, g["post%d" % i], {b.scan: k for k, b in enumerate(mine[i])}))
+    return out
+
+
+def test_new_fixtures_exercise_their_edges():
+    """computed from the reference's own pre / post arrays: the non-square and class-count cases have NMS work, every
+    engineered class tie reaches the candidates with the LOWER class index, both infinite boxes are candidates (and the
+    reference keeps both: their IoU is NaN)"""
+    for name in sorted(cases.CASES):
+        c = cases.CASES[name]
+        if "input_hw" in c or c["classes"] not in (20, 80):
+            for pre, post, _ in _pre_with_rows(name):
+                assert len(pre) >= 10 and len(post) < len(pre), (name, len(pre), len(post))
+        if c.get("class_ties"):
+            for pre, _, at in _pre_with_rows(name):
+                for row, cls in cases.class_tie_rows(name):
+                    assert row in at and int(pre[at[row], 4]) == cls, (name, row, cls)
+        if c.get("saturated"):
+            rows = cases.saturated_rows(name)
+            for pre, post, at in _pre_with_rows(name):
+                inf = [rows[k] for k in cases.SATURATED_INF]
+                assert all(r in at and np.isinf(pre[at[r], 2]) and np.isinf(pre[at[r], 3]) for r in inf), name
+                assert int(np.isinf(post[:, 2]).sum()) == 2, name
+                assert rows[2] not in at and rows[3] not in at                     # objectness -30 / -104
+                assert pre[at[rows[1]], 5] == (1.0 if c["version"] == 3 else 0.5) and int(pre[at[rows[1]], 4]) == 11
+                assert pre[at[rows[5]], 2] == 0.0 and pre[at[rows[5]], 3] == 0.0     # w = h = 0
+                assert np.isfinite(pre[at[rows[4]], 2:4]).all() and pre[at[rows[4]], 2:4].max() < 3.0e38
+                assert not np.isnan(pre).any()
 
 
 @pytest.mark.parametrize("name", sorted(cases.NMS_CASES))
