@@ -29,6 +29,9 @@
  *   yolo_letterbox_geometry, yolo_boxes_to_frames
  *                           no reference call site: net/base.py:121 only stretches, so its boxes are normalised to the frame as they are
  *                           (net/base.py:212-226 draw_boxes scales them by the frame size)
+ *   yolo_eval_reset, yolo_eval_add, yolo_eval_finish (+ yolo_eval_state_bytes, yolo_eval_result_bytes, yolo_eval_state_layout)
+ *                           no reference call site: the reference parses annotations (net/base.py:69-97) but never scores a detector;
+ *                           VOC average precision with the IoU of net/base.py:180-192
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -46,7 +49,10 @@ extern "C" {
                                           yolo_net_tune_streams_u8, yolo_preprocess_resize_u8, yolo_u8_unit_table;
                                           added WITHIN ABI 7 (new exports, struct yolo_frame and enum yolo_resize_mode only: no existing struct or
                                           entry changed) -- the frame entries yolo_letterbox_geometry, yolo_preprocess_frames,
-                                          yolo_preprocess_frames_u8, yolo_boxes_to_frames, yolo_net_detect_frames_u8 */
+                                          yolo_preprocess_frames_u8, yolo_boxes_to_frames, yolo_net_detect_frames_u8;
+                                          added WITHIN ABI 7 in the same way (new exports and the yolo_gt / yolo_eval_* PODs and enums only) -- the evaluation
+                                          entries yolo_eval_state_bytes, yolo_eval_result_bytes, yolo_eval_state_layout, yolo_eval_reset, yolo_eval_add,
+                                          yolo_eval_finish */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -344,6 +350,105 @@ int yolo_boxes_to_frames(yolo_box *boxes_dev, const int32_t *counts_dev, int bat
 int yolo_net_detect_frames_u8(yolo_net *net, const yolo_frame *frames_host, int batch, int mode, uint8_t *batch_dev, double threshold,
                               double iou_threshold, int nms_mode, yolo_box *boxes_dev, int32_t *counts_dev, int32_t *status_dev,
                               void *stream);
+
+/* ---- VOC-style evaluation on the device: match, AP, mAP (added within ABI 7: new exports, new PODs, nothing existing changed) ------
+ * Average precision against ground truth as VOCdevkit's voc_eval and Darknet's `detector map` define it, on the records that
+ * yolo_net_detect* left on the device.  No reference call site: the reference has parse_annotations (net/base.py:69-97) and nothing
+ * that scores a detector; the IoU is its net/base.py:180-192.
+ *
+ * Definitions.
+ *   IoU           net/base.py:180-192 in float64 with all eight float32 fields promoted, union floored at 1e-8 (np.maximum: a NaN
+ *                 stays a NaN).  Every operation is rounded on its own, as NumPy rounds it -- the intersection's product of two float64
+ *                 differences is not exact in general, so the kernel forbids FMA contraction here: the value equals NumPy's bit for bit.
+ *   best truth    of a detection: among the truths of the SAME image and SAME class_idx, difficult ones included, the one of largest IoU;
+ *                 ties go to the lowest index; an IoU that is NaN never wins.  No candidate: best_gt = -1, best_iou = 0, verdict FP.
+ *   verdict       detections in the global order (prob descending, then seq ascending; seq = image_index * max_boxes + rank in the
+ *                 image's list, a uint32).  best_iou > match_iou and the best truth difficult: IGNORED (neither TP nor FP, the truth is
+ *                 not taken).  best_iou > match_iou and the best truth not yet taken: TP, the truth is taken.  Otherwise FP.  The
+ *                 comparison is STRICT, as in VOCdevkit and Darknet -- a deliberate difference from the `>=` of NMS (net/base.py:204):
+ *                 a detection whose IoU is exactly match_iou is a false positive.
+ *   per image     a list in non-increasing prob order (yolo_net_detect* guarantees it) decides the global rule per image: the TP of a
+ *                 truth is the FIRST detection in list order that claims it.  A list that is not ordered sets YOLO_EVAL_UNSORTED.
+ *   per class c   n_gt[c] counts the non-difficult truths; the records of c sorted by (prob descending, seq ascending); ctp[k], cfp[k]
+ *                 integer cumulative counts with IGNORED records contributing nothing; in float64 recall = ctp / n_gt and
+ *                 precision = ctp / max(ctp + cfp, 2^-52) (VOCdevkit's eps).  ap_voc12 = sum over the TPs of (envelope precision at that
+ *                 TP) / n_gt, the area under the monotone precision envelope; ap_voc07 = sum over i = 0..10 of (the envelope at the first
+ *                 record with recall >= i / 10.0, else 0) / 11.  n_gt[c] == 0: both NaN, the class is left out of the means.
+ *   mAP           the mean over the classes with truths, NaN if there are none. */
+typedef struct yolo_gt {
+    float x, y, w, h;       /* centre / size, normalised like yolo_box (to the frame where the detections come from the frame entries) */
+    int32_t class_idx;
+    int32_t difficult;      /* VOC's flag: != 0 -- matching it is IGNORED, it is not counted in n_gt */
+} yolo_gt;
+
+enum yolo_eval_verdict { YOLO_EVAL_FP = 0, YOLO_EVAL_TP = 1, YOLO_EVAL_IGNORED = 2 };
+
+/* bits of the status word (yolo_eval_result.status; also readable in the state at yolo_eval_layout.status_offset) */
+enum yolo_eval_status {
+    YOLO_EVAL_OVERFLOW = 1,     /* more records than det_capacity: nothing was written behind the capacity, the result covers the first ones kept */
+    YOLO_EVAL_UNSORTED = 2,     /* an image's list was not in non-increasing prob order                                    */
+    YOLO_EVAL_BAD_CLASS = 4,    /* a truth or a detection with class_idx outside [0, n_classes): skipped                  */
+    YOLO_EVAL_BAD_COUNT = 8     /* a count below 0 or above max_boxes / max_gt: clamped                                    */
+};
+
+#define YOLO_EVAL_MAX_GT 1024               /* truths per image (they live in LDS)  */
+#define YOLO_EVAL_MAX_DET_CAPACITY (1 << 20)
+#define YOLO_EVAL_MAX_CLASSES 65536
+
+typedef struct yolo_eval_desc {
+    int32_t n_classes;      /* 1 .. YOLO_EVAL_MAX_CLASSES                                */
+    int32_t det_capacity;   /* records the state holds, 1 .. YOLO_EVAL_MAX_DET_CAPACITY */
+    int32_t max_gt;         /* truths per image the caller's arrays hold, 1 .. YOLO_EVAL_MAX_GT */
+    int32_t pad_;
+    double match_iou;       /* in [0, 1]; VOC: 0.5                                       */
+} yolo_eval_desc;
+
+/* one detection after matching (32 bytes) */
+typedef struct yolo_eval_record {
+    double best_iou;
+    float prob;
+    int32_t class_idx;
+    uint32_t seq;
+    int32_t verdict;        /* enum yolo_eval_verdict */
+    int32_t best_gt;        /* index into the image's truths or -1 */
+    int32_t pad_;
+} yolo_eval_record;
+
+typedef struct yolo_eval_class {
+    double ap_voc12, ap_voc07;
+    int32_t n_gt, n_det, tp, fp, ignored, pad_;
+} yolo_eval_class;
+
+/* result block: this header, then yolo_eval_class[n_classes] */
+typedef struct yolo_eval_result {
+    double map_voc12, map_voc07;
+    int32_t n_records;      /* records kept (at most det_capacity) */
+    int32_t status;         /* enum yolo_eval_status bits          */
+    int32_t n_classes, pad_;
+} yolo_eval_result;
+
+/* Where the readable parts of the state are (byte offsets): status word (uint32), n_gt int32[n_classes], the records in arrival order,
+ * and after yolo_eval_finish the records in sorted order (class ascending, prob descending, seq ascending) with ctp / cfp uint32 per
+ * sorted position; the first yolo_eval_result.n_records entries of each are valid. */
+typedef struct yolo_eval_layout {
+    uint64_t status_offset, n_gt_offset, records_offset, sorted_offset, ctp_offset, cfp_offset, total_bytes;
+} yolo_eval_layout;
+
+/* Device bytes of the caller-owned state / of the result block; 0 for a bad descriptor (yolo_last_error says why).  Replaces nothing. */
+size_t yolo_eval_state_bytes(const yolo_eval_desc *desc);
+size_t yolo_eval_result_bytes(const yolo_eval_desc *desc);
+int yolo_eval_state_layout(const yolo_eval_desc *desc, yolo_eval_layout *out);
+/* An empty state: no records, no truths, status 0.  state_bytes >= yolo_eval_state_bytes (YOLO_ERR_ARG otherwise).  Enqueued.  Replaces nothing. */
+int yolo_eval_reset(const yolo_eval_desc *desc, void *state_dev, size_t state_bytes, void *stream);
+/* One step's detections against its truths: boxes_dev [batch][max_boxes] and counts_dev [batch] as yolo_net_detect* wrote them,
+ * gt_dev [batch][max_gt] yolo_gt with gt_counts_dev [batch]; image_base = index of image 0 of this call in the dataset (seq).  One
+ * workgroup per image, enqueued on `stream` with no host synchronisation: it can follow yolo_net_detect* directly.  YOLO_ERR_ARG if
+ * (image_base + batch) * max_boxes does not fit 32 bits.  Replaces nothing in the reference (there is no evaluation there). */
+int yolo_eval_add(const yolo_eval_desc *desc, void *state_dev, const yolo_box *boxes_dev, const int32_t *counts_dev, int batch, int max_boxes,
+                  const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int64_t image_base, void *stream);
+/* Once per dataset: sorts the records, scans TP / FP per class, computes both APs per class and the means into result_dev
+ * (yolo_eval_result_bytes).  Enqueued; the state stays valid and further yolo_eval_add calls may follow.  Replaces nothing. */
+int yolo_eval_finish(const yolo_eval_desc *desc, void *state_dev, void *result_dev, void *stream);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

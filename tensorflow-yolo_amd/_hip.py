@@ -18,6 +18,9 @@ DTYPE_F32, DTYPE_F16, DTYPE_MXF8 = 0, 1, 2
 NMS_AGNOSTIC, NMS_PER_CLASS = 0, 1
 RESIZE_STRETCH, RESIZE_LETTERBOX = 0, 1         # enum yolo_resize_mode
 RESIZE_MODES = {"stretch": RESIZE_STRETCH, "letterbox": RESIZE_LETTERBOX}
+EVAL_FP, EVAL_TP, EVAL_IGNORED = 0, 1, 2        # enum yolo_eval_verdict
+EVAL_OVERFLOW, EVAL_UNSORTED, EVAL_BAD_CLASS, EVAL_BAD_COUNT = 1, 2, 4, 8       # enum yolo_eval_status
+EVAL_MAX_GT, EVAL_MAX_DET_CAPACITY, EVAL_MAX_CLASSES = 1024, 1 << 20, 65536
 FRAMES_PER_LAUNCH = 64                          # frames one launch of the batched resize covers (larger batches: consecutive launches)
 MAX_SRC, MAX_ANCHORS, MAX_SCALES = 4, 8, 4
 # Records per image every Python entry point asks for unless told otherwise.  The reference's lists are unbounded
@@ -52,6 +55,36 @@ class HeadDesc(C.Structure):
 class Frame(C.Structure):
     """yolo_frame: one decoded uint8 HWC3 frame on the device"""
     _fields_ = [("pixels_dev", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("row_bytes", C.c_int32), ("swap_rb", C.c_int32)]
+
+
+class Gt(C.Structure):
+    """yolo_gt: one ground-truth box (centre / size normalised like Box)"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("w", C.c_float), ("h", C.c_float), ("class_idx", C.c_int32), ("difficult", C.c_int32)]
+
+
+class EvalDesc(C.Structure):
+    _fields_ = [("n_classes", C.c_int32), ("det_capacity", C.c_int32), ("max_gt", C.c_int32), ("pad_", C.c_int32), ("match_iou", C.c_double)]
+
+
+class EvalRecord(C.Structure):
+    _fields_ = [("best_iou", C.c_double), ("prob", C.c_float), ("class_idx", C.c_int32), ("seq", C.c_uint32), ("verdict", C.c_int32),
+                ("best_gt", C.c_int32), ("pad_", C.c_int32)]
+
+
+class EvalClass(C.Structure):
+    _fields_ = [("ap_voc12", C.c_double), ("ap_voc07", C.c_double), ("n_gt", C.c_int32), ("n_det", C.c_int32), ("tp", C.c_int32),
+                ("fp", C.c_int32), ("ignored", C.c_int32), ("pad_", C.c_int32)]
+
+
+class EvalResultHeader(C.Structure):
+    """yolo_eval_result: the head of the result block, EvalClass[n_classes] follows"""
+    _fields_ = [("map_voc12", C.c_double), ("map_voc07", C.c_double), ("n_records", C.c_int32), ("status", C.c_int32),
+                ("n_classes", C.c_int32), ("pad_", C.c_int32)]
+
+
+class EvalLayout(C.Structure):
+    _fields_ = [("status_offset", C.c_uint64), ("n_gt_offset", C.c_uint64), ("records_offset", C.c_uint64), ("sorted_offset", C.c_uint64),
+                ("ctp_offset", C.c_uint64), ("cfp_offset", C.c_uint64), ("total_bytes", C.c_uint64)]
 
 
 class WsRegion(C.Structure):
@@ -116,6 +149,14 @@ SIGNATURES = {
     "yolo_boxes_to_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Frame), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_net_detect_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # VOC-style evaluation on the device (added within ABI 7)
+    "yolo_eval_state_bytes": (C.c_size_t, [C.POINTER(EvalDesc)]),
+    "yolo_eval_result_bytes": (C.c_size_t, [C.POINTER(EvalDesc)]),
+    "yolo_eval_state_layout": (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalLayout)]),
+    "yolo_eval_reset": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_eval_add": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_int64, C.c_void_p]),
+    "yolo_eval_finish": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "yolo_nms_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int,
                                 C.c_void_p, C.POINTER(C.c_int32)]),
 }

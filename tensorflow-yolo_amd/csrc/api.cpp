@@ -1081,6 +1081,94 @@ int yolo_net_detect_frames_u8(yolo_net *net, const yolo_frame *frames_host, int 
     return boxes_to_frames_any(boxes_dev, counts_dev, batch, net->opt.max_boxes, frames_host, mode, in.H, in.W, stream, who);
 }
 
+// ---- evaluation (yolo_hip.h: added within ABI 7; kernels in eval.hip) --------------------------------------------------------------
+// every check here is made on the host, before any device call
+static int check_eval_desc(const yolo_eval_desc *d, const char *who) {
+    if (!d) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (d->n_classes < 1 || d->n_classes > YOLO_EVAL_MAX_CLASSES)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": n_classes must be 1.." + std::to_string(YOLO_EVAL_MAX_CLASSES));
+    if (d->det_capacity < 1 || d->det_capacity > YOLO_EVAL_MAX_DET_CAPACITY)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": det_capacity must be 1.." + std::to_string(YOLO_EVAL_MAX_DET_CAPACITY));
+    if (d->max_gt < 1 || d->max_gt > YOLO_EVAL_MAX_GT)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": max_gt must be 1.." + std::to_string(YOLO_EVAL_MAX_GT));
+    if (!(d->match_iou >= 0. && d->match_iou <= 1.)) return fail(YOLO_ERR_ARG, std::string(who) + ": match_iou must be in [0, 1]");
+    return YOLO_OK;
+}
+
+size_t yolo_eval_state_bytes(const yolo_eval_desc *desc) {
+    if (check_eval_desc(desc, "yolo_eval_state_bytes")) return 0;
+    return eval_layout(desc->n_classes, desc->det_capacity).total;
+}
+
+size_t yolo_eval_result_bytes(const yolo_eval_desc *desc) {
+    if (check_eval_desc(desc, "yolo_eval_result_bytes")) return 0;
+    return sizeof(yolo_eval_result) + sizeof(yolo_eval_class) * (size_t)desc->n_classes;
+}
+
+int yolo_eval_state_layout(const yolo_eval_desc *desc, yolo_eval_layout *out) {
+    int rc = check_eval_desc(desc, "yolo_eval_state_layout");
+    if (rc) return rc;
+    if (!out) return fail(YOLO_ERR_ARG, "yolo_eval_state_layout: null argument");
+    const EvalLayout L = eval_layout(desc->n_classes, desc->det_capacity);
+    out->status_offset = L.header + offsetof(EvalHeader, status);
+    out->n_gt_offset = L.n_gt; out->records_offset = L.records; out->sorted_offset = L.sorted;
+    out->ctp_offset = L.ctp; out->cfp_offset = L.cfp; out->total_bytes = L.total;
+    return YOLO_OK;
+}
+
+int yolo_eval_reset(const yolo_eval_desc *desc, void *state_dev, size_t state_bytes, void *stream) {
+    int rc = check_eval_desc(desc, "yolo_eval_reset");
+    if (rc) return rc;
+    if (!state_dev) return fail(YOLO_ERR_ARG, "yolo_eval_reset: null argument");
+    const EvalLayout L = eval_layout(desc->n_classes, desc->det_capacity);
+    if (state_bytes < L.total) return fail(YOLO_ERR_ARG, "yolo_eval_reset: state too small (yolo_eval_state_bytes)");
+    HIP_TRY(hipMemsetAsync(state_dev, 0, L.records, static_cast<hipStream_t>(stream)));      // header + n_gt: the records behind are unread until written
+    return YOLO_OK;
+}
+
+int yolo_eval_add(const yolo_eval_desc *desc, void *state_dev, const yolo_box *boxes_dev, const int32_t *counts_dev, int batch, int max_boxes,
+                  const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int64_t image_base, void *stream) {
+    int rc = check_eval_desc(desc, "yolo_eval_add");
+    if (rc) return rc;
+    if (!state_dev || !boxes_dev || !counts_dev || !gt_dev || !gt_counts_dev) return fail(YOLO_ERR_ARG, "yolo_eval_add: null argument");
+    if (batch < 1 || max_boxes < 1) return fail(YOLO_ERR_ARG, "yolo_eval_add: batch and max_boxes must be at least 1");
+    if (image_base < 0) return fail(YOLO_ERR_ARG, "yolo_eval_add: image_base must not be negative");
+    if (image_base > (int64_t)1 << 32 || (unsigned long long)(image_base + batch) * (unsigned long long)max_boxes > (1ull << 32))
+        return fail(YOLO_ERR_ARG, "yolo_eval_add: (image_base + batch) * max_boxes does not fit 32 bits (seq)");
+    const EvalLayout L = eval_layout(desc->n_classes, desc->det_capacity);
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    EvalMatchParams p;
+    p.boxes = boxes_dev; p.counts = counts_dev; p.gt = gt_dev; p.gt_counts = gt_counts_dev;
+    p.max_boxes = max_boxes; p.max_gt = desc->max_gt; p.n_classes = desc->n_classes; p.det_capacity = desc->det_capacity;
+    p.match_iou = desc->match_iou;
+    p.seq_base = (unsigned)((unsigned long long)image_base * (unsigned long long)max_boxes);
+    p.hdr = reinterpret_cast<EvalHeader *>(st + L.header);
+    p.n_gt = reinterpret_cast<int *>(st + L.n_gt);
+    p.records = reinterpret_cast<yolo_eval_record *>(st + L.records);
+    HIP_TRY(launch_eval_match(p, batch, static_cast<hipStream_t>(stream)));
+    return YOLO_OK;
+}
+
+int yolo_eval_finish(const yolo_eval_desc *desc, void *state_dev, void *result_dev, void *stream) {
+    int rc = check_eval_desc(desc, "yolo_eval_finish");
+    if (rc) return rc;
+    if (!state_dev || !result_dev) return fail(YOLO_ERR_ARG, "yolo_eval_finish: null argument");
+    const EvalLayout L = eval_layout(desc->n_classes, desc->det_capacity);
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    EvalFinishParams p;
+    p.hdr = reinterpret_cast<EvalHeader *>(st + L.header);
+    p.n_gt = reinterpret_cast<const int *>(st + L.n_gt);
+    p.records = reinterpret_cast<const yolo_eval_record *>(st + L.records);
+    p.sorted = reinterpret_cast<yolo_eval_record *>(st + L.sorted);
+    p.ctp = reinterpret_cast<unsigned *>(st + L.ctp);
+    p.cfp = reinterpret_cast<unsigned *>(st + L.cfp);
+    p.entries = reinterpret_cast<EvalEntry *>(st + L.entries);
+    p.n2 = L.n2; p.n_classes = desc->n_classes; p.det_capacity = desc->det_capacity;
+    p.result = static_cast<yolo_eval_result *>(result_dev);
+    HIP_TRY(launch_eval_finish(p, static_cast<hipStream_t>(stream)));
+    return YOLO_OK;
+}
+
 int yolo_u8_unit_table(float *out256) {
     if (!out256) return fail(YOLO_ERR_ARG, "yolo_u8_unit_table: null argument");
     for (unsigned u = 0; u < 256; ++u) out256[u] = u8_unit(u);     // the function the input kernels run on every byte

@@ -319,6 +319,50 @@ struct NmsParams {
     size_t scratch_stride;
 };
 
+// ---- evaluation (eval.hip): the caller-owned state of the yolo_eval_* entries ------------------------------------------------
+// [ EvalHeader | n_gt int32[n_classes] | records[cap] (arrival order) | sorted[cap] | ctp u32[cap] | cfp u32[cap] | sort entries[n2] ],
+// every part 256-byte aligned; n2 = the power of two >= max(cap, kEvalSortTile) the bitonic network runs on.
+struct EvalHeader {            // 256 bytes
+    unsigned long long cursor; // records appended so far (may pass the capacity: then YOLO_EVAL_OVERFLOW is set and nothing was written there)
+    unsigned status;           // enum yolo_eval_status bits
+    unsigned pad_[61];
+};
+struct EvalEntry {             // sort item: (hi, lo, idx) ascending = class ascending, prob descending, seq ascending
+    unsigned long long lo;     // ~orderable(prob) << 32 | seq
+    unsigned hi;               // class; 0xffffffff = padding behind the records
+    unsigned idx;              // arrival position of the record
+};
+constexpr int kEvalSortTile = 2048;     // entries one workgroup sorts in LDS (32 KiB)
+struct EvalLayout {
+    size_t header, n_gt, records, sorted, ctp, cfp, entries, total;
+    int n2;
+};
+EvalLayout eval_layout(int n_classes, int det_capacity);
+struct EvalMatchParams {
+    const yolo_box *boxes;     // [batch][max_boxes]
+    const int *counts;
+    const yolo_gt *gt;         // [batch][max_gt]
+    const int *gt_counts;
+    int max_boxes, max_gt, n_classes, det_capacity;
+    double match_iou;
+    unsigned seq_base;         // image_base * max_boxes
+    EvalHeader *hdr;
+    int *n_gt;
+    yolo_eval_record *records;
+};
+struct EvalFinishParams {
+    EvalHeader *hdr;
+    const int *n_gt;
+    const yolo_eval_record *records;
+    yolo_eval_record *sorted;
+    unsigned *ctp, *cfp;
+    EvalEntry *entries;
+    int n2, n_classes, det_capacity;
+    yolo_eval_result *result;  // header, then yolo_eval_class[n_classes]
+};
+hipError_t launch_eval_match(const EvalMatchParams &p, int batch, hipStream_t s);
+hipError_t launch_eval_finish(const EvalFinishParams &p, hipStream_t s);
+
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);
 // conv_dma.hip: 8-wave LDS-DMA kernel for the heavy fp16 layers; conv_tap.hip: 3x3 with tap reuse.  What a tile id is: conv_tiles.h.

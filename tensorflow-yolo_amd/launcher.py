@@ -4,7 +4,8 @@ Keeps the reference launcher's surface (reference launcher.py:15-60): the two fl
 `--mode` with the same defaults (mode defaults to "anchor", exactly as there), `.ini` sections
 COMMON / ANCHOR / TRAIN / TEST merged as {**section, **COMMON}, relative `*_dir` / `*_path` values
 resolved against the .ini's directory, `anchors` / `class_names` parsed as Python literals, and the
-network picked by COMMON.version.  Only `test` runs on this backend; `train` and `anchor` end with a
+network picked by COMMON.version.  `test` runs on this backend, and `eval` (not in the reference): VOC-style mAP of the
+network on an annotated directory, from an [EVAL] section laid over [TEST] (eval_params); `train` and `anchor` end with a
 clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up),
 `resize` (stretch, the reference's geometry and the default | letterbox, Darknet's: aspect ratio kept, grey canvas, boxes mapped back to the frame);
 version additionally accepts `v2-tiny`, `v3-tiny` and `v3-spp`.  `--section` selects another TEST-like section (the
@@ -57,6 +58,28 @@ def test_options(params):
     return {"resize": _hip.resize_mode(params.get("resize", "stretch"))}
 
 
+EVAL_DEFAULTS = {"threshold": "0.005", "max_boxes": "1024", "match_iou": "0.5"}
+
+
+def eval_params(cfg, section=None):
+    """`--mode eval`: the [TEST] keys (or those of --section), overridden by [EVAL] -- `annotation_dir`, `image_dir`, `match_iou` and
+    whatever else it sets -- then [COMMON].  threshold and max_boxes default to a mAP run's 0.005 and 1024 unless [EVAL] sets them
+    (the [TEST] values are a demo's).  Raises ValueError without an [EVAL] section or its two directories."""
+    if "EVAL" not in cfg:
+        raise ValueError("mode 'eval' needs an [EVAL] section with annotation_dir and image_dir")
+    params = dict(cfg.get(section or "TEST", {}))
+    params.update(EVAL_DEFAULTS)
+    params.update(cfg["EVAL"])
+    params.update(cfg["COMMON"])
+    for key in ("annotation_dir", "image_dir"):
+        if key not in cfg["EVAL"]:
+            raise ValueError("[EVAL] needs {}".format(key))
+    m = float(params["match_iou"])
+    if not 0. <= m <= 1.:
+        raise ValueError("match_iou must be in [0, 1], got {}".format(params["match_iou"]))
+    return params
+
+
 def run(cfg, mode, section=None):
     yolo = pick_model(cfg["COMMON"]["version"])
     if mode == "test":
@@ -64,6 +87,12 @@ def run(cfg, mode, section=None):
         params.update(cfg["COMMON"])
         test_options(params)
         yolo.test(params)
+    elif mode == "eval":
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:      # (Yolo.evaluate itself is not sharded: every caller scores the whole set)
+            raise SystemExit("mode 'eval' runs in one process: sharded evaluation needs a merge of the records, which is not built")
+        params = eval_params(cfg, section)
+        test_options(params)
+        yolo.evaluate(params)
     elif mode in ("train", "anchor"):
         raise SystemExit("mode '{}' is not supported by the HIP inference backend (TEST mode only)".format(mode))
     else:
@@ -73,7 +102,7 @@ def run(cfg, mode, section=None):
 def main(argv=None):
     ap = argparse.ArgumentParser(description="YOLO v2/v3 TEST-mode inference on MI355X")
     ap.add_argument("--config", dest="config", help="Path to configuration file", default=DEFAULT_CONFIG)
-    ap.add_argument("--mode", dest="mode", help="Mode: (train|test|anchor)", default="anchor")
+    ap.add_argument("--mode", dest="mode", help="Mode: (train|test|anchor|eval)", default="anchor")
     ap.add_argument("--section", dest="section", help="section to use for test mode (default TEST)", default=None)
     args = ap.parse_args(argv)
     group = init_distributed()

@@ -259,6 +259,65 @@ class Yolo(object):
         if rank == 0:
             print("Done")
 
+    # ---- EVAL mode (no reference counterpart: net/base.py:69-97 parses annotations, nothing scores a detector) ----------------
+    def evaluate(self, params):
+        """VOC-style mAP of the network on an annotated directory, matched and scored on the device (net/evaluate.py, yolo_eval_*).
+        The [TEST] keys plus `annotation_dir`, `image_dir`, `match_iou` (0.5); `threshold` defaults to 0.005 and `max_boxes` to 1024, the
+        usual settings of a mAP run.  Frames go through the predict_frames step (`resize` = stretch | letterbox), so boxes and truths
+        are both normalised to the frame; the records never leave the device.  Prints one line per class with truths and the two
+        means, writes `eval.json` under `out_dir`, returns the EvalResult.  A candidate overflow (detect status 1) raises, as in
+        test(); truncated lists (status 2) are counted and reported as `images_truncated`."""
+        import json
+        from . import evaluate as yeval
+        annotation_dir, image_dir = params["annotation_dir"], params["image_dir"]
+        out_dir = params["out_dir"]
+        batch_size = int(params["batch_size"])
+        threshold = float(params.get("threshold", 0.005))
+        iou_threshold = float(params["iou_threshold"])
+        match_iou = float(params.get("match_iou", 0.5))
+        anchors = np.reshape(params["anchors"], [-1, 2])
+        class_names = params["class_names"]
+        input_shape = (int(params["input_h"]), int(params["input_w"]), int(params["input_c"]))
+        nms_mode = {"agnostic": _hip.NMS_AGNOSTIC, "per_class": _hip.NMS_PER_CLASS}[params.get("nms_mode", "agnostic")]
+        resize = _hip.resize_mode(params.get("resize", "stretch"))
+        annotations, skipped = yeval.parse_voc_annotations(annotation_dir, image_dir, class_names)
+        if not annotations:
+            print("No annotations found in {}".format(annotation_dir))
+            return None
+        caps = {"max_boxes": int(params.get("max_boxes", 1024))}
+        if "cand_capacity" in params:
+            caps["cand_capacity"] = int(params["cand_capacity"])
+        if self.net is None or getattr(self.net, "engine", None) is None:
+            self.build(anchors, class_names, input_shape, dtype=params.get("dtype", "fp32"), max_batch=batch_size, **caps)
+            type(self).load_weights(self.net, params["pretrained_weights_path"])
+            print("Pre-trained weights loaded.")
+        eng = self.net.engine
+        max_gt = max(1, max(len(t) for _, t in annotations))
+        ev = yeval.Evaluator(len(class_names), det_capacity=int(params.get("det_capacity", 1 << 18)), max_gt=max_gt, match_iou=match_iou,
+                             device=eng.device)
+        overflow = eng.torch.zeros(1, dtype=eng.torch.int32, device=eng.device)
+        gt_dev, gt_counts = ev.upload_gts([t for _, t in annotations])     # the truths of the whole set: packed and copied once
+        for start in range(0, len(annotations), batch_size):
+            chunk = annotations[start:start + batch_size]
+            frames = base.decode_frames([p for p, _ in chunk])
+            boxes, counts, status = eng.detect_frames(frames, threshold, iou_threshold, nms_mode, resize)
+            # same stream, no copy of the records to the host, nothing read from the host
+            ev.add(boxes, counts, (gt_dev[start:start + len(chunk)], gt_counts[start:start + len(chunk)]), status)
+            overflow |= (status & 1).max()
+        if int(overflow.item()):
+            raise _hip.YoloHipError("candidate capacity exceeded during evaluation: raise cand_capacity or the threshold")
+        result = ev.finish()
+        report = result.to_json(class_names)
+        report.update(images=len(annotations), images_truncated=ev.images_truncated, names_skipped=skipped, match_iou=match_iou,
+                      threshold=threshold, iou_threshold=iou_threshold, resize=str(params.get("resize", "stretch")))
+        for line in eval_lines(report):
+            print(line)
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "eval.json"), "w") as f:
+            json.dump(report, f, indent=1)
+        self.last_eval = result
+        return result
+
     def _test_pipelined(self, image_paths, out_dir, batch_size, input_shape, threshold, iou_threshold, nms_mode, class_names, workers=0,
                         timings=None, staging="f32", resize=_hip.RESIZE_STRETCH):
         """The body of the reference's test loop (net/yolo.py:80-95) as a pipeline over batches:
@@ -393,6 +452,20 @@ class Yolo(object):
         pool.shutdown()
         if writers is not pool:
             writers.shutdown()
+
+
+def eval_lines(report):
+    """the console lines of Yolo.evaluate: one per class with truths, then the two means and what was not clean"""
+    fmt = lambda v: "nan" if v is None else "%.6f" % v
+    lines = ["{}: AP12 {} AP07 {} (truths {}, detections {}, tp {}, fp {}, ignored {})".format(
+        c["name"], fmt(c["ap_voc12"]), fmt(c["ap_voc07"]), c["n_gt"], c["n_det"], c["tp"], c["fp"], c["ignored"])
+        for c in report["classes"] if c["n_gt"] > 0]
+    lines.append("mAP12 {} mAP07 {} over {} images, {} records".format(fmt(report["map_voc12"]), fmt(report["map_voc07"]), report["images"],
+                                                                      report["n_records"]))
+    if report["images_truncated"] or report["status"] or report["names_skipped"]:
+        lines.append("images_truncated {} status {} names_skipped {}".format(report["images_truncated"], report["status_names"],
+                                                                             report["names_skipped"]))
+    return lines
 
 
 class YoloV2(Yolo):
