@@ -1,48 +1,13 @@
-// C ABI of libyolo_hip.so (declared in include/yolo_hip.h).  No exceptions cross the boundary.
+// C ABI of libyolo_hip.so (declared in include/yolo_hip.h): argument and state checks, then one call into the planner (plan.cpp), the
+// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame and the evaluation entries live here whole.  No exceptions cross the boundary.
 #include <cstdio>
 #include <cstring>
 #include <new>
 
 #include <cmath>
-#include "conv_tiles.h"
 #include "yolo_internal.h"
 
-namespace yolo {
-const char *get_error();
-}
 using namespace yolo;
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-            return YOLO_ERR_HIP;                                                               \
-        }                                                                                      \
-    } while (0)
-
-static int fail(int code, const std::string &msg) {
-    set_error(msg);
-    return code;
-}
-
-namespace {
-// packed weights of a kernel; nullptr while no weights are bound (yolo_net_kernel_info / describe build launch parameters of a plan that
-// has none yet: no offset is applied to a null pointer -- found by the sanitizer build, tests/test_sanitizer.py)
-static inline const unsigned char *weights_at(const yolo_net *net, size_t off) { return net->dev_weights ? net->dev_weights + off : nullptr; }
-
-// Ticket counters of the in-launch pair split: every launch returns them to zero, so they are cleared when the workspace is bound
-// and again after any failed forward (a launch that did not run may leave the forward half-way).  The memset goes to the null
-// stream, which does not order against the non-blocking streams a caller may launch on: hence the device-wide synchronise.
-int zero_pair_counters(yolo_net *net) {
-    if (!net->splitk_bytes || !net->dev_ws) return YOLO_OK;
-    const size_t per = net->splitk_bytes / (size_t)net->arenas;
-    for (int a = 0; a < net->arenas; ++a)
-        HIP_TRY(hipMemset(net->dev_ws + net->splitk_off + (size_t)a * arena_slab_bytes(net), 0, per < kPairCounterBytes ? per : kPairCounterBytes));
-    HIP_TRY(hipDeviceSynchronize());
-    return YOLO_OK;
-}
-}
 
 extern "C" {
 
@@ -110,6 +75,7 @@ int yolo_net_create(const yolo_layer_desc *layers, int n_layers, const yolo_net_
             if (k.kind == K_CONV && k.stem < 2 && conv_tile_valid(net, k, net->opt.force_tile - 1)) k.tile = net->opt.force_tile - 1;
     // the split-K slab is the last region of the workspace (plan.cpp reserves nothing for it): sized from the launches that can split
     net->splitk_bytes = splitk_slab_bytes(net) * (size_t)net->arenas;
+    if (net->splitk_bytes) net->tail.push_back({"split-K tickets + slabs", net->splitk_off, net->splitk_bytes, net->splitk_bytes});
     net->workspace_bytes = net->splitk_off + net->splitk_bytes;
     *out = net;
     return YOLO_OK;
@@ -117,12 +83,7 @@ int yolo_net_create(const yolo_layer_desc *layers, int n_layers, const yolo_net_
 
 void yolo_net_destroy(yolo_net *net) {
     if (!net) return;
-    if (net->e_fork) (void)hipEventDestroy(net->e_fork);
-    for (hipEvent_t e : net->e_join) (void)hipEventDestroy(e);
-    for (hipStream_t st : net->side) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : net->e_bfork) (void)hipEventDestroy(e);
-    for (hipEvent_t e : net->e_bjoin) (void)hipEventDestroy(e);
-    for (hipStream_t st : net->branch) (void)hipStreamDestroy(st);
+    destroy_streams(net);
     delete net;
 }
 
@@ -178,13 +139,7 @@ int yolo_net_workspace_regions(const yolo_net *net, yolo_ws_region *out, int cap
             if (!B.bytes) continue;
             add("tensor " + std::to_string(b) + " arena " + std::to_string(a), (size_t)a * net->arena_bytes + B.offset, B.used, B.bytes);
         }
-    const size_t mb = (size_t)net->opt.max_batch;
-    add("head logits", net->logits_off, net->out_count * 4 * mb, net->cand_off - net->logits_off);
-    add("candidates", net->cand_off, sizeof(Candidate) * (size_t)net->opt.cand_capacity * mb, net->count_off - net->cand_off);
-    add("candidate counters", net->count_off, sizeof(int) * mb * kCandCountStride, net->nms_off - net->count_off);
-    add("nms scratch", net->nms_off, nms_scratch_bytes(net->opt.cand_capacity) * mb, net->obj_off - net->nms_off);
-    add("objectness", net->obj_off, net->obj_bytes, net->splitk_off - net->obj_off);
-    if (net->splitk_bytes) add("split-K tickets + slabs", net->splitk_off, net->splitk_bytes, net->splitk_bytes);
+    for (const WsRegion &r : net->tail) add(r.name, r.offset, r.used, r.bytes);
     return n;
 }
 
@@ -220,378 +175,12 @@ int yolo_net_bind_workspace(yolo_net *net, void *ws, size_t bytes) {
     net->dev_ws = static_cast<unsigned char *>(ws);
     net->cand_clean = 0;        // (whatever the new workspace holds where the candidate counters live)
     net->dev_ws_bytes = bytes;
-    int rc = zero_pair_counters(net);
-    if (rc) return rc;
-    return YOLO_OK;
+    return zero_pair_counters(net);
 }
 
 }  // extern "C"
 
-// ---- forward ------------------------------------------------------------------------------------
 namespace {
-
-// The network input of one call: the caller's float32 tensor, or (ABI 7: the *_u8 entries) its uint8 one.  Only the five kernels that
-// read the input look at the tag (K_PREP, K_FIRST, the stem); a byte u is to them float32(u / 255.) (yolo_internal.h: u8_unit).
-struct NetIn {
-    const void *ptr;
-    bool u8;
-    NetIn at(size_t elems) const { return NetIn{static_cast<const unsigned char *>(ptr) + elems * (u8 ? 1 : 4), u8}; }
-};
-
-struct Ptrs {
-    yolo_net *net;
-    NetIn in;                   // already advanced to image `img0` by the caller
-    float *out;                 // ditto
-    int img0 = 0;               // first image of this pass in the batch (two-stream halves: compact per-image arrays)
-    int arena = 0;              // activation arena of this pass
-    unsigned char *buf_base(int b) const {
-        if (b == BUF_USER_IN) return static_cast<unsigned char *>(const_cast<void *>(in.ptr));
-        if (b == BUF_USER_OUT) return reinterpret_cast<unsigned char *>(out);
-        return net->dev_ws + (size_t)arena * net->arena_bytes + net->buffers[b].offset;
-    }
-    int esz(const View &v) const { return v.f32 ? 4 : net->esize; }
-    // element pointer of channel 0 of pixel 0 of image 0 of the view
-    unsigned char *view_ptr(const View &v) const { return buf_base(v.buf) + (size_t)(v.base + v.coff) * esz(v); }
-};
-
-// conv launch parameters for one planned kernel at the given batch: the shape half (conv_dispatch.cpp) + pointers, the byte-limit
-// checks and the objectness block
-int make_conv_params(yolo_net *net, const Kernel &k, const Ptrs &P, int batch, ConvParams &p) {
-    const long long in_bytes = (long long)batch * k.in.img_stride * net->esize;
-    if (in_bytes > 0x7ffffff0LL)
-        return fail(YOLO_ERR_ARG, "conv input tensor exceeds 2 GiB (32-bit buffer addressing): lower the batch");
-    if ((long long)batch * net->layers[k.src_layer].H * net->layers[k.src_layer].W > 0x7fffffffLL)
-        return fail(YOLO_ERR_ARG, "too many output pixels for one launch");
-    conv_shape_params(net, k, batch, p);
-    p.in = P.buf_base(k.in.buf);
-    p.in_bytes = (uint32_t)in_bytes;
-    p.wgt = weights_at(net, k.w_off);
-    p.bias = reinterpret_cast<const float *>(weights_at(net, k.b_off));
-    p.out = P.view_ptr(k.out);
-    p.vec_out = p.vec_out && ((uintptr_t)P.buf_base(k.out.buf) % 16 == 0);
-    if (k.head && net->obj_bytes && net->head.n_classes > 0 && !p.vec_out && p.out_f32 && k.outmode == OUT_NORMAL && !k.has_res) {
-        const int width = 5 + net->head.n_classes;
-        const long long base = k.out.base + k.out.coff;
-        const size_t rows = net->out_count / (size_t)width;
-        if (k.out.ld % width == 0 && base % width == 0 && rows * width == net->out_count && (size_t)batch * rows * 4 <= net->obj_bytes) {
-            p.obj_out = reinterpret_cast<float *>(net->dev_ws + net->obj_off) + (size_t)P.img0 * rows;
-            p.obj_width = width; p.obj_rows = (int)rows; p.obj_row0 = (int)(base / width); p.obj_na = k.out.ld / width;
-            p.obj_min = net->obj_min_logit;     // -inf outside yolo_net_detect: every row is written
-        }
-    }
-    if (k.has_res) p.res = P.view_ptr(k.in2);
-    return YOLO_OK;
-}
-
-// Back-to-back 1x1 (ConvLaunch.fuse2): `p`, the 3x3's launch parameters, takes the weights, bias and output view of the 1x1 `b` behind it
-void attach_fuse2(const yolo_net *net, const Kernel &b, const Ptrs &P, int batch, ConvParams &p) {
-    p.fuse2 = 1;
-    p.w2 = weights_at(net, b.w_off);
-    p.w2_bytes = (uint32_t)b.w_bytes;
-    p.wrow2_bytes = (uint32_t)b.ktiles * 128;
-    p.b2 = reinterpret_cast<const float *>(weights_at(net, b.b_off));
-    p.out2 = P.view_ptr(b.out);
-    p.out2_bytes = (uint32_t)((long long)batch * b.out.img_stride * net->esize);       // (below 2 GiB: resolve_conv)
-    p.out2_ld = b.out.ld;
-    p.out2_img_stride = b.out.img_stride;
-    p.leaky2 = b.leaky;
-}
-
-// one conv launch as its record says (the split fields are set here, after the record was built from the whole-K parameters)
-hipError_t launch_conv_any(const yolo_net *net, const Kernel &k, const ConvParams &p0, const ConvLaunch &L, hipStream_t s, int arena = 0) {
-    const int tile = L.tile, ks = L.ks;
-    ConvParams p = p0;
-    if (ks > 1) {
-        p.ksplit = ks; p.kunits = L.ku;
-        p.cout_pad = (p.Cout + 127) / 128 * 128;
-        unsigned char *base = net->dev_ws + net->splitk_off + (size_t)arena * arena_slab_bytes(net);
-        p.part = reinterpret_cast<float *>(base + kPairCounterBytes);
-        if (L.pair) {       // counters (zeroed at bind, returned to zero by every launch) in front of the partial sums
-            const size_t data_bytes = arena_slab_data_bytes(net);
-            p.pair = 1;
-            p.pair_cnt = reinterpret_cast<int *>(base);
-            p.part_bytes = (uint32_t)(data_bytes < 0x7ffffff0u ? data_bytes : 0x7ffffff0u);
-        }
-    }
-    if (tile <= 0) p.f32_emu = conv_f32_emu_rule(net->opt.f32_products, net->opt.dtype, p, k.cfg, k.perchunk != 0, ks) ? 1 : 0;
-    hipError_t e = tile > 0 ? launch_conv_dma(p, tile, s) : launch_conv(p, net->opt.dtype, k.cfg, k.perchunk != 0, s);
-    if (e != hipSuccess || ks <= 1 || L.pair) return e;
-    ReduceParams r;
-    memset(&r, 0, sizeof r);
-    r.part = p.part; r.bias = p.bias; r.res = p.has_res ? p.res : nullptr; r.out = p.out;
-    r.obj_out = p.obj_out; r.obj_width = p.obj_width; r.obj_rows = p.obj_rows; r.obj_row0 = p.obj_row0; r.obj_na = p.obj_na;
-    r.ksplit = ks; r.M = p.M; r.Cout = p.Cout; r.cout_pad = p.cout_pad; r.HoWo = p.HoWo; r.Wo = p.Wo;
-    r.out_ld = p.out_ld; r.res_ld = p.res_ld; r.leaky = p.leaky; r.outmode = p.outmode; r.out_f32 = p.out_f32; r.f32 = p.f32;
-    r.out_img_stride = p.out_img_stride; r.res_img_stride = p.res_img_stride;
-    return launch_splitk_reduce(r, s);
-}
-
-// May the branch tails of this net run beside its main chain at this batch?  Yes when the plan has any and no launch of the pass splits K.
-bool branch_tails_ok(yolo_net *net, int batch) {
-    static const bool off = getenv("YOLO_NO_BRANCH_STREAM") != nullptr;       // A/B switch (same results either way)
-    if (off || net->side_chains <= 0 || net->opt.keep_all || batch <= 0 || batch > net->opt.max_batch) return false;
-    if (net->side_ok.size() != (size_t)net->opt.max_batch + 1) net->side_ok.assign((size_t)net->opt.max_batch + 1, -1);
-    signed char &memo = net->side_ok[(size_t)batch];
-    if (memo < 0) memo = pass_splits_k(net, batch) ? 0 : 1;
-    return memo == 1;
-}
-int branch_streams(yolo_net *net, int arena) {
-    if (net->branch.empty()) {
-        const size_t n = (size_t)(net->arenas > 0 ? net->arenas : 1);
-        net->branch.assign(n, nullptr);
-        net->e_bjoin.assign(n, nullptr);
-        net->e_bfork.assign(n * 4, nullptr);
-        for (size_t i = 0; i < n; ++i)
-            if (hipStreamCreateWithFlags(&net->branch[i], hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&net->e_bjoin[i], hipEventDisableTiming) != hipSuccess)
-                return fail(YOLO_ERR_HIP, "branch tail: stream / event creation failed");
-        for (size_t i = 0; i < n * 4; ++i)
-            if (hipEventCreateWithFlags(&net->e_bfork[i], hipEventDisableTiming) != hipSuccess)
-                return fail(YOLO_ERR_HIP, "branch tail: event creation failed");
-    }
-    return (size_t)arena < net->branch.size() ? YOLO_OK : fail(YOLO_ERR_STATE, "branch tail: arena out of range");
-}
-
-int run_forward_pass(yolo_net *net, const NetIn in, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev, int img0, int arena,
-                     long long *obj_rows_out) {
-    Ptrs P{net, in, out_dev, img0, arena};
-    const int dtype = net->opt.dtype;
-    const int epc = net->epc;
-    long long obj_rows_written = 0;          // rows of the compact objectness array the head convs of this pass fill
-    bool fused2_done = false;                // the previous conv launch has computed this 1x1 conv too (back-to-back fusion)
-    // branch tails (plan.cpp: side_chains) on a second stream of this part: fork by an event behind the kernel in front of the tail,
-    // one join in front of whatever follows the pass (the decode, the caller).  Not under per-kernel events, and not at a batch where
-    // any launch of the pass splits K (the split-K slab and its ticket counters are one per arena)
-    const bool use_branch = !ev && branch_tails_ok(net, batch);
-    hipStream_t const s_main = s;
-    hipStream_t s_branch = nullptr;
-    int cur_tail = 0;
-    if (use_branch) {
-        const int rc = branch_streams(net, arena);
-        if (rc) return rc;
-        s_branch = net->branch[arena];
-    }
-    for (size_t ki = 0; ki < net->kernels.size(); ++ki) {
-        const Kernel &k = net->kernels[ki];
-        hipError_t e = hipSuccess;
-        s = s_main;
-        if (use_branch && k.side) {
-            if (k.side != cur_tail) {
-                hipEvent_t ef = net->e_bfork[(size_t)arena * 4 + (size_t)((k.side - 1) & 3)];
-                if (hipEventRecord(ef, s_main) != hipSuccess || hipStreamWaitEvent(s_branch, ef, 0) != hipSuccess)
-                    return fail(YOLO_ERR_HIP, "branch tail: fork failed");
-                cur_tail = k.side;
-            }
-            s = s_branch;
-        }
-        if (ev && hipEventRecord(ev[2 * ki], s) != hipSuccess) return fail(YOLO_ERR_HIP, "hipEventRecord failed");
-        switch (k.kind) {
-        case K_PREP: {
-            PrepParams p;
-            p.in = in.ptr;
-            p.out = P.view_ptr(k.out);
-            p.pixels = (long long)batch * k.in.H * k.in.W;
-            p.C = k.in.C;
-            p.Cpad = k.out.ld;
-            e = launch_prep(p, dtype, s, in.u8);
-            break;
-        }
-        case K_CONV: {
-            if (k.stem == 2) {      // the previous kernel (first layer) is folded into this launch
-                const Kernel &f = net->kernels[ki - 1];
-                StemParams p;
-                memset(&p, 0, sizeof p);
-                p.in = in.ptr;
-                p.w1 = reinterpret_cast<const float *>(net->dev_weights + f.w_off);
-                p.b1 = reinterpret_cast<const float *>(net->dev_weights + f.b_off);
-                p.w2 = net->dev_weights + k.w_off;
-                p.b2 = reinterpret_cast<const float *>(net->dev_weights + k.b_off);
-                p.w2_bytes = (uint32_t)k.w_bytes;
-                p.wrow2 = (uint32_t)k.ktiles * 128;
-                p.out = P.view_ptr(k.out);
-                p.H = f.in.H; p.W = f.in.W; p.Ho = k.out.H; p.Wo = k.out.W;
-                p.out_ld = k.out.ld; p.out_img_stride = k.out.img_stride;
-                p.in_img_stride = (long long)f.in.H * f.in.W * 3;
-                if (ki + 1 < net->kernels.size() && net->kernels[ki + 1].stem == 3) {      // 1x1 64->32 on the same pixels
-                    const Kernel &t = net->kernels[ki + 1];
-                    p.w3 = net->dev_weights + t.w_off;
-                    p.b3 = reinterpret_cast<const float *>(net->dev_weights + t.b_off);
-                    p.out3 = P.view_ptr(t.out);
-                    p.out3_ld = t.out.ld; p.out3_img_stride = t.out.img_stride;
-                }
-                e = launch_stem(p, batch, s, net->halves ? 512 / net->parts : 512, in.u8);
-                break;
-            }
-            if (k.stem == 3) break;     // computed by the stem kernel
-            if (k.fuse2_prev && fused2_done) { fused2_done = false; break; }       // computed by the conv in front of it
-            ConvParams p;
-            int rc = make_conv_params(net, k, P, batch, p);
-            if (rc) return rc;
-            if (k.head && p.obj_out) obj_rows_written += (long long)p.Ho * p.Wo * p.obj_na;
-            if (k.mx) {
-                e = launch_conv_mx(p, s);
-                break;
-            }
-            const ConvLaunch L = resolve_conv(net, ki, p, k.tile, arena_slab_data_bytes(net));
-            if (L.fuse2) attach_fuse2(net, net->kernels[ki + 1], P, batch, p);
-            fused2_done = L.fuse2 != 0;
-            e = launch_conv_any(net, k, p, L, s, P.arena);
-            break;
-        }
-        case K_FIRST: {
-            if (k.stem == 1) break;     // runs inside the next kernel (stem.hip)
-            FirstParams p;
-            p.in = in.ptr;
-            p.wgt = reinterpret_cast<const float *>(net->dev_weights + k.w_off);
-            p.bias = reinterpret_cast<const float *>(net->dev_weights + k.b_off);
-            p.out = P.view_ptr(k.out);
-            p.H = k.in.H; p.W = k.in.W; p.Cout = k.cout; p.out_ld = k.out.ld; p.leaky = k.leaky;
-            p.pool = k.pool_fused;
-            p.round_half = dtype == YOLO_DTYPE_F16;
-            p.out_img_stride = k.out.img_stride;
-            p.total = (long long)batch * k.in.H * k.in.W;
-            if (k.out.ld % epc || (k.out.base + k.out.coff) % epc || k.out.img_stride % epc)
-                return fail(YOLO_ERR_PLAN, "first-layer kernel needs a 16-byte aligned output view");
-            e = launch_first(p, dtype, s, in.u8);
-            break;
-        }
-        case K_POOL: {
-            if (k.spp) {        // the three pools of an SPP block in one launch
-                SppParams p;
-                memset(&p, 0, sizeof p);
-                p.in = P.view_ptr(k.in);
-                p.H = k.in.H; p.W = k.in.W; p.chunks = k.in.C / 8;
-                p.in_ld = k.in.ld; p.in_img_stride = k.in.img_stride;
-                const View *ov[3] = {&k.out, &k.out2, &k.out3};
-                for (int l = 0; l < 3; ++l) {
-                    p.out[l] = P.view_ptr(*ov[l]);
-                    p.out_ld[l] = ov[l]->ld; p.out_img_stride[l] = ov[l]->img_stride;
-                }
-                e = launch_spp(p, (k.pool_k - 1) / 2, batch, s);
-                break;
-            }
-            PoolParams p;
-            p.in = P.view_ptr(k.in);
-            p.out = P.view_ptr(k.out);
-            p.H = k.in.H; p.W = k.in.W; p.C = k.in.C; p.in_ld = k.in.ld;
-            p.Ho = k.out.H; p.Wo = k.out.W; p.out_ld = k.out.ld; p.stride = k.pool_stride;
-            p.in_img_stride = k.in.img_stride; p.out_img_stride = k.out.img_stride;
-            p.total = (long long)batch * k.out.H * k.out.W;
-            p.ksize = k.pool_k;
-            e = k.pool_k == 2 ? launch_pool(p, dtype, s) : launch_pool_same(p, dtype, s);
-            break;
-        }
-        case K_ELTWISE: {
-            EltParams p;
-            memset(&p, 0, sizeof p);
-            p.a = P.view_ptr(k.in);
-            p.a_f32 = k.in.f32;
-            p.b = k.has_res ? P.view_ptr(k.in2) : nullptr;
-            p.out = P.view_ptr(k.out);
-            p.H = k.in.H; p.W = k.in.W; p.C = k.in.C;
-            p.a_ld = k.in.ld; p.b_ld = k.in2.ld; p.out_ld = k.out.ld;
-            p.outmode = k.outmode;
-            p.out_f32 = k.out.f32 || dtype == YOLO_DTYPE_F32;
-            p.a_img_stride = k.in.img_stride; p.b_img_stride = k.in2.img_stride; p.out_img_stride = k.out.img_stride;
-            p.total = (long long)batch * k.in.H * k.in.W * k.in.C;
-            e = launch_eltwise(p, dtype, s);
-            break;
-        }
-        }
-        if (e != hipSuccess) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "kernel %zu (layer %d) launch failed: %s", ki, k.layer, hipGetErrorString(e));
-            return fail(YOLO_ERR_HIP, msg);
-        }
-        if (ev && hipEventRecord(ev[2 * ki + 1], s) != hipSuccess) return fail(YOLO_ERR_HIP, "hipEventRecord failed");
-    }
-    if (cur_tail) {
-        if (hipEventRecord(net->e_bjoin[arena], s_branch) != hipSuccess || hipStreamWaitEvent(s_main, net->e_bjoin[arena], 0) != hipSuccess)
-            return fail(YOLO_ERR_HIP, "branch tail: join failed");
-    }
-    *obj_rows_out = obj_rows_written;
-    return YOLO_OK;
-}
-
-// One forward pass; with YOLO_STREAMS=N (N = 2..4) the batch goes out as N parts on N streams (the caller's and internal
-// ones, fork/join by events): images are independent, so the ragged tail + cold start of every kernel of one part overlaps
-// the bulk of the other parts' kernels instead of leaving CUs idle at each of the ~73 kernel boundaries.  Every part has
-// its own activation arena (plan.cpp: allocate).
-// every head conv of the plan fills the compact objectness array at this batch (what run_forward_impl finds out afterwards as obj_valid)
-bool all_heads_write_objectness(yolo_net *net, const NetIn in_dev, float *out_dev, int batch) {
-    if (!net->obj_bytes || net->head.n_classes <= 0) return false;
-    const int per = net->parts >= 2 && batch > part_batch(net) ? part_batch(net) : batch;
-    Ptrs P{net, in_dev, out_dev, 0, 0};
-    bool any = false;
-    for (const Kernel &k : net->kernels) {
-        if (k.kind != K_CONV || !k.head) continue;
-        ConvParams p;
-        if (make_conv_params(net, k, P, per, p) != 0 || !p.obj_out) return false;
-        // (the rows reach the compact array through the staged float32 epilogue of the LDS-DMA tiles or the 4-wave kernel, or through
-        // the split-K reduce kernel: all of them honour obj_out)
-        any = true;
-    }
-    return any;
-}
-
-int run_forward_impl(yolo_net *net, const NetIn in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev);
-int run_forward(yolo_net *net, const NetIn in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev = nullptr) {
-    const int rc = run_forward_impl(net, in_dev, batch, out_dev, s, ev);
-    if (rc != YOLO_OK) {        // leave the pair-split counters as every later launch expects them; keep the first error's message
-        const std::string msg = get_error();
-        (void)hipGetLastError();
-        (void)zero_pair_counters(net);
-        set_error(msg);
-    }
-    return rc;
-}
-int run_forward_impl(yolo_net *net, const NetIn in_dev, int batch, float *out_dev, hipStream_t s, hipEvent_t *ev) {
-    const long long rows = net->head.n_classes > 0 ? (long long)(net->out_count / (size_t)(5 + net->head.n_classes)) : -1;
-    const int parts = net->parts;
-    const int per = (net->opt.max_batch + parts - 1) / parts;       // images a part holds
-    if (parts >= 2 && batch > per) {
-        if (ev) return fail(YOLO_ERR_STATE, "per-kernel events need the parts timed one by one (yolo_net_forward_timed)");
-        if (net->side.empty()) {
-            net->side.resize(parts - 1);
-            net->e_join.resize(parts - 1);
-            for (int i = 0; i < parts - 1; ++i)
-                if (hipStreamCreateWithFlags(&net->side[i], hipStreamNonBlocking) != hipSuccess ||
-                    hipEventCreateWithFlags(&net->e_join[i], hipEventDisableTiming) != hipSuccess)
-                    return fail(YOLO_ERR_HIP, "multi-stream forward: stream/event creation failed");
-            if (hipEventCreateWithFlags(&net->e_fork, hipEventDisableTiming) != hipSuccess)
-                return fail(YOLO_ERR_HIP, "multi-stream forward: event creation failed");
-        }
-        const yolo_layer_desc &d0 = net->layers[0].d;
-        const size_t in_img = (size_t)d0.h * d0.w * d0.c;
-        net->halves = true;         // persistent kernels size their grids for a share of the chip
-        HIP_TRY(hipEventRecord(net->e_fork, s));
-        bool all = true;
-        int used = 0;
-        for (int part = 0, img0 = 0; img0 < batch; ++part, img0 += per) {
-            const int nb = batch - img0 < per ? batch - img0 : per;
-            hipStream_t st = part == 0 ? s : net->side[part - 1];
-            if (part > 0) HIP_TRY(hipStreamWaitEvent(st, net->e_fork, 0));
-            long long w = 0;
-            const int rc = run_forward_pass(net, in_dev.at((size_t)img0 * in_img), nb, out_dev + (size_t)img0 * net->out_count, st, nullptr,
-                                            img0, part, &w);
-            if (rc) return rc;
-            all = all && w == rows;
-            used = part + 1;
-        }
-        for (int part = 1; part < used; ++part) {
-            HIP_TRY(hipEventRecord(net->e_join[part - 1], net->side[part - 1]));
-            HIP_TRY(hipStreamWaitEvent(s, net->e_join[part - 1], 0));
-        }
-        net->obj_valid = net->obj_bytes > 0 && rows > 0 && all;
-        return YOLO_OK;
-    }
-    net->halves = false;
-    long long w0 = 0;
-    int rc = run_forward_pass(net, in_dev, batch, out_dev, s, ev, 0, 0, &w0);
-    if (rc) return rc;
-    net->obj_valid = net->obj_bytes > 0 && rows > 0 && w0 == rows;
-    return YOLO_OK;
-}
 
 int check_ready(yolo_net *net, const void *in, int batch, const char *who) {
     if (!net || !in) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
@@ -671,37 +260,7 @@ static int forward_timed_any(yolo_net *net, const NetIn in_dev, int batch, float
     int rc = check_ready(net, in_dev.ptr, batch, who);
     if (rc) return rc;
     if (!out_dev || !ms_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null output");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t nk = net->kernels.size();
-    std::vector<hipEvent_t> ev(2 * nk, nullptr);
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) return fail(YOLO_ERR_HIP, "hipEventCreate failed");
-    // with several arenas the parts are timed one after the other on the caller's stream (each kernel alone on the chip)
-    // and their times added per kernel
-    const int parts = net->parts;
-    const int per = (net->opt.max_batch + parts - 1) / parts;
-    const yolo_layer_desc &d0 = net->layers[0].d;
-    const size_t in_img = (size_t)d0.h * d0.w * d0.c;
-    for (size_t k = 0; k < nk; ++k) ms_host[k] = 0.f;
-    net->halves = false;
-    long long rows_written = 0;
-    for (int part = 0, img0 = 0; rc == YOLO_OK && img0 < batch; ++part, img0 += per) {
-        const int nb = batch - img0 < per ? batch - img0 : per;
-        long long w = 0;
-        rc = run_forward_pass(net, in_dev.at((size_t)img0 * in_img), nb, out_dev + (size_t)img0 * net->out_count, s, ev.data(), img0, part, &w);
-        rows_written += w;
-        if (rc == YOLO_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(YOLO_ERR_HIP, "hipStreamSynchronize failed");
-        for (size_t k = 0; rc == YOLO_OK && k < nk; ++k) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, ev[2 * k], ev[2 * k + 1]) != hipSuccess) rc = fail(YOLO_ERR_HIP, "hipEventElapsedTime failed");
-            ms_host[k] += t;
-        }
-    }
-    net->obj_valid = false;     // (the timed pass is not followed by a decode)
-    (void)rows_written;
-    if (rc != YOLO_OK) { const std::string msg = get_error(); (void)hipGetLastError(); (void)zero_pair_counters(net); set_error(msg); }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    return rc;
+    return run_forward_timed(net, in_dev, batch, out_dev, static_cast<hipStream_t>(stream), ms_host);
 }
 int yolo_net_forward_timed(yolo_net *net, const float *in_dev, int batch, float *out_dev, void *stream, float *ms_host) {
     return forward_timed_any(net, NetIn{in_dev, false}, batch, out_dev, stream, ms_host, "yolo_net_forward_timed");
@@ -715,81 +274,15 @@ int yolo_net_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out)
     const Kernel &k = net->kernels[kernel];
     memset(out, 0, sizeof *out);
     out->kind = k.kind; out->layer = k.layer;
-    auto set_symbol = [&](const std::string &sym) { snprintf(out->symbol, sizeof out->symbol, "%s", sym.c_str()); };
-    const char *t = net->opt.dtype == YOLO_DTYPE_F16 ? "f16" : "f32";
-    auto elems = [](const View &v) { return (double)v.H * v.W * v.C; };
-    auto esz = [&](const View &v) { return v.f32 ? 4.0 : (double)net->esize; };
-    if (k.kind == K_CONV) {
-        conv_kernel_info(net, kernel, out);
-    } else if (k.kind == K_FIRST) {
-        out->ksize = 3; out->stride = 1; out->cin = 3; out->cout = k.cout; out->out_h = k.out.H; out->out_w = k.out.W;
-        out->flops = 2.0 * k.out.H * k.out.W * k.cout * 27;
-        out->bytes = (double)k.in.H * k.in.W * 3 * 4 + elems(k.out) * esz(k.out);
-        out->weight_bytes = 28.0 * k.cout * 4;
-        snprintf(out->name, sizeof out->name, k.pool_fused ? "conv_first_pool<%s,%d>" : "conv_first<%s,%d>", t, k.cout);
-        if (k.pool_fused) { out->out_h = k.in.H; out->out_w = k.in.W; out->flops = 2.0 * k.in.H * k.in.W * k.cout * 27; }
-        set_symbol(first_symbol(net->opt.dtype, k.cout, k.pool_fused != 0));
-        if (k.stem == 1) {
-            out->symbol[0] = 0;          // no launch of its own: accounted for in the conv_stem kernel that follows
-            out->flops = 0; out->bytes = 0; out->weight_bytes = 0;
-            snprintf(out->name, sizeof out->name, "conv_first<fused into conv_stem>");
-        }
-    } else {
-        out->out_h = k.out.H; out->out_w = k.out.W; out->cout = k.out.C; out->cin = k.in.C;
-        out->bytes = elems(k.in) * (k.in.f32 ? 4.0 : net->esize) + elems(k.out) * esz(k.out) + (k.has_res ? elems(k.in2) * net->esize : 0.0);
-        snprintf(out->name, sizeof out->name, "%s<%s>", k.kind == K_PREP ? "prep" : k.kind == K_POOL ? "pool" : "eltwise", t);
-        const int epc = net->epc;       // pool: the 16-byte-vector instantiation runs when every stride is chunk-aligned (aux.hip)
-        const bool vec = k.kind == K_POOL && k.in.C % epc == 0 && k.in.ld % epc == 0 && k.out.ld % epc == 0 && (k.in.base + k.in.coff) % epc == 0 &&
-                         (k.out.base + k.out.coff) % epc == 0 && k.in.img_stride % epc == 0 && k.out.img_stride % epc == 0;
-        set_symbol(aux_symbol(k.kind, net->opt.dtype, vec));
-        if (k.kind == K_POOL && k.spp) {        // one read, three writes
-            out->ksize = k.pool_k; out->stride = 1;
-            out->bytes += elems(k.out2) * esz(k.out2) + elems(k.out3) * esz(k.out3);
-            snprintf(out->name, sizeof out->name, "spp_pool<%s,%d-%d-%d>", t, k.pool_k, 2 * k.pool_k - 1, 3 * k.pool_k - 2);
-            set_symbol(spp_pool_symbol((k.pool_k - 1) / 2));
-        } else if (k.kind == K_POOL && k.pool_k != 2) {
-            out->ksize = k.pool_k; out->stride = 1;
-            snprintf(out->name, sizeof out->name, "pool_same<%s,%dx%d>", t, k.pool_k, k.pool_k);
-            set_symbol(pool_same_symbol(net->opt.dtype, vec));
-        }
-    }
+    if (k.kind == K_CONV) conv_kernel_info(net, kernel, out);
+    else aux_kernel_info(net, kernel, out);
     return YOLO_OK;
 }
 
 static int tune_streams_any(yolo_net *net, const NetIn in_dev, int batch, void *stream, const char *who) {
     int rc = check_ready(net, in_dev.ptr, batch, who);
     if (rc) return rc;
-    if (!net->arena_full || batch <= (net->opt.max_batch + 1) / 2) return YOLO_OK;       // nothing to choose (or not with this batch)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        return fail(YOLO_ERR_HIP, std::string(who) + ": hipEventCreate failed");
-    }
-    // interleaved: one pass, two halves, one pass, ... -- three forward passes per sample, the first round of each only warms up,
-    // the best of the other four counts (boxes differ: the same build gains 3-4 % from two halves on one MI355X and loses 1-2 % on
-    // another, so the rule's answer is re-measured where the net runs)
-    float best[3] = {0.f, 1e30f, 1e30f};
-    for (int rep = 0; rep < 5 && rc == YOLO_OK; ++rep)
-        for (int parts = 1; parts <= 2 && rc == YOLO_OK; ++parts) {
-            net->parts = parts;
-            if (hipEventRecord(e0, s) != hipSuccess) rc = fail(YOLO_ERR_HIP, std::string(who) + ": hipEventRecord failed");
-            for (int k = 0; k < 3 && rc == YOLO_OK; ++k) rc = run_forward(net, in_dev, batch, logits, s);
-            if (rc == YOLO_OK && (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess))
-                rc = fail(YOLO_ERR_HIP, std::string(who) + ": event failed");
-            float ms = 0.f;
-            if (rc == YOLO_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && rep > 0 && ms < best[parts]) best[parts] = ms;
-        }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    // two halves must win by 1.5 %: where they do not gain 3-4 % they are within +-1 % of one pass, which the later steady state
-    // (warmer chip, decode + NMS behind the join) has been seen to turn into a loss
-    net->parts = (rc == YOLO_OK && best[2] < 0.985f * best[1]) ? 2 : (rc == YOLO_OK ? 1 : net->arenas);
-    net->parts_tuned = rc == YOLO_OK;
-    net->obj_valid = false;
-    return rc;
+    return tune_streams(net, in_dev, batch, static_cast<hipStream_t>(stream), who);
 }
 int yolo_net_tune_streams(yolo_net *net, const float *in_dev, int batch, void *stream) {
     return tune_streams_any(net, NetIn{in_dev, false}, batch, stream, "yolo_net_tune_streams");
@@ -812,47 +305,7 @@ int yolo_net_set_streams(yolo_net *net, int parts) {
 int yolo_net_autotune(yolo_net *net, const float *in_dev, int batch, void *stream) {
     int rc = check_ready(net, in_dev, batch, "yolo_net_autotune");
     if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
-    {   // every launch of a multi-stream net sees one part of the batch: tune for that size (arena 0)
-        const int per = part_batch(net);
-        if (batch > per) batch = per;
-    }
-    rc = run_forward(net, NetIn{in_dev, false}, batch, logits, s);      // real activations in every buffer
-    if (rc) return rc;
-    Ptrs P{net, NetIn{in_dev, false}, logits};
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    for (size_t ki = 0; ki < net->kernels.size(); ++ki) {
-        Kernel &k = net->kernels[ki];
-        if (k.kind != K_CONV || k.stem >= 2 || k.mx || !dma_eligible(net, k)) continue;      // (MX convs: one kernel, weights packed for it)
-        ConvParams p;
-        rc = make_conv_params(net, k, P, batch, p);
-        if (rc) break;
-        float best = 1e30f;
-        int best_tile = -1;
-        for (int tile = 0; tile < kNumTiles; ++tile) {
-            if (!conv_tile_valid(net, k, tile)) continue;
-            const ConvLaunch L = resolve_conv(net, ki, p, tile, arena_slab_data_bytes(net));       // (timed without the 1x1 behind it: L.fuse2 is not attached)
-            float ms = 1e30f;
-            bool ok = true;
-            for (int rep = 0; rep < 4 && ok; ++rep) {       // first launch warms caches; keep the best of the rest
-                ok = hipEventRecord(e0, s) == hipSuccess && launch_conv_any(net, k, p, L, s) == hipSuccess &&
-                     hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
-                float t = 0.f;
-                if (ok && rep > 0 && hipEventElapsedTime(&t, e0, e1) == hipSuccess && t < ms) ms = t;
-            }
-            if (!ok) { rc = fail(YOLO_ERR_HIP, "yolo_net_autotune: launch failed"); break; }
-            if (ms < best) { best = ms; best_tile = tile; }
-        }
-        if (rc) break;
-        k.tile = best_tile;
-        net->side_ok.clear();       // (whether a pass splits K -- branch_tails_ok -- depends on the tiles)
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    return autotune_tiles(net, NetIn{in_dev, false}, batch, static_cast<hipStream_t>(stream));
 }
 
 static int detect_any(yolo_net *net, const NetIn in_dev, int batch, double threshold, double iou_threshold, int nms_mode,
@@ -919,12 +372,21 @@ int yolo_net_read_layer(yolo_net *net, int layer, int batch, float *host_out, si
     return YOLO_OK;
 }
 
+static size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// scratch of the standalone decode + NMS: candidates at 0 | counters | NMS slabs
+struct DecodeScratch {
+    size_t counters, slabs, total;
+    DecodeScratch(int batch, int cap) {
+        counters = align256(sizeof(Candidate) * (size_t)cap * batch);
+        slabs = counters + align256(sizeof(int) * (size_t)batch * kCandCountStride);
+        total = slabs + nms_scratch_bytes(cap) * (size_t)batch;
+    }
+};
+
 size_t yolo_decode_scratch_bytes(const yolo_head_desc *head, int batch, int cand_capacity) {
     (void)head;
     if (batch <= 0) return 0;
-    if (cand_capacity <= 0) cand_capacity = 4096;
-    return ((sizeof(Candidate) * (size_t)cand_capacity * batch + 255) & ~(size_t)255) + ((sizeof(int) * (size_t)batch * kCandCountStride + 255) & ~(size_t)255) +
-           nms_scratch_bytes(cand_capacity) * (size_t)batch;
+    return DecodeScratch(batch, cand_capacity <= 0 ? 4096 : cand_capacity).total;
 }
 
 int yolo_decode_nms(const yolo_head_desc *head, const float *logits_dev, int batch, double threshold, double iou_threshold,
@@ -938,12 +400,12 @@ int yolo_decode_nms(const yolo_head_desc *head, const float *logits_dev, int bat
     int rc = check_head(head, 0, err);
     if (rc) return fail(rc, "yolo_decode_nms: " + err);
     if (cand_capacity > 65536) return fail(YOLO_ERR_ARG, "yolo_decode_nms: cand_capacity above 65536");
-    if (scratch_bytes < yolo_decode_scratch_bytes(head, batch, cand_capacity)) return fail(YOLO_ERR_ARG, "yolo_decode_nms: scratch too small");
-    unsigned char *cand = static_cast<unsigned char *>(scratch_dev);
-    int *cnt = reinterpret_cast<int *>(cand + ((sizeof(Candidate) * (size_t)cand_capacity * batch + 255) & ~(size_t)255));
-    unsigned char *slabs = reinterpret_cast<unsigned char *>(cnt) + ((sizeof(int) * (size_t)batch * kCandCountStride + 255) & ~(size_t)255);
-    return run_decode_nms(*head, logits_dev, batch, threshold, iou_threshold, nms_mode, cand_capacity, max_boxes, cand, cnt,
-                          boxes_dev, counts_dev, status_dev, nullptr, static_cast<hipStream_t>(stream), slabs);
+    const DecodeScratch L(batch, cand_capacity);
+    if (scratch_bytes < L.total) return fail(YOLO_ERR_ARG, "yolo_decode_nms: scratch too small");
+    unsigned char *base = static_cast<unsigned char *>(scratch_dev);
+    return run_decode_nms(*head, logits_dev, batch, threshold, iou_threshold, nms_mode, cand_capacity, max_boxes, base,
+                          reinterpret_cast<int *>(base + L.counters), boxes_dev, counts_dev, status_dev, nullptr,
+                          static_cast<hipStream_t>(stream), base + L.slabs);
 }
 
 static int resize_any(const uint8_t *src_dev, int src_h, int src_w, int src_row_bytes, void *dst_dev, bool dst_u8, int dst_h, int dst_w,
@@ -1187,11 +649,12 @@ int yolo_nms_host(const double *xywh, const float *prob, const int32_t *class_id
         c[i].prob = prob[i]; c[i].cls = class_idx[i]; c[i].scan = (unsigned)i; c[i].pad_ = 0;
     }
     unsigned char *dev = nullptr;
-    const size_t cb = sizeof(Candidate) * (size_t)n, bb = sizeof(yolo_box) * (size_t)n, ib = sizeof(int) * (size_t)n;
-    const size_t total = ((cb + 255) & ~(size_t)255) + ((bb + 255) & ~(size_t)255) + ((ib + 255) & ~(size_t)255) + 768 + nms_scratch_bytes(n);
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dev), total));
-    unsigned char *d_c = dev, *d_b = d_c + ((cb + 255) & ~(size_t)255), *d_i = d_b + ((bb + 255) & ~(size_t)255);
-    int *d_cnt = reinterpret_cast<int *>(d_i + ((ib + 255) & ~(size_t)255));    // [count, kept, status] 256 B apart
+    const size_t cb = sizeof(Candidate) * (size_t)n;
+    struct { size_t boxes, idx, cnt, scratch; } L;      // candidates at 0 | boxes | kept indices | [count, kept, status] 256 B apart | NMS slab (only used above 4096 boxes)
+    L.boxes = align256(cb); L.idx = L.boxes + align256(sizeof(yolo_box) * (size_t)n); L.cnt = L.idx + align256(sizeof(int) * (size_t)n); L.scratch = L.cnt + 768;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dev), L.scratch + nms_scratch_bytes(n)));
+    unsigned char *d_c = dev, *d_b = dev + L.boxes, *d_i = dev + L.idx;
+    int *d_cnt = reinterpret_cast<int *>(dev + L.cnt);
     int rc = YOLO_OK;
     do {
         if (hipMemcpy(d_c, c.data(), cb, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1204,7 +667,7 @@ int yolo_nms_host(const double *xywh, const float *prob, const int32_t *class_id
         np.boxes = reinterpret_cast<yolo_box *>(d_b);
         np.counts = d_cnt + 64; np.status = d_cnt + 128;
         np.keep_idx = reinterpret_cast<int *>(d_i);
-        np.scratch = reinterpret_cast<unsigned char *>(d_cnt) + 768;      // only used above 4096 boxes
+        np.scratch = dev + L.scratch;
         np.scratch_stride = nms_scratch_bytes(n);
         hipError_t e = launch_nms(np, 1, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();

@@ -3,6 +3,7 @@
 // element-wise fallback (standalone shortcut / upsample / reorg / concat-copy / f32 convert) the
 // planner uses when a fusion into a conv epilogue is not possible.
 #include "yolo_internal.h"
+#include <cstring>
 #include <type_traits>
 
 namespace yolo {
@@ -442,43 +443,30 @@ hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s, bool in_u8
     return hipGetLastError();
 }
 
-hipError_t launch_pool(const PoolParams &p0, int dtype, hipStream_t s) {
+// pool_kernel and pool_same_kernel: one host side.  kern[float32][vec]; the 16-byte-vector instantiation runs when the strides allow it
+// (pool_vec_strides: what yolo_net_kernel_info reports from) and both pointers are aligned; p.total arrives as B*Ho*Wo pixels and
+// leaves as work items.
+typedef void (*PoolKernel)(const PoolParams);
+static hipError_t launch_pool_with(PoolKernel const (&kern)[2][2], const PoolParams &p0, int dtype, hipStream_t s) {
     PoolParams p = p0;
     const int epc = dtype == YOLO_DTYPE_F16 ? 8 : 4;
-    const bool vec = (p.C % epc == 0) && (p.in_ld % epc == 0) && (p.out_ld % epc == 0) &&
-                     ((uintptr_t)p.in % 16 == 0) && ((uintptr_t)p.out % 16 == 0) &&
-                     (p.in_img_stride % epc == 0) && (p.out_img_stride % epc == 0);
-    const long long pix = p.total;      // caller passes B*Ho*Wo
-    p.total = pix * (vec ? p.C / epc : p.C);
-    const dim3 g(grid_for(p.total)), b(256);
-    if (dtype == YOLO_DTYPE_F16) {
-        if (vec) hipLaunchKernelGGL((pool_kernel<false, true>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((pool_kernel<false, false>), g, b, 0, s, p);
-    } else {
-        if (vec) hipLaunchKernelGGL((pool_kernel<true, true>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((pool_kernel<true, false>), g, b, 0, s, p);
-    }
+    const bool vec = pool_vec_strides(p.C, p.in_ld, p.out_ld, p.in_img_stride, p.out_img_stride, epc) &&
+                     ((uintptr_t)p.in % 16 == 0) && ((uintptr_t)p.out % 16 == 0);
+    p.total *= vec ? p.C / epc : p.C;
+    hipLaunchKernelGGL(kern[dtype != YOLO_DTYPE_F16][vec], dim3(grid_for(p.total)), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
-hipError_t launch_pool_same(const PoolParams &p0, int dtype, hipStream_t s) {
-    PoolParams p = p0;
+hipError_t launch_pool(const PoolParams &p, int dtype, hipStream_t s) {
+    static const PoolKernel kern[2][2] = {{pool_kernel<false, false>, pool_kernel<false, true>}, {pool_kernel<true, false>, pool_kernel<true, true>}};
+    return launch_pool_with(kern, p, dtype, s);
+}
+
+hipError_t launch_pool_same(const PoolParams &p, int dtype, hipStream_t s) {
+    static const PoolKernel kern[2][2] = {{pool_same_kernel<false, false>, pool_same_kernel<false, true>},
+                                          {pool_same_kernel<true, false>, pool_same_kernel<true, true>}};
     if (p.ksize < 3 || p.ksize > 13 || !(p.ksize & 1) || p.Ho != p.H || p.Wo != p.W) return hipErrorInvalidValue;
-    const int epc = dtype == YOLO_DTYPE_F16 ? 8 : 4;
-    const bool vec = (p.C % epc == 0) && (p.in_ld % epc == 0) && (p.out_ld % epc == 0) &&
-                     ((uintptr_t)p.in % 16 == 0) && ((uintptr_t)p.out % 16 == 0) &&
-                     (p.in_img_stride % epc == 0) && (p.out_img_stride % epc == 0);
-    const long long pix = p.total;      // caller passes B*H*W
-    p.total = pix * (vec ? p.C / epc : p.C);
-    const dim3 g(grid_for(p.total)), b(256);
-    if (dtype == YOLO_DTYPE_F16) {
-        if (vec) hipLaunchKernelGGL((pool_same_kernel<false, true>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((pool_same_kernel<false, false>), g, b, 0, s, p);
-    } else {
-        if (vec) hipLaunchKernelGGL((pool_same_kernel<true, true>), g, b, 0, s, p);
-        else hipLaunchKernelGGL((pool_same_kernel<true, false>), g, b, 0, s, p);
-    }
-    return hipGetLastError();
+    return launch_pool_with(kern, p, dtype, s);
 }
 
 // 16-byte channel chunks per workgroup of spp_pool_kernel: as many as two copies of their planes fit 64 KiB of LDS, up to 8 (a 128-byte
@@ -576,6 +564,18 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ReduceParams p
             }
         }
     }
+}
+
+// the reduce pass of a conv launched with p.ksplit > 1 into p.part: the epilogue fields of its parameters
+ReduceParams reduce_params(const ConvParams &p) {
+    ReduceParams r;
+    memset(&r, 0, sizeof r);
+    r.part = p.part; r.bias = p.bias; r.res = p.has_res ? p.res : nullptr; r.out = p.out;
+    r.obj_out = p.obj_out; r.obj_width = p.obj_width; r.obj_rows = p.obj_rows; r.obj_row0 = p.obj_row0; r.obj_na = p.obj_na;
+    r.ksplit = p.ksplit; r.M = p.M; r.Cout = p.Cout; r.cout_pad = p.cout_pad; r.HoWo = p.HoWo; r.Wo = p.Wo;
+    r.out_ld = p.out_ld; r.res_ld = p.res_ld; r.leaky = p.leaky; r.outmode = p.outmode; r.out_f32 = p.out_f32; r.f32 = p.f32;
+    r.out_img_stride = p.out_img_stride; r.res_img_stride = p.res_img_stride;
+    return r;
 }
 
 hipError_t launch_splitk_reduce(const ReduceParams &p, hipStream_t s) {

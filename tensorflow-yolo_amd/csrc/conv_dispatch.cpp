@@ -16,12 +16,12 @@ static void conv_vec_flags(const yolo_net *net, const Kernel &k, bool out_f32, i
     const int epc = net->epc;
     const int ch = k.cfg == CFG_N32 ? 8 : 16;
     const int oepc = out_f32 ? 4 : epc;
-    vec_out = (k.cout % ch == 0) && (k.out.ld % oepc == 0) && ((k.out.base + k.out.coff) % oepc == 0) && (k.out.img_stride % oepc == 0);
-    vec_res = k.has_res && (k.cout % ch == 0) && (k.in2.ld % epc == 0) && (k.in2.coff % epc == 0) && (k.in2.img_stride % epc == 0);
+    vec_out = (k.cout % ch == 0) && view_chunk_aligned(k.out, oepc);
+    vec_res = k.has_res && (k.cout % ch == 0) && view_chunk_aligned(k.in2, epc);       // (a residual has no base: plan.cpp refuses float32 head views)
 }
 
 // Every field of a conv's launch parameters that needs no device pointer, for one planned kernel at the given batch: all that
-// resolve_conv and the symbol functions read.  api.cpp's make_conv_params adds the pointers, the 2 GiB checks and the objectness block.
+// resolve_conv and the symbol functions read.  forward.cpp's conv_params adds the pointers, the 2 GiB checks and the objectness block.
 void conv_shape_params(const yolo_net *net, const Kernel &k, int batch, ConvParams &p) {
     memset(&p, 0, sizeof p);
     const yolo_layer_desc &d = net->layers[k.src_layer].d;
@@ -243,15 +243,12 @@ bool pass_splits_k(const yolo_net *net, int batch) {
 // max_batch) -- the record the launch path builds, formatted
 void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
     const Kernel &k = net->kernels[kernel];
-    auto set_symbol = [&](const std::string &sym) { snprintf(out->symbol, sizeof out->symbol, "%s", sym.c_str()); };
-    const char *t = net->opt.dtype == YOLO_DTYPE_F16 ? "f16" : "f32";
-    auto elems = [](const View &v) { return (double)v.H * v.W * v.C; };
-    auto esz = [&](const View &v) { return v.f32 ? 4.0 : (double)net->esize; };
+    const char *t = dtype_tag(net);
     const LayerInfo &li = net->layers[k.src_layer];
     out->variant = k.cfg + 4 * k.perchunk;
     out->ksize = k.ksize; out->stride = k.stride; out->cin = k.cin; out->cout = k.cout; out->out_h = li.H; out->out_w = li.W;
     out->flops = 2.0 * li.H * li.W * k.cout * k.ksize * k.ksize * k.cin;
-    out->bytes = (double)k.in.H * k.in.W * k.cin * net->esize + elems(k.out) * esz(k.out) + (k.has_res ? elems(k.in2) * net->esize : 0.0);
+    out->bytes = (double)k.in.H * k.in.W * k.cin * net->esize + view_elems(k.out) * view_esz(net, k.out) + (k.has_res ? view_elems(k.in2) * net->esize : 0.0);
     out->weight_bytes = (double)k.cout * k.ksize * k.ksize * k.cin * net->esize + 4.0 * k.cout;
     if (k.stem == 3) {          // no launch of its own
         out->flops = 0; out->bytes = 0; out->weight_bytes = 0;
@@ -261,14 +258,14 @@ void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
     if (k.stem == 2) {
         const Kernel &f = net->kernels[kernel - 1];
         out->flops += 2.0 * f.out.H * f.out.W * f.cout * 27;
-        out->bytes = (double)f.in.H * f.in.W * 3 * 4 + elems(k.out) * esz(k.out);
+        out->bytes = (double)f.in.H * f.in.W * 3 * 4 + view_elems(k.out) * view_esz(net, k.out);
         out->weight_bytes += 28.0 * f.cout * 4;
         snprintf(out->name, sizeof out->name, "conv_stem<f16,3-32-64>");
-        set_symbol("yolo::stem_v3_kernel(yolo::StemParams)");
+        set_symbol(out, "yolo::stem_v3_kernel(yolo::StemParams)");
         if (kernel + 1 < (int)net->kernels.size() && net->kernels[kernel + 1].stem == 3) {
             const Kernel &t3 = net->kernels[kernel + 1];
             out->flops += 2.0 * li.H * li.W * t3.cout * t3.cin;
-            out->bytes += elems(t3.out) * esz(t3.out);
+            out->bytes += view_elems(t3.out) * view_esz(net, t3.out);
             out->weight_bytes += (double)t3.cout * t3.cin * net->esize + 4.0 * t3.cout;
             snprintf(out->name, sizeof out->name, "conv_stem<f16,3-32-64-32>");
         }
@@ -280,7 +277,7 @@ void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
         out->variant = 8 + kMxTile;
         out->weight_bytes = (double)k.cout * k.ksize * k.ksize * k.cin * (1.0 + 1.0 / 32) + 4.0 * k.cout;
         snprintf(out->name, sizeof out->name, "conv_mx<mxf8,128x256>");
-        set_symbol(conv_mx_symbol(conv_fast_epilogue_ok(mp)));
+        set_symbol(out, conv_mx_symbol(conv_fast_epilogue_ok(mp)));
         return;
     }
     ConvParams sp;
@@ -299,7 +296,7 @@ void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
     if (fused2) {       // this launch also computes the 1x1 behind it: its work and its output belong here
         const Kernel &b2 = net->kernels[kernel + 1];
         out->flops += 2.0 * li.H * li.W * b2.cout * b2.cin;
-        out->bytes += elems(b2.out) * esz(b2.out);
+        out->bytes += view_elems(b2.out) * view_esz(net, b2.out);
         out->weight_bytes += (double)b2.cout * b2.cin * net->esize + 4.0 * b2.cout;
     }
     const int tile = pk.tile;
@@ -307,10 +304,10 @@ void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
         out->variant = 8 + tile;
         snprintf(out->name, sizeof out->name, "conv_igemm_dma<%s,%s>", t, conv_tile(tile).name);
         sp.ksplit = pk.ks; sp.pair = pk.pair; sp.fuse2 = pk.fuse2;       // as launched
-        set_symbol(conv_tile_symbol(tile, sp));
+        set_symbol(out, conv_tile_symbol(tile, sp));
     } else {
         const bool emu = conv_f32_emu_rule(net->opt.f32_products, net->opt.dtype, sp, k.cfg, k.perchunk != 0, pk.ks);
-        set_symbol(conv_symbol(net->opt.dtype, k.cfg, k.perchunk != 0, emu));
+        set_symbol(out, conv_symbol(net->opt.dtype, k.cfg, k.perchunk != 0, emu));
         if (emu) snprintf(out->name, sizeof out->name, "conv_igemm_emu<f32 as 9 x bf16,N128>");
         else snprintf(out->name, sizeof out->name, "conv_igemm<%s,N%d,%s>", t, k.cfg == CFG_N128 ? 128 : k.cfg == CFG_N64 ? 64 : 32,
                       k.perchunk ? "perchunk" : "uniform");

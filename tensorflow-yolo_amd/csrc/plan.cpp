@@ -262,7 +262,7 @@ struct Planner {
     }
 
     bool chunk_aligned(const View &v) const {
-        return !v.f32 && v.C % epc == 0 && v.ld % epc == 0 && (v.base + v.coff) % epc == 0 && v.img_stride % epc == 0;
+        return !v.f32 && v.C % epc == 0 && view_chunk_aligned(v, epc);
     }
 
     // The Darknet SPP block (yolov3-spp.cfg): three stride-1 pools of odd sizes k1 < k2 < k3 over the same tensor with k2 - 1 = 2 (k1 - 1)
@@ -434,16 +434,15 @@ struct Planner {
                 if (i == 2 && first_direct && !net->kernels.empty() && net->kernels.back().kind == K_FIRST && s == 1 && sole(1, 2) &&
                     !net->opt.keep_all && net->opt.dtype == YOLO_DTYPE_F16 && d.ksize == 3 && d.stride == 2 && d.filters == 64 &&
                     L[1].d.filters == 32 && d.leaky && L[1].d.leaky && f.kind == 0 && !has_head[i] && L[1].H % 2 == 0 && L[1].W % 2 == 0 &&
-                    k.out.ld % epc == 0 && (k.out.base + k.out.coff) % epc == 0 && k.out.img_stride % epc == 0 && !k.out.f32 &&
-                    !getenv("YOLO_NO_STEM")) {
+                    view_chunk_aligned(k.out, epc) && !k.out.f32 && !getenv("YOLO_NO_STEM")) {
                     net->kernels.back().stem = 1;
                     k.stem = 2;
                     k.note += " fused with the first layer (stem.hip): the 32-channel tensor stays in LDS";
                 }
                 // ... and the 1x1 64->32 conv behind the stem (Darknet-53 layer 3) is computed by the stem kernel too
                 if (i == 3 && net->kernels.size() >= 2 && net->kernels.back().stem == 2 && s == 2 && d.ksize == 1 && d.stride == 1 &&
-                    d.filters == 32 && cin == 64 && d.leaky && f.kind == 0 && !has_head[i] && !k.out.f32 && k.out.ld % epc == 0 &&
-                    (k.out.base + k.out.coff) % epc == 0 && k.out.img_stride % epc == 0 && k.in.ld == net->kernels.back().out.ld &&
+                    d.filters == 32 && cin == 64 && d.leaky && f.kind == 0 && !has_head[i] && !k.out.f32 &&
+                    view_chunk_aligned(k.out, epc) && k.in.ld == net->kernels.back().out.ld &&
                     k.in.coff == net->kernels.back().out.coff && k.in.buf == net->kernels.back().out.buf && !getenv("YOLO_NO_STEM3")) {
                     k.stem = 3;
                     k.note += " computed inside the stem kernel (no launch)";
@@ -455,7 +454,7 @@ struct Planner {
                 // picks (conv_dispatch.cpp: resolve_conv), else the 1x1 runs as a launch of its own.
                 if (!net->kernels.empty() && net->opt.dtype == YOLO_DTYPE_F16 && !net->opt.keep_all && !getenv("YOLO_NO_FUSE2") &&
                     d.ksize == 1 && d.stride == 1 && d.filters == 64 && cin == 128 && f.kind == 0 && !has_head[i] && !k.out.f32 &&
-                    k.out.ld % epc == 0 && (k.out.base + k.out.coff) % epc == 0 && k.out.img_stride % epc == 0) {
+                    view_chunk_aligned(k.out, epc)) {
                     Kernel &c = net->kernels.back();
                     if (c.kind == K_CONV && c.layer == s && c.stem == 0 && c.cout == 128 && c.ksize == 3 && c.cpt % 4 == 0 &&
                         c.outmode == OUT_NORMAL && !c.head && !c.out.f32 && c.out.buf == k.in.buf && c.out.ld == k.in.ld &&
@@ -478,7 +477,7 @@ struct Planner {
                 if (i == 2 && s == 1 && first_direct && !net->kernels.empty() && net->kernels.back().kind == K_FIRST && sole(1, 2) &&
                     !net->opt.keep_all && d.stride == 2 && L[1].H % 2 == 0 && L[1].W % 2 == 0 && !getenv("YOLO_NO_FIRST_POOL")) {
                     View pv = out_view_for(i);
-                    if (!pv.f32 && pv.ld % epc == 0 && (pv.base + pv.coff) % epc == 0 && pv.img_stride % epc == 0) {
+                    if (!pv.f32 && view_chunk_aligned(pv, epc)) {
                         Kernel &f = net->kernels.back();
                         f.pool_fused = 1;
                         f.out = pv;
@@ -502,7 +501,7 @@ struct Planner {
                     if (c.ksize == 3 && c.stride == 1 && c.outmode == OUT_NORMAL && !c.has_res && !c.head && !c.stem && !has_claim[s] &&
                         c.cpt % 4 == 0 && c.cout % 16 == 0 && pool_tile >= 0 && (f16 || conv_tile(pool_tile).f32_ok())) {
                         View pv = out_view_for(i);
-                        if (!pv.f32 && pv.ld % epc == 0 && (pv.base + pv.coff) % epc == 0 && pv.img_stride % epc == 0) {
+                        if (!pv.f32 && view_chunk_aligned(pv, epc)) {
                             c.outmode = OUT_POOL2;
                             c.out = pv;
                             c.layer = i;
@@ -610,14 +609,11 @@ struct Planner {
         // a final layer produced by something that cannot write the user tensor directly
         {
             int last = n - 1;
-            int op = L[last].d.op;
-            bool fused_last = (op == YOLO_OP_SHORTCUT || op == YOLO_OP_UPSAMPLE || op == YOLO_OP_REORG);
-            if (op == YOLO_OP_INPUT) {
+            if (L[last].d.op == YOLO_OP_INPUT) {
                 View fin = out_view_for(last);
                 add_eltwise(last, L[last].view, nullptr, fin, OUT_NORMAL, "convert final layer to float32");
                 L[last].view = fin;
             }
-            (void)fused_last;
             if (!L[last].materialised) return fail("final layer was not materialised");
         }
         net->weight_count = wsrc;
@@ -751,19 +747,21 @@ int plan_network(yolo_net *net, const yolo_layer_desc *layers, int n, std::strin
     if (!P.emit()) { err = P.err; return YOLO_ERR_PLAN; }
     P.side_chains();
     P.allocate();
-    // workspace tail: head logits for detect(), candidate lists, counters
+    // workspace tail: head logits for detect(), candidate lists, counters -- each region recorded as it is laid out (net->tail:
+    // yolo_net_workspace_regions), 4096-byte aligned
     size_t off = roundup_sz(net->act_bytes, 4096);
-    net->logits_off = off;
-    off += roundup_sz(net->out_count * 4 * (size_t)net->opt.max_batch, 4096);
-    net->cand_off = off;
-    off += roundup_sz(sizeof(Candidate) * (size_t)net->opt.cand_capacity * net->opt.max_batch, 4096);
-    net->count_off = off;
-    off += roundup_sz(sizeof(int) * (size_t)net->opt.max_batch * kCandCountStride, 4096);
-    net->nms_off = off;
-    off += roundup_sz(nms_scratch_bytes(net->opt.cand_capacity) * (size_t)net->opt.max_batch, 4096);
-    net->obj_off = off;
-    net->obj_bytes = net->head.n_classes > 0 ? (size_t)net->opt.max_batch * (net->out_count / (size_t)(5 + net->head.n_classes)) * 4 : 0;
-    off += roundup_sz(net->obj_bytes, 4096);
+    auto region = [&](const char *name, size_t used) {
+        net->tail.push_back({name, off, used, roundup_sz(used, 4096)});
+        off += net->tail.back().bytes;
+        return net->tail.back().offset;
+    };
+    const size_t mb = (size_t)net->opt.max_batch;
+    net->obj_bytes = net->head.n_classes > 0 ? mb * (net->out_count / (size_t)(5 + net->head.n_classes)) * 4 : 0;
+    net->logits_off = region("head logits", net->out_count * 4 * mb);
+    net->cand_off = region("candidates", sizeof(Candidate) * (size_t)net->opt.cand_capacity * mb);
+    net->count_off = region("candidate counters", sizeof(int) * mb * kCandCountStride);
+    net->nms_off = region("nms scratch", nms_scratch_bytes(net->opt.cand_capacity) * mb);
+    net->obj_off = region("objectness", net->obj_bytes);
     // split-K slabs (float32 partial sums of the convs whose launch would leave the chip idle): last region of the workspace,
     // sized by yolo_net_create from the launches that can actually split (conv_dispatch.cpp: splitk_slab_bytes) -- 0 for most big-batch nets
     net->splitk_off = off;
@@ -779,7 +777,7 @@ bool mx_eligible(const yolo_net *net, const Kernel &k) {
     if (!net->mx || k.kind != K_CONV || k.ksize != 3 || k.stride != 1 || k.cin % 128 || k.cin_s != k.cin) return false;
     if (k.stem || k.fuse2_next || k.fuse2_prev || k.head || k.outmode == OUT_POOL2 || k.in.f32) return false;
     if (!conv_mx_fits(k.in.W) || k.in.H != k.out.H || k.in.W != k.out.W) return false;
-    return k.in.ld % 8 == 0 && k.in.coff % 8 == 0 && k.in.img_stride % 8 == 0 && k.in.coff + k.cin <= k.in.ld;
+    return view_chunk_aligned(k.in, 8) && k.in.coff + k.cin <= k.in.ld;        // (k.in.base is 0: only float32 head views have one)
 }
 
 // float -> e4m3fn, round to nearest even; |x| <= 448 (the caller clamps)
@@ -855,7 +853,6 @@ int pack_weights(const yolo_net *net, const float *host, size_t n, std::vector<u
     }
     blob.assign(net->weights_bytes, 0);
     const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-    const int epc = net->epc;
     for (const Kernel &k : net->kernels) {
         if (k.kind == K_FIRST) {        // [27 = (kh,kw,cin)][cout] float32 (first.hip)
             const float *p = host + k.w_src;
@@ -925,7 +922,6 @@ int pack_weights(const yolo_net *net, const float *host, size_t n, std::vector<u
                 }
             }
         }
-        (void)epc;
     }
     return YOLO_OK;
 }

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -32,6 +33,9 @@ struct View {
     long long base = 0;         // extra element offset (head scale offset inside the output)
     bool f32 = false;           // float32 elements whatever the net dtype (head logits)
 };
+// every stride of the view, and its first element, is a multiple of `epc` elements (epc = elements per 16-byte chunk: 16-byte accesses
+// are possible in a buffer that is itself aligned).  What else a caller asks of the view -- C % epc, !f32 -- stands at the call.
+inline bool view_chunk_aligned(const View &v, int epc) { return v.ld % epc == 0 && (v.base + v.coff) % epc == 0 && v.img_stride % epc == 0; }
 
 struct Buffer {
     long long elems_per_image = 0;  // elements per image
@@ -246,6 +250,11 @@ struct PoolParams {            // net/layers.py:70-81
     long long total;           // B*Ho*Wo*(C/EPC) work items
     int ksize = 2;             // pool_same_kernel: odd window size (stride 1, SAME); pool_kernel is the 2x2 window whatever this says
 };
+// pool_kernel / pool_same_kernel: the strides allow the 16-byte-vector instantiation.  The launchers (aux.hip) add the alignment of their
+// two pointers; the report (forward.cpp: pool_info) that of the views' first elements, which is the same thing in a planned buffer.
+inline bool pool_vec_strides(int C, int in_ld, int out_ld, long long in_img_stride, long long out_img_stride, int epc) {
+    return C % epc == 0 && in_ld % epc == 0 && out_ld % epc == 0 && in_img_stride % epc == 0 && out_img_stride % epc == 0;
+}
 
 struct SppParams {             // aux.hip: spp_pool_kernel -- the three stride-1 SAME pools of an SPP block (windows 2r+1, 4r+1, 6r+1) of one fp16 tensor
     const void *in;            // element pointers incl. view base / coff; every stride a multiple of the 16-byte chunk
@@ -392,6 +401,7 @@ std::string first_symbol(int dtype, int cout, bool pool);
 std::string aux_symbol(int kind, int dtype, bool vec);
 std::string pool_same_symbol(int dtype, bool vec);
 std::string spp_pool_symbol(int rad);
+__attribute__((visibility("hidden"))) ReduceParams reduce_params(const ConvParams &p);           // the second pass of the split-K launch `p` (p.ksplit, p.part as launched)
 hipError_t launch_splitk_reduce(const ReduceParams &p, hipStream_t s);
 // in_u8 / dst_u8: the kernel's uint8 twin runs -- `in` (`dst`) holds bytes, dense, any alignment (the parameter blocks are the same)
 hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s, bool in_u8 = false);
@@ -452,6 +462,20 @@ struct LayerInfo {
     bool materialised = false;
 };
 
+// One region of the workspace behind the activation arenas (yolo_net_workspace_regions reports them as laid out)
+struct __attribute__((visibility("hidden"))) WsRegion {
+    const char *name;
+    size_t offset, used, bytes;
+};
+
+// The streams and events a net creates at first use (forward.cpp: side_streams, branch_streams; destroy_streams at yolo_net_destroy).
+struct __attribute__((visibility("hidden"))) StreamPool {
+    std::vector<hipStream_t> side;         // multi-stream forward (YOLO_STREAMS=N): parts 1.. run here, part 0 on the caller's stream
+    std::vector<hipEvent_t> fork, join;    // ... one fork event, one join event per side stream
+    std::vector<hipStream_t> branch;       // one stream per arena for the branch tails (Kernel.side)
+    std::vector<hipEvent_t> bfork, bjoin;  // ... with four fork events and one join event per arena
+};
+
 }  // namespace yolo
 
 struct yolo_net {
@@ -466,17 +490,14 @@ struct yolo_net {
     size_t act_bytes = 0;          // activation part of the workspace
     size_t logits_off = 0, cand_off = 0, count_off = 0, nms_off = 0;   // nms_off: global NMS slabs (cand_capacity > 4096)
     size_t splitk_off = 0, splitk_bytes = 0;   // float32 partial-sum slabs of the split-K convs (small feature maps at small batch)
+    std::vector<yolo::WsRegion> tail;      // the regions from logits_off on, in offset order: plan_network lays them out, yolo_net_create appends the split-K one
     size_t obj_off = 0, obj_bytes = 0;     // compact objectness logits [max_batch][rows] written by the head convs for the decode
     bool obj_valid = false;                // ... and whether the last forward filled all of it
     int cand_clean = 0;                    // how many candidate counters, from the first, are known to be zero (the last detect's NMS returned them): no memset launch in front of a decode of at most that batch
     int side_chains = 0;                   // number of branch tails (Kernel.side ids 1..side_chains)
-    std::vector<hipStream_t> branch;       // one stream per part for the branch tails, created at first use ...
-    std::vector<hipEvent_t> e_bfork, e_bjoin;      // ... with fork events (4 per part) and one join event per part
     std::vector<signed char> side_ok;      // per batch: may the branch tails run beside the main chain (-1 unknown; no split-K launch in the pass)
     float obj_min_logit = -__builtin_inff();      // inside yolo_net_detect: objectness logit below which a row can never be a candidate (ConvParams.obj_min)
-    std::vector<hipStream_t> side;         // multi-stream forward (YOLO_STREAMS=N): internal streams + fork/join events
-    hipEvent_t e_fork = nullptr;
-    std::vector<hipEvent_t> e_join;
+    yolo::StreamPool streams;
     int arenas = 1;                        // activation arenas (2: one per half batch)
     // streams = 0 picked two parts by rule: every arena is then planned for the FULL batch, so that the same net can also run one pass
     // on one stream, and `parts` (1 or 2) says what a forward does -- the rule's answer until yolo_net_tune_streams has timed both
@@ -503,6 +524,19 @@ bool mx_eligible(const yolo_net *net, const Kernel &k);
 int pack_weights(const yolo_net *net, const float *host, size_t n, std::vector<unsigned char> &blob, std::string &err);
 std::string describe(const yolo_net *net);
 void set_error(const std::string &s);
+const char *get_error();
+inline int fail(int code, const std::string &msg) {
+    set_error(msg);
+    return code;
+}
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) {                                                                \
+            yolo::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                \
+            return YOLO_ERR_HIP;                                                               \
+        }                                                                                      \
+    } while (0)
 
 // ---- conv dispatch (conv_dispatch.cpp) ------------------------------------------------------
 // images one part of a full batch holds (what every launch of a forward pass sees at most)
@@ -530,4 +564,30 @@ bool conv_tile_valid(const yolo_net *net, const Kernel &k, int tile);
 size_t splitk_slab_bytes(const yolo_net *net);          // per arena, tickets included
 bool pass_splits_k(const yolo_net *net, int batch);     // any conv launch of a forward pass at this batch splits K
 void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out);
+// what the yolo_kernel_info reports (conv_kernel_info, aux_kernel_info) are written with
+inline double view_elems(const View &v) { return (double)v.H * v.W * v.C; }
+inline double view_esz(const yolo_net *net, const View &v) { return v.f32 ? 4.0 : (double)net->esize; }
+inline const char *dtype_tag(const yolo_net *net) { return net->opt.dtype == YOLO_DTYPE_F16 ? "f16" : "f32"; }
+inline void set_symbol(yolo_kernel_info *out, const std::string &sym) { snprintf(out->symbol, sizeof out->symbol, "%s", sym.c_str()); }
+
+// ---- forward engine (forward.cpp) -----------------------------------------------------------
+// The network input of one call: the caller's float32 tensor, or (ABI 7: the *_u8 entries) its uint8 one.  Only the five kernels that
+// read the input look at the tag (K_PREP, K_FIRST, the stem); a byte u is to them float32(u / 255.) (u8_unit).
+struct NetIn {
+    const void *ptr;
+    bool u8;
+    NetIn at(size_t elems) const { return NetIn{static_cast<const unsigned char *>(ptr) + elems * (u8 ? 1 : 4), u8}; }
+};
+// Every entry below expects a checked call (api.cpp: check_ready) and leaves its message in set_error.  (Hidden: what moved out of
+// api.cpp's anonymous namespace adds nothing to the symbols the library exports.)
+#pragma GCC visibility push(hidden)
+int run_forward(yolo_net *net, NetIn in_dev, int batch, float *out_dev, hipStream_t s);
+int run_forward_timed(yolo_net *net, NetIn in_dev, int batch, float *out_dev, hipStream_t s, float *ms_host);   // ms_host[kernel]
+int tune_streams(yolo_net *net, NetIn in_dev, int batch, hipStream_t s, const char *who);
+int autotune_tiles(yolo_net *net, NetIn in_dev, int batch, hipStream_t s);
+bool all_heads_write_objectness(yolo_net *net, NetIn in_dev, float *out_dev, int batch);   // every head conv fills the compact objectness array at this batch
+int zero_pair_counters(yolo_net *net);
+void destroy_streams(yolo_net *net);
+void aux_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out);              // yolo_net_kernel_info of every kind but K_CONV
+#pragma GCC visibility pop
 }  // namespace yolo

@@ -489,7 +489,7 @@ def test_back_to_back_1x1_fusion(case, monkeypatch):
                                          ("fp32", (24, 13, 13, 128, 512)), ("fp32", (24, 19, 19, 128, 256))])
 def test_in_launch_pair_split_k(dtype, shape):
     """The K split INSIDE one launch (conv_tap.hip: two half-K workgroups per tile hand their accumulators over through write-through
-    slabs and a ticket, the second arriver sums and runs the fused epilogue; api.cpp: pick_conv) at op level: 13 x 13 and 19 x 19
+    slabs and a ticket, the second arriver sums and runs the fused epilogue; conv_dispatch.cpp: resolve_conv) at op level: 13 x 13 and 19 x 19
     maps at the batch that gives 64-128 tiles of 128 x 256 (fp16) or 129-256 tiles of 128 x 128 (float32: the only tile whose
     float32 pair instantiation exists).  Asserted: the pair kernel is what runs; the result against the oracle (with a residual, so
     the fused epilogue of the second arriver is the full one); bit-identical results on a second and third launch of the same engine
