@@ -32,6 +32,10 @@
  *   yolo_eval_reset, yolo_eval_add, yolo_eval_finish (+ yolo_eval_state_bytes, yolo_eval_result_bytes, yolo_eval_state_layout)
  *                           no reference call site: the reference parses annotations (net/base.py:69-97) but never scores a detector;
  *                           VOC average precision with the IoU of net/base.py:180-192
+ *   yolo_v2_loss            net/v2.py:123-198 create_loss_fn (the loss graph, forward only) over net/v2.py:242-295 _make_ground_truths
+ *   yolo_net_loss, yolo_net_loss_u8
+ *                           net/yolo.py:177-193: sess.run(loss, ...) of one validation batch, forward pass included
+ *   yolo_loss_reduce        net/yolo.py:185-187: the sums behind `val_total / val_count`, over the per-image records of a whole set
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -52,7 +56,9 @@ extern "C" {
                                           yolo_preprocess_frames_u8, yolo_boxes_to_frames, yolo_net_detect_frames_u8;
                                           added WITHIN ABI 7 in the same way (new exports and the yolo_gt / yolo_eval_* PODs and enums only) -- the evaluation
                                           entries yolo_eval_state_bytes, yolo_eval_result_bytes, yolo_eval_state_layout, yolo_eval_reset, yolo_eval_add,
-                                          yolo_eval_finish */
+                                          yolo_eval_finish;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_loss_* PODs and enum only) -- the YOLOv2 loss entries
+                                          yolo_v2_loss, yolo_net_loss, yolo_net_loss_u8, yolo_loss_reduce */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -449,6 +455,94 @@ int yolo_eval_add(const yolo_eval_desc *desc, void *state_dev, const yolo_box *b
 /* Once per dataset: sorts the records, scans TP / FP per class, computes both APs per class and the means into result_dev
  * (yolo_eval_result_bytes).  Enqueued; the state stays valid and further yolo_eval_add calls may follow.  Replaces nothing. */
 int yolo_eval_finish(const yolo_eval_desc *desc, void *state_dev, void *result_dev, void *stream);
+
+/* ---- YOLOv2 loss on the device, forward only (added within ABI 7: new exports, new PODs, nothing existing changed) ------------------
+ * The number net/yolo.py:177-193 prints as `validation loss`: net/v2.py:123-198 create_loss_fn over the truth tensors of
+ * net/v2.py:242-295 _make_ground_truths.  No gradient.  YOLOv2 heads only (the reference binds no loss to YoloV3, net/yolo.py:208-211).
+ *
+ * Inputs.     logits float32 [B][h][w][A][5 + C], the v2 layout of yolo_net_forward; a yolo_head_desc with version == 2, n_scales == 1 and
+ *             anchors (aw, ah) in grid units; truths yolo_gt [B][max_gt] with int32 counts [B], centre / size normalised float32 -- to
+ *             the frame, which under the reference's stretch resize (net/base.py:121) is also the network input.  `difficult` is ignored:
+ *             the reference's parser does not read it (net/base.py:69-97).
+ * Truth to grid (net/v2.py:252-257), in float64: bx = double(x) * w, by = double(y) * h, bw = double(w_) * w, bh = double(h_) * h,
+ *             cx = floor(bx), cy = floor(by).  Skipped, with a bit in the status word: a truth whose cx or cy lies outside the grid
+ *             (YOLO_LOSS_OUT_OF_GRID; x == 1.0 too, where the reference would index out of range; a NaN centre too), one whose w_ or h_
+ *             is negative or NaN (YOLO_LOSS_BAD_BOX), one whose class_idx is outside [0, C) (YOLO_LOSS_BAD_CLASS).  A count outside
+ *             [0, max_gt] is clamped (YOLO_LOSS_BAD_COUNT).
+ * Assignment (net/v2.py:261-289).  Per grid cell, over its truths in list order and the anchors in index order: the float64 IoU of
+ *             net/base.py:180-192 of the box (w / 2, h / 2, bw, bh) against (w / 2, h / 2, aw, ah), every operation rounded on its own
+ *             (the arithmetic of the evaluation's IoU, one function for both: union floored at 1e-8, no FMA contraction).  The winner is
+ *             the FIRST (truth, anchor) pair that reaches the cell's largest IoU: the reference replaces on strict `best_iou < iou`
+ *             starting from -1, so a zero-size truth takes anchor 0 and a NaN never wins (a cell all of whose IoUs are NaN has no winner;
+ *             the reference would fail there).  One winner per cell: its anchor slot holds gt = float32(bx, by, bw, bh) and the truth's
+ *             class; mask_ij = 1 for that slot, mask_i = 1 for the cell.
+ * Terms (net/v2.py:128-188), float32 operations (the graph is float32, the anchors are rounded to float32), each rounded on its own:
+ *             px = sigmoid(t0) + c, py = sigmoid(t1) + r, pw = exp(t2) * aw, ph = exp(t3) * ah, po = sigmoid(t4), with the sigmoid and
+ *             exp of the decode (1 / (1 + expf(-t)), expf); iou = the float32 IoU of net/v2.py:157-173 of gt against (px, py, pw, ph),
+ *             no floor on the union.
+ *               winner slot:      xy = (gx - px)^2 + (gy - py)^2;  wh = (sqrt gw - sqrt pw)^2 + (sqrt gh - sqrt ph)^2;  obj = (iou - po)^2
+ *               every other slot: noobj = po^2
+ *               class:            softmax cross-entropy of t[5:], log(sum_k exp(t_k - m)) - (t_label - m) with m = max_k t_k.
+ *                                 REFERENCE BEHAVIOUR, reproduced as it is: it applies to ALL A anchor slots of a cell with mask_i = 1
+ *                                 (mask_i broadcasts over the anchors, v2.py:185-186) -- label = the winner's class on the winner slot and
+ *                                 0 on the others (the argmax of an all-zero one-hot, v2.py:155);
+ *                                 REFERENCE BEHAVIOUR, reproduced as it is: the class sum is NOT divided by the batch (v2.py:185).
+ * Totals.     loss_xy = S xy / B, loss_wh = S wh / B, loss_obj = 5 * S obj / B, loss_noobj = S noobj / B, loss_class = S class,
+ *             loss = loss_xy + loss_wh + loss_obj + loss_noobj + loss_class (added in this order).
+ * Two DELIBERATE DIFFERENCES from the reference:
+ *   (a) cell offsets.  The reference's offset tensor (v2.py:128-134) is (k % h, k / h) at k = r * w + c, which is (c, r) only on a
+ *       square grid.  Here the offsets are (c, r) on every grid.
+ *   (b) masked-out slots.  Their terms are never formed, so an infinite pw on a slot that is not a winner does not turn a sum into NaN
+ *       as 0 * inf does in TensorFlow.  The two agree whenever every exp is finite.
+ * Sums.       Every float32 term is widened to float64 and added in a FIXED order: a thread's own slots in index order, the lane tree
+ *             inside a wave, the waves in index order through LDS, the images in index order.  No floating-point atomics: two calls on
+ *             the same input return the same bits. */
+enum yolo_loss_status {
+    YOLO_LOSS_OUT_OF_GRID = 1,  /* a truth whose cell lies outside the grid: skipped                */
+    YOLO_LOSS_BAD_BOX = 2,      /* a truth with a negative or NaN size: skipped                     */
+    YOLO_LOSS_BAD_CLASS = 4,    /* a truth with class_idx outside [0, n_classes): skipped           */
+    YOLO_LOSS_BAD_COUNT = 8     /* a count below 0 or above max_gt: clamped                         */
+};
+
+#define YOLO_LOSS_MAX_CELLS 4096            /* h * w of the head (the winner table lives in LDS) */
+
+/* one image: the float64 sums of its terms, before weights and 1 / B (56 bytes) */
+typedef struct yolo_loss_image {
+    double xy, wh, obj, noobj, cls;
+    int32_t n_assigned;     /* cells with a winner                  */
+    int32_t n_truths;       /* truths that were not skipped         */
+    int32_t status;         /* enum yolo_loss_status bits           */
+    int32_t pad_;
+} yolo_loss_image;
+
+typedef struct yolo_loss_result {
+    double loss, loss_xy, loss_wh, loss_obj, loss_noobj, loss_class;
+    int32_t n_assigned, n_truths;   /* sums over the records added (a repeated record counts twice) */
+    int32_t status;                 /* OR of the records' bits                                      */
+    int32_t pad_;
+} yolo_loss_result;
+
+/* The standalone entry, as yolo_decode_nms is for the decode: logits already on the device.  images_dev [batch] receives the per-image
+ * records, result_dev the totals; assign_dev, if not NULL, int32 [batch][h][w], receives the winner of every cell as
+ * truth_index * 8 + anchor, or -1.  Two kernels (one workgroup per image; one workgroup that adds the records in image order), enqueued
+ * on `stream` with no host synchronisation.  YOLO_ERR_ARG for a null pointer, batch < 1, max_gt outside 1..YOLO_EVAL_MAX_GT, a head
+ * that is not version 2 / single-scale, or h * w > YOLO_LOSS_MAX_CELLS. */
+int yolo_v2_loss(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                 int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream);
+/* One enqueue for a validation batch: a DENSE forward pass into the workspace logits (yolo_net_detect leaves rows below its threshold
+ * unwritten, so its logits cannot be reused), then the kernels of yolo_v2_loss on them with the head of yolo_net_set_head: bit-identical
+ * to yolo_net_forward[_u8] followed by yolo_v2_loss.  Checks and messages as yolo_net_forward plus those of yolo_v2_loss; a net whose
+ * head was never set is told so first (YOLO_ERR_STATE, "head geometry not set"), before the head's version is looked at. */
+int yolo_net_loss(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                  yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream);
+int yolo_net_loss_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                     yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream);
+/* The second kernel alone, over records collected from many calls (a validation set): adds images_dev[0 .. n_images) in index order,
+ * then images_dev[0 .. n_repeat) once more (net/v2.py:215-217 pads the last batch with the first annotations of the set), and applies
+ * the weights with B = batch_size.  The reference's `validation loss` (net/yolo.py:185-187) is each of the six values divided by the
+ * number of batches, (n_images + n_repeat) / batch_size.  0 <= n_repeat <= n_images, n_images and batch_size >= 1.  Enqueued. */
+int yolo_loss_reduce(const yolo_loss_image *images_dev, int n_images, int n_repeat, int batch_size, yolo_loss_result *result_dev,
+                     void *stream);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

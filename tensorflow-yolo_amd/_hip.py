@@ -21,6 +21,8 @@ RESIZE_MODES = {"stretch": RESIZE_STRETCH, "letterbox": RESIZE_LETTERBOX}
 EVAL_FP, EVAL_TP, EVAL_IGNORED = 0, 1, 2        # enum yolo_eval_verdict
 EVAL_OVERFLOW, EVAL_UNSORTED, EVAL_BAD_CLASS, EVAL_BAD_COUNT = 1, 2, 4, 8       # enum yolo_eval_status
 EVAL_MAX_GT, EVAL_MAX_DET_CAPACITY, EVAL_MAX_CLASSES = 1024, 1 << 20, 65536
+LOSS_OUT_OF_GRID, LOSS_BAD_BOX, LOSS_BAD_CLASS, LOSS_BAD_COUNT = 1, 2, 4, 8     # enum yolo_loss_status
+LOSS_MAX_CELLS = 4096
 FRAMES_PER_LAUNCH = 64                          # frames one launch of the batched resize covers (larger batches: consecutive launches)
 MAX_SRC, MAX_ANCHORS, MAX_SCALES = 4, 8, 4
 # Records per image every Python entry point asks for unless told otherwise.  The reference's lists are unbounded
@@ -85,6 +87,17 @@ class EvalResultHeader(C.Structure):
 class EvalLayout(C.Structure):
     _fields_ = [("status_offset", C.c_uint64), ("n_gt_offset", C.c_uint64), ("records_offset", C.c_uint64), ("sorted_offset", C.c_uint64),
                 ("ctp_offset", C.c_uint64), ("cfp_offset", C.c_uint64), ("total_bytes", C.c_uint64)]
+
+
+class LossImage(C.Structure):
+    """yolo_loss_image: one image's float64 sums of the loss terms, before weights and 1 / B"""
+    _fields_ = [("xy", C.c_double), ("wh", C.c_double), ("obj", C.c_double), ("noobj", C.c_double), ("cls", C.c_double),
+                ("n_assigned", C.c_int32), ("n_truths", C.c_int32), ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
+class LossResult(C.Structure):
+    _fields_ = [("loss", C.c_double), ("loss_xy", C.c_double), ("loss_wh", C.c_double), ("loss_obj", C.c_double), ("loss_noobj", C.c_double),
+                ("loss_class", C.c_double), ("n_assigned", C.c_int32), ("n_truths", C.c_int32), ("status", C.c_int32), ("pad_", C.c_int32)]
 
 
 class WsRegion(C.Structure):
@@ -157,6 +170,14 @@ SIGNATURES = {
     "yolo_eval_add": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_int64, C.c_void_p]),
     "yolo_eval_finish": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    # YOLOv2 loss, forward only (added within ABI 7)
+    "yolo_v2_loss": (C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "yolo_net_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    "yolo_net_loss_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "yolo_loss_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "yolo_nms_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int,
                                 C.c_void_p, C.POINTER(C.c_int32)]),
 }

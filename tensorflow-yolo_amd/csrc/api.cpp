@@ -1,5 +1,5 @@
 // C ABI of libyolo_hip.so (declared in include/yolo_hip.h): argument and state checks, then one call into the planner (plan.cpp), the
-// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame and the evaluation entries live here whole.  No exceptions cross the boundary.
+// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame, the evaluation and the loss entries live here whole.  No exceptions cross the boundary.
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -628,6 +628,82 @@ int yolo_eval_finish(const yolo_eval_desc *desc, void *state_dev, void *result_d
     p.n2 = L.n2; p.n_classes = desc->n_classes; p.det_capacity = desc->det_capacity;
     p.result = static_cast<yolo_eval_result *>(result_dev);
     HIP_TRY(launch_eval_finish(p, static_cast<hipStream_t>(stream)));
+    return YOLO_OK;
+}
+
+// ---- YOLOv2 loss (yolo_hip.h: added within ABI 7; kernels in loss.hip) -----------------------------------------------------------------
+// every check here is made on the host, before any device call
+static int check_loss_args(const yolo_head_desc *head, const void *gt_dev, const void *gt_counts_dev, int max_gt, const void *images_dev,
+                           const void *result_dev, const char *who) {
+    if (!head || !gt_dev || !gt_counts_dev || !images_dev || !result_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (max_gt < 1 || max_gt > YOLO_EVAL_MAX_GT) return fail(YOLO_ERR_ARG, std::string(who) + ": max_gt must be 1.." + std::to_string(YOLO_EVAL_MAX_GT));
+    if (head->version != 2 || head->n_scales != 1)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 2 with one scale (the reference has a loss for YOLOv2 only)");
+    std::string err;
+    int rc = check_head(head, 0, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    if ((long long)head->h[0] * head->w[0] > YOLO_LOSS_MAX_CELLS)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": h * w must be at most " + std::to_string(YOLO_LOSS_MAX_CELLS));
+    return YOLO_OK;
+}
+
+static int run_loss(const yolo_head_desc &h, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+                    yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, hipStream_t s) {
+    LossParams p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.gt = gt; p.gt_counts = gt_counts; p.max_gt = max_gt;
+    p.h = h.h[0]; p.w = h.w[0]; p.na = h.n_anchors[0]; p.n_classes = h.n_classes;
+    for (int a = 0; a < p.na; ++a) {
+        p.aw[a] = h.anchors[0][2 * a]; p.ah[a] = h.anchors[0][2 * a + 1];
+        p.awf[a] = (float)p.aw[a]; p.ahf[a] = (float)p.ah[a];
+    }
+    p.images = images; p.assign = assign;
+    HIP_TRY(launch_loss_images(p, batch, s));
+    HIP_TRY(launch_loss_finish(LossFinishParams{images, batch, 0, batch, result}, s));
+    return YOLO_OK;
+}
+
+int yolo_v2_loss(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                 int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream) {
+    if (!logits_dev) return fail(YOLO_ERR_ARG, "yolo_v2_loss: null argument");
+    int rc = check_loss_args(head, gt_dev, gt_counts_dev, max_gt, images_dev, result_dev, "yolo_v2_loss");
+    if (rc) return rc;
+    if (batch < 1) return fail(YOLO_ERR_ARG, "yolo_v2_loss: batch must be at least 1");
+    return run_loss(*head, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, static_cast<hipStream_t>(stream));
+}
+
+static int net_loss_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                        yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream, const char *who) {
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    std::string err;        // whether a head was set at all comes before what kind of head it is
+    int rc = check_head(&net->head, net->out_count, err);
+    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
+    rc = check_loss_args(&net->head, gt_dev, gt_counts_dev, max_gt, images_dev, result_dev, who);
+    if (rc) return rc;
+    if (batch < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": batch must be at least 1");
+    rc = check_ready(net, in_dev.ptr, batch, who);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // a DENSE pass into the workspace logits (obj_min_logit is -inf outside detect_any: every row is written)
+    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
+    rc = run_forward(net, in_dev, batch, logits, s);
+    if (rc) return rc;
+    return run_loss(net->head, logits, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, s);
+}
+int yolo_net_loss(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                  yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream) {
+    return net_loss_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, stream, "yolo_net_loss");
+}
+int yolo_net_loss_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                     yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream) {
+    return net_loss_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, stream, "yolo_net_loss_u8");
+}
+
+int yolo_loss_reduce(const yolo_loss_image *images_dev, int n_images, int n_repeat, int batch_size, yolo_loss_result *result_dev, void *stream) {
+    if (!images_dev || !result_dev) return fail(YOLO_ERR_ARG, "yolo_loss_reduce: null argument");
+    if (n_images < 1 || batch_size < 1) return fail(YOLO_ERR_ARG, "yolo_loss_reduce: n_images and batch_size must be at least 1");
+    if (n_repeat < 0 || n_repeat > n_images) return fail(YOLO_ERR_ARG, "yolo_loss_reduce: n_repeat must be 0..n_images");
+    HIP_TRY(launch_loss_finish(LossFinishParams{images_dev, n_images, n_repeat, batch_size, result_dev}, static_cast<hipStream_t>(stream)));
     return YOLO_OK;
 }
 

@@ -12,10 +12,9 @@
 #include <atomic>
 
 #include "yolo_internal.h"
+#include "head_math.h"       // sigmoid_f32
 
 namespace yolo {
-
-__device__ __forceinline__ float sigmoid_f32(float x) { return 1.f / (1.f + expf(-x)); }   // base.py:171-172
 
 __global__ void __launch_bounds__(256) decode_kernel(const DecodeParams p) {
     const int width = 5 + p.n_classes;

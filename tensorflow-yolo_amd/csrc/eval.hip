@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "yolo_internal.h"
+#include "head_math.h"       // np_max, np_min, eval_iou
 
 namespace yolo {
 
@@ -28,24 +29,6 @@ EvalLayout eval_layout(int n_classes, int det_capacity) {
 __device__ __forceinline__ unsigned eval_orderable(float f) {   // monotone float -> uint (detect.hip: orderable)
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// np.maximum / np.minimum: a NaN operand is the result (fmax / fmin would drop it)
-__device__ __forceinline__ double np_max(double a, double b) { return (a >= b || a != a) ? a : b; }
-__device__ __forceinline__ double np_min(double a, double b) { return (a <= b || a != a) ? a : b; }
-
-// net/base.py:180-192 with float64 operands, every operation rounded on its own as NumPy rounds it.  w1 * h1 and w2 * h2 are exact
-// (float32-valued factors), but iw and ih are float64 differences and iw * ih is rounded in general: an FMA that took the unrounded
-// product into the union would change its low bits (boxes at a frame edge, centre << extent).  So no contraction in this function.
-__device__ __forceinline__ double eval_iou(double x1, double y1, double w1, double h1, double x2, double y2, double w2, double h2) {
-#pragma clang fp contract(off)
-    const double ax1 = x1 - w1 / 2., ay1 = y1 - h1 / 2., ax2 = x1 + w1 / 2., ay2 = y1 + h1 / 2.;      // base.py:267-272
-    const double bx1 = x2 - w2 / 2., by1 = y2 - h2 / 2., bx2 = x2 + w2 / 2., by2 = y2 + h2 / 2.;
-    const double iw = np_max(np_min(ax2, bx2) - np_max(ax1, bx1), 0.);
-    const double ih = np_max(np_min(ay2, by2) - np_max(ay1, by1), 0.);
-    const double inter = iw * ih;
-    const double uni = np_max(w1 * h1 + w2 * h2 - inter, 1e-8);                                       // base.py:190
-    return inter / uni;
 }
 
 // One workgroup per image.  The truths live in LDS; the list is walked in chunks of 256 ranks, in rank order:

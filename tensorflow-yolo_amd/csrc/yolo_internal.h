@@ -372,6 +372,25 @@ struct EvalFinishParams {
 hipError_t launch_eval_match(const EvalMatchParams &p, int batch, hipStream_t s);
 hipError_t launch_eval_finish(const EvalFinishParams &p, hipStream_t s);
 
+// ---- YOLOv2 loss (loss.hip) ---------------------------------------------------------------------------------------------------
+struct LossParams {
+    const float *logits;       // [B][h][w][A][5 + C]
+    const yolo_gt *gt;         // [B][max_gt]
+    const int *gt_counts;
+    int max_gt, h, w, na, n_classes;
+    double aw[YOLO_MAX_ANCHORS], ah[YOLO_MAX_ANCHORS];     // grid units, float64: the assignment (net/v2.py:270-272)
+    float awf[YOLO_MAX_ANCHORS], ahf[YOLO_MAX_ANCHORS];    // ... rounded to float32: the terms (net/v2.py:136,140)
+    yolo_loss_image *images;   // [B]
+    int *assign;               // [B][h][w] or null
+};
+struct LossFinishParams {
+    const yolo_loss_image *images;
+    int n, n_repeat, batch_size;
+    yolo_loss_result *result;
+};
+hipError_t launch_loss_images(const LossParams &p, int batch, hipStream_t s);
+hipError_t launch_loss_finish(const LossFinishParams &p, hipStream_t s);
+
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);
 // conv_dma.hip: 8-wave LDS-DMA kernel for the heavy fp16 layers; conv_tap.hip: 3x3 with tap reuse.  What a tile id is: conv_tiles.h.

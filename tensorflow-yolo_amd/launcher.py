@@ -7,7 +7,8 @@ resolved against the .ini's directory, `anchors` / `class_names` parsed as Pytho
 network picked by COMMON.version.  `test` runs on this backend, and `eval` (not in the reference): VOC-style mAP of the
 network on an annotated directory, from an [EVAL] section laid over [TEST] (eval_params); `train` and `anchor` end with a
 clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up),
-`resize` (stretch, the reference's geometry and the default | letterbox, Darknet's: aspect ratio kept, grey canvas, boxes mapped back to the frame);
+`resize` (stretch, the reference's geometry and the default | letterbox, Darknet's: aspect ratio kept, grey canvas, boxes mapped back to the frame),
+`loss` ([EVAL] only; true: also report the reference's validation loss, net/yolo.py:177-193 -- YOLOv2, resize = stretch);
 version additionally accepts `v2-tiny`, `v3-tiny` and `v3-spp`.  `--section` selects another TEST-like section (the
 reference's yolo_2.ini keeps its COCO settings in [TEST_COCO], which no mode reaches there).
 """
@@ -58,6 +59,15 @@ def test_options(params):
     return {"resize": _hip.resize_mode(params.get("resize", "stretch"))}
 
 
+def eval_options(params):
+    """test_options plus the optional [EVAL] key `loss` (true | false: also report the reference's validation loss; YOLOv2 and
+    resize = stretch only), checked before a network is built.  Returns them parsed; anything else raises ValueError."""
+    from .net import evaluate
+    out = test_options(params)
+    out["loss"] = evaluate.loss_option(params, params.get("version", ""))
+    return out
+
+
 EVAL_DEFAULTS = {"threshold": "0.005", "max_boxes": "1024", "match_iou": "0.5"}
 
 
@@ -91,7 +101,7 @@ def run(cfg, mode, section=None):
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:      # (Yolo.evaluate itself is not sharded: every caller scores the whole set)
             raise SystemExit("mode 'eval' runs in one process: sharded evaluation needs a merge of the records, which is not built")
         params = eval_params(cfg, section)
-        test_options(params)
+        eval_options(params)
         yolo.evaluate(params)
     elif mode in ("train", "anchor"):
         raise SystemExit("mode '{}' is not supported by the HIP inference backend (TEST mode only)".format(mode))

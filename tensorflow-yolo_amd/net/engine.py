@@ -193,6 +193,12 @@ class HipNetwork(Plan):
             raise ValueError("batch %d outside 1..%d (max_batch)" % (x.shape[0], self.max_batch))
         return x
 
+    def is_u8(self, x_batch):
+        """a torch tensor of torch.uint8 or a NumPy array of np.uint8 (what decides between an entry point and its uint8 twin)"""
+        if isinstance(x_batch, self.torch.Tensor):
+            return x_batch.dtype == self.torch.uint8
+        return getattr(x_batch, "dtype", None) == np.uint8
+
     def check_u8(self, x_batch):
         """Shape / dtype rule of the uint8 entry points (no GPU needed): a uint8 NumPy array or torch tensor [B,H,W,C] of the net's input
         shape with 1 <= B <= max_batch; anything else raises ValueError (a float array is NOT scaled or cast here: use forward / detect)."""
@@ -375,7 +381,76 @@ class HipNetwork(Plan):
                                                           self._status.data_ptr(), self._stream()), "yolo_net_detect_frames_u8")
         self.u8_calls += 1
         self._frames_keep = keep        # (the frames stay allocated until the next call: the work is only enqueued)
+        self._frames_last = x           # (the batch this step resized: what loss_frames runs on)
         return self._boxes[:n], self._counts[:n], self._status[:n]
+
+    # -- YOLOv2 loss, forward only (yolo_net_loss / yolo_net_loss_u8) ------------------------------------------------------------------
+    def _loss_gts(self, gts, b):
+        """gts -> (gt_dev uint8 [b, max_gt * 24], counts_dev int32 [b], max_gt): a list per image of (x, y, w, h, class_idx[, difficult]),
+        the pair of evaluate.pack_gts, or the device tensors of Evaluator.upload_gts (their [lo:hi] slices)"""
+        from . import evaluate as yeval
+        torch = self.torch
+        if isinstance(gts, tuple) and isinstance(gts[0], torch.Tensor):
+            gt_dev, gc_dev = gts
+            isz = yeval.GT_DTYPE.itemsize
+            if (gt_dev.device != self.device or gc_dev.device != self.device or gt_dev.dtype != torch.uint8 or gc_dev.dtype != torch.int32
+                    or gt_dev.dim() != 2 or gt_dev.shape[0] != b or gt_dev.shape[1] % isz or gt_dev.shape[1] == 0 or tuple(gc_dev.shape) != (b,)
+                    or not gt_dev.is_contiguous() or not gc_dev.is_contiguous()):
+                raise ValueError("expected the [%d] slice of upload_gts" % b)
+            return gt_dev, gc_dev, gt_dev.shape[1] // isz
+        if isinstance(gts, tuple):
+            arr, gcounts = gts
+        else:
+            arr, gcounts = yeval.pack_gts(gts, max(1, max([len(g) for g in gts] or [1])))
+        if arr.ndim != 2 or arr.shape[0] != b or arr.dtype != yeval.GT_DTYPE or len(gcounts) != b:
+            raise ValueError("expected truths [%d, max_gt] of GT_DTYPE with %d counts" % (b, b))
+        raw = np.ascontiguousarray(arr).view(np.uint8).reshape(b, -1)
+        return (torch.from_numpy(raw).to(self.device), torch.from_numpy(np.ascontiguousarray(gcounts, dtype=np.int32)).to(self.device),
+                arr.shape[1])
+
+    def _loss_any(self, x, gts, u8, images, assign):
+        from . import evaluate as yeval
+        torch = self.torch
+        if getattr(self, "head", None) is None or self.head.version != 2:
+            raise ValueError("the loss is defined for YOLOv2 heads only (the reference has a loss for YOLOv2 only)")
+        x = self.to_device_u8(x) if u8 else self.to_device(x)
+        self._tune_streams(x)
+        b = x.shape[0]
+        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
+        if images is None:
+            images = torch.empty((b, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        elif (images.device != self.device or images.dtype != torch.uint8 or tuple(images.shape) != (b, yeval.LOSS_IMAGE_DTYPE.itemsize)
+              or not images.is_contiguous()):
+            raise ValueError("images: expected a contiguous uint8 device tensor [%d, %d]" % (b, yeval.LOSS_IMAGE_DTYPE.itemsize))
+        result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        if assign is True:
+            assign = torch.empty((b, self.head.h[0], self.head.w[0]), dtype=torch.int32, device=self.device)
+        name = "yolo_net_loss_u8" if u8 else "yolo_net_loss"
+        with torch.cuda.device(self.device):
+            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt), images.data_ptr(),
+                                               assign.data_ptr() if assign is not None else None, result.data_ptr(), self._stream()), name)
+        self.u8_calls += int(u8)
+        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
+        return (images, result) if assign is None else (images, result, assign)
+
+    def loss(self, x, gts, images=None, assign=None):
+        """The YOLOv2 loss of a batch against its truths (include/yolo_hip.h has the definition): a dense forward pass and the loss kernels
+        in one enqueue, no host sync.  Returns device tensors (images uint8 [B, 56] = yolo_loss_image records, result uint8 [64] =
+        yolo_loss_result; evaluate.loss_to_host reads them); `images`: a slice of a caller's record tensor to write into; assign = True
+        adds the winner table int32 [B, h, w] (truth_index * 8 + anchor | -1)."""
+        return self._loss_any(x, gts, False, images, assign)
+
+    def loss_u8(self, x, gts, images=None, assign=None):
+        """loss() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as loss(float32(x / 255.))"""
+        return self._loss_any(x, gts, True, images, assign)
+
+    def loss_frames(self, gts, images=None):
+        """loss_u8() on the uint8 batch the last detect_frames call resized, enqueued behind it on the same stream: the loss of the frames
+        that step detected on, without resizing them again.  Stretch only: letterboxed truths are not mapped into the canvas."""
+        x = getattr(self, "_frames_last", None)
+        if x is None:
+            raise RuntimeError("loss_frames follows a detect_frames call")
+        return self.loss_u8(x, gts, images=images)
 
     def forward_timed_u8(self, x, out=None):
         """forward_timed() for a uint8 batch: the input kernel's entry is the time of its uint8 twin."""

@@ -18,6 +18,13 @@ RECORD_DTYPE = np.dtype([("best_iou", "f8"), ("prob", "f4"), ("class_idx", "i4")
 CLASS_DTYPE = np.dtype([("ap_voc12", "f8"), ("ap_voc07", "f8"), ("n_gt", "i4"), ("n_det", "i4"), ("tp", "i4"), ("fp", "i4"),
                         ("ignored", "i4"), ("pad_", "i4")])
 HEADER_DTYPE = np.dtype([("map_voc12", "f8"), ("map_voc07", "f8"), ("n_records", "i4"), ("status", "i4"), ("n_classes", "i4"), ("pad_", "i4")])
+LOSS_IMAGE_DTYPE = np.dtype([("xy", "f8"), ("wh", "f8"), ("obj", "f8"), ("noobj", "f8"), ("cls", "f8"), ("n_assigned", "i4"), ("n_truths", "i4"),
+                             ("status", "i4"), ("pad_", "i4")])
+LOSS_RESULT_DTYPE = np.dtype([("loss", "f8"), ("loss_xy", "f8"), ("loss_wh", "f8"), ("loss_obj", "f8"), ("loss_noobj", "f8"), ("loss_class", "f8"),
+                              ("n_assigned", "i4"), ("n_truths", "i4"), ("status", "i4"), ("pad_", "i4")])
+LOSS_KEYS = ("loss", "loss_xy", "loss_wh", "loss_obj", "loss_noobj", "loss_class")
+LOSS_STATUS_NAMES = ((_hip.LOSS_OUT_OF_GRID, "out_of_grid"), (_hip.LOSS_BAD_BOX, "bad_box"), (_hip.LOSS_BAD_CLASS, "bad_class"),
+                     (_hip.LOSS_BAD_COUNT, "bad_count"))
 DEFAULT_MAX_GT = 256
 STATUS_NAMES = ((_hip.EVAL_OVERFLOW, "overflow"), (_hip.EVAL_UNSORTED, "unsorted"), (_hip.EVAL_BAD_CLASS, "bad_class"),
                 (_hip.EVAL_BAD_COUNT, "bad_count"))
@@ -182,6 +189,65 @@ class Evaluator(object):
         n = int(header["n_records"])
         return EvalResult(header, classes, self._part(self.layout.sorted_offset, RECORD_DTYPE, n),
                           self._part(self.layout.ctp_offset, np.uint32, n), self._part(self.layout.cfp_offset, np.uint32, n))
+
+
+def loss_option(params, version):
+    """The optional [EVAL] key `loss` (true | false, default false): also report the reference's validation loss.  Checked before a
+    network is built: it needs a YOLOv2 head (the reference binds no loss to v3) and the stretch resize (under letterbox the truths
+    would have to be mapped into the canvas, which is not built); anything else raises ValueError."""
+    raw = str(params.get("loss", "false")).strip().lower()
+    if raw not in ("true", "false"):
+        raise ValueError("loss must be true or false, got %r" % (params.get("loss"),))
+    if raw == "false":
+        return False
+    if not str(version).startswith("v2"):
+        raise ValueError("loss = true needs a YOLOv2 network (version v2 or v2-tiny), got %s: the reference has a loss for YOLOv2 only" % version)
+    if _hip.resize_mode(params.get("resize", "stretch")) != _hip.RESIZE_STRETCH:
+        raise ValueError("loss = true needs resize = stretch: letterboxed truths are not built")
+    return True
+
+
+def loss_batches(n_images, batch_size):
+    """How the reference's make_batch (net/v2.py:209-217) groups a set of n_images annotations: (bs, n_batches, pad) -- the batch shrinks
+    to the set if the set is smaller, and the last batch is filled with the first `pad` annotations of the set."""
+    n, bs = int(n_images), int(batch_size)
+    if n < 1 or bs < 1:
+        raise ValueError("n_images and batch_size must be at least 1")
+    bs = min(bs, n)
+    nb = -(-n // bs)
+    return bs, nb, nb * bs - n
+
+
+def validation_loss(partials, batch_size):
+    """The reference's `validation loss` (net/yolo.py:177-193) from the per-image partials (LOSS_IMAGE_DTYPE array, one record per
+    annotated image in set order): the mean over the batches of make_batch of the batch loss.  With (bs, nb, pad) = loss_batches and
+    S_t = sum of term t over ALL records in index order, then over the first `pad` records once more,
+
+        loss_xy = S_xy / bs / nb     loss_wh = S_wh / bs / nb     loss_obj = 5 S_obj / bs / nb     loss_noobj = S_noobj / bs / nb
+        loss_class = S_cls / nb      validation_loss = (loss_xy + loss_wh + loss_obj + loss_noobj + loss_class as of one batch) / nb
+
+    Four terms are divided by the batch and the class term is not, in every batch alike, so the result does not depend on how the
+    images are grouped: make_batch's shuffle needs no counterpart.  The host mirror of yolo_loss_reduce followed by the division by nb
+    (Yolo.evaluate runs that on the device).  Returns a dict of the six LOSS_KEYS."""
+    bs, nb, pad = loss_batches(len(partials), batch_size)
+    s = {k: 0.0 for k in ("xy", "wh", "obj", "noobj", "cls")}
+    for rec in list(partials) + list(partials[:pad]):
+        for k in s:
+            s[k] += float(rec[k])
+    one = {"loss_xy": s["xy"] / bs, "loss_wh": s["wh"] / bs, "loss_obj": 5. * s["obj"] / bs, "loss_noobj": s["noobj"] / bs, "loss_class": s["cls"]}
+    one["loss"] = one["loss_xy"] + one["loss_wh"] + one["loss_obj"] + one["loss_noobj"] + one["loss_class"]
+    return {k: one[k] / nb for k in LOSS_KEYS}
+
+
+def loss_to_host(images, result):
+    """the device tensors of HipNetwork.loss* -> dict: the six totals, n_assigned, n_truths, status, status_names, and `images`, the
+    per-image partials as a LOSS_IMAGE_DTYPE array (synchronises)"""
+    rec = result.cpu().numpy().view(LOSS_RESULT_DTYPE)[0]
+    out = {k: float(rec[k]) for k in LOSS_KEYS}
+    out.update(n_assigned=int(rec["n_assigned"]), n_truths=int(rec["n_truths"]), status=int(rec["status"]),
+               status_names=[name for bit, name in LOSS_STATUS_NAMES if int(rec["status"]) & bit],
+               images=images.cpu().numpy().reshape(-1).view(LOSS_IMAGE_DTYPE).copy())
+    return out
 
 
 def parse_voc_annotations(annotation_dir, image_dir, class_names):

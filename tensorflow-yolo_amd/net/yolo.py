@@ -153,6 +153,20 @@ class Yolo(object):
         """forward() for a uint8 batch (0..255): the same array as forward(float32(x_batch_u8 / 255.))."""
         return self.net.engine.forward_u8(x_batch_u8).cpu().numpy()
 
+    def loss(self, x_batch, truths):
+        """The YOLOv2 loss of one batch, forward only (net/v2.py:123-198 create_loss_fn over net/v2.py:242-295; include/yolo_hip.h has
+        the definition): a dense forward pass and the loss kernels in one enqueue.  x_batch: [B,H,W,C] float in [0,1], or uint8 0..255;
+        truths: a list per image of (x, y, w, h, class_idx) normalised to the image, the pair of evaluate.pack_gts, or the device
+        tensors of Evaluator.upload_gts.  Returns a dict: loss, loss_xy, loss_wh, loss_obj, loss_noobj, loss_class, n_assigned, n_truths,
+        status, status_names and `images`, the per-image partial sums.  The create_loss_fn / make_batch stubs above stay: a TensorFlow
+        graph and its placeholders cannot be mirrored."""
+        from . import evaluate as yeval
+        eng = self.net.engine
+        if not eng.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
+        images, result = (eng.loss_u8 if eng.is_u8(x_batch) else eng.loss)(x_batch, truths)
+        return yeval.loss_to_host(images, result)
+
     # ---- TEST mode --------------------------------------------------------------------------------
     def test(self, params):
         image_dir = params["image_dir"]
@@ -266,7 +280,13 @@ class Yolo(object):
         usual settings of a mAP run.  Frames go through the predict_frames step (`resize` = stretch | letterbox), so boxes and truths
         are both normalised to the frame; the records never leave the device.  Prints one line per class with truths and the two
         means, writes `eval.json` under `out_dir`, returns the EvalResult.  A candidate overflow (detect status 1) raises, as in
-        test(); truncated lists (status 2) are counted and reported as `images_truncated`."""
+        test(); truncated lists (status 2) are counted and reported as `images_truncated`.
+
+        `loss = true` (optional, default off; YOLOv2 and resize = stretch only): every step also enqueues the loss (HipNetwork.loss_frames) on
+        the batch tensor the step resized, against the step's slice of the truths; the per-image partials stay on the device, are added
+        there once at the end (yolo_loss_reduce) and read once.  The report gains `validation_loss` -- the reference's number
+        (net/yolo.py:177-193): the mean over make_batch's batches, the last one padded with the first annotations of the set
+        (evaluate.validation_loss has the formula) -- and its five components; one more console line."""
         import json
         from . import evaluate as yeval
         annotation_dir, image_dir = params["annotation_dir"], params["image_dir"]
@@ -280,6 +300,7 @@ class Yolo(object):
         input_shape = (int(params["input_h"]), int(params["input_w"]), int(params["input_c"]))
         nms_mode = {"agnostic": _hip.NMS_AGNOSTIC, "per_class": _hip.NMS_PER_CLASS}[params.get("nms_mode", "agnostic")]
         resize = _hip.resize_mode(params.get("resize", "stretch"))
+        want_loss = yeval.loss_option(params, self.version)
         annotations, skipped = yeval.parse_voc_annotations(annotation_dir, image_dir, class_names)
         if not annotations:
             print("No annotations found in {}".format(annotation_dir))
@@ -297,6 +318,8 @@ class Yolo(object):
                              device=eng.device)
         overflow = eng.torch.zeros(1, dtype=eng.torch.int32, device=eng.device)
         gt_dev, gt_counts = ev.upload_gts([t for _, t in annotations])     # the truths of the whole set: packed and copied once
+        if want_loss:
+            loss_images = eng.torch.empty((len(annotations), yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=eng.torch.uint8, device=eng.device)
         for start in range(0, len(annotations), batch_size):
             chunk = annotations[start:start + batch_size]
             frames = base.decode_frames([p for p, _ in chunk])
@@ -304,6 +327,8 @@ class Yolo(object):
             # same stream, no copy of the records to the host, nothing read from the host
             ev.add(boxes, counts, (gt_dev[start:start + len(chunk)], gt_counts[start:start + len(chunk)]), status)
             overflow |= (status & 1).max()
+            if want_loss:       # a dense pass on the batch tensor detect_frames resized; the partials go to this step's slice
+                eng.loss_frames((gt_dev[start:start + len(chunk)], gt_counts[start:start + len(chunk)]), images=loss_images[start:start + len(chunk)])
         if int(overflow.item()):
             raise _hip.YoloHipError("candidate capacity exceeded during evaluation: raise cand_capacity or the threshold")
         result = ev.finish()
@@ -312,6 +337,18 @@ class Yolo(object):
                       threshold=threshold, iou_threshold=iou_threshold, resize=str(params.get("resize", "stretch")))
         for line in eval_lines(report):
             print(line)
+        if want_loss:
+            bs, nb, pad = yeval.loss_batches(len(annotations), batch_size)
+            total = eng.torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=eng.torch.uint8, device=eng.device)
+            with eng.torch.cuda.device(eng.device):
+                _hip.check(eng.lib.yolo_loss_reduce(loss_images.data_ptr(), len(annotations), pad, bs, total.data_ptr(), eng._stream()),
+                           "yolo_loss_reduce")
+            rec = total.cpu().numpy().view(yeval.LOSS_RESULT_DTYPE)[0]          # the one read
+            self.last_loss = {k: float(rec[k]) / nb for k in yeval.LOSS_KEYS}
+            report["validation_loss"] = self.last_loss["loss"]
+            report.update({k: self.last_loss[k] for k in yeval.LOSS_KEYS[1:]})
+            report.update(loss_batches=nb, loss_batch_size=bs, loss_status=[name for bit, name in yeval.LOSS_STATUS_NAMES if int(rec["status"]) & bit])
+            print("validation loss: {}".format(report["validation_loss"]))
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "eval.json"), "w") as f:
             json.dump(report, f, indent=1)
