@@ -36,6 +36,7 @@
  *   yolo_net_loss, yolo_net_loss_u8
  *                           net/yolo.py:177-193: sess.run(loss, ...) of one validation batch, forward pass included
  *   yolo_loss_reduce        net/yolo.py:185-187: the sums behind `val_total / val_count`, over the per-image records of a whole set
+ *   yolo_v2_loss_grad       tf.gradients of net/v2.py:188 with respect to net[-1].out, as AdamOptimizer.minimize (net/v2.py:205) takes it
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -58,7 +59,8 @@ extern "C" {
                                           entries yolo_eval_state_bytes, yolo_eval_result_bytes, yolo_eval_state_layout, yolo_eval_reset, yolo_eval_add,
                                           yolo_eval_finish;
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_loss_* PODs and enum only) -- the YOLOv2 loss entries
-                                          yolo_v2_loss, yolo_net_loss, yolo_net_loss_u8, yolo_loss_reduce */
+                                          yolo_v2_loss, yolo_net_loss, yolo_net_loss_u8, yolo_loss_reduce;
+                                          added WITHIN ABI 7 in the same way (one new export) -- the loss gradient yolo_v2_loss_grad */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -456,9 +458,9 @@ int yolo_eval_add(const yolo_eval_desc *desc, void *state_dev, const yolo_box *b
  * (yolo_eval_result_bytes).  Enqueued; the state stays valid and further yolo_eval_add calls may follow.  Replaces nothing. */
 int yolo_eval_finish(const yolo_eval_desc *desc, void *state_dev, void *result_dev, void *stream);
 
-/* ---- YOLOv2 loss on the device, forward only (added within ABI 7: new exports, new PODs, nothing existing changed) ------------------
+/* ---- YOLOv2 loss on the device (added within ABI 7: new exports, new PODs, nothing existing changed) ------------------
  * The number net/yolo.py:177-193 prints as `validation loss`: net/v2.py:123-198 create_loss_fn over the truth tensors of
- * net/v2.py:242-295 _make_ground_truths.  No gradient.  YOLOv2 heads only (the reference binds no loss to YoloV3, net/yolo.py:208-211).
+ * net/v2.py:242-295 _make_ground_truths.  Its gradient: yolo_v2_loss_grad below.  YOLOv2 heads only (the reference binds no loss to YoloV3, net/yolo.py:208-211).
  *
  * Inputs.     logits float32 [B][h][w][A][5 + C], the v2 layout of yolo_net_forward; a yolo_head_desc with version == 2, n_scales == 1 and
  *             anchors (aw, ah) in grid units; truths yolo_gt [B][max_gt] with int32 counts [B], centre / size normalised float32 -- to
@@ -543,6 +545,48 @@ int yolo_net_loss_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo
  * number of batches, (n_images + n_repeat) / batch_size.  0 <= n_repeat <= n_images, n_images and batch_size >= 1.  Enqueued. */
 int yolo_loss_reduce(const yolo_loss_image *images_dev, int n_images, int n_repeat, int batch_size, yolo_loss_result *result_dev,
                      void *stream);
+
+/* ---- The gradient of the YOLOv2 loss with respect to the logits (added within ABI 7: one new export, nothing existing changed) ------
+ * G = d loss / d logits, `loss` being the total of yolo_v2_loss above for the same call: the same truths to grid, skipped truths and
+ * status bits, the same assignment, the same two reference behaviours and two deliberate differences.  Replaces tf.gradients of
+ * net/v2.py:188 with respect to net[-1].out, as AdamOptimizer.minimize (net/v2.py:205) takes it; everything behind it (the backward pass
+ * of a backbone, an optimizer) is not here.  G is float32 [B][h][w][A][5 + C] like the logits; EVERY element is written by every call,
+ * zeros included.  Weights: lxy = lwh = lnoobj = 1 / B, lobj = 5 / B, lcls = 1 (the class term is not divided by the batch, v2.py:185;
+ * its gradient is not either).
+ *   slot that is not a winner:  G[0..3] = +0 exactly -- the terms of a masked-out slot are never formed (difference (b)), so an infinite
+ *                      exp there gives 0, not NaN;  G[4] = lnoobj * 2 po * po (1 - po), po = sigmoid(t4).
+ *   class rows:        every anchor slot of a cell WITH a winner (the reference's mask_i broadcast): G[5 + k] = softmax(t[5:])_k -
+ *                      [k == label], label = the winner's class on the winner slot and 0 on the others, softmax as
+ *                      exp(t_k - m) / sum_j exp(t_j - m), m = max_j t_j.  A cell without a winner: G[5:] = +0 exactly.
+ *   winner slot:       in the notation of the terms above, sx = sigmoid(t0), px = sx + c, pw = exp(t2) * aw, gx .. gh the float32 truth,
+ *                      iou = I(px, py, pw, ph), e = iou - po, k = lobj * 2 e:
+ *                        dL/dpx = lxy * 2 (px - gx) + k * dI/dpx                    G[0] = dL/dpx * sx (1 - sx)      (G[1] likewise with y)
+ *                        dL/dpw = lwh * (sqrt pw - sqrt gw) / sqrt pw + k * dI/dpw  G[2] = dL/dpw * pw               (G[3] likewise with h)
+ *                        G[4] = -k * po (1 - po)
+ *                      REFERENCE BEHAVIOUR, reproduced as it is: the gradient DOES flow through the IoU into x, y, w, h.  The reference
+ *                      multiplies iou_score into gt_obj without a stop_gradient (v2.py:173-176), so its Adam step sees that path.
+ *                      Darknet treats the IoU of its objectness target as a constant.
+ *   IoU partials:      I = inter / uni, inter = iw * ih, uni = pw * ph + gw * gh - inter, rw = min(px2, gx2) - max(px1, gx1),
+ *                      iw = max(rw, 0):
+ *                        diw/dpx = [rw >= 0] ([px2 <= gx2] - [px1 >= gx1])          diw/dpw = [rw >= 0] ([px2 <= gx2] + [px1 >= gx1]) / 2
+ *                        dI/dv = (dinter/dv * (uni + inter) - inter * d(pw ph)/dv) / uni^2, dinter/dpx = ih * diw/dpx,
+ *                        dinter/dpw = ih * diw/dpw, d(pw ph)/dpw = ph, d(pw ph)/dpx = 0; y / h alike.
+ *   ties:              the brackets are TensorFlow's rules, fixed here as part of the definition: maximum(x, y) gives its gradient to x
+ *                      when x >= y, minimum(x, y) to x when x <= y, maximum(rw, 0) passes it when rw >= 0 (torch splits a tie in half).
+ *                      A prediction that equals its truth therefore has dI/dpw = 1 / gw and dI/dpx = 0.
+ * Arithmetic.   float32, element by element, with the sigmoid and expf of the decode and of the loss.  Nothing here is bit-exact against
+ *               anything: an element is a product of several rounded factors.  The tests hold each group of elements (xy, wh, obj, class)
+ *               of a call within 4 x the float32-against-float64 gap of a sequential restatement plus one float32 ulp.  Where float32
+ *               arithmetic is not finite (an overflowing exp on a winner slot) the element is not finite; no other slot is affected.
+ *
+ * Runs the two kernels of yolo_v2_loss exactly as yolo_v2_loss does -- images_dev and result_dev receive the same bytes -- then the
+ * gradient kernel (a wave per grid cell, grid = chunks of cells x images), all enqueued on `stream` with no host synchronisation.
+ * assign_dev is REQUIRED here: the gradient kernel reads the winner table from it; caller-owned like every other buffer.  grad_dev:
+ * batch * h * w * A * (5 + C) floats that do not overlap logits_dev.  Checks and messages as yolo_v2_loss, plus YOLO_ERR_ARG for a NULL
+ * assign_dev or grad_dev and for grad_dev == logits_dev. */
+int yolo_v2_loss_grad(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                      int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, float *grad_dev,
+                      void *stream);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

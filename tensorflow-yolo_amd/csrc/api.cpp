@@ -672,6 +672,25 @@ int yolo_v2_loss(const yolo_head_desc *head, const float *logits_dev, int batch,
     return run_loss(*head, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, static_cast<hipStream_t>(stream));
 }
 
+int yolo_v2_loss_grad(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                      int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, float *grad_dev, void *stream) {
+    if (!logits_dev || !assign_dev || !grad_dev) return fail(YOLO_ERR_ARG, "yolo_v2_loss_grad: null argument");
+    int rc = check_loss_args(head, gt_dev, gt_counts_dev, max_gt, images_dev, result_dev, "yolo_v2_loss_grad");
+    if (rc) return rc;
+    if (batch < 1) return fail(YOLO_ERR_ARG, "yolo_v2_loss_grad: batch must be at least 1");
+    if (grad_dev == logits_dev) return fail(YOLO_ERR_ARG, "yolo_v2_loss_grad: grad_dev must not be logits_dev (the gradient is not computed in place)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = run_loss(*head, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, s);
+    if (rc) return rc;
+    LossGradParams p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits_dev; p.gt = gt_dev; p.assign = assign_dev; p.grad = grad_dev; p.batch = batch; p.max_gt = max_gt;
+    p.h = head->h[0]; p.w = head->w[0]; p.na = head->n_anchors[0]; p.n_classes = head->n_classes;
+    for (int a = 0; a < p.na; ++a) { p.awf[a] = (float)head->anchors[0][2 * a]; p.ahf[a] = (float)head->anchors[0][2 * a + 1]; }
+    HIP_TRY(launch_loss_grad(p, s));
+    return YOLO_OK;
+}
+
 static int net_loss_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
                         yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream, const char *who) {
     if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");

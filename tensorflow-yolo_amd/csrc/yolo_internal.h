@@ -388,8 +388,17 @@ struct LossFinishParams {
     int n, n_repeat, batch_size;
     yolo_loss_result *result;
 };
+struct LossGradParams {
+    const float *logits;       // [B][h][w][A][5 + C]
+    const yolo_gt *gt;         // [B][max_gt]
+    const int *assign;         // [B][h][w]: truth * 8 + anchor | -1, as loss_image_kernel wrote it
+    float *grad;               // [B][h][w][A][5 + C], every element written
+    int batch, max_gt, h, w, na, n_classes;
+    float awf[YOLO_MAX_ANCHORS], ahf[YOLO_MAX_ANCHORS];
+};
 hipError_t launch_loss_images(const LossParams &p, int batch, hipStream_t s);
 hipError_t launch_loss_finish(const LossFinishParams &p, hipStream_t s);
+hipError_t launch_loss_grad(const LossGradParams &p, hipStream_t s);
 
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);

@@ -386,27 +386,7 @@ class HipNetwork(Plan):
 
     # -- YOLOv2 loss, forward only (yolo_net_loss / yolo_net_loss_u8) ------------------------------------------------------------------
     def _loss_gts(self, gts, b):
-        """gts -> (gt_dev uint8 [b, max_gt * 24], counts_dev int32 [b], max_gt): a list per image of (x, y, w, h, class_idx[, difficult]),
-        the pair of evaluate.pack_gts, or the device tensors of Evaluator.upload_gts (their [lo:hi] slices)"""
-        from . import evaluate as yeval
-        torch = self.torch
-        if isinstance(gts, tuple) and isinstance(gts[0], torch.Tensor):
-            gt_dev, gc_dev = gts
-            isz = yeval.GT_DTYPE.itemsize
-            if (gt_dev.device != self.device or gc_dev.device != self.device or gt_dev.dtype != torch.uint8 or gc_dev.dtype != torch.int32
-                    or gt_dev.dim() != 2 or gt_dev.shape[0] != b or gt_dev.shape[1] % isz or gt_dev.shape[1] == 0 or tuple(gc_dev.shape) != (b,)
-                    or not gt_dev.is_contiguous() or not gc_dev.is_contiguous()):
-                raise ValueError("expected the [%d] slice of upload_gts" % b)
-            return gt_dev, gc_dev, gt_dev.shape[1] // isz
-        if isinstance(gts, tuple):
-            arr, gcounts = gts
-        else:
-            arr, gcounts = yeval.pack_gts(gts, max(1, max([len(g) for g in gts] or [1])))
-        if arr.ndim != 2 or arr.shape[0] != b or arr.dtype != yeval.GT_DTYPE or len(gcounts) != b:
-            raise ValueError("expected truths [%d, max_gt] of GT_DTYPE with %d counts" % (b, b))
-        raw = np.ascontiguousarray(arr).view(np.uint8).reshape(b, -1)
-        return (torch.from_numpy(raw).to(self.device), torch.from_numpy(np.ascontiguousarray(gcounts, dtype=np.int32)).to(self.device),
-                arr.shape[1])
+        return loss_gts(self.torch, self.device, gts, b)
 
     def _loss_any(self, x, gts, u8, images, assign):
         from . import evaluate as yeval
@@ -451,6 +431,26 @@ class HipNetwork(Plan):
         if x is None:
             raise RuntimeError("loss_frames follows a detect_frames call")
         return self.loss_u8(x, gts, images=images)
+
+    # -- the gradient of the YOLOv2 loss with respect to the logits (yolo_v2_loss_grad) ---------------------------------------------------
+    def _loss_grad_any(self, x, gts, u8):
+        if getattr(self, "head", None) is None or self.head.version != 2:
+            raise ValueError("the loss is defined for YOLOv2 heads only (the reference has a loss for YOLOv2 only)")
+        logits = (self.forward_u8 if u8 else self.forward)(x)
+        images, result, assign, grad, keep = v2_loss_grad(self.head, logits, gts)
+        self._loss_keep = (logits,) + keep         # (alive until the next call: the work is only enqueued)
+        return images, result, assign, grad
+
+    def loss_grad(self, x, gts):
+        """The YOLOv2 loss of a batch and its gradient with respect to the head logits (include/yolo_hip.h has the definition): a dense
+        forward pass into an output tensor, then the loss kernels and the gradient kernel on it, on the same stream, no host sync.
+        Returns device tensors (images, result as loss(); assign int32 [B, h, w]; grad float32 [B, h, w, A * (5 + C)]).  There is no
+        backward pass through the network: the gradient stops at the logits."""
+        return self._loss_grad_any(x, gts, False)
+
+    def loss_grad_u8(self, x, gts):
+        """loss_grad() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as loss_grad(float32(x / 255.))"""
+        return self._loss_grad_any(x, gts, True)
 
     def forward_timed_u8(self, x, out=None):
         """forward_timed() for a uint8 batch: the input kernel's entry is the time of its uint8 twin."""
@@ -499,6 +499,49 @@ class HipNetwork(Plan):
         host = np.empty((batch, h, w, c), dtype=np.float32)
         _hip.check(self.lib.yolo_net_read_layer(self.handle, index, batch, host.ctypes.data, host.size), "yolo_net_read_layer")
         return host
+
+
+def loss_gts(torch, device, gts, b):
+    """gts -> (gt_dev uint8 [b, max_gt * 24], counts_dev int32 [b], max_gt): a list per image of (x, y, w, h, class_idx[, difficult]),
+    the pair of evaluate.pack_gts, or the device tensors of Evaluator.upload_gts (their [lo:hi] slices)"""
+    from . import evaluate as yeval
+    if isinstance(gts, tuple) and isinstance(gts[0], torch.Tensor):
+        gt_dev, gc_dev = gts
+        isz = yeval.GT_DTYPE.itemsize
+        if (gt_dev.device != device or gc_dev.device != device or gt_dev.dtype != torch.uint8 or gc_dev.dtype != torch.int32
+                or gt_dev.dim() != 2 or gt_dev.shape[0] != b or gt_dev.shape[1] % isz or gt_dev.shape[1] == 0 or tuple(gc_dev.shape) != (b,)
+                or not gt_dev.is_contiguous() or not gc_dev.is_contiguous()):
+            raise ValueError("expected the [%d] slice of upload_gts" % b)
+        return gt_dev, gc_dev, gt_dev.shape[1] // isz
+    if isinstance(gts, tuple):
+        arr, gcounts = gts
+    else:
+        arr, gcounts = yeval.pack_gts(gts, max(1, max([len(g) for g in gts] or [1])))
+    if arr.ndim != 2 or arr.shape[0] != b or arr.dtype != yeval.GT_DTYPE or len(gcounts) != b:
+        raise ValueError("expected truths [%d, max_gt] of GT_DTYPE with %d counts" % (b, b))
+    raw = np.ascontiguousarray(arr).view(np.uint8).reshape(b, -1)
+    return (torch.from_numpy(raw).to(device), torch.from_numpy(np.ascontiguousarray(gcounts, dtype=np.int32)).to(device),
+            arr.shape[1])
+
+
+def v2_loss_grad(head, logits, gts):
+    """yolo_v2_loss_grad on float32 device logits [B, ...] (contiguous, B * h * w * A * (5 + C) values) with a version 2 head: the loss
+    kernels and the gradient kernel in one enqueue on the current stream, no host sync.  gts as HipNetwork.loss takes them.  Returns device
+    tensors (images uint8 [B, 56], result uint8 [64], assign int32 [B, h, w], grad float32 of the logits' shape) and the pair of uploaded
+    truths, which the caller keeps alive with the logits until the work has run."""
+    from . import evaluate as yeval
+    torch = _torch()
+    dev, b = logits.device, logits.shape[0]
+    gt_dev, gc_dev, max_gt = loss_gts(torch, dev, gts, b)
+    images = torch.empty((b, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    assign = torch.empty((b, head.h[0], head.w[0]), dtype=torch.int32, device=dev)
+    grad = torch.empty_like(logits)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.lib().yolo_v2_loss_grad(C.byref(head), logits.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt),
+                                                images.data_ptr(), assign.data_ptr(), result.data_ptr(), grad.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream), "yolo_v2_loss_grad")
+    return images, result, assign, grad, (gt_dev, gc_dev)
 
 
 def check_status(status, allow_truncation=False):

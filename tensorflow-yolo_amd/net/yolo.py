@@ -2,7 +2,9 @@
 and the factored-out per-batch body `predict(x_batch)`.
 
 Counterpart of the reference's net/yolo.py (TEST path :41-96; binding classes :198-211).
-Training (`train`, `generate_anchors`, loss, batches) is out of scope: those entries raise.
+Training (`train`, `generate_anchors`, `create_loss_fn`, batches) is out of scope: those entries raise.  The loss itself and its
+gradient with respect to the head logits exist (`Yolo.loss`, `Yolo.loss_grad`, net/lossfn.py); a backward pass through the network and
+an optimizer do not.
 """
 import os
 
@@ -166,6 +168,20 @@ class Yolo(object):
             raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
         images, result = (eng.loss_u8 if eng.is_u8(x_batch) else eng.loss)(x_batch, truths)
         return yeval.loss_to_host(images, result)
+
+    def loss_grad(self, x_batch, truths):
+        """loss() and the gradient of that loss with respect to the head logits (tf.gradients of net/v2.py:188 with respect to
+        net[-1].out; include/yolo_hip.h has the definition): a dense forward pass, the loss kernels and the gradient kernel on one
+        stream.  Arguments as loss().  Returns loss()'s dict plus `grad`, a float32 DEVICE tensor [B, h, w, A * (5 + C)].  The gradient
+        stops at the logits: there is no backward pass through the network here."""
+        from . import evaluate as yeval
+        eng = self.net.engine
+        if not eng.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
+        images, result, _, grad = (eng.loss_grad_u8 if eng.is_u8(x_batch) else eng.loss_grad)(x_batch, truths)
+        out = yeval.loss_to_host(images, result)
+        out["grad"] = grad
+        return out
 
     # ---- TEST mode --------------------------------------------------------------------------------
     def test(self, params):
