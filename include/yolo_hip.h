@@ -60,7 +60,8 @@ extern "C" {
                                           yolo_eval_finish;
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_loss_* PODs and enum only) -- the YOLOv2 loss entries
                                           yolo_v2_loss, yolo_net_loss, yolo_net_loss_u8, yolo_loss_reduce;
-                                          added WITHIN ABI 7 in the same way (one new export) -- the loss gradient yolo_v2_loss_grad */
+                                          added WITHIN ABI 7 in the same way (one new export) -- the loss gradient yolo_v2_loss_grad;
+                                          added WITHIN ABI 7 in the same way (one new export, one new POD) -- the test hook yolo_launch_caps */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -231,6 +232,18 @@ int yolo_net_tune_streams_u8(yolo_net *net, const uint8_t *in_dev, int batch, vo
 /* The conversion above for u = 0..255, computed on the host by the function the input kernels run on every byte: out256[u] = float32(u / 255.)
  * (test hook; no reference call site beyond net/base.py:153). */
 int yolo_u8_unit_table(float *out256);
+
+/* How much work one ROUND of the looping kernels holds (test hook, added within ABI 7: one new export and this POD): the persistent
+ * kernels run at most this many workgroups and each walks tiles blockIdx, blockIdx + grid, ...; the grid-stride kernels launch at most this
+ * many threads.  Work beyond a cap is what gives a workgroup its second tile (a thread its second item) -- the tests of that hand-over
+ * size their cases from these numbers, so a changed cap shows there instead of quietly turning them into one-round tests.
+ * tap_stream_workgroups: conv3x3_tap_stream_kernel, tiles of 16 x 16 positions; stem_workgroups: stem_v3_kernel on ONE part (a batch
+ * split over n streams runs cap / n per part), tiles of 8 x 16 outputs; first_mfma_workgroups: first_pool_mfma*_kernel, tiles of 8 x 16
+ * pooled outputs; aux_work_items: prep / pool / pool_same / eltwise / splitk_reduce; decode_rows: decode_kernel. */
+struct yolo_launch_caps {
+    int32_t tap_stream_workgroups, stem_workgroups, first_mfma_workgroups, aux_work_items, decode_rows;
+};
+int yolo_launch_caps(struct yolo_launch_caps *out);
 
 /* Optional: time every valid tile configuration of each heavy conv on the device (synchronous, a few
  * hundred launches) and keep the fastest per layer for later forward/detect calls at this batch. */

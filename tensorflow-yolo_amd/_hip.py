@@ -100,6 +100,12 @@ class LossResult(C.Structure):
                 ("loss_class", C.c_double), ("n_assigned", C.c_int32), ("n_truths", C.c_int32), ("status", C.c_int32), ("pad_", C.c_int32)]
 
 
+class LaunchCaps(C.Structure):
+    """yolo_launch_caps: how much work one round of the looping kernels holds"""
+    _fields_ = [("tap_stream_workgroups", C.c_int32), ("stem_workgroups", C.c_int32), ("first_mfma_workgroups", C.c_int32),
+                ("aux_work_items", C.c_int32), ("decode_rows", C.c_int32)]
+
+
 class WsRegion(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("offset", C.c_uint64), ("used_bytes", C.c_uint64), ("region_bytes", C.c_uint64)]
 
@@ -140,6 +146,7 @@ SIGNATURES = {
     "yolo_net_tune_streams_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_preprocess_resize_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "yolo_u8_unit_table": (C.c_int, [C.c_void_p]),
+    "yolo_launch_caps": (C.c_int, [C.POINTER(LaunchCaps)]),
     "yolo_net_autotune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_net_tune_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_net_set_streams": (C.c_int, [C.c_void_p, C.c_int]),
@@ -232,6 +239,13 @@ def letterbox_geometry(src_h, src_w, dst_h, dst_w, mode):
     check(lib().yolo_letterbox_geometry(int(src_h), int(src_w), int(dst_h), int(dst_w), int(mode), *[C.byref(v) for v in out]),
           "yolo_letterbox_geometry")
     return tuple(int(v.value) for v in out)
+
+
+def launch_caps():
+    """yolo_launch_caps as a dict (host only)"""
+    caps = LaunchCaps()
+    check(lib().yolo_launch_caps(C.byref(caps)), "yolo_launch_caps")
+    return {name: int(getattr(caps, name)) for name, _ in LaunchCaps._fields_}
 
 
 def check(rc, what=""):

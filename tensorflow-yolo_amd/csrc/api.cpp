@@ -732,6 +732,16 @@ int yolo_u8_unit_table(float *out256) {
     return YOLO_OK;
 }
 
+int yolo_launch_caps(struct yolo_launch_caps *out) {
+    if (!out) return fail(YOLO_ERR_ARG, "yolo_launch_caps: null argument");
+    out->tap_stream_workgroups = kTapStreamGrid;
+    out->stem_workgroups = kStemGrid;
+    out->first_mfma_workgroups = kFirstMfmaGrid;
+    out->aux_work_items = kAuxGrid * kAuxBlock;
+    out->decode_rows = kDecodeGrid * kDecodeBlock;
+    return YOLO_OK;
+}
+
 int yolo_nms_host(const double *xywh, const float *prob, const int32_t *class_idx, int n, double iou_threshold, int nms_mode,
                   int32_t *keep_idx, int32_t *n_keep) {
     if (n < 0 || !n_keep || (n && (!xywh || !prob || !class_idx || !keep_idx))) return fail(YOLO_ERR_ARG, "yolo_nms_host: null argument");

@@ -259,8 +259,8 @@ __global__ void __launch_bounds__(256) eltwise_kernel(const EltParams p) {
 }
 
 static inline unsigned grid_for(long long work) {
-    long long g = (work + 255) / 256;
-    if (g > 256 * 16) g = 256 * 16;     // 16 blocks per CU, grid-stride the rest
+    long long g = (work + kAuxBlock - 1) / kAuxBlock;
+    if (g > kAuxGrid) g = kAuxGrid;     // 16 blocks per CU, grid-stride the rest
     if (g < 1) g = 1;
     return (unsigned)g;
 }

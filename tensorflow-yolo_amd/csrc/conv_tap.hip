@@ -1066,7 +1066,8 @@ static hipError_t launch_tap_tile(ConvForm f, const ConvParams &p0, dim3 grid, h
             if constexpr (t.has(CAP_STREAM)) {
                 ConvParams p = p0;
                 p.cout_pad = (p.Cout + 127) / 128 * 128;
-                const int slots = 256 * t.per_cu();
+                constexpr int slots = kTapStreamCUs * t.per_cu();
+                static_assert(slots == kTapStreamGrid, "yolo_launch_caps reports kTapStreamGrid");
                 hipLaunchKernelGGL((conv3x3_tap_stream_kernel<t.wm, t.wn, t.tm, t.tp, t.prg, t.occ, t.mode>), dim3((unsigned)(p.n_blocks < slots ? p.n_blocks : slots)), dim3(512), 0, s, p);
                 return hipGetLastError();
             }

@@ -367,10 +367,10 @@ hipError_t launch_decode(const DecodeParams &p, int batch, hipStream_t s, bool z
         hipError_t e = hipMemsetAsync(p.cand_count, 0, sizeof(int) * (size_t)batch * kCandCountStride, s);
         if (e != hipSuccess) return e;
     }
-    long long g = (p.total_rows + 255) / 256;
-    if (g > 256 * 8) g = 256 * 8;
+    long long g = (p.total_rows + kDecodeBlock - 1) / kDecodeBlock;
+    if (g > kDecodeGrid) g = kDecodeGrid;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL(decode_kernel, dim3((unsigned)g), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(decode_kernel, dim3((unsigned)g), dim3(kDecodeBlock), 0, s, p);
     return hipGetLastError();
 }
 

@@ -478,7 +478,7 @@ hipError_t launch_first(const FirstParams &p0, int dtype, hipStream_t s, bool in
         const long long tiles = p.total / ((long long)p.H * p.W) * p.xblocks * p.tiles_y;
         if (tiles < 1 || tiles > 0x7fffffffLL || (long long)p.H * p.W * 3 > 0x7fffffffLL) return hipErrorInvalidValue;
         p.n_tiles = (int)tiles;
-        const dim3 mgrid((unsigned)(tiles < 1024 ? tiles : 1024));
+        const dim3 mgrid((unsigned)(tiles < kFirstMfmaGrid ? tiles : kFirstMfmaGrid));
         if (in_u8) {
             if (dtype == YOLO_DTYPE_F16) hipLaunchKernelGGL(first_pool_mfma_u8_kernel, mgrid, dim3(512), 0, s, p);
             else if (p.Cout == 16) hipLaunchKernelGGL(first_pool_mfma_f32_u8_kernel<1>, mgrid, dim3(512), 0, s, p);

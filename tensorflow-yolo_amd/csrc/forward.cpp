@@ -305,7 +305,7 @@ int run_forward_pass(const Ptrs &P, hipStream_t s, hipEvent_t *ev, long long *ob
         } else if (k.kind == K_CONV && k.stem == 2) {
             StemParams p;
             stem_params(net, ki, P, p);
-            e = launch_stem(p, batch, s, net->halves ? 512 / net->parts : 512, u8);
+            e = launch_stem(p, batch, s, net->halves ? kStemGrid / net->parts : kStemGrid, u8);
         } else if (k.kind == K_CONV) {
             ConvParams p;
             const int rc = conv_params(net, k, P, p);

@@ -105,6 +105,16 @@ __host__ __device__ __forceinline__ float u8_unit(unsigned u) {
 // no candidate at all).
 constexpr int kCandCountStride = 32;
 
+// Launch caps: the kernels below loop over more work than their grid holds (persistent workgroups walk tiles blockIdx, blockIdx + grid, ...;
+// grid-stride loops).  Past these counts a workgroup gets a second tile / a thread a second item -- the hand-over code of those kernels
+// runs only then, so the tests size their cases from these numbers (yolo_launch_caps; tests/test_rounds_cpu.py).
+constexpr int kTapStreamCUs = 256, kTapStreamPerCu = 2;        // conv3x3_tap_stream_kernel: ConvTile.per_cu() resident workgroups on each CU
+constexpr int kTapStreamGrid = kTapStreamCUs * kTapStreamPerCu;
+constexpr int kStemGrid = 512;                                 // stem_v3_kernel: two workgroups per CU; split over the parts of a batch on streams
+constexpr int kFirstMfmaGrid = 1024;                           // first_pool_mfma*_kernel: four workgroups per CU
+constexpr int kAuxBlock = 256, kAuxGrid = 256 * 16;            // aux.hip grid_for: 16 blocks per CU, grid-stride the rest
+constexpr int kDecodeBlock = 256, kDecodeGrid = 256 * 8;       // decode_kernel: one row per thread and round
+
 struct ConvParams {
     const void *in;            // base of the input BUFFER (view offsets are folded into byte offsets)
     const void *wgt;
@@ -437,7 +447,7 @@ hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8 = fal
 hipError_t launch_frames_resize(const FramesParams &p, int n, hipStream_t s, bool dst_u8);     // n <= kFramesPerLaunch frames
 hipError_t launch_boxes_to_frames(const RemapParams &p, int n, hipStream_t s);                 // n <= kFramesPerLaunch images
 hipError_t launch_first(const FirstParams &p, int dtype, hipStream_t s, bool in_u8 = false);
-hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = 512, bool in_u8 = false);     // stem.hip
+hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = kStemGrid, bool in_u8 = false);     // stem.hip
 hipError_t launch_pool(const PoolParams &p, int dtype, hipStream_t s);
 hipError_t launch_pool_same(const PoolParams &p, int dtype, hipStream_t s);     // stride 1, SAME, odd window PoolParams.ksize
 constexpr int kSppMaxSide = 32;         // spp_pool_kernel: the H x W plane of a chunk lives in LDS twice (2 x 16 KiB at 32 x 32)

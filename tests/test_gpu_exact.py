@@ -149,8 +149,8 @@ def g_reorg():
     return g
 
 
-def g_fallback():
-    g = new_graph(8, 8, 16)
+def g_fallback(H=8, W=8, cin=16):
+    g = new_graph(H, W, cin)
     _conv(g, g[-1], 32, 3)
     g.append(PL.max_pool2d(g[-1].out, 2, 1))
     g.append(PL.shortcut(g[1].out, g[2].out))
@@ -369,6 +369,76 @@ for _dt in ("fp16", "fp32"):
 for _sh in ((2, 19, 19, 128, 128), (1, 38, 38, 256, 256)):
     case("shortcut-last-%s" % _shape_name(_sh), ("g_probe", _sh[1:] + (3, 1, True, "leaky")), _sh[0], "fp16", expect=("fused: +shortcut",), variants=("res_last",))
 
+# ---- past the first round --------------------------------------------------------------------------------------------------------
+# The persistent kernels (conv3x3_tap_stream_kernel, stem_v3_kernel, first_pool_mfma*_kernel) launch at most a fixed number of workgroups,
+# each of which walks tiles blockIdx, blockIdx + grid, ...; the grid-stride kernels of aux.hip launch at most a fixed number of threads.
+# What happens between two tiles of one workgroup (the next tile's patch and weights requested under the current tile's last slice, the
+# epilogue's stores between the DMAs of the counted waits, the accumulators restarted from the bias copy in LDS, the register prefetch one
+# tile ahead, tile i + 1 overwriting the patches of tile i) runs only past those caps: the cases below are the smallest shapes that get
+# there.  ROUNDS says, per case, which cap of yolo_launch_caps it is about, how its work is counted from the shape and what it claims
+# ("control": exactly one round; "one-more": cap + 1, ONE workgroup gets a second tile; "three": at least three rounds; "two": more than
+# one round); tests/test_rounds_cpu.py holds every claim against the library's own caps, so a changed cap turns them red instead of
+# quietly turning these into one-round tests.  The default tile rules apply (no forced tile).
+TAP_STREAM_SYM = "conv3x3_tap_stream_kernel<1, 8, 4, 2, 27, 4, 2>"
+ROUNDS = {}       # case id -> dict(cap, tile=(rows, columns of OUTPUT positions per tile) | None, work, claim, parts)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def rounds_case(id, cap, work, claim, tile=None, parts=1, **kw):
+    ROUNDS[id] = dict(cap=cap, tile=tile, work=int(work), claim=claim, parts=parts)
+    case(id, **kw)
+
+
+# the stream tap kernel, fp16: tiles of 16 x 16 positions.  "pool" reads the fp16 store through a stride-1 pool ("res": + the fused residual,
+# where Cin = Cout); the float32 output is not a stream launch (tap_stream_ok).  The pool behind the 1089-tile case is pool_kernel<false, true>
+# on 2.2 M items as well: aux.hip's grid-stride loop in its third round (no case of its own).
+for (_B, _H, _W, _ci, _co), _bn, _claim in [
+        ((2, 256, 256, 32, 64), True, "control"),      # 512 tiles: exactly the grid, nobody gets a second tile
+        ((3, 304, 144, 32, 64), True, "one-more"),     # 513: one workgroup gets a second tile
+        ((9, 176, 176, 32, 64), True, "three"),        # 1089: three rounds, the last of 65; one slice per tile: consecutive tiles alternate patch buffers
+        ((3, 200, 210, 64, 64), True, "two"),          # 546 (= 2 mod 8: xcd_remap on a count that is no multiple of 8), two slices per tile, partial tiles both ways
+        ((3, 200, 210, 128, 48), True, "two"),         # four slices, Cout 48: lanes beyond Cout, bias from LDS
+        ((3, 200, 210, 192, 64), True, "two"),         # six slices
+        ((4, 192, 200, 32, 64), False, "two")]:        # 624, no BN, linear, bias: the other epilogue arm
+    rounds_case("rounds-tap-%s%s" % (_shape_name((_B, _H, _W, _ci, _co)), "" if _bn else "-linear"), "tap_stream_workgroups",
+                _B * _cdiv(_H, 16) * _cdiv(_W, 16), _claim, tile=(16, 16),
+                graph=("g_probe", (_H, _W, _ci, _co, 3, 1, _bn, "leaky" if _bn else "linear")), B=_B, dtype="fp16", expect=(TAP_STREAM_SYM,), ties=True, neg=_bn,
+                variants=("pool",) + (("res",) if _ci == _co else ()))
+
+# the stem, both forms: tiles of 8 x 16 outputs (16 x 32 input pixels).  The 3x3 32 -> 64 conv + shortcut behind the Darknet-53 form is a
+# stream-kernel launch at these sizes as well.
+for (_B, _H, _W), _claim in [((2, 256, 512), "control"), ((3, 144, 608), "one-more"), ((6, 224, 416), "three"), ((5, 180, 300), "two")]:
+    for _third in (32, 64):
+        rounds_case("rounds-stem-3-32-64%s-%s" % ("-32" if _third == 32 else "", _shape_name((_B, _H, _W))), "stem_workgroups",
+                    _B * _cdiv(_H, 16) * _cdiv(_W, 32), _claim, tile=(8, 16), graph=("g_stem", (_H, _W, _third)), B=_B, dtype="fp16", ties=True,
+                    expect=("conv_stem<f16,3-32-64-32>", "yolo::stem_v3_kernel(", TAP_STREAM_SYM) if _third == 32 else ("conv_stem<f16,3-32-64>", "yolo::stem_v3_kernel("),
+                    absent=() if _third == 32 else ("3-32-64-32",))
+# ... and as two parts on two streams: 546 tiles each on a grid of 256 (the cap is divided by the parts)
+rounds_case("rounds-stem-3-32-64-32-6x224x416-streams2", "stem_workgroups", 3 * _cdiv(224, 16) * _cdiv(416, 32), "three", tile=(8, 16), parts=2,
+            graph=("g_stem", (224, 416, 32)), B=6, dtype="fp16", ties=True, kw={"streams": 2, "max_batch": 6}, repeat=True,
+            expect=("conv_stem<f16,3-32-64-32>", "yolo::stem_v3_kernel("))
+
+# first layer + pool on the matrix cores: tiles of 8 x 16 POOLED outputs (16 x 32 input pixels)
+for (_B, _H, _W), _claim in [((4, 256, 512), "control"), ((5, 80, 1312), "one-more"), ((10, 240, 464), "three"), ((5, 244, 470), "two")]:
+    for _dt, _co, _sym in [("fp16", 32, "yolo::first_pool_mfma_kernel("), ("fp32", 32, "first_pool_mfma_f32_kernel<2>("), ("fp32", 16, "first_pool_mfma_f32_kernel<1>(")]:
+        rounds_case("rounds-firstpool-%s-%d-%s" % (_shape_name((_B, _H, _W)), _co, _dt), "first_mfma_workgroups", _B * _cdiv(_H, 16) * _cdiv(_W, 32), _claim,
+                    tile=(8, 16), graph=("g_first_pool", (_H, _W, _co, 32)), B=_B, dtype=_dt, ties=_dt == "fp16", expect=("conv_first_pool", _sym))
+
+# the grid-stride kernels of aux.hip past 1 048 576 work items, every layer read back.  eltwise_kernel counts elements of its input: the
+# standalone add, the reorg and the concat copies (4.5 M), the upsample of the pooled map (1 115 136: the count the case is sized by).
+# pool_kernel counts 16-byte vectors where the strides allow them: the 2/1 pool is 1 115 136 items in float32 and 557 568 in fp16, the 2/2
+# pool a quarter of that -- fp16 pools get past the cap behind the 1089-tile stream case above.  prep_kernel counts pixels: 1 076 480
+# (8 input channels: not a first-layer kernel) in front of a 1x1 conv.  (Every rounds case ends in an eltwise copy to the float32 output
+# that is past the cap as well.)
+for _dt in ("fp16", "fp32"):
+    rounds_case("rounds-fallback-kernels-2x264x264x16-%s" % _dt, "aux_work_items", 2 * 132 * 132 * 32, "two", graph=("g_fallback", (264, 264, 16)), B=2, dtype=_dt,
+                keep_all=True, expect=("eltwise<", "pool<"))
+    rounds_case("rounds-prep-5x464x464x8-%s" % _dt, "aux_work_items", 5 * 464 * 464, "two", graph=("g_probe", (464, 464, 8, 16, 1, 1, True, "leaky")), B=5, dtype=_dt,
+                keep_all=True, expect=("prep<",), ties=_dt == "fp16", variants=("pool",))
+
 RAW_CASES = CASES
 KERNELS_JSON = os.path.join(GOLDEN, "exact_kernels.json")
 
@@ -419,7 +489,7 @@ def _load_golden():
         return json.load(f)
 
 
-CASES = select_cases(RAW_CASES, _load_golden())
+CASES = select_cases(RAW_CASES, None if __name__ == "__main__" else _load_golden())      # (the record is being rewritten: new cases are not in it yet)
 IDS = [c["id"] for c in CASES]
 assert len(set(IDS)) == len(IDS)
 
@@ -497,12 +567,46 @@ def case_report(c):
 
 
 # ---- device side --------------------------------------------------------------------------------------------------------------
-def assert_equal(got, want, what):
+def _launch_position(cap, g, n_tiles):
+    """conv3x3_tap_stream_kernel walks launch positions it = blockIdx, blockIdx + grid, ... and computes tile xcd_remap(it, n_tiles)
+    (conv_common.h: the positions of one XCD, it % 8, take consecutive tiles): the position whose tile is g"""
+    if cap != "tap_stream_workgroups":
+        return g
+    q, r = n_tiles >> 3, n_tiles & 7
+    start = lambda x: x * (q + 1) if x < r else r * (q + 1) + (x - r) * q
+    x = max(v for v in range(8) if start(v) <= g)
+    return (g - start(x)) * 8 + x
+
+
+def where_in_rounds(rounds, idx, shape, batch):
+    """What whoever reads a failure of a rounds case needs first: the tile (image, tile row, tile column) of the element at idx = (n, y, x, c)
+    of a tensor of `shape`, and whether the workgroup that computed it was past its first tile -- its launch position at or above the cap (a
+    cap divided by the parts of the batch on streams; tiles counted per part).  A tensor that is not on the kernel's output grid, and the
+    grid-stride kernels: the linear element index against the cap."""
+    from tensorflow_yolo_amd import _hip
+    cap = _hip.launch_caps()[rounds["cap"]] // rounds["parts"]
+    n, y, x = (int(v) for v in idx[:3])
+    if rounds["tile"] is None:
+        lin = int(np.ravel_multi_index(tuple(int(v) for v in idx), shape))
+        return "element %d of %d: %s the cap of %d work items (%s)" % (lin, int(np.prod(shape)), "AT OR ABOVE" if lin >= cap else "below", cap, rounds["cap"])
+    th, tw = rounds["tile"]
+    tiles_y, tiles_x = _cdiv(shape[1], th), _cdiv(shape[2], tw)
+    per_part = _cdiv(batch, rounds["parts"])
+    images = min(per_part, batch - n // per_part * per_part)           # images of the part image n is in
+    g = ((n % per_part) * tiles_y + y // th) * tiles_x + x // tw
+    pos = _launch_position(rounds["cap"], g, images * tiles_y * tiles_x)
+    return "tile (image %d, tile row %d, tile column %d) = tile %d, launch position %d of its part: %s the cap of %d workgroups (%s): the %s tile of its workgroup" % (
+        n, y // th, x // tw, g, pos, "AT OR ABOVE" if pos >= cap else "below", cap, rounds["cap"], "%d." % (pos // cap + 1))
+
+
+def assert_equal(got, want, what, rounds=None, batch=None):
     assert got.shape == want.shape, (what, got.shape, want.shape)
     if np.array_equal(got, want):
         return
     bad = np.argwhere(got != want)
     rows = ["  (n, y, x, c) = %s: got %r want %r" % (tuple(int(v) for v in i), float(got[tuple(i)]), float(want[tuple(i)])) for i in bad[:12]]
+    if rounds is not None:
+        rows.insert(0, "  first difference in " + where_in_rounds(rounds, bad[0], got.shape, batch or got.shape[0]))
     raise AssertionError("%s: %d of %d elements differ\n%s" % (what, len(bad), got.size, "\n".join(rows)))
 
 
@@ -523,18 +627,19 @@ def test_exact(cid):
         if variant == "res_last":       # the case is about values an fp16 store would have changed
             assert np.any(want != X.round_f16(want)), "nothing in the reference that an fp16 rounding would change"
         what = "%s/%s %s" % (cid, variant, names)
-        assert_equal(got, want, what)
+        rounds = ROUNDS.get(cid)                    # (a rounds case: a failure names the tile and which round of its workgroup it was)
+        assert_equal(got, want, what, rounds)
         if c["keep_all"]:
             for i in range(1, len(L) - 1):          # (the last layer lives in the caller's tensor: it is `got`)
-                assert_equal(eng.read_layer(i, c["B"]), kept[i], what + " layer %d" % i)
+                assert_equal(eng.read_layer(i, c["B"]), kept[i], what + " layer %d" % i, rounds and dict(rounds, tile=None))
         if tune:
             eng.autotune(d["x"])
             assert_equal(eng.forward(d["x"]).cpu().numpy(), want, what + " after autotune")
         if c["repeat"]:
             for r in range(2):
-                assert_equal(eng.forward(d["x"]).cpu().numpy(), want, what + " launch %d" % (r + 2))
+                assert_equal(eng.forward(d["x"]).cpu().numpy(), want, what + " launch %d" % (r + 2), rounds)
             if c["B"] > 1:          # a smaller batch than max_batch: the same bits per image
-                assert_equal(eng.forward(d["x"][:c["B"] - 1]).cpu().numpy(), want[:c["B"] - 1], what + " at batch %d" % (c["B"] - 1))
+                assert_equal(eng.forward(d["x"][:c["B"] - 1]).cpu().numpy(), want[:c["B"] - 1], what + " at batch %d" % (c["B"] - 1), rounds, c["B"] - 1)
 
 
 if __name__ == "__main__":      # rewrite the recorded plans of the single-conv probes (no GPU needed)

@@ -25,17 +25,20 @@ def oracle_out(net, w, x, dtype, keep=None):
     return FR.forward(L, w, x, keep=keep, storage="fp16" if dtype == "fp16" else None)
 
 
-def check_graph(net, x, dtype, seed=0, read=(), max_batch=None, tile=None, **engine_kw):
+def check_graph(net, x, dtype, seed=0, read=(), max_batch=None, tile=None, where=None, **engine_kw):
+    """where (optional): callable(key, got, want, tolerance) -> a line for the failure message about a tensor above the tolerance"""
     w = synth.darknet_stream(net, seed=seed)
     want, kept = oracle_out(net, w, x, dtype, keep=set(read))
     got, eng = run_hip(net, w, x, dtype, keep_all=bool(read), max_batch=max_batch, force_tile=tile, **engine_kw)
     assert got.shape == want.shape, (got.shape, want.shape)
-    errs = {"final": rel_err(got, want)}
+    pairs = {"final": (got, want)}
     for i in read:
-        errs[i] = rel_err(eng.read_layer(i, x.shape[0]), kept[i])
+        pairs[i] = (eng.read_layer(i, x.shape[0]), kept[i])
+    errs = {k: rel_err(g, v) for k, (g, v) in pairs.items()}
     print(dtype, "kernels=%d" % eng.num_kernels, {k: "%.2e" % v for k, v in errs.items()})
     bad = {k: v for k, v in errs.items() if not v <= TOL[dtype]}
-    assert not bad, "relative error above %g: %s\n%s" % (TOL[dtype], bad, eng.describe())
+    notes = "".join("\n" + where(k, pairs[k][0], pairs[k][1], TOL[dtype]) for k in bad) if where else ""
+    assert not bad, "relative error above %g: %s%s\n%s" % (TOL[dtype], bad, notes, eng.describe())
     return eng
 
 
