@@ -146,3 +146,75 @@ def guarded_run(net, w, x, dtype, tile=None, keep_all=True, detect=False, guard=
             checked += b - a
     assert checked >= guard, "nothing to check"
     return eng, checked
+
+
+# ---- a poisoned workspace -----------------------------------------------------------------------------------------------------------
+# INTEGRATION.md lets a C-ABI caller bind a workspace it never zeroed; engine.HipNetwork allocates torch.zeros, so without these helpers
+# every test starts from zero bytes, where a kernel that reads what no kernel of the pass wrote gets 0 (or, later, stale FINITE data).
+#   "ones": every byte 0xFF -- NaN as fp16, float32 and float64, -1 / 4 294 967 295 as any integer;
+#   "inf":  +inf of the plan's storage type through a typed view -- 0x7C00 per 16 bits (fp16 and mxfp8 plans), 0x7F800000 per 32 bits
+#           (fp32 plans).  On an fp16 plan the float32 regions then read 2.66e36: finite, but wrong wherever it is used.
+# A NaN poisons every sum it enters and is dropped by max; +inf wins every max and turns sums into inf or NaN.
+POISONS = ("ones", "inf")
+
+
+def poison_fill(t, poison, f32_storage):
+    """fill a device tensor of bytes with a poison pattern (the whole tensor: its size is a multiple of 4)"""
+    import torch
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() % 4 == 0, (t.dtype, t.numel())
+    if poison == "ones":
+        t.fill_(0xFF)
+    elif poison == "inf":
+        if f32_storage:
+            t.view(torch.int32).fill_(0x7F800000)
+        else:
+            t.view(torch.int16).fill_(0x7C00)
+    else:
+        raise ValueError(poison)
+
+
+def poison_and_bind(eng, poison):
+    """Fill the WHOLE workspace of an engine with the poison, the record buffer detect() writes (boxes, counts, status) with 0xFF, and bind
+    the workspace again: the documented contract (bind after allocation; yolo_net_bind_workspace clears what the library counts on).
+    The fills are complete before the bind, whose clears would otherwise be overwritten."""
+    import torch
+    from tensorflow_yolo_amd import _hip
+    torch.cuda.synchronize()
+    poison_fill(eng._workspace, poison, eng.dtype == _hip.DTYPE_F32)
+    eng.records.fill_(-1)
+    torch.cuda.synchronize()
+    _hip.check(eng.lib.yolo_net_bind_workspace(eng.handle, eng._workspace.data_ptr(), eng._workspace.numel()), "yolo_net_bind_workspace")
+
+
+def poisoned_out(eng, batch):
+    """a caller's output tensor of `batch` images with every byte 0xFF (NaN): an element the pass does not write stays NaN"""
+    import torch
+    out = torch.empty((batch,) + tuple(eng.output_shape), dtype=torch.float32, device=eng.device)
+    out.view(torch.int32).fill_(-1)
+    return out
+
+
+def forward_poisoned(eng, x, poison, u8=False):
+    """poison + bind, then ONE forward of x into a poisoned output tensor -> the output on the host"""
+    poison_and_bind(eng, poison)
+    out = poisoned_out(eng, x.shape[0])
+    (eng.forward_u8 if u8 else eng.forward)(x, out=out)
+    return out.cpu().numpy()
+
+
+def run_hip_poisoned(net, weights, x, dtype, poison, before_pass=None, **engine_kw):
+    """run_hip on memory nobody zeroed: construct the engine, fill the weight buffer with 0xFF and load the weights, fill the whole workspace
+    with the poison, bind, fill the output tensor with 0xFF, forward.  before_pass(eng): called between the bind and the pass (the
+    sensitivity check of tests/test_gpu_poison.py reads every layer there).  Uses the engine's own buffers and the C ABI's bind only."""
+    import torch
+    engine_kw.setdefault("max_batch", x.shape[0])
+    eng = engine.HipNetwork(net, dtype=dtype, **engine_kw)
+    eng._weights.fill_(0xFF)
+    torch.cuda.synchronize()
+    eng.load_weights(weights)
+    poison_and_bind(eng, poison)
+    if before_pass is not None:
+        before_pass(eng)
+    out = poisoned_out(eng, x.shape[0])
+    eng.forward(x, out=out)
+    return out.cpu().numpy(), eng
