@@ -37,6 +37,11 @@
  *                           net/yolo.py:177-193: sess.run(loss, ...) of one validation batch, forward pass included
  *   yolo_loss_reduce        net/yolo.py:185-187: the sums behind `val_total / val_count`, over the per-image records of a whole set
  *   yolo_v2_loss_grad       tf.gradients of net/v2.py:188 with respect to net[-1].out, as AdamOptimizer.minimize (net/v2.py:205) takes it
+ *   yolo_conv1x1_wgrad      tf.gradients of net/v2.py:188 with respect to the last conv's kernel and bias (net/v2.py:52-56), from that gradient
+ *   yolo_adam_step          the update of tf.train.AdamOptimizer(lr).minimize(loss), net/v2.py:205, on those two variables
+ *   yolo_net_train_head_step, yolo_net_train_head_step_u8
+ *                           net/yolo.py:161-173: sess.run([optimizer, loss, ...]) of one training batch, for the detection layer alone
+ *                           (+ yolo_wgrad_plan, yolo_net_head_input, yolo_net_head_train_bytes / _layout / _init / _read: no reference call site)
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -61,7 +66,11 @@ extern "C" {
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_loss_* PODs and enum only) -- the YOLOv2 loss entries
                                           yolo_v2_loss, yolo_net_loss, yolo_net_loss_u8, yolo_loss_reduce;
                                           added WITHIN ABI 7 in the same way (one new export) -- the loss gradient yolo_v2_loss_grad;
-                                          added WITHIN ABI 7 in the same way (one new export, one new POD) -- the test hook yolo_launch_caps */
+                                          added WITHIN ABI 7 in the same way (one new export, one new POD) -- the test hook yolo_launch_caps;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_wgrad_plan, yolo_tensor_view and yolo_head_train_layout
+                                          PODs only) -- training the detection layer: yolo_wgrad_plan, yolo_conv1x1_wgrad, yolo_adam_step,
+                                          yolo_net_head_input, yolo_net_head_train_bytes, yolo_net_head_train_layout, yolo_net_head_train_init,
+                                          yolo_net_head_train_read, yolo_net_train_head_step, yolo_net_train_head_step_u8 */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -600,6 +609,96 @@ int yolo_loss_reduce(const yolo_loss_image *images_dev, int n_images, int n_repe
 int yolo_v2_loss_grad(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
                       int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, float *grad_dev,
                       void *stream);
+
+/* ---- Training the detection layer on the device (added within ABI 7: new exports, the yolo_wgrad_plan and yolo_tensor_view PODs only) ------
+ * The detection layer is the last conv of every YOLOv2 network here (net/v2.py:52-56): 1 x 1, stride 1, linear, with bias and no batch
+ * norm, so its folded weights are its raw weights.  The entries below are its backward pass with respect to kernel and bias, the update
+ * AdamOptimizer.minimize (net/v2.py:205) applies to them, and one enqueue for a whole step of net/yolo.py:161-173 on that layer.
+ * Two DELIBERATE DIFFERENCES from the reference's training:
+ *   (a) only the last conv's kernel and bias receive updates; the reference's minimize() updates every variable of the graph;
+ *   (b) the backbone's batch norms run on their stored statistics (the inference pass); the reference builds its training graph with
+ *       is_training = True, normalises with batch statistics and updates the moving averages.
+ * What a fine-tune of a pretrained, frozen backbone does.  The input gradient dX, and with it everything in front of the last conv, is
+ * not here.
+ *
+ * Weight gradient.  dW[o][c] = S_p G[p][o] * X[p][c] and db[o] = S_p G[p][o], p over the P = batch * positions_per_image positions.
+ *   G   float32 [P][cout], dense: the gradient in the logits' layout (yolo_v2_loss_grad).
+ *   X   the conv's input, a strided NHWC view: element (image n, position q, channel c) at n * image_stride + q * ld + coff + c from
+ *       x_dev, fp16 (YOLO_DTYPE_F16) or float32 (YOLO_DTYPE_F32).  cin % 8 == 0 (YOLO_ERR_ARG otherwise).
+ *   Arithmetic: X is widened to float32 (exact); products and sums on the float32-input matrix cores (v_mfma_f32_32x32x2_f32: every
+ *   product rounded once, float32 accumulators); nothing is narrowed to fp16 or bf16.  The positions are split into n_chunks chunks of
+ *   positions_per_chunk; a workgroup adds its chunk in ascending position order into a float32 slab of the caller's scratch, a second
+ *   kernel adds the slabs in chunk order.  No floating-point atomics: two calls return the same bits.  Every element of dW and db is
+ *   written by every call, and nothing depends on what scratch, dW or db held before.  Against exact arithmetic, per element,
+ *   |dW - exact| <= (P + 2) 2^-24 S_p |G[p][o]| |X[p][c]| for any split.
+ * yolo_wgrad_plan: how a call with these sizes is split (a host-side query: the sizing call for the scratch, and the hook the tests size
+ * their cases from -- a changed split shows there).  tiles_cout x tiles_cin tiles of tile_cout x tile_cin elements of dW, each walked
+ * tile_positions positions at a time; chunk k holds the positions [k * positions_per_chunk, min(P, (k + 1) * positions_per_chunk));
+ * scratch_bytes = n_chunks * cout * (cin + 1) * 4.  P is 1 .. 2^30 and cout * (cin + 1) fits 31 bits (YOLO_ERR_ARG otherwise). */
+struct yolo_wgrad_plan {
+    int32_t tile_cout, tile_cin, tile_positions;
+    int32_t tiles_cout, tiles_cin;
+    int32_t positions_per_chunk, n_chunks, pad_;
+    uint64_t scratch_bytes;
+};
+int yolo_wgrad_plan(int64_t P, int cin, int cout, int x_dtype, struct yolo_wgrad_plan *out);
+/* The standalone entry, as yolo_v2_loss is for the loss: dw_dev float32 [cout][cin], db_dev float32 [cout], scratch_dev at least
+ * yolo_wgrad_plan's scratch_bytes.  Two kernels, enqueued on `stream` with no host synchronisation.  YOLO_ERR_ARG for a null pointer, a
+ * dtype that is not F16 / F32, cin % 8 != 0, a view whose channels do not fit ld or whose images overlap, a scratch that is too small. */
+int yolo_conv1x1_wgrad(const void *x_dev, int x_dtype, int ld, int coff, int64_t image_stride, int positions_per_image, int batch, int cin,
+                       const float *g_dev, int cout, float *dw_dev, float *db_dev, void *scratch_dev, size_t scratch_bytes, void *stream);
+
+/* tf.train.AdamOptimizer's update (net/v2.py:205; its defaults: beta1 = 0.9, beta2 = 0.999, eps = 1e-8) of n_w weights and n_b biases
+ * with their moments, in place, every operation float32 and rounded on its own, IEEE division and square root:
+ *     m = beta1 * m + (1 - beta1) * g       v = beta2 * v + (1 - beta2) * (g * g)       w = w - (lr_t * m) / (sqrt(v) + eps)
+ * lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) for step t = 1, 2, ... is the caller's, computed in float64 and passed as one float32.
+ * The standalone update, without the re-pack of yolo_net_train_head_step.  n_b may be 0 (then the bias pointers are not looked at).
+ * One kernel, enqueued. */
+int yolo_adam_step(float *w, float *b, float *m_w, float *v_w, float *m_b, float *v_b, const float *dw, const float *db, int64_t n_w,
+                   int64_t n_b, float lr_t, float beta1, float beta2, float eps, void *stream);
+
+/* Where the detection layer's input lives in the bound workspace after a dense forward (yolo_net_forward*, yolo_net_loss*): element
+ * (n, q, c) at byte offset + (n * image_stride + q * ld + coff + c) * (2 for YOLO_DTYPE_F16, 4 for YOLO_DTYPE_F32) of the workspace,
+ * q = row * w + column.  Valid until the next call on the net.  YOLO_ERR_ARG unless the last kernel of the plan is a 1 x 1 / stride 1
+ * linear conv with bias that writes the logits; YOLO_ERR_STATE when the plan has fused its input away or runs the batch in several
+ * stream parts (each part has its own arena: call yolo_net_set_streams(net, 1)). */
+typedef struct yolo_tensor_view {
+    uint64_t offset;        /* bytes from the start of the workspace to element 0 of the tensor's buffer */
+    int64_t image_stride;   /* elements */
+    int32_t ld, coff;       /* elements between consecutive positions; first channel inside a position */
+    int32_t dtype;          /* YOLO_DTYPE_F16 | YOLO_DTYPE_F32 */
+    int32_t cin, h, w;
+} yolo_tensor_view;
+int yolo_net_head_input(const yolo_net *net, yolo_tensor_view *out);
+
+/* Caller-owned device state of the head training: the float32 master W [cout][cin] and b [cout], their four moment arrays, dW and db, the
+ * gradient G of a full batch, the winner table, the per-image loss records and the weight-gradient scratch, every part 256-byte aligned.
+ * yolo_net_head_train_bytes: its size, 0 with a message for a net that cannot train its head (a head that is not version 2, a last kernel
+ * that is not the 1 x 1 conv above, several stream parts).  yolo_net_head_train_init (synchronous; weights loaded first): copies
+ * head_w_host [cout][cin] -- the kernel as the Darknet stream holds it, [out][in] -- and head_b_host [cout] into the master arrays AND,
+ * packed, into the net's device weights, and zeroes the moments.  yolo_net_head_train_read: synchronous copy of the master values back
+ * (checkpoints, tests).  yolo_net_head_train_layout: where the parts are, as byte offsets into the state (like yolo_eval_state_layout). */
+typedef struct yolo_head_train_layout {
+    uint64_t w_offset, b_offset, m_w_offset, v_w_offset, m_b_offset, v_b_offset, dw_offset, db_offset;
+    uint64_t grad_offset, assign_offset, images_offset, scratch_offset, scratch_bytes, total_bytes;
+    int32_t cin, cout;
+} yolo_head_train_layout;
+int yolo_net_head_train_layout(const yolo_net *net, yolo_head_train_layout *out);
+size_t yolo_net_head_train_bytes(const yolo_net *net);
+int yolo_net_head_train_init(yolo_net *net, void *state_dev, size_t bytes, const float *head_w_host, const float *head_b_host);
+int yolo_net_head_train_read(yolo_net *net, const void *state_dev, float *w_host, float *b_host);
+/* ONE enqueue with no host synchronisation for a step of net/yolo.py:161-173 on the detection layer: a dense forward pass into the
+ * workspace logits, the kernels of yolo_v2_loss_grad on them (head of yolo_net_set_head), the weight gradient on the view of
+ * yolo_net_head_input, the Adam update of the master values -- which in the same pass writes the layer's packed form into the net's device
+ * weights: exactly the bytes yolo_net_load_weights would have produced from the master values (an MXFP8 plan keeps its head conv fp16), so
+ * the next forward runs on the updated layer with no host round trip.  result_dev receives the yolo_loss_result of the weights BEFORE the
+ * update, what the reference prints per step.  Bit-identical to yolo_net_forward[_u8] -> yolo_v2_loss_grad -> yolo_conv1x1_wgrad ->
+ * yolo_adam_step on the same buffers.  Checks and messages as yolo_net_loss plus those of yolo_net_head_train_bytes; a null state is
+ * YOLO_ERR_ARG. */
+int yolo_net_train_head_step(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                             void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+int yolo_net_train_head_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

@@ -106,6 +106,26 @@ class LaunchCaps(C.Structure):
                 ("aux_work_items", C.c_int32), ("decode_rows", C.c_int32)]
 
 
+class WgradPlan(C.Structure):
+    """yolo_wgrad_plan: how a weight-gradient call is split (tiles of dW, chunks of positions, scratch)"""
+    _fields_ = [("tile_cout", C.c_int32), ("tile_cin", C.c_int32), ("tile_positions", C.c_int32), ("tiles_cout", C.c_int32),
+                ("tiles_cin", C.c_int32), ("positions_per_chunk", C.c_int32), ("n_chunks", C.c_int32), ("pad_", C.c_int32),
+                ("scratch_bytes", C.c_uint64)]
+
+
+class TensorView(C.Structure):
+    """yolo_tensor_view: a strided NHWC tensor inside the bound workspace"""
+    _fields_ = [("offset", C.c_uint64), ("image_stride", C.c_int64), ("ld", C.c_int32), ("coff", C.c_int32), ("dtype", C.c_int32),
+                ("cin", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+class HeadTrainLayout(C.Structure):
+    """yolo_head_train_layout: byte offsets of the parts of the head-training state"""
+    _fields_ = [(n, C.c_uint64) for n in ("w_offset", "b_offset", "m_w_offset", "v_w_offset", "m_b_offset", "v_b_offset", "dw_offset",
+                                          "db_offset", "grad_offset", "assign_offset", "images_offset", "scratch_offset", "scratch_bytes",
+                                          "total_bytes")] + [("cin", C.c_int32), ("cout", C.c_int32)]
+
+
 class WsRegion(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("offset", C.c_uint64), ("used_bytes", C.c_uint64), ("region_bytes", C.c_uint64)]
 
@@ -188,6 +208,20 @@ SIGNATURES = {
     # the gradient of the YOLOv2 loss with respect to the logits (added within ABI 7)
     "yolo_v2_loss_grad": (C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    # training the detection layer (added within ABI 7)
+    "yolo_wgrad_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(WgradPlan)]),
+    "yolo_conv1x1_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_adam_step": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "yolo_net_head_input": (C.c_int, [C.c_void_p, C.POINTER(TensorView)]),
+    "yolo_net_head_train_layout": (C.c_int, [C.c_void_p, C.POINTER(HeadTrainLayout)]),
+    "yolo_net_head_train_bytes": (C.c_size_t, [C.c_void_p]),
+    "yolo_net_head_train_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "yolo_net_head_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_net_train_head_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                           C.c_void_p, C.c_void_p]),
+    "yolo_net_train_head_step_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                              C.c_void_p, C.c_void_p]),
     "yolo_nms_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int,
                                 C.c_void_p, C.POINTER(C.c_int32)]),
 }
@@ -246,6 +280,13 @@ def launch_caps():
     caps = LaunchCaps()
     check(lib().yolo_launch_caps(C.byref(caps)), "yolo_launch_caps")
     return {name: int(getattr(caps, name)) for name, _ in LaunchCaps._fields_}
+
+
+def wgrad_plan(P, cin, cout, x_dtype=DTYPE_F16):
+    """yolo_wgrad_plan as a dict (host only)"""
+    pl = WgradPlan()
+    check(lib().yolo_wgrad_plan(int(P), int(cin), int(cout), int(x_dtype), C.byref(pl)), "yolo_wgrad_plan")
+    return {name: int(getattr(pl, name)) for name, _ in WgradPlan._fields_ if name != "pad_"}
 
 
 def check(rc, what=""):

@@ -1,5 +1,5 @@
 // C ABI of libyolo_hip.so (declared in include/yolo_hip.h): argument and state checks, then one call into the planner (plan.cpp), the
-// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame, the evaluation and the loss entries live here whole.  No exceptions cross the boundary.
+// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame, the evaluation, the loss and the head-training entries live here whole.  No exceptions cross the boundary.
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -663,6 +663,20 @@ static int run_loss(const yolo_head_desc &h, const float *logits, int batch, con
     return YOLO_OK;
 }
 
+// the kernels of yolo_v2_loss_grad: the two of run_loss, then the gradient kernel on the winner table they left
+static int run_loss_grad(const yolo_head_desc &h, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+                         yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad, hipStream_t s) {
+    int rc = run_loss(h, logits, batch, gt, gt_counts, max_gt, images, assign, result, s);
+    if (rc) return rc;
+    LossGradParams p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.gt = gt; p.assign = assign; p.grad = grad; p.batch = batch; p.max_gt = max_gt;
+    p.h = h.h[0]; p.w = h.w[0]; p.na = h.n_anchors[0]; p.n_classes = h.n_classes;
+    for (int a = 0; a < p.na; ++a) { p.awf[a] = (float)h.anchors[0][2 * a]; p.ahf[a] = (float)h.anchors[0][2 * a + 1]; }
+    HIP_TRY(launch_loss_grad(p, s));
+    return YOLO_OK;
+}
+
 int yolo_v2_loss(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
                  int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream) {
     if (!logits_dev) return fail(YOLO_ERR_ARG, "yolo_v2_loss: null argument");
@@ -679,16 +693,8 @@ int yolo_v2_loss_grad(const yolo_head_desc *head, const float *logits_dev, int b
     if (rc) return rc;
     if (batch < 1) return fail(YOLO_ERR_ARG, "yolo_v2_loss_grad: batch must be at least 1");
     if (grad_dev == logits_dev) return fail(YOLO_ERR_ARG, "yolo_v2_loss_grad: grad_dev must not be logits_dev (the gradient is not computed in place)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = run_loss(*head, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, s);
-    if (rc) return rc;
-    LossGradParams p;
-    memset(&p, 0, sizeof p);
-    p.logits = logits_dev; p.gt = gt_dev; p.assign = assign_dev; p.grad = grad_dev; p.batch = batch; p.max_gt = max_gt;
-    p.h = head->h[0]; p.w = head->w[0]; p.na = head->n_anchors[0]; p.n_classes = head->n_classes;
-    for (int a = 0; a < p.na; ++a) { p.awf[a] = (float)head->anchors[0][2 * a]; p.ahf[a] = (float)head->anchors[0][2 * a + 1]; }
-    HIP_TRY(launch_loss_grad(p, s));
-    return YOLO_OK;
+    return run_loss_grad(*head, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, images_dev, assign_dev, result_dev, grad_dev,
+                         static_cast<hipStream_t>(stream));
 }
 
 static int net_loss_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
@@ -724,6 +730,235 @@ int yolo_loss_reduce(const yolo_loss_image *images_dev, int n_images, int n_repe
     if (n_repeat < 0 || n_repeat > n_images) return fail(YOLO_ERR_ARG, "yolo_loss_reduce: n_repeat must be 0..n_images");
     HIP_TRY(launch_loss_finish(LossFinishParams{images_dev, n_images, n_repeat, batch_size, result_dev}, static_cast<hipStream_t>(stream)));
     return YOLO_OK;
+}
+
+// ---- training the detection layer (yolo_hip.h: added within ABI 7; kernels in train.hip, split and checks in train_host.cpp) ---------------
+int yolo_wgrad_plan(int64_t P, int cin, int cout, int x_dtype, struct yolo_wgrad_plan *out) {
+    std::string err;
+    const int rc = wgrad_plan(P, cin, cout, x_dtype, out, err);
+    return rc ? fail(rc, "yolo_wgrad_plan: " + err) : YOLO_OK;
+}
+
+static int run_wgrad(const void *x, int x_dtype, int ld, int coff, long long image_stride, int ppi, int batch, int cin, const float *g, int cout,
+                     float *dw, float *db, void *scratch, const struct yolo_wgrad_plan &pl, hipStream_t s) {
+    WgradParams p;
+    memset(&p, 0, sizeof p);
+    p.x = x; p.g = g; p.slab = static_cast<float *>(scratch); p.dw = dw; p.db = db;
+    p.P = ppi * batch; p.cin = cin; p.cout = cout; p.ld = ld; p.coff = coff; p.ppi = ppi; p.img_stride = image_stride;
+    p.ppc = pl.positions_per_chunk; p.n_chunks = pl.n_chunks; p.tiles_cout = pl.tiles_cout; p.tiles_cin = pl.tiles_cin;
+    p.slab_stride = cout * (cin + 1);
+    HIP_TRY(launch_head_wgrad(p, x_dtype, s));
+    return YOLO_OK;
+}
+
+int yolo_conv1x1_wgrad(const void *x_dev, int x_dtype, int ld, int coff, int64_t image_stride, int positions_per_image, int batch, int cin,
+                       const float *g_dev, int cout, float *dw_dev, float *db_dev, void *scratch_dev, size_t scratch_bytes, void *stream) {
+    std::string err;
+    struct yolo_wgrad_plan pl;
+    const int rc = wgrad_check(x_dev, x_dtype, ld, coff, image_stride, positions_per_image, batch, cin, g_dev, cout, dw_dev, db_dev, scratch_dev,
+                               scratch_bytes, &pl, err);
+    if (rc) return fail(rc, "yolo_conv1x1_wgrad: " + err);
+    return run_wgrad(x_dev, x_dtype, ld, coff, image_stride, positions_per_image, batch, cin, g_dev, cout, dw_dev, db_dev, scratch_dev, pl,
+                     static_cast<hipStream_t>(stream));
+}
+
+int yolo_adam_step(float *w, float *b, float *m_w, float *v_w, float *m_b, float *v_b, const float *dw, const float *db, int64_t n_w,
+                   int64_t n_b, float lr_t, float beta1, float beta2, float eps, void *stream) {
+    std::string err;
+    const int rc = adam_check(w, b, m_w, v_w, m_b, v_b, dw, db, n_w, n_b, lr_t, beta1, beta2, eps, err);
+    if (rc) return fail(rc, "yolo_adam_step: " + err);
+    AdamParams p;
+    memset(&p, 0, sizeof p);
+    p.w = w; p.b = b; p.m_w = m_w; p.v_w = v_w; p.m_b = m_b; p.v_b = v_b; p.dw = dw; p.db = db; p.n_w = n_w; p.n_b = n_b;
+    p.lr_t = lr_t; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
+    HIP_TRY(launch_adam_step(p, static_cast<hipStream_t>(stream)));
+    return YOLO_OK;
+}
+
+// The detection layer of a net: the last kernel of the plan, if it is the 1 x 1 / stride 1 linear conv with bias that writes the logits
+// from a tensor of the workspace (plan.cpp; net/v2.py:52-56).  The message says what is in the way.
+static int head_conv(const yolo_net *net, const Kernel **out, const char *who) {
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (net->kernels.empty()) return fail(YOLO_ERR_ARG, std::string(who) + ": the plan has no kernels");
+    const Kernel &k = net->kernels.back();
+    if (k.kind != K_CONV || k.ksize != 1 || k.stride != 1 || k.leaky || k.batch_norm || k.out.buf != BUF_USER_OUT || !k.out.f32 || k.has_res || k.outmode != OUT_NORMAL)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": the last kernel of the plan must be the detection layer, a 1 x 1 / stride 1 linear conv with "
+                                                     "bias and no batch norm that writes the logits (the YOLOv2 networks; v3 heads are not trained)");
+    if (k.stem || k.fuse2_prev || k.mx || k.in.buf < 0 || k.in.f32 || k.in.base)
+        return fail(YOLO_ERR_STATE, std::string(who) + ": the plan has fused the detection layer's input away");
+    if (k.cin % 8 || k.cin_s != k.cin) return fail(YOLO_ERR_ARG, std::string(who) + ": the detection layer's input channels must be a multiple of 8");
+    if (net->parts != 1)
+        return fail(YOLO_ERR_STATE, std::string(who) + ": this net runs a batch as " + std::to_string(net->parts) +
+                                        " stream parts, each in its own arena; call yolo_net_set_streams(net, 1)");
+    *out = &k;
+    return YOLO_OK;
+}
+
+int yolo_net_head_input(const yolo_net *net, yolo_tensor_view *out) {
+    const Kernel *k = nullptr;
+    int rc = head_conv(net, &k, "yolo_net_head_input");
+    if (rc) return rc;
+    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_head_input: null argument");
+    memset(out, 0, sizeof *out);
+    out->offset = net->buffers[k->in.buf].offset;
+    out->image_stride = k->in.img_stride;
+    out->ld = k->in.ld; out->coff = k->in.coff;
+    out->dtype = net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32;
+    out->cin = k->cin; out->h = k->in.H; out->w = k->in.W;
+    return YOLO_OK;
+}
+
+static int head_train_layout(const yolo_net *net, const Kernel **kout, yolo_head_train_layout *L, struct yolo_wgrad_plan *pl, const char *who) {
+    const Kernel *k = nullptr;
+    int rc = head_conv(net, &k, who);
+    if (rc) return rc;
+    std::string err;
+    rc = check_head(&net->head, net->out_count, err);
+    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
+    if (net->head.version != 2 || net->head.n_scales != 1)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 2 with one scale (the reference has a loss for YOLOv2 only)");
+    const size_t mb = (size_t)net->opt.max_batch, hw = (size_t)k->in.H * k->in.W;
+    rc = wgrad_plan((long long)(mb * hw), k->cin, k->cout, net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32, pl, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
+    size_t off = 0;
+    auto part = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return (uint64_t)at; };
+    memset(L, 0, sizeof *L);
+    L->w_offset = part(nw); L->b_offset = part(nb);
+    L->m_w_offset = part(nw); L->v_w_offset = part(nw); L->m_b_offset = part(nb); L->v_b_offset = part(nb);
+    L->dw_offset = part(nw); L->db_offset = part(nb);
+    L->grad_offset = part(mb * net->out_count * 4);
+    L->assign_offset = part(mb * hw * 4);
+    L->images_offset = part(mb * sizeof(yolo_loss_image));
+    // a smaller batch never needs more chunks than the full one at the same tile counts, but its chunks may be laid out otherwise:
+    // the scratch is sized for the largest split of any batch up to max_batch
+    uint64_t need = pl->scratch_bytes;
+    for (size_t b = 1; b < mb; ++b) {
+        struct yolo_wgrad_plan q;
+        if (wgrad_plan((long long)(b * hw), k->cin, k->cout, YOLO_DTYPE_F32, &q, err) == YOLO_OK && q.scratch_bytes > need) need = q.scratch_bytes;
+    }
+    L->scratch_bytes = need;
+    L->scratch_offset = part((size_t)need);
+    L->total_bytes = off;
+    L->cin = k->cin; L->cout = k->cout;
+    if (kout) *kout = k;
+    return YOLO_OK;
+}
+
+int yolo_net_head_train_layout(const yolo_net *net, yolo_head_train_layout *out) {
+    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_head_train_layout: null argument");
+    struct yolo_wgrad_plan pl;
+    return head_train_layout(net, nullptr, out, &pl, "yolo_net_head_train_layout");
+}
+
+size_t yolo_net_head_train_bytes(const yolo_net *net) {
+    yolo_head_train_layout L;
+    struct yolo_wgrad_plan pl;
+    if (head_train_layout(net, nullptr, &L, &pl, "yolo_net_head_train_bytes")) return 0;
+    return (size_t)L.total_bytes;
+}
+
+int yolo_net_head_train_init(yolo_net *net, void *state_dev, size_t bytes, const float *head_w_host, const float *head_b_host) {
+    const char *who = "yolo_net_head_train_init";
+    if (!net || !state_dev || !head_w_host || !head_b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    yolo_head_train_layout L;
+    struct yolo_wgrad_plan pl;
+    const Kernel *k = nullptr;
+    int rc = head_train_layout(net, &k, &L, &pl, who);
+    if (rc) return rc;
+    if (bytes < L.total_bytes) return fail(YOLO_ERR_ARG, std::string(who) + ": state too small (yolo_net_head_train_bytes)");
+    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
+    if (!net->weights_loaded || !net->dev_weights) return fail(YOLO_ERR_STATE, std::string(who) + ": weights not loaded");
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(st + L.w_offset, head_w_host, nw, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(st + L.b_offset, head_b_host, nb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(st + L.m_w_offset, 0, (size_t)(L.dw_offset - L.m_w_offset)));       // the four moment arrays lie one behind the other
+    // the layer's packed form, as pack_weights (plan.cpp) writes a 1 x 1 conv without batch norm: row o at o * wrow bytes, bias as it is
+    const size_t wrow = (size_t)k->ktiles * 128;
+    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
+    std::vector<unsigned char> rows((size_t)k->cout * wrow, 0);
+    for (int o = 0; o < k->cout; ++o)
+        for (int c = 0; c < k->cin; ++c) {
+            const float v = head_w_host[(size_t)o * k->cin + c];
+            if (f16) reinterpret_cast<_Float16 *>(rows.data() + (size_t)o * wrow)[c] = (_Float16)v;
+            else reinterpret_cast<float *>(rows.data() + (size_t)o * wrow)[c] = v;
+        }
+    HIP_TRY(hipMemcpy(net->dev_weights + k->w_off, rows.data(), rows.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(net->dev_weights + k->b_off, head_b_host, nb, hipMemcpyHostToDevice));
+    return YOLO_OK;
+}
+
+int yolo_net_head_train_read(yolo_net *net, const void *state_dev, float *w_host, float *b_host) {
+    const char *who = "yolo_net_head_train_read";
+    if (!net || !state_dev || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    yolo_head_train_layout L;
+    struct yolo_wgrad_plan pl;
+    const Kernel *k = nullptr;
+    int rc = head_train_layout(net, &k, &L, &pl, who);
+    if (rc) return rc;
+    const unsigned char *st = static_cast<const unsigned char *>(state_dev);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(w_host, st + L.w_offset, (size_t)k->cout * k->cin * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b_host, st + L.b_offset, (size_t)k->cout * 4, hipMemcpyDeviceToHost));
+    return YOLO_OK;
+}
+
+static int train_head_step_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                               void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream, const char *who) {
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    yolo_head_train_layout L;
+    struct yolo_wgrad_plan pl;
+    const Kernel *k = nullptr;
+    int rc = head_train_layout(net, &k, &L, &pl, who);
+    if (rc) return rc;
+    if (!state_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null state (yolo_net_head_train_init)");
+    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    yolo_loss_image *images = reinterpret_cast<yolo_loss_image *>(st + L.images_offset);
+    rc = check_loss_args(&net->head, gt_dev, gt_counts_dev, max_gt, images, result_dev, who);
+    if (rc) return rc;
+    if (batch < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": batch must be at least 1");
+    rc = check_ready(net, in_dev.ptr, batch, who);
+    if (rc) return rc;
+    if (!(lr_t == lr_t)) return fail(YOLO_ERR_ARG, std::string(who) + ": lr_t is NaN");
+    const int ppi = k->in.H * k->in.W;
+    const int x_dtype = net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32;
+    std::string err;
+    rc = wgrad_plan((long long)ppi * batch, k->cin, k->cout, x_dtype, &pl, err);
+    if (rc || pl.scratch_bytes > L.scratch_bytes) return fail(YOLO_ERR_ARG, std::string(who) + ": " + (rc ? err : std::string("weight-gradient scratch too small")));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
+    float *grad = reinterpret_cast<float *>(st + L.grad_offset);
+    float *dw = reinterpret_cast<float *>(st + L.dw_offset), *db = reinterpret_cast<float *>(st + L.db_offset);
+    rc = run_forward(net, in_dev, batch, logits, s);        // dense: obj_min_logit is -inf outside detect_any
+    if (rc) return rc;
+    rc = run_loss_grad(net->head, logits, batch, gt_dev, gt_counts_dev, max_gt, images, reinterpret_cast<int32_t *>(st + L.assign_offset), result_dev, grad, s);
+    if (rc) return rc;
+    rc = run_wgrad(net->dev_ws + net->buffers[k->in.buf].offset, x_dtype, k->in.ld, k->in.coff, k->in.img_stride, ppi, batch, k->cin, grad, k->cout,
+                   dw, db, st + L.scratch_offset, pl, s);
+    if (rc) return rc;
+    AdamParams p;
+    memset(&p, 0, sizeof p);
+    p.w = reinterpret_cast<float *>(st + L.w_offset); p.b = reinterpret_cast<float *>(st + L.b_offset);
+    p.m_w = reinterpret_cast<float *>(st + L.m_w_offset); p.v_w = reinterpret_cast<float *>(st + L.v_w_offset);
+    p.m_b = reinterpret_cast<float *>(st + L.m_b_offset); p.v_b = reinterpret_cast<float *>(st + L.v_b_offset);
+    p.dw = dw; p.db = db; p.n_w = (long long)k->cout * k->cin; p.n_b = k->cout;
+    p.lr_t = lr_t; p.beta1 = 0.9f; p.beta2 = 0.999f; p.eps = 1e-8f;        // tf.train.AdamOptimizer's defaults (net/v2.py:205)
+    p.pack_w = net->dev_weights + k->w_off; p.pack_b = reinterpret_cast<float *>(net->dev_weights + k->b_off);
+    p.pack_cin = k->cin; p.pack_f16 = x_dtype == YOLO_DTYPE_F16;
+    p.pack_row = (int)((size_t)k->ktiles * 128 / (p.pack_f16 ? 2 : 4));
+    HIP_TRY(launch_adam_step(p, s));
+    return YOLO_OK;
+}
+int yolo_net_train_head_step(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                             void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
+    return train_head_step_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, state_dev, lr_t, result_dev, stream, "yolo_net_train_head_step");
+}
+int yolo_net_train_head_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
+    return train_head_step_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, state_dev, lr_t, result_dev, stream, "yolo_net_train_head_step_u8");
 }
 
 int yolo_u8_unit_table(float *out256) {

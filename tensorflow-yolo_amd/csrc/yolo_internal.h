@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "yolo_hip.h"
+#include "train_host.h"
 
 namespace yolo {
 
@@ -409,6 +410,30 @@ struct LossGradParams {
 hipError_t launch_loss_images(const LossParams &p, int batch, hipStream_t s);
 hipError_t launch_loss_finish(const LossFinishParams &p, hipStream_t s);
 hipError_t launch_loss_grad(const LossGradParams &p, hipStream_t s);
+
+// ---- training the detection layer (train.hip; the launch split and the argument checks: train_host.h) ---------------------------
+constexpr int kWgradThreads = 256;
+struct WgradParams {
+    const void *x;             // element 0 of the view's buffer: fp16 or float32 (launch_head_wgrad: x_dtype)
+    const float *g;            // [P][cout]
+    float *slab;               // [n_chunks][cout * cin + cout]
+    float *dw, *db;            // [cout][cin], [cout]
+    int P, cin, cout, ld, coff, ppi;       // ppi: positions per image
+    long long img_stride;
+    int ppc, n_chunks, tiles_cout, tiles_cin;      // yolo_wgrad_plan
+    int slab_stride;           // cout * (cin + 1)
+};
+struct AdamParams {
+    float *w, *b, *m_w, *v_w, *m_b, *v_b;
+    const float *dw, *db;
+    long long n_w, n_b;
+    float lr_t, beta1, beta2, eps;
+    void *pack_w;              // the conv's packed weights (row o at o * pack_row elements) or null
+    float *pack_b;             // its float32 bias or null
+    int pack_cin, pack_row, pack_f16;
+};
+hipError_t launch_head_wgrad(const WgradParams &p, int x_dtype, hipStream_t s);     // both kernels
+hipError_t launch_adam_step(const AdamParams &p, hipStream_t s);
 
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);

@@ -5,8 +5,9 @@ Keeps the reference launcher's surface (reference launcher.py:15-60): the two fl
 COMMON / ANCHOR / TRAIN / TEST merged as {**section, **COMMON}, relative `*_dir` / `*_path` values
 resolved against the .ini's directory, `anchors` / `class_names` parsed as Python literals, and the
 network picked by COMMON.version.  `test` runs on this backend, and `eval` (not in the reference): VOC-style mAP of the
-network on an annotated directory, from an [EVAL] section laid over [TEST] (eval_params); `train` and `anchor` end with a
-clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up),
+network on an annotated directory, from an [EVAL] section laid over [TEST] (eval_params); `train` runs when [TRAIN] has
+`train_layers = head` (the detection layer on a frozen backbone: net/train.py; `seed` seeds the shuffle and a drawn head); otherwise
+`train` and `anchor` end with a clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up),
 `resize` (stretch, the reference's geometry and the default | letterbox, Darknet's: aspect ratio kept, grey canvas, boxes mapped back to the frame),
 `loss` ([EVAL] only; true: also report the reference's validation loss, net/yolo.py:177-193 -- YOLOv2, resize = stretch);
 version additionally accepts `v2-tiny`, `v3-tiny` and `v3-spp`.  `--section` selects another TEST-like section (the
@@ -103,6 +104,13 @@ def run(cfg, mode, section=None):
         params = eval_params(cfg, section)
         eval_options(params)
         yolo.evaluate(params)
+    elif mode == "train" and "train_layers" in cfg.get("TRAIN", {}):      # the detection layer on a frozen backbone (net/train.py)
+        from .net import train as ytrain
+        params = dict(cfg["TRAIN"])
+        params.update(cfg["COMMON"])
+        ytrain.train_option(params)
+        ytrain.check_params(params, cfg["COMMON"]["version"])
+        yolo.train(params)
     elif mode in ("train", "anchor"):
         raise SystemExit("mode '{}' is not supported by the HIP inference backend (TEST mode only)".format(mode))
     else:

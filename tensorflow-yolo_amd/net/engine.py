@@ -127,6 +127,18 @@ class Plan(object):
         _hip.check(self.lib.yolo_net_set_head(self.handle, C.byref(hd)), "yolo_net_set_head")
         self.head = hd
 
+    def head_input(self):
+        """yolo_net_head_input: where the detection layer's input lives in the workspace after a dense forward (a _hip.TensorView; host only)"""
+        v = _hip.TensorView()
+        _hip.check(self.lib.yolo_net_head_input(self.handle, C.byref(v)), "yolo_net_head_input")
+        return v
+
+    def head_train_layout(self):
+        """yolo_net_head_train_layout: byte offsets of the parts of the head-training state (a _hip.HeadTrainLayout; host only)"""
+        lay = _hip.HeadTrainLayout()
+        _hip.check(self.lib.yolo_net_head_train_layout(self.handle, C.byref(lay)), "yolo_net_head_train_layout")
+        return lay
+
     def describe(self):
         n = self.lib.yolo_net_describe(self.handle, None, 0)
         buf = C.create_string_buffer(n)
@@ -452,6 +464,67 @@ class HipNetwork(Plan):
         """loss_grad() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as loss_grad(float32(x / 255.))"""
         return self._loss_grad_any(x, gts, True)
 
+    # -- training the detection layer (yolo_net_head_train_init / yolo_net_train_head_step / yolo_net_head_train_read) ------------------
+    def head_train_init(self, head_w, head_b):
+        """Allocate the head-training state and start it from head_w [cout, cin] (the Darknet kernel, [out][in]) and head_b [cout]: master
+        values, zeroed moments, and the layer packed into the device weights.  Synchronous.  A net whose streams = 0 rule runs two halves is
+        set to one pass first (each part has its own arena)."""
+        torch = self.torch
+        if not self.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights first")
+        if self._auto_streams and self.num_streams != 1:
+            _hip.check(self.lib.yolo_net_set_streams(self.handle, 1), "yolo_net_set_streams")
+        self._streams_tuned = True
+        lay = self.head_train_layout()
+        w = np.ascontiguousarray(head_w, dtype=np.float32).reshape(-1)
+        b = np.ascontiguousarray(head_b, dtype=np.float32).reshape(-1)
+        if w.size != lay.cout * lay.cin or b.size != lay.cout:
+            raise ValueError("expected a head kernel of %d x %d values and %d biases, got %d and %d" % (lay.cout, lay.cin, lay.cout, w.size, b.size))
+        with torch.cuda.device(self.device):
+            self._train_state = torch.empty(int(lay.total_bytes), dtype=torch.uint8, device=self.device)
+            _hip.check(self.lib.yolo_net_head_train_init(self.handle, self._train_state.data_ptr(), self._train_state.numel(), w.ctypes.data,
+                                                         b.ctypes.data), "yolo_net_head_train_init")
+        self.train_layout = lay
+        return self._train_state
+
+    def _train_head_step_any(self, x, gts, lr_t, u8, result):
+        from . import evaluate as yeval
+        torch = self.torch
+        if getattr(self, "_train_state", None) is None:
+            raise RuntimeError("train_head_step follows head_train_init")
+        x = self.to_device_u8(x) if u8 else self.to_device(x)
+        b = x.shape[0]
+        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
+        if result is None:
+            result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        name = "yolo_net_train_head_step_u8" if u8 else "yolo_net_train_head_step"
+        with torch.cuda.device(self.device):
+            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt),
+                                               self._train_state.data_ptr(), float(lr_t), result.data_ptr(), self._stream()), name)
+        self.u8_calls += int(u8)
+        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
+        return result
+
+    def train_head_step(self, x, gts, lr_t, result=None):
+        """One training step of the detection layer in one enqueue, no host sync (include/yolo_hip.h: yolo_net_train_head_step): dense
+        forward, loss and its gradient, weight gradient, Adam update and re-pack.  lr_t: adam_lr_t(lr, step).  Returns the device record
+        (uint8 [64] = yolo_loss_result) of the loss BEFORE the update; `result`: a caller's tensor to write it into."""
+        return self._train_head_step_any(x, gts, lr_t, False, result)
+
+    def train_head_step_u8(self, x, gts, lr_t, result=None):
+        """train_head_step() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as train_head_step(float32(x / 255.))"""
+        return self._train_head_step_any(x, gts, lr_t, True, result)
+
+    def head_train_read(self):
+        """The master values of the detection layer (synchronous): (kernel float32 [cout, cin], bias float32 [cout])"""
+        lay = self.train_layout
+        w = np.empty((lay.cout, lay.cin), dtype=np.float32)
+        b = np.empty(lay.cout, dtype=np.float32)
+        with self.torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_head_train_read(self.handle, self._train_state.data_ptr(), w.ctypes.data, b.ctypes.data),
+                       "yolo_net_head_train_read")
+        return w, b
+
     def forward_timed_u8(self, x, out=None):
         """forward_timed() for a uint8 batch: the input kernel's entry is the time of its uint8 twin."""
         torch = self.torch
@@ -499,6 +572,12 @@ class HipNetwork(Plan):
         host = np.empty((batch, h, w, c), dtype=np.float32)
         _hip.check(self.lib.yolo_net_read_layer(self.handle, index, batch, host.ctypes.data, host.size), "yolo_net_read_layer")
         return host
+
+
+def adam_lr_t(lr, step, beta1=0.9, beta2=0.999):
+    """tf.train.AdamOptimizer's step size for step = 1, 2, ...: lr * sqrt(1 - beta2^t) / (1 - beta1^t), in float64, rounded to float32 once"""
+    t = float(step)
+    return np.float32(float(lr) * np.sqrt(1.0 - float(beta2) ** t) / (1.0 - float(beta1) ** t))
 
 
 def loss_gts(torch, device, gts, b):

@@ -1,0 +1,211 @@
+"""`--mode train` for the detection layer: the reference's loop (net/yolo.py:98-195) around yolo_net_train_head_step.
+
+Runs only when [TRAIN] has `train_layers = head`.  Two deliberate differences from the reference (include/yolo_hip.h):
+only the last conv's kernel and bias receive updates, and the backbone's batch norms run on their stored statistics -- a fine-tune of the
+detection layer on a frozen, pretrained backbone.  Batching is the reference's (net/v2.py:209-219: the last batch is padded with the
+first annotations, the list is shuffled per epoch), the console lines are its strings, the validation loss is its number (the
+yolo_loss_reduce path of Yolo.evaluate).  Checkpoints are Darknet .weights files, `<checkpoint_dir>/<prefix>-<step>.weights`: the
+pretrained stream with the head's floats replaced by the master values.  No augmentation, no TensorBoard, no TensorFlow checkpoints.
+"""
+import os
+import random
+import re
+
+import numpy as np
+
+from .. import _hip
+from . import base, engine, v3
+
+NOT_SUPPORTED = "train mode is not supported by the HIP inference backend"
+
+
+def train_option(params):
+    """The [TRAIN] key `train_layers`: absent -> False (train keeps raising), `head` -> True, anything else raises ValueError."""
+    raw = params.get("train_layers")
+    if raw is None:
+        return False
+    if str(raw).strip().lower() != "head":
+        raise ValueError("train_layers must be head (the detection layer on a frozen backbone), got %r" % (raw,))
+    return True
+
+
+def check_params(params, version):
+    """What the head training refuses, before a network is built: a v3 network (the reference binds no loss to YoloV3,
+    net/yolo.py:208-211) and any augmentation."""
+    if not str(version).startswith("v2"):
+        raise NotImplementedError(NOT_SUPPORTED + " for %s networks: the reference has a loss for YOLOv2 only" % version)
+    if float(params.get("augment_probability", 0)) != 0:
+        raise ValueError("augment_probability must be 0: augmentation is not built (got %s)" % params.get("augment_probability"))
+
+
+def make_batches(annotations, batch_size, rng):
+    """net/v2.py:209-219: the batch shrinks to a smaller set, the list is padded IN PLACE with its first annotations up to a whole number
+    of batches, then shuffled in place with `rng` (a random.Random; the reference uses the module's generator).  -> list of batches"""
+    if len(annotations) == 0:
+        return []
+    if len(annotations) < batch_size:
+        batch_size = len(annotations)
+    total_batches = int(np.ceil(len(annotations) / batch_size))
+    if len(annotations) % batch_size > 0:
+        annotations.extend(annotations[0:batch_size - len(annotations) % batch_size])
+    rng.shuffle(annotations)
+    return [annotations[b * batch_size:(b + 1) * batch_size] for b in range(total_batches)]
+
+
+def head_counts(net):
+    """(cout, cin, floats of the head in the Darknet stream, floats of the whole stream) of a v2 layer list"""
+    from .layers import conv2d_bn_act
+    convs = [l for l in net if isinstance(l, conv2d_bn_act)]
+    need = sum(l.weight_count() for l in convs)
+    n_head = convs[-1].weight_count()
+    cout = int(net[-1].out.hwc[2])
+    cin = (n_head - cout) // cout
+    if cout * (cin + 1) != n_head:
+        raise ValueError("the last conv is not a 1 x 1 conv with bias")
+    return cout, cin, n_head, need
+
+
+def split_head(body, cout, cin):
+    """the head's (kernel [cout, cin], bias [cout]) at the end of a Darknet stream: bias first, then kernel[out][in] (net/layers.py:53-63)"""
+    n_head = cout * (cin + 1)
+    tail = np.asarray(body[len(body) - n_head:], dtype=np.float32)
+    return tail[cout:].reshape(cout, cin).copy(), tail[:cout].copy()
+
+
+def replace_head(body, w, b):
+    """a copy of the stream with the head's floats replaced"""
+    out = np.array(body, dtype=np.float32, copy=True)
+    cout, cin = w.shape
+    n_head = cout * (cin + 1)
+    out[len(out) - n_head:len(out) - n_head + cout] = np.asarray(b, dtype=np.float32)
+    out[len(out) - cout * cin:] = np.asarray(w, dtype=np.float32).reshape(-1)
+    return out
+
+
+def initial_stream(body, net, seed):
+    """The stream training starts from: a full file as it is; a backbone-only file (it ends exactly where the head conv begins, such as
+    darknet19_448.conv.23) gets a seeded N(0, 0.02) head kernel and a zero bias.  Anything else raises."""
+    cout, cin, n_head, need = head_counts(net)
+    body = np.asarray(body, dtype=np.float32)
+    if len(body) == need:
+        return body, False
+    if len(body) == need - n_head:
+        w = np.random.RandomState(seed).normal(0.0, 0.02, size=(cout, cin)).astype(np.float32)
+        return replace_head(np.concatenate([body, np.zeros(n_head, dtype=np.float32)]), w, np.zeros(cout, dtype=np.float32)), True
+    raise ValueError("weight file holds {} values, the network needs {} ({} without the detection layer)".format(len(body), need, need - n_head))
+
+
+def checkpoint_path(checkpoint_dir, prefix, step):
+    return os.path.join(checkpoint_dir, "{}-{}.weights".format(prefix, step))
+
+
+def write_checkpoint(path, header, body):
+    """a Darknet v2 .weights file: the pretrained file's four header words, then the stream"""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        np.asarray(header, dtype=np.int32).tofile(f)
+        np.ascontiguousarray(body, dtype=np.float32).tofile(f)
+
+
+def latest_checkpoint(checkpoint_dir, prefix):
+    """(step, path) of the `<prefix>-<step>.weights` file with the largest step, or (-1, None) (net/base.py:49-61 load_checkpoint)"""
+    best = (-1, None)
+    if os.path.isdir(checkpoint_dir):
+        for name in os.listdir(checkpoint_dir):
+            m = re.match(re.escape(prefix) + r"-(\d+)\.weights$", name)
+            if m and int(m.group(1)) > best[0]:
+                best = (int(m.group(1)), os.path.join(checkpoint_dir, name))
+    return best
+
+
+def batch_to_device(eng, batch):
+    """a batch of (image_path, truths) -> (uint8 device tensor [B, H, W, 3] stretched to the network input, truths per image)"""
+    descs, keep = eng.frame_descs(base.decode_frames([p for p, _ in batch]))
+    x = eng.preprocess_frames(descs, len(batch), _hip.RESIZE_STRETCH, u8=True)
+    eng._frames_keep = keep
+    return x, [t for _, t in batch]
+
+
+def validation_loss(eng, annotations, batch_size):
+    """net/yolo.py:177-193 on the device: per-image partials of every image (HipNetwork.loss_u8), added once (yolo_loss_reduce) with the
+    padding of make_batch counted twice, divided by the number of batches.  One read."""
+    from . import evaluate as yeval
+    torch = eng.torch
+    n = len(annotations)
+    bs, nb, pad = yeval.loss_batches(n, batch_size)
+    images = torch.empty((n, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=eng.device)
+    for start in range(0, n, bs):
+        x, truths = batch_to_device(eng, annotations[start:start + bs])
+        eng.loss_u8(x, truths, images=images[start:start + len(truths)])
+    total = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=eng.device)
+    with torch.cuda.device(eng.device):
+        _hip.check(eng.lib.yolo_loss_reduce(images.data_ptr(), n, pad, bs, total.data_ptr(), eng._stream()), "yolo_loss_reduce")
+    rec = total.cpu().numpy().view(yeval.LOSS_RESULT_DTYPE)[0]
+    return float(rec["loss"]) / nb
+
+
+def train_head(model, params):
+    """Yolo.train with `train_layers = head`"""
+    from . import evaluate as yeval
+    check_params(params, model.version)
+    batch_size = int(params["batch_size"])
+    learning_rate = float(params["learning_rate"])
+    checkpoint_prefix, checkpoint_dir = params["checkpoint_prefix"], params["checkpoint_dir"]
+    checkpoint_step = int(params["checkpoint_step"])
+    anchors = np.reshape(params["anchors"], [-1, 2])
+    class_names = params["class_names"]
+    input_shape = (int(params["input_h"]), int(params["input_w"]), int(params["input_c"]))
+    epochs, max_step = int(params["epochs"]), int(params["max_step"])
+    seed = int(params.get("seed", 0))
+    if params.get("tensorboard_log_dir"):
+        print("tensorboard_log_dir is ignored: this backend writes no TensorBoard summaries")
+    if str(params.get("cpu_only", "false")).lower() == "true":
+        print("cpu_only = True is ignored: this backend runs on the MI355X only")
+
+    train_annotations, _ = yeval.parse_voc_annotations(params["annotation_dir"], params["image_dir"], class_names)
+    assert len(train_annotations) > 0
+    val_annotations, _ = yeval.parse_voc_annotations(params["val_annotation_dir"], params["val_image_dir"], class_names)
+
+    model.build(anchors, class_names, input_shape, dtype=params.get("dtype", "fp32"), max_batch=batch_size, streams=1)
+    net, eng = model.net, model.net.engine
+    cout, cin, _, _ = head_counts(net)
+    header, pretrained = base.read_darknet_weights(params["pretrained_weights_path"], "v2")
+    step, path = latest_checkpoint(checkpoint_dir, checkpoint_prefix)
+    if step < 0:
+        body, drawn = initial_stream(pretrained, net, seed)
+        v3.attach_weights(net, body)
+        print("Pre-trained weights loaded." + (" Detection layer drawn from N(0, 0.02), seed {}.".format(seed) if drawn else ""))
+        step = 0
+        write_checkpoint(checkpoint_path(checkpoint_dir, checkpoint_prefix, step), header, body)
+    else:
+        header, body = base.read_darknet_weights(path, "v2")
+        v3.attach_weights(net, body)
+        print("Checkpoint restored. step:{}".format(step))
+    eng.head_train_init(*split_head(body, cout, cin))       # (the moments are not part of a .weights file: they start at zero)
+
+    rng = random.Random(seed)
+    result = eng.torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=eng.torch.uint8, device=eng.device)
+    train_loss_mva, updates = None, 0
+    for epoch in range(1, epochs + 1):
+        if 0 <= max_step < step:
+            break
+        for batch in make_batches(train_annotations, batch_size, rng):
+            step += 1
+            if 0 <= max_step < step:
+                break
+            updates += 1
+            x, truths = batch_to_device(eng, batch)
+            eng.train_head_step_u8(x, truths, engine.adam_lr_t(learning_rate, updates), result=result)
+            train_loss = np.float32(result.cpu().numpy().view(yeval.LOSS_RESULT_DTYPE)[0]["loss"])
+            train_loss_mva = train_loss_mva * 0.9 + train_loss * 0.1 if train_loss_mva is not None else train_loss
+            print("step {} ({}/{}): {} (moving average: {})".format(step, epoch, epochs, train_loss, train_loss_mva))
+            if step > 0 and step % checkpoint_step == 0:
+                w, b = eng.head_train_read()
+                write_checkpoint(checkpoint_path(checkpoint_dir, checkpoint_prefix, step), header, replace_head(body, w, b))
+                if val_annotations:
+                    print("validation loss: {}".format(validation_loss(eng, val_annotations, batch_size)))
+                else:
+                    print("no validation annotations: validation skipped")
+        print("Epoch ({}/{}) completed.".format(epoch, epochs))
+    model.trained_head = eng.head_train_read()
+    print("Done")

@@ -2,9 +2,10 @@
 and the factored-out per-batch body `predict(x_batch)`.
 
 Counterpart of the reference's net/yolo.py (TEST path :41-96; binding classes :198-211).
-Training (`train`, `generate_anchors`, `create_loss_fn`, batches) is out of scope: those entries raise.  The loss itself and its
-gradient with respect to the head logits exist (`Yolo.loss`, `Yolo.loss_grad`, net/lossfn.py); a backward pass through the network and
-an optimizer do not.
+Training (`generate_anchors`, `create_loss_fn`, batches) is out of scope: those entries raise, and so does `train` unless [TRAIN] has
+`train_layers = head` -- then the detection layer is trained on the device on a frozen backbone (net/train.py).  The loss itself and its
+gradient with respect to the head logits exist (`Yolo.loss`, `Yolo.loss_grad`, net/lossfn.py); a backward pass through the rest of the
+network does not.
 """
 import os
 
@@ -26,9 +27,14 @@ class Yolo(object):
         self.params = None
         self.last_status = None
 
-    # ---- out of scope for an inference backend ------------------------------------------------
+    # ---- out of scope for an inference backend (train: but for the detection layer) -----------------
     def train(self, params):
-        raise NotImplementedError("train mode is not supported by the HIP inference backend")
+        """The reference's loop (net/yolo.py:98-195) for the detection layer on a frozen backbone, only when [TRAIN] has
+        `train_layers = head` (net/train.py); without the key train mode is what it was: not supported."""
+        from . import train as ytrain
+        if not ytrain.train_option(params):
+            raise NotImplementedError("train mode is not supported by the HIP inference backend")
+        ytrain.train_head(self, params)
 
     def generate_anchors(self, params):
         raise NotImplementedError("anchor mode is not supported by the HIP inference backend")
