@@ -42,6 +42,10 @@
  *   yolo_net_train_head_step, yolo_net_train_head_step_u8
  *                           net/yolo.py:161-173: sess.run([optimizer, loss, ...]) of one training batch, for the detection layer alone
  *                           (+ yolo_wgrad_plan, yolo_net_head_input, yolo_net_head_train_bytes / _layout / _init / _read: no reference call site)
+ *   yolo_augment_u8         net/base.py:15-23, :100-107: seq.to_deterministic().augment_images of a resized batch, on the device
+ *   yolo_augment_truths_host
+ *                           net/base.py:107-111: augment_bounding_boxes(...).remove_out_of_image().cut_out_of_image()
+ *                           (+ yolo_augment_check, yolo_augment_tile: no reference call site)
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -70,7 +74,9 @@ extern "C" {
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_wgrad_plan, yolo_tensor_view and yolo_head_train_layout
                                           PODs only) -- training the detection layer: yolo_wgrad_plan, yolo_conv1x1_wgrad, yolo_adam_step,
                                           yolo_net_head_input, yolo_net_head_train_bytes, yolo_net_head_train_layout, yolo_net_head_train_init,
-                                          yolo_net_head_train_read, yolo_net_train_head_step, yolo_net_train_head_step_u8 */
+                                          yolo_net_head_train_read, yolo_net_train_head_step, yolo_net_train_head_step_u8;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_augment_image POD only) -- training augmentation:
+                                          yolo_augment_u8, yolo_augment_check, yolo_augment_truths_host, yolo_augment_tile */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -699,6 +705,62 @@ int yolo_net_train_head_step(yolo_net *net, const float *in_dev, int batch, cons
                              void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 int yolo_net_train_head_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
                                 void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+
+/* ---- Training augmentation on the device: flips, blur, dropout, noise, shift (added within ABI 7: new exports, one new POD) ------
+ * The reference trains through an imgaug pipeline (net/base.py:15-23): Fliplr(0.5), Flipud(0.5), GaussianBlur((0, 3.0)), Dropout(0.02),
+ * AdditiveGaussianNoise(scale = 0.01 * 255), AdditiveGaussianNoise(loc = 32, scale = 0.0001 * 255), Affine(translate_px x in -40 .. 40),
+ * with the truth boxes carried along and remove_out_of_image().cut_out_of_image() at the end (net/base.py:100-112).  Here the same list of
+ * operations in the same order, in integers, with the parameters of every image drawn on the host (net/augment.py) and one POD per image.
+ * DELIBERATE DIFFERENCES from imgaug: (a) the random stream is this header's counter-based generator, not imgaug's; (b) a noise value is
+ * an Irwin-Hall(4) variate -- the sum of four uniform 16-bit numbers, tails end at +-3.46 sigma -- not a true normal; (c) the blur's taps
+ * are 8-bit fixed point (they add up to 256), the radius at most 9; (d) at the reference's scale the second noise step is exactly + 32;
+ * (e) a truth is dropped when it lies fully outside the image (the rule below), where imgaug's remove_out_of_image has its own test.
+ *
+ * For an image S[h][w][3] (uint8) and its yolo_augment_image:
+ *   1 flips   F[y][x] = S[flip_ud ? h-1-y : y][flip_lr ? w-1-x : x]
+ *   2 blur    separable, per channel, border reflect-101 (index -k -> k, h-1+k -> h-1-k; radius < h and radius < w):
+ *             Hs[y][x] = S_k taps[|k|] * F[y][x+k] (k = -radius .. radius; at most 65280, not rounded), V[y][x] = S_k taps[|k|] * Hs[y+k][x],
+ *             B = (V + 32768) >> 16.  taps[0] is the centre and taps[0] + 2 * (taps[1] + .. + taps[radius]) == 256; radius == 0 is the identity.
+ *             The taps are data: the library validates them and evaluates no exp.
+ *   3 random  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with the key key[0..1] and the
+ *             counter (y * w + x, draw, 0, 0) gives four 32-bit words per pixel and draw.  Known answers: counter and key all zero ->
+ *             6627e8d5 e169c58d bc57ac4c 9b00dbd8; all ones (0xffffffff) -> 408f276d 41c83b0e a20bc7c6 6d5451fd.
+ *   4 dropout draw 0, word 0 < drop_thr: the three channels of the pixel become 0 (one decision per pixel: iaa.Dropout, per_channel = False)
+ *   5 noise   step i = 0, 1 uses draw i: with h0..h3 the 16-bit halves of two words (step 0: words 1 and 2; step 1: words 0 and 1),
+ *             s = h0 + h1 + h2 + h3 - 131070 and d = (s * noise_q[i] + 2^23) >> 24 (64-bit, arithmetic shift); every channel becomes
+ *             clamp(v + noise_loc[i] + d, 0, 255), clamped after each step.  s has standard deviation sqrt((65536^2 - 1) / 3) = 37837.227,
+ *             so noise_q = round(scale * 2^24 / 37837.227).  A step with 131070 * noise_q < 2^23 has d == 0 everywhere.
+ *   6 shift   O[y][x] = T[y][x - tx] where 0 <= x - tx < w, else 0 (imgaug's cval = 0).  Steps 3-5 are indexed by the position BEFORE the shift.
+ *   7 enabled == 0: O = S byte for byte; no other field of the record is looked at.
+ * Field ranges (yolo_augment_check; YOLO_ERR_ARG with a message of its own each): enabled, flip_lr, flip_ud 0 | 1; radius 0 .. 9 and below
+ * h and w; the taps' sum; noise_q 0 .. 16383; noise_loc -255 .. 255; |tx| <= 2^30; h, w >= 1, w % 4 == 0, h * w < 2^31. */
+typedef struct yolo_augment_image {
+    int32_t enabled, flip_lr, flip_ud;
+    int32_t radius;
+    uint16_t taps[10];
+    uint32_t drop_thr;
+    int32_t noise_q[2];
+    int32_t noise_loc[2];
+    int32_t tx;
+    uint32_t key[2];
+} yolo_augment_image;
+/* The checks of ONE record for an h x w image (pure host function, no device). */
+int yolo_augment_check(const yolo_augment_image *params, int h, int w);
+/* src_dev uint8 [n][h][w][3] -> dst_dev of the same shape, image i by params_host[i] (a HOST array: the records travel in the kernel
+ * arguments, images_per_launch of yolo_augment_tile per launch, larger n as consecutive launches).  A workgroup produces a rows x cols
+ * tile of an output image from the tile plus a 9-pixel halo held in LDS; the source is read and the destination written, never re-read.
+ * src and dst must not overlap (YOLO_ERR_ARG); every byte of dst is written by each call; a dst that is not 4-byte aligned is served by
+ * byte stores.  Checks as yolo_augment_check for every record ("image i: ..." in the message).  Enqueued on `stream`. */
+int yolo_augment_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int w, const yolo_augment_image *params_host, void *stream);
+/* The truths of one image under its record (pure host function; `in` and `out` may be the same array; out holds n_in records).  Each
+ * truth in order, in float64, every operation rounded on its own: x1 = x - w / 2, x2 = x + w / 2, the same for y; flip_lr maps (x1, x2)
+ * to (1 - x2, 1 - x1), flip_ud the same in y; the shift adds tx / W (W = the image width w, one division) to both x corners; the truth is
+ * dropped if x2 <= 0, x1 >= 1, y2 <= 0, y1 >= 1 or any of the four is NaN; otherwise each corner is clipped to [0, 1] and
+ * x = float32((x1 + x2) / 2), w = float32(x2 - x1), the same for y.  class_idx and difficult are kept, the order is kept.  enabled == 0
+ * copies the records untouched.  *n_out receives the number of records written. */
+int yolo_augment_truths_host(const yolo_gt *in, int n_in, const yolo_augment_image *params, int h, int w, yolo_gt *out, int32_t *n_out);
+/* The kernel's constants (test hook): the output tile of a workgroup and the images one launch covers.  Any pointer may be null. */
+int yolo_augment_tile(int32_t *rows, int32_t *cols, int32_t *images_per_launch);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

@@ -126,6 +126,12 @@ class HeadTrainLayout(C.Structure):
                                           "total_bytes")] + [("cin", C.c_int32), ("cout", C.c_int32)]
 
 
+class AugmentImage(C.Structure):
+    """yolo_augment_image: how one image of a training batch is augmented (net/augment.py draws it)"""
+    _fields_ = [("enabled", C.c_int32), ("flip_lr", C.c_int32), ("flip_ud", C.c_int32), ("radius", C.c_int32), ("taps", C.c_uint16 * 10),
+                ("drop_thr", C.c_uint32), ("noise_q", C.c_int32 * 2), ("noise_loc", C.c_int32 * 2), ("tx", C.c_int32), ("key", C.c_uint32 * 2)]
+
+
 class WsRegion(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("offset", C.c_uint64), ("used_bytes", C.c_uint64), ("region_bytes", C.c_uint64)]
 
@@ -222,6 +228,11 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p]),
     "yolo_net_train_head_step_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                               C.c_void_p, C.c_void_p]),
+    # training augmentation (added within ABI 7)
+    "yolo_augment_check": (C.c_int, [C.POINTER(AugmentImage), C.c_int, C.c_int]),
+    "yolo_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(AugmentImage), C.c_void_p]),
+    "yolo_augment_truths_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(AugmentImage), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]),
+    "yolo_augment_tile": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "yolo_nms_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int,
                                 C.c_void_p, C.POINTER(C.c_int32)]),
 }
@@ -287,6 +298,13 @@ def wgrad_plan(P, cin, cout, x_dtype=DTYPE_F16):
     pl = WgradPlan()
     check(lib().yolo_wgrad_plan(int(P), int(cin), int(cout), int(x_dtype), C.byref(pl)), "yolo_wgrad_plan")
     return {name: int(getattr(pl, name)) for name, _ in WgradPlan._fields_ if name != "pad_"}
+
+
+def augment_tile():
+    """yolo_augment_tile: (rows, cols, images_per_launch) of the augmentation kernel (host only)"""
+    out = [C.c_int32() for _ in range(3)]
+    check(lib().yolo_augment_tile(*[C.byref(v) for v in out]), "yolo_augment_tile")
+    return tuple(int(v.value) for v in out)
 
 
 def check(rc, what=""):

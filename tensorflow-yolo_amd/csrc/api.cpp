@@ -1,5 +1,5 @@
 // C ABI of libyolo_hip.so (declared in include/yolo_hip.h): argument and state checks, then one call into the planner (plan.cpp), the
-// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame, the evaluation, the loss and the head-training entries live here whole.  No exceptions cross the boundary.
+// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame, the evaluation, the loss, the head-training and the augmentation entries live here whole.  No exceptions cross the boundary.
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -772,6 +772,47 @@ int yolo_adam_step(float *w, float *b, float *m_w, float *v_w, float *m_b, float
     p.w = w; p.b = b; p.m_w = m_w; p.v_w = v_w; p.m_b = m_b; p.v_b = v_b; p.dw = dw; p.db = db; p.n_w = n_w; p.n_b = n_b;
     p.lr_t = lr_t; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
     HIP_TRY(launch_adam_step(p, static_cast<hipStream_t>(stream)));
+    return YOLO_OK;
+}
+
+// ---- training augmentation (augment_host.cpp: checks, records, truths; augment.hip: the kernel)
+int yolo_augment_check(const yolo_augment_image *params, int h, int w) {
+    std::string err;
+    const int rc = augment_check(params, h, w, err);
+    if (rc) return fail(rc, "yolo_augment_check: " + err);
+    return YOLO_OK;
+}
+
+int yolo_augment_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int w, const yolo_augment_image *params_host, void *stream) {
+    std::string err;
+    const int rc = augment_call_check(src_dev, dst_dev, n, h, w, params_host, err);
+    if (rc) return fail(rc, "yolo_augment_u8: " + err);
+    const size_t img_bytes = (size_t)h * w * 3;
+    AugmentParams p;
+    memset(&p, 0, sizeof p);
+    p.h = h; p.w = w;
+    p.wide = (uintptr_t)dst_dev % 4 == 0;       // (an image is a multiple of 12 bytes: the alignment holds for every image)
+    for (int i0 = 0; i0 < n; i0 += kAugPerLaunch) {
+        const int m = n - i0 < kAugPerLaunch ? n - i0 : kAugPerLaunch;
+        for (int i = 0; i < m; ++i) p.g[i] = augment_geom(params_host[i0 + i]);
+        p.src = src_dev + (size_t)i0 * img_bytes;
+        p.dst = dst_dev + (size_t)i0 * img_bytes;
+        HIP_TRY(launch_augment(p, m, static_cast<hipStream_t>(stream)));
+    }
+    return YOLO_OK;
+}
+
+int yolo_augment_truths_host(const yolo_gt *in, int n_in, const yolo_augment_image *params, int h, int w, yolo_gt *out, int32_t *n_out) {
+    std::string err;
+    const int rc = augment_truths(in, n_in, params, h, w, out, n_out, err);
+    if (rc) return fail(rc, "yolo_augment_truths_host: " + err);
+    return YOLO_OK;
+}
+
+int yolo_augment_tile(int32_t *rows, int32_t *cols, int32_t *images_per_launch) {
+    if (rows) *rows = kAugTileRows;
+    if (cols) *cols = kAugTileCols;
+    if (images_per_launch) *images_per_launch = kAugPerLaunch;
     return YOLO_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include "yolo_hip.h"
 #include "train_host.h"
+#include "augment_host.h"
 
 namespace yolo {
 
@@ -471,6 +472,7 @@ hipError_t launch_prep(const PrepParams &p, int dtype, hipStream_t s, bool in_u8
 hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8 = false);
 hipError_t launch_frames_resize(const FramesParams &p, int n, hipStream_t s, bool dst_u8);     // n <= kFramesPerLaunch frames
 hipError_t launch_boxes_to_frames(const RemapParams &p, int n, hipStream_t s);                 // n <= kFramesPerLaunch images
+hipError_t launch_augment(const AugmentParams &p, int n, hipStream_t s);                      // augment.hip: n <= kAugPerLaunch images
 hipError_t launch_first(const FirstParams &p, int dtype, hipStream_t s, bool in_u8 = false);
 hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = kStemGrid, bool in_u8 = false);     // stem.hip
 hipError_t launch_pool(const PoolParams &p, int dtype, hipStream_t s);

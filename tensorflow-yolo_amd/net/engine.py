@@ -396,6 +396,31 @@ class HipNetwork(Plan):
         self._frames_last = x           # (the batch this step resized: what loss_frames runs on)
         return self._boxes[:n], self._counts[:n], self._status[:n]
 
+    # -- training augmentation (yolo_augment_u8) ------------------------------------------------------------------------------------------
+    def augment_u8(self, x, params, out=None):
+        """yolo_augment_u8: a uint8 batch [B, H, W, 3] (the network input; host or device) and one yolo_augment_image per image (a list,
+        net/augment.py draws them) -> the augmented batch in `out` (a second buffer of the engine's, allocated once, unless given: the
+        source and the result must not overlap).  Enqueued; returns the tensor."""
+        from . import augment as yaug
+        torch = self.torch
+        x = self.to_device_u8(x)
+        b, (h, w, c) = x.shape[0], self.input_hwc
+        if c != 3:
+            raise ValueError("augmentation needs a network input of 3 channels, this one has %d" % c)
+        if len(params) != b:
+            raise ValueError("expected %d augmentation records, got %d" % (b, len(params)))
+        if out is None:
+            if getattr(self, "_augment_out", None) is None:
+                self._augment_out = torch.empty((self.max_batch, h, w, 3), dtype=torch.uint8, device=self.device)
+            out = self._augment_out[:b]
+        elif out.device != self.device or out.dtype != torch.uint8 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+            raise ValueError("out: expected a contiguous uint8 device tensor %s" % (tuple(x.shape),))
+        with torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_augment_u8(x.data_ptr(), out.data_ptr(), b, h, w, yaug.params_array(params), self._stream()),
+                       "yolo_augment_u8")
+        self._augment_keep = x          # (alive until the next call: the work is only enqueued)
+        return out
+
     # -- YOLOv2 loss, forward only (yolo_net_loss / yolo_net_loss_u8) ------------------------------------------------------------------
     def _loss_gts(self, gts, b):
         return loss_gts(self.torch, self.device, gts, b)

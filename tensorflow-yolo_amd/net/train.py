@@ -5,7 +5,13 @@ only the last conv's kernel and bias receive updates, and the backbone's batch n
 detection layer on a frozen, pretrained backbone.  Batching is the reference's (net/v2.py:209-219: the last batch is padded with the
 first annotations, the list is shuffled per epoch), the console lines are its strings, the validation loss is its number (the
 yolo_loss_reduce path of Yolo.evaluate).  Checkpoints are Darknet .weights files, `<checkpoint_dir>/<prefix>-<step>.weights`: the
-pretrained stream with the head's floats replaced by the master values.  No augmentation, no TensorBoard, no TensorFlow checkpoints.
+pretrained stream with the head's floats replaced by the master values.  No TensorBoard, no TensorFlow checkpoints.
+
+Augmentation (the reference's imgaug pipeline, net/base.py:15-23, :100-112, :134-135) runs on the device when [TRAIN] has
+`augment = device`: then `0 < augment_probability <= 1` is accepted, every training batch is augmented from the resized uint8 batch into a
+second buffer (HipNetwork.augment_u8) and its truths are transformed on the host (net/augment.py), with parameters drawn from a generator
+of their own seeded by `seed`.  Validation batches are never augmented (the reference's augment_prob = 0).  Without the key a non-zero
+probability is refused as before.
 """
 import os
 import random
@@ -29,13 +35,30 @@ def train_option(params):
     return True
 
 
+def augment_option(params):
+    """The [TRAIN] key `augment`: absent -> False, `device` -> True (augmentation on the device), anything else raises ValueError."""
+    raw = params.get("augment")
+    if raw is None:
+        return False
+    if str(raw).strip().lower() != "device":
+        raise ValueError("augment must be device (the augmentation kernel), got %r" % (raw,))
+    return True
+
+
 def check_params(params, version):
     """What the head training refuses, before a network is built: a v3 network (the reference binds no loss to YoloV3,
-    net/yolo.py:208-211) and any augmentation."""
+    net/yolo.py:208-211), any augmentation without `augment = device`, and with it a probability outside [0, 1].
+    -> the augmentation probability that will run (0.0: none)"""
     if not str(version).startswith("v2"):
         raise NotImplementedError(NOT_SUPPORTED + " for %s networks: the reference has a loss for YOLOv2 only" % version)
-    if float(params.get("augment_probability", 0)) != 0:
-        raise ValueError("augment_probability must be 0: augmentation is not built (got %s)" % params.get("augment_probability"))
+    prob = float(params.get("augment_probability", 0))
+    if not augment_option(params):
+        if prob != 0:
+            raise ValueError("augment_probability must be 0: augmentation is not built (got %s)" % params.get("augment_probability"))
+        return 0.0
+    if not 0 <= prob <= 1:
+        raise ValueError("augment_probability must be in [0, 1] with augment = device (got %s)" % params.get("augment_probability"))
+    return prob
 
 
 def make_batches(annotations, batch_size, rng):
@@ -118,12 +141,21 @@ def latest_checkpoint(checkpoint_dir, prefix):
     return best
 
 
-def batch_to_device(eng, batch):
-    """a batch of (image_path, truths) -> (uint8 device tensor [B, H, W, 3] stretched to the network input, truths per image)"""
+def batch_to_device(eng, batch, augment=None):
+    """a batch of (image_path, truths) -> (uint8 device tensor [B, H, W, 3] stretched to the network input, truths per image).
+    augment = (random.Random, probability): one record per image in batch order (net/augment.py: draw), the resized batch augmented into
+    a second buffer, the truths transformed with the same records (stretch: frame-normalised truths are input-normalised too)."""
     descs, keep = eng.frame_descs(base.decode_frames([p for p, _ in batch]))
     x = eng.preprocess_frames(descs, len(batch), _hip.RESIZE_STRETCH, u8=True)
     eng._frames_keep = keep
-    return x, [t for _, t in batch]
+    truths = [t for _, t in batch]
+    if augment is not None and augment[1] > 0:
+        from . import augment as yaug
+        h, w, _ = eng.input_hwc
+        records = [yaug.draw(augment[0], augment[1], h, w) for _ in batch]
+        x = eng.augment_u8(x, records)
+        truths = [yaug.truths(p, t, h, w) for p, t in zip(records, truths)]
+    return x, truths
 
 
 def validation_loss(eng, annotations, batch_size):
@@ -147,7 +179,7 @@ def validation_loss(eng, annotations, batch_size):
 def train_head(model, params):
     """Yolo.train with `train_layers = head`"""
     from . import evaluate as yeval
-    check_params(params, model.version)
+    augment_prob = check_params(params, model.version)
     batch_size = int(params["batch_size"])
     learning_rate = float(params["learning_rate"])
     checkpoint_prefix, checkpoint_dir = params["checkpoint_prefix"], params["checkpoint_dir"]
@@ -184,6 +216,11 @@ def train_head(model, params):
     eng.head_train_init(*split_head(body, cout, cin))       # (the moments are not part of a .weights file: they start at zero)
 
     rng = random.Random(seed)
+    augment = None
+    if augment_prob > 0:
+        from . import augment as yaug
+        augment = (yaug.stream(seed), augment_prob)
+        print("Augmentation on the device with probability {}.".format(augment_prob))
     result = eng.torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=eng.torch.uint8, device=eng.device)
     train_loss_mva, updates = None, 0
     for epoch in range(1, epochs + 1):
@@ -194,7 +231,7 @@ def train_head(model, params):
             if 0 <= max_step < step:
                 break
             updates += 1
-            x, truths = batch_to_device(eng, batch)
+            x, truths = batch_to_device(eng, batch, augment)
             eng.train_head_step_u8(x, truths, engine.adam_lr_t(learning_rate, updates), result=result)
             train_loss = np.float32(result.cpu().numpy().view(yeval.LOSS_RESULT_DTYPE)[0]["loss"])
             train_loss_mva = train_loss_mva * 0.9 + train_loss * 0.1 if train_loss_mva is not None else train_loss
