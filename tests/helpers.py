@@ -218,3 +218,178 @@ def run_hip_poisoned(net, weights, x, dtype, poison, before_pass=None, **engine_
     out = poisoned_out(eng, x.shape[0])
     eng.forward(x, out=out)
     return out.cpu().numpy(), eng
+
+
+# ---- tensors at and past the 2 GiB line (tests/large_cases.py, test_large_cpu.py, test_gpu_large.py) ---------------------------------------
+# Where a planned tensor lies: yolo_net_describe prints every kernel with its views ("out=b1[252x266x128 ld128+0]": buffer 1, H x W x C,
+# row pitch ld, first channel coff), yolo_net_workspace_regions the bytes of every buffer ("tensor 1 arena 0").  Both need no GPU.
+_VIEW_RE = r"b(-?\d+)\[(\d+)x(\d+)x(\d+) ld(\d+)\+(\d+)( f32)?\]"
+
+
+def plan_kernels(p):
+    """the kernels of a Plan from its description -> [dict(kernel, kind, layer, in=view | None, out=view, text)], a view being
+    dict(buf, h, w, c, ld, coff, f32); buf < 0: a caller's tensor"""
+    import re
+    out = []
+    for line in p.describe().splitlines():
+        m = re.match(r"\s*\[(\d+)\] (\w+) layer (\d+)", line)
+        if not m:
+            continue
+        k = dict(kernel=int(m.group(1)), kind=m.group(2), layer=int(m.group(3)), text=line.strip())
+        k["in"] = k["out"] = None
+        for key in ("in", "out"):
+            v = re.search(r"\b%s=%s" % (key, _VIEW_RE), line)
+            if v:
+                k[key] = dict(zip(("buf", "h", "w", "c", "ld", "coff"), (int(t) for t in v.groups()[:6])), f32=v.group(7) is not None)
+        out.append(k)
+    assert len(out) == p.num_kernels, (len(out), p.num_kernels)
+    return out
+
+
+def layer_view(p, layer):
+    """the view a layer's values are stored in: the output view of the (last) kernel that writes for it"""
+    ks = [k for k in plan_kernels(p) if k["layer"] == layer and k["out"] is not None and k["out"]["buf"] >= 0]
+    assert ks, "layer %r has no kernel that writes it into the workspace in this plan\n%s" % (layer, p.describe())
+    return ks[-1]["out"]
+
+
+def buffer_region(p, buf, arena=0):
+    """(offset, used bytes, region bytes) of a planned buffer in the workspace"""
+    name = "tensor %d arena %d" % (buf, arena)
+    found = [(off, used, region) for n, off, used, region in p.workspace_regions() if n == name]
+    assert len(found) == 1, (name, found)
+    return found[0]
+
+
+def view_esize(p, view):
+    from tensorflow_yolo_amd import _hip
+    return 4 if view["f32"] or p.dtype == _hip.DTYPE_F32 else 2
+
+
+def view_image_bytes(p, view):
+    """S of a planned tensor: bytes from one image to the next (the WHOLE buffer's pitch where the view is a channel slice); every
+    buffer of a plan is sized for max_batch images (per arena: plans of one part only)"""
+    off, used, region = buffer_region(p, view["buf"])
+    assert used % p.max_batch == 0, (used, p.max_batch)
+    return used // p.max_batch
+
+
+def buffer_is_alone(p, buf):
+    """no other region's payload overlaps this buffer's (always so under keep_all; in a lifetime-packed plan only for some): only then do its
+    bytes still hold after the pass what its kernel wrote"""
+    off, used, _ = buffer_region(p, buf)
+    name = "tensor %d arena 0" % buf
+    return all(n == name or not u or o + u <= off or o >= off + used for n, o, u, _ in p.workspace_regions())
+
+
+def layer_tensor(eng, layer, batch, side="out"):
+    """a typed, strided view [batch, H, W, C] of a layer's values in the engine's workspace (no copy) and where it lies: dict(image_bytes,
+    ld, coff, esize, w).  side = "in": what the layer's kernel READS instead (the whole concat buffer behind a route)"""
+    import torch
+    v = layer_view(eng, layer) if side == "out" else [k for k in plan_kernels(eng) if k["layer"] == layer][0]["in"]
+    assert v["buf"] >= 0 and buffer_is_alone(eng, v["buf"]), "layer %d: no view possible\n%s" % (layer, eng.describe())
+    off, used, _ = buffer_region(eng, v["buf"])
+    es = view_esize(eng, v)
+    isb = view_image_bytes(eng, v)
+    assert isb % es == 0 and v["h"] * v["w"] * v["ld"] * es <= isb and v["coff"] + v["c"] <= v["ld"], (v, isb)
+    t = eng._workspace[off:off + batch * isb].view(torch.float32 if es == 4 else torch.float16).view(batch, isb // es)
+    t = t[:, :v["h"] * v["w"] * v["ld"]].view(batch, v["h"], v["w"], v["ld"])[..., v["coff"]:v["coff"] + v["c"]]
+    return t, dict(image_bytes=isb, ld=v["ld"], coff=v["coff"], esize=es, w=v["w"])
+
+
+def large_batch(x, batch):
+    """distinct images [D, ...] (NumPy) -> the batch on the device by an index gather: image n is distinct image n mod D"""
+    import torch
+    xd = torch.tensor(np.asarray(x)).cuda()                 # (a copy: the reference's arrays are read-only)
+    return xd[torch.arange(batch, device=xd.device) % xd.shape[0]]
+
+
+LARGE_CHUNK = 1 << 25       # elements compared at a time: the comparison holds a few hundred MB beside the tensors
+
+
+def large_difference(got, want):
+    """got: a device tensor [B, H, W, C] of any strides; want: the D expected images as a NumPy float32 array [D, H, W, C].  Element (n, y, x, c)
+    must equal want[n mod D, y, x, c] BIT for bit (compared as integers: a NaN that nothing overwrote differs, -0 differs from 0).  Runs on the device
+    in chunks of whole images, over the whole tensor, torch.equal per chunk.  None when equal, else the FIRST differing element in
+    memory order: dict(index=(n, y, x, c), got, want, differing = how many of its chunk differ, chunk = (first image, images))."""
+    import torch
+    assert got.dim() == 4 and tuple(got.shape[1:]) == tuple(want.shape[1:]), (tuple(got.shape), want.shape)
+    D = want.shape[0]
+    wd = torch.tensor(np.asarray(want, np.float32)).to(got.device)
+    if got.dtype == torch.float16:
+        w16 = wd.to(torch.float16)
+        assert torch.equal(w16.to(torch.float32), wd), "the expected values are not fp16 values"
+        wd = w16
+    bits = torch.int16 if got.dtype == torch.float16 else torch.int32
+    gi, wi = got.view(bits), wd.view(bits)
+    per = int(np.prod(got.shape[1:]))
+    step = max(1, LARGE_CHUNK // per)
+    for n0 in range(0, got.shape[0], step):
+        n1 = min(got.shape[0], n0 + step)
+        e = wi[torch.arange(n0, n1, device=got.device) % D]
+        g = gi[n0:n1]
+        if torch.equal(g, e):
+            continue
+        ne = g != e
+        flat = int(ne.view(-1).to(torch.int32).argmax())         # (the first maximum: the first differing element)
+        n, y, x, c = (int(v) for v in np.unravel_index(flat, tuple(ne.shape)))
+        return dict(index=(n0 + n, y, x, c), got=float(got[n0 + n, y, x, c]), want=float(want[(n0 + n) % D, y, x, c]),
+                    differing=int(ne.sum()), chunk=(n0, n1 - n0))
+    return None
+
+
+def large_offset(index, where, shape):
+    """byte offset of element (n, y, x, c) inside its tensor: from the first byte of the planned buffer (where = layer_tensor's dict), or of
+    the caller's dense float32 tensor (where = None)"""
+    n, y, x, c = index
+    if where is None:
+        return int(np.ravel_multi_index((n, y, x, c), shape)) * 4
+    return n * where["image_bytes"] + ((y * where["w"] + x) * where["ld"] + where["coff"] + c) * where["esize"]
+
+
+def large_report(diff, what, where, shape, kernel):
+    """what a failed comparison says: the case and layer, the first differing element, its byte offset and which lines it is past, the kernel"""
+    off = large_offset(diff["index"], where, shape)
+    return ("%s: first difference at (image, y, x, channel) = %s: got %r, want %r; byte offset %d inside the tensor (%s 2^31, %s 2^32); %d of the "
+            "elements of images %d..%d differ; written by kernel %s [%s]"
+            % (what, diff["index"], diff["got"], diff["want"], off, "AT OR PAST" if off >= 1 << 31 else "below", "AT OR PAST" if off >= 1 << 32 else "below",
+               diff["differing"], diff["chunk"][0], diff["chunk"][0] + diff["chunk"][1] - 1, kernel[0], kernel[1]))
+
+
+def assert_large_equal(got, want, what, where, kernel):
+    diff = large_difference(got, want)
+    assert diff is None, large_report(diff, what, where, tuple(got.shape), kernel)
+
+
+def kernel_of_layer(infos, layer):
+    """(name, symbol) of the kernel that computes a layer, from yolo_net_kernel_info records: the first with a launch of its own (the
+    conversion of the last layer to float32 comes behind it under the same layer)"""
+    ks = [(ki.name.decode(), ki.symbol.decode()) for ki in infos if ki.layer == layer]
+    assert ks, layer
+    launched = [k for k in ks if k[1]]
+    return (launched or ks)[0]
+
+
+def assert_slack_intact(eng, value, what):
+    """guarded_run's check for a workspace filled with `value` bytes: every byte no plan region claims as payload still holds it"""
+    regions = eng.workspace_regions()
+    payload = sorted((off, off + used) for _, off, used, _ in regions if used)
+    checked = 0
+    for name, off, used, region in regions:
+        lo, hi = off + used, off + region
+        spans, cur = [], lo
+        for a, b in payload:
+            if b <= cur or a >= hi:
+                continue
+            if a > cur:
+                spans.append((cur, a))
+            cur = max(cur, b)
+            if cur >= hi:
+                break
+        if cur < hi:
+            spans.append((cur, hi))
+        for a, b in spans:
+            bad = (eng._workspace[a:b] != value).nonzero()
+            assert bad.numel() == 0, "%s: %s: byte %d behind the payload of a %d-byte region was written" % (what, name, int(bad[0]) + a - lo, used)
+            checked += b - a
+    return checked
