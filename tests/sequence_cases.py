@@ -1,0 +1,359 @@
+"""The call sequences of tests/test_gpu_sequences.py, as a table that needs no GPU (tests/test_sequences_cpu.py keeps it honest).
+
+The rule under test: the result of call i of a sequence equals, bit for bit, the result of the same call on a TWIN -- an engine built the
+same way that has executed only the CHANGING calls in front of i, in order, and then this call.  PURE calls (forward, forward_u8,
+forward_timed, detect / detect_u8 at 0.5, 0.05 and 0.9999 in both NMS modes, detect_frames, loss, loss_u8, loss_grad, a refused call) must
+leave nothing behind that a later call can observe; changing calls (a train step, head_train_init, load_weights, a re-bind onto a poisoned
+buffer, set_streams, autotune, tune_streams) are what a twin replays.  twin_key(sequence, i) is the key a twin's result is cached under.
+
+A call is a tuple: (kind, lo, n) runs on images lo .. lo + n - 1 of the plan's four distinct images, ("refuse", what) is a call the library
+must refuse (REFUSALS), a changing call is (kind, ...) of CHANGING.  Every list below is a constant: the walks are generated at import by
+a fixed algorithm and a fixed seed, nothing is drawn while the tests run.
+
+Two claims are built into twin_key and are therefore asserted by every comparison behind them: yolo_net_load_weights of the ORIGINAL
+stream takes the net back to the bytes of a net that never trained, and yolo_net_head_train_init starts the training state again (a
+train step behind it equals the first step)."""
+import functools
+import random
+
+import poison_cases as P
+from tensorflow_yolo_amd import _hip
+
+MAX_BATCH = 4
+N_IMAGES = 4
+IOU = 0.6
+TWIN_KEY_CAP = 112           # distinct twin keys per plan, over all its sequences: each is one engine built and one call (GPU time)
+
+# ---- call kinds --------------------------------------------------------------------------------------------------------------------------
+# kind -> (engine method, threshold, NMS mode)
+DETECT = {"detect@0.5": ("detect", 0.5, _hip.NMS_AGNOSTIC), "detect@0.5/per-class": ("detect", 0.5, _hip.NMS_PER_CLASS),
+          "detect@0.05": ("detect", 0.05, _hip.NMS_AGNOSTIC), "detect@0.05/per-class": ("detect", 0.05, _hip.NMS_PER_CLASS),
+          "detect@0.9999": ("detect", 0.9999, _hip.NMS_AGNOSTIC), "detect@0.9999/per-class": ("detect", 0.9999, _hip.NMS_PER_CLASS),
+          "detect_u8@0.5": ("detect_u8", 0.5, _hip.NMS_AGNOSTIC), "detect_frames@0.5": ("detect_frames", 0.5, _hip.NMS_AGNOSTIC)}
+FORWARD = ("forward", "forward_u8", "forward_timed")
+LOSS = ("loss", "loss_u8", "loss_grad")
+REFUSE = "refuse"
+CHANGING = ("train", "train_u8", "head_train_init", "load_weights", "rebind", "set_streams", "autotune", "tune_streams")
+V3_KINDS = FORWARD + tuple(DETECT) + (REFUSE,)
+V2_KINDS = FORWARD + tuple(DETECT) + LOSS + (REFUSE,)
+SWITCH_KINDS = ("forward", "forward_u8", "forward_timed", "detect@0.5", "detect@0.05/per-class", "detect@0.9999", REFUSE)
+
+# what -> (status code, a part of yolo_last_error): include/yolo_hip.h, csrc/api.cpp
+ERR_ARG, ERR_STATE = 1, 5
+REFUSALS = {"batch+1": (ERR_ARG, "batch outside 1..max_batch"),
+            "loss-on-v3": (ERR_ARG, "the head must be version 2"),
+            "loss_grad-on-v3": (ERR_ARG, "the head must be version 2"),
+            "set_streams(3)": (ERR_STATE, "yolo_net_set_streams"),
+            "train-null-state": (ERR_ARG, "null state"),
+            "train-two-parts": (ERR_STATE, "call yolo_net_set_streams(net, 1)"),
+            "set_streams(1)-split-arenas": (ERR_STATE, "part(s) only")}
+V3_REFUSALS = ("batch+1", "loss-on-v3", "set_streams(3)", "loss_grad-on-v3")
+V2_REFUSALS = ("batch+1", "set_streams(3)", "train-null-state")
+
+# truths of the four images (x, y, w, h, class): one image has none
+TRUTHS = [[(0.3, 0.4, 0.2, 0.5, 1), (0.8, 0.2, 0.3, 0.3, 2)], [], [(0.5, 0.5, 0.6, 0.4, 7)],
+          [(0.2, 0.7, 0.15, 0.25, 3), (0.6, 0.3, 0.4, 0.5, 0), (0.9, 0.9, 0.1, 0.1, 12)]]
+MAX_GT = 3
+FRAME_SIZES = ((120, 90), (75, 200), (64, 64), (50, 131))     # detect_frames: frame i of the plan's four, letterboxed
+LR = 1e-3
+
+
+def is_changing(call):
+    return call[0] in CHANGING
+
+
+def is_pure(call):
+    return not is_changing(call)
+
+
+def is_sparse_detect(call):
+    """a detect whose head convs skip rows below the threshold's logit (api.cpp detect_any: thresholds inside (0, 1 - 1e-4))"""
+    return call[0] in DETECT and 0.0 < DETECT[call[0]][1] < 1.0 - 1e-4
+
+
+def batch_of(call):
+    """images of a call, None where it has none (a refusal, a call that takes no batch)"""
+    return call[2] if call[0] != REFUSE and len(call) >= 3 else None
+
+
+def twin_key(sequence, i):
+    """(the changing calls a twin executes first, in order; the call itself).  load_weights of the original stream drops every training
+    call in front of it (and itself: the net is as it was loaded); head_train_init drops the training calls in front of it."""
+    prefix = []
+    for c in sequence[:i]:
+        if not is_changing(c):
+            continue
+        if c[0] in ("load_weights", "head_train_init"):
+            prefix = [p for p in prefix if p[0] not in ("train", "train_u8", "head_train_init")]
+        if c[0] != "load_weights":
+            prefix.append(c)
+    return tuple(prefix), sequence[i]
+
+
+# ---- plans -------------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def switch_max_batch(net="v3", dtype="fp16"):
+    """the smallest max_batch at which streams = 0 (the library's rule) plans two full arenas for the network at the table's input size:
+    read from engine.Plan (yolo_net_set_streams(net, 1) is accepted only by such a plan), found by doubling and bisection"""
+    from tensorflow_yolo_amd.net import engine
+
+    def two(mb):
+        p = engine.Plan(P.create_network(net), dtype=dtype, max_batch=mb, streams=0)
+        ok = p.num_streams == 2 and p.lib.yolo_net_set_streams(p.handle, 1) == 0
+        p.close()
+        return ok
+    hi = 2
+    while not two(hi):
+        hi *= 2
+        assert hi <= 4096, "the rule never plans two full arenas for %s %s" % (net, dtype)
+    lo = hi // 2            # (not two, or hi == 2)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if two(mid) else (mid, hi)
+    return hi
+
+
+PLANS = {}      # id -> dict(pid = row of poison_cases.PLANS, more = engine options over that row's, kinds, refusals, train, streams)
+
+
+def _plan(sid, pid, kinds, refusals, train=False, streams=1, max_batch=MAX_BATCH):
+    PLANS[sid] = dict(pid=pid, more={"streams": streams, "max_batch": max_batch}, kinds=kinds, refusals=refusals, train=train, streams=streams)
+
+
+_plan("v2-fp16", "v2-fp16-plan", V2_KINDS, V2_REFUSALS, train=True)
+_plan("v2-fp32", "v2-fp32-plan", V2_KINDS, V2_REFUSALS, train=True)
+_plan("v2-tiny-fp16", "v2-tiny-fp16-plan", V2_KINDS, V2_REFUSALS)
+_plan("v3-fp16", "v3-fp16-plan", V3_KINDS, V3_REFUSALS)
+_plan("v3-mxfp8", "v3-mxfp8-plan", V3_KINDS, V3_REFUSALS)
+_plan("v3-spp-fp16", "v3-spp-fp16-plan", V3_KINDS, V3_REFUSALS)
+_plan("v3-tiny-fp32", "v3-tiny-fp32-plan", V3_KINDS, V3_REFUSALS)
+# streams = 0 at the smallest max_batch where the rule plans two full arenas: the plan yolo_net_set_streams can switch (max_batch: None
+# until asked for -- plan_kw -- since finding it plans the network a dozen times)
+_plan("v3-fp16-switch", "v3-fp16-plan", SWITCH_KINDS, ("batch+1", "set_streams(3)"), streams=0, max_batch=None)
+# YOLOv2 is never given two arenas by the rule (fewer than 40 conv launches), so its two-part plan is one with streams = 2: split arenas,
+# which yolo_net_set_streams cannot switch.  The train step is refused there; that it is accepted after set_streams(1) cannot be shown.
+_plan("v2-fp16-two-parts", "v2-fp16-plan", ("forward", "detect@0.5", "loss", REFUSE), ("train-two-parts", "set_streams(1)-split-arenas"), streams=2)
+
+
+def plan_kw(sid):
+    """engine options of a plan over its poison_cases row"""
+    more = dict(PLANS[sid]["more"])
+    if more["max_batch"] is None:
+        more["max_batch"] = switch_max_batch()
+    return more
+
+
+def build_model(sid, weights=None, **more):
+    return P.build_model(PLANS[sid]["pid"], weights=weights, **dict(plan_kw(sid), **more))
+
+
+def plan_only(sid):
+    from tensorflow_yolo_amd.net import engine
+    p = P.PLANS[PLANS[sid]["pid"]]
+    kw = plan_kw(sid)
+    return engine.Plan(P.create_network(p["net"]), dtype=p["dtype"], max_batch=kw["max_batch"], keep_all=p["keep_all"], streams=kw["streams"])
+
+
+# ---- batches: slices of the four images ---------------------------------------------------------------------------------------------------
+SLICES = ((0, 1), (0, 2), (0, 3), (0, 4), (2, 2), (1, 3), (3, 1), (1, 2))
+
+
+def variants(kinds, kind):
+    """the two slices a kind runs on in the walks: different batch sizes, spread over the table by the kind's place in the plan's list"""
+    j = kinds.index(kind)
+    a = SLICES[j % len(SLICES)]
+    b = next(s for k in range(1, len(SLICES)) for s in [SLICES[(j + 3 * k) % len(SLICES)]] if s[1] != a[1])
+    return a, b
+
+
+def _call(sid, kind, which):
+    pl = PLANS[sid]
+    if kind == REFUSE:
+        return (REFUSE, pl["refusals"][which % len(pl["refusals"])])
+    lo, n = variants(pl["kinds"], kind)[which % 2]
+    return (kind, lo, n)
+
+
+def euler_kinds(kinds):
+    """a closed walk over the kinds in which every ordered pair (a, b), a == b included, is adjacent exactly once: an Euler circuit of the
+    complete directed graph with loops (Hierholzer, edges taken in the order of the list)"""
+    k = len(kinds)
+    nxt = [0] * k
+    stack, out = [0], []
+    while stack:
+        v = stack[-1]
+        if nxt[v] < k:
+            stack.append((v + 1 + nxt[v]) % k)      # (the loop edge v -> v comes last)
+            nxt[v] += 1
+        else:
+            out.append(stack.pop())
+    out.reverse()
+    return [kinds[v] for v in out]
+
+
+def _with_batches(sid, kind_walk, prev_n=None):
+    """kinds -> calls: of a kind's two slices the one whose batch differs from its predecessor's (both differ: the two in turn)"""
+    pl = PLANS[sid]
+    used, out = {}, []
+    for kind in kind_walk:
+        if kind == REFUSE:
+            out.append(_call(sid, kind, used.get(kind, 0)))
+            used[kind] = used.get(kind, 0) + 1
+            continue
+        a, b = variants(pl["kinds"], kind)
+        ok = [s for s in (a, b) if s[1] != prev_n]
+        s = ok[used.get(kind, 0) % len(ok)]
+        used[kind] = used.get(kind, 0) + 1
+        out.append((kind, s[0], s[1]))
+        prev_n = s[1]
+    return out
+
+
+def _next(sid, kind, prev, other_images=False, small=False):
+    """a call of `kind` at a batch size different from prev's (other_images: on images prev's call did not see as well): one of the kind's
+    two slices where one fits -- no twin of its own then --, else the first slice of the table that does"""
+    fits = lambda v: v[1] != prev[2] and (not other_images or not (prev[1] <= v[0] and v[0] + v[1] <= prev[1] + prev[2]))
+    own = [v for v in variants(PLANS[sid]["kinds"], kind) if fits(v)]
+    if small:       # (the call in front of an `other_images` step: not the whole set of images)
+        own = [v for v in sorted(own, key=lambda v: v[1]) if v[1] < N_IMAGES]
+    return (kind,) + (own + [v for v in SLICES if fits(v) and v[1] < N_IMAGES])[0]
+
+
+def named_prologue(sid):
+    """the leaks the issue names, each at a batch size different from its predecessor's: detect at 0.5 -> forward (obj_min_logit);
+    detect at 0.5 -> detect at 0.05 on OTHER images (rows the first did not write); 0.9999 <-> 0.5; loss -> detect -> loss_grad;
+    forward_timed -> detect (obj_valid, halves)"""
+    kinds = PLANS[sid]["kinds"]
+    chain = [("detect@0.5", False), ("forward", False), ("detect@0.5", "small"), ("detect@0.05", True), ("detect@0.9999", False), ("detect@0.5", False),
+             ("detect@0.9999", False)]
+    if "loss" in kinds:
+        chain += [("loss", False), ("detect@0.5", False), ("loss_grad", False)]
+    chain += [("forward_timed", False), ("detect@0.5", False)]
+    out = [("detect@0.5",) + variants(kinds, "detect@0.5")[0]]
+    for kind, other in chain[1:]:
+        out.append(_next(sid, kind, out[-1], other is True, other == "small"))
+    return out
+
+
+def cover_walk(sid):
+    pro = named_prologue(sid)
+    return pro + _with_batches(sid, euler_kinds(list(PLANS[sid]["kinds"])), prev_n=pro[-1][2] if pro else None)
+
+
+def all_calls(sid):
+    """every (kind, slice) of a plan's pure calls, and its refusals"""
+    pl = PLANS[sid]
+    out = []
+    for kind in pl["kinds"]:
+        if kind == REFUSE:
+            out += [(REFUSE, w) for w in pl["refusals"]]
+        else:
+            out += [(kind, lo, n) for lo, n in variants(pl["kinds"], kind)]
+    return out
+
+
+def random_walk(sid, seed=0, length=24):
+    rng = random.Random("%s/%d" % (sid, seed))
+    pool = all_calls(sid)
+    return [pool[rng.randrange(len(pool))] for _ in range(length)]
+
+
+def each_pure(sid, which):
+    """every pure kind of the plan once, on its slice `which`"""
+    return [_call(sid, kind, which) for kind in PLANS[sid]["kinds"]]
+
+
+SEQUENCES = {}      # plan id -> {name: [calls]}
+MAIN = ("v2-fp16", "v2-fp32", "v2-tiny-fp16", "v3-fp16", "v3-mxfp8", "v3-spp-fp16", "v3-tiny-fp32")
+for _sid in MAIN:
+    SEQUENCES[_sid] = {"cover": cover_walk(_sid), "random": random_walk(_sid)}
+
+# 3. training (YOLOv2 fp16 and fp32), in three items so that none builds more than one round of twins
+for _sid in ("v2-fp16", "v2-fp32"):
+    _start = [("head_train_init",), ("train", 0, 3, 1)]
+    SEQUENCES[_sid]["train-1"] = _start + each_pure(_sid, 0)
+    SEQUENCES[_sid]["train-2"] = _start + [("forward", 0, 2), ("train", 0, 4, 2)] + each_pure(_sid, 1)
+    SEQUENCES[_sid]["train-u8-load-init"] = (_start + [("detect@0.5", 0, 2), ("train_u8", 1, 2, 2)] + each_pure(_sid, 0)
+                                             + [("load_weights",)] + each_pure(_sid, 0) + each_pure(_sid, 1)       # back to the untrained twins
+                                             + [("head_train_init",), ("train", 0, 3, 1)] + each_pure(_sid, 0))    # the first step again
+
+# 5. a re-bind onto an 0xFF-filled buffer in the middle of a walk
+for _sid in ("v2-fp16", "v3-fp16", "v3-tiny-fp32"):
+    SEQUENCES[_sid]["rebind"] = SEQUENCES[_sid]["random"][:8] + [("rebind",)] + each_pure(_sid, 1) + [("detect@0.05", 0, 4), ("forward", 0, 1)]
+
+# 6. refusals in the middle of a walk: every refusal of the plan between two calls of the covering walk's set
+for _sid in MAIN:
+    _seq = []
+    for _i, _w in enumerate(PLANS[_sid]["refusals"]):
+        _seq += [_call(_sid, ("detect@0.5", "forward", "detect@0.05/per-class")[_i % 3], _i), (REFUSE, _w), _call(_sid, ("forward", "detect@0.5", "forward_u8")[_i % 3], _i + 1)]
+    SEQUENCES[_sid]["refusals"] = _seq
+
+
+# 4. the plan yolo_net_set_streams can switch: a full batch and one image more than half of it run as two parts, 4, 2 and 3 images as one
+def switch_sequence(mb):
+    body = [("forward", 0, mb), ("detect@0.5", 0, mb // 2 + 1), ("forward", 0, 4), ("detect@0.5", 0, 2), ("detect@0.05/per-class", 0, 3), ("forward_timed", 0, 2),
+            (REFUSE, "set_streams(3)"), ("forward_u8", 0, 4), ("detect@0.9999", 0, 3)]
+    return [("set_streams", 2)] + body + [("set_streams", 1)] + body + [("set_streams", 2)] + body
+
+
+SEQUENCES["v2-fp16-two-parts"] = {"refused-train": [("forward", 0, 4), (REFUSE, "train-two-parts"), ("forward", 0, 4), ("detect@0.5", 0, 3),
+                                                    (REFUSE, "set_streams(1)-split-arenas"), ("detect@0.5", 0, 3), ("loss", 0, 4), (REFUSE, "train-two-parts"),
+                                                    ("loss", 0, 4), ("forward", 0, 1)]}
+ALL_PLANS = MAIN + ("v3-fp16-switch", "v2-fp16-two-parts")
+
+
+def sequences_of(sid):
+    if sid == "v3-fp16-switch" and sid not in SEQUENCES:        # (planned a dozen times to find its max_batch: when first asked for)
+        SEQUENCES[sid] = {"switch": switch_sequence(switch_max_batch())}
+    return SEQUENCES[sid]
+
+
+# One pytest item per (plan, sequence, part).  A part runs its sequence from the start to its own end and compares the calls from its own
+# start on: the parts of a sequence together compare every call of it, and each part meets at most TWINS_PER_ITEM twin keys that no part
+# in front of it (in the order of this list) has met -- the twins it has to build, which is where an item's time goes.
+TWINS_PER_ITEM = 8
+
+
+def items():
+    out = []
+    for sid in ALL_PLANS:
+        met = set()
+        for name, seq in sequences_of(sid).items():
+            start, new, part = 0, 0, 1
+            for i in range(len(seq)):
+                key = twin_key(seq, i)
+                fresh = key not in met and not (is_changing(seq[i]) and seq[i][0] not in ("train", "train_u8"))
+                if fresh and new == TWINS_PER_ITEM:
+                    out.append((sid, name, part, start, i))
+                    start, new, part = i, 0, part + 1
+                if fresh:
+                    met.add(key)
+                    new += 1
+            out.append((sid, name, part, start, len(seq)))
+    return out
+
+
+ITEMS = items()
+
+# 8. two engines of different plans alive at once, their calls interleaved on one stream: (plan, call)
+PAIR = ("v3-fp16", "v2-tiny-fp16")
+INTERLEAVED = [(PAIR[i % 2], c) for i, c in enumerate(
+    x for pair in zip(SEQUENCES[PAIR[0]]["random"][:12], SEQUENCES[PAIR[1]]["random"][:12]) for x in pair)]
+
+# 9. the covering walk without any host synchronisation between the calls
+ASYNC_PLANS = ("v2-fp16", "v3-fp16")
+
+# 7. exact chains (tests/test_gpu_exact.py's list; integer data: every tile and every split must give the integer reference), each run as
+# forward (1 image) -> autotune -> forward (3) -> tune_streams -> forward (2) -> forward_u8 -> forward (3) at max_batch 3
+EXACT_CHAINS = {"conv-c256to512_linear_bias-fp16-tdef": dict(variant="pool", feature=",1launch"),         # a ticketed split-K conv
+                "stem-3-32-64-32-3x40x56": dict(variant=None, feature="conv_stem<f16,3-32-64-32>")}       # the stem
+EXACT_BATCH = 3
+EXACT_STEPS = (("forward", 0, 1), ("autotune", 0, 3), ("forward", 0, 3), ("tune_streams", 0, 3), ("forward", 0, 2), ("forward_u8", 0, 3), ("forward", 0, 3))
+
+
+def twin_keys(sid):
+    """the distinct twin keys of all sequences of a plan (the interleaved and the unsynchronised walks use calls of these sequences)"""
+    keys = set()
+    for seq in sequences_of(sid).values():
+        keys.update(twin_key(seq, i) for i in range(len(seq)))
+    return keys

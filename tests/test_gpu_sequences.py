@@ -1,0 +1,409 @@
+"""GPU: a net's answers must not depend on the calls before them.
+
+A yolo_net carries state from one call to the next -- on the host (obj_min_logit, obj_valid, cand_clean, side_ok, parts / halves, the
+tiles autotune chose, the head's packed weights) and on the device (split-K ticket counters, candidate counters, the logits region with
+rows a sparse detect did not write, the compact objectness array, split-K slabs, the lifetime-packed arenas, the fork / join events).
+Every other GPU test asks its question of a freshly built engine.  Here whole sequences of calls run on ONE engine (tests/sequence_cases.py
+has the table and the rule, tests/test_sequences_cpu.py its properties), and the result of every call is compared, bit for bit, with the
+result of the same call on a TWIN: a fresh engine that has executed only the changing calls in front of it.  Twins are cached per module
+by sequence_cases.twin_key; every twin is closed as soon as its one result is on the host, every other engine when the module ends.
+
+What is compared: logits and gradients as bytes; counts, status and the first counts[n] records of every image of a detect; the named
+fields of the loss records; the result and the six state arrays of a train step; the status code and message of a refused call.
+
+A control comes first, per plan: two fresh twins making the same call give the same bytes.  If it fails the finding is NON-DETERMINISM,
+not call order, and the plan's sequences stop there.
+
+How to read a failure: it names the plan and the sequence, the index and the call, the call in front of it (and whether that was a sparse
+detect: head rows below the threshold's logit not written) and the last changing call, and the first differing (image, row, column) or
+record.  The call in front is the suspect; the state it may have left is listed in DESIGN.md section 5, "Call order"."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import exact_ref as X
+import poison_cases as P
+import sequence_cases as S
+import test_gpu_exact as E
+from helpers import poison_and_bind, poisoned_out
+from tensorflow_yolo_amd import _hip
+from tensorflow_yolo_amd.net import engine, evaluate as yeval, synth, train as ytrain
+
+pytestmark = pytest.mark.gpu
+
+CALIBRATION = {"v2": 1, "v2-tiny": 1, "v3": 8, "v3-spp": 8, "v3-tiny": 10}        # x synth.HEAD_DEFAULTS' fraction, as the detect tests of these sizes use
+RIGS, TWINS, CONTROL, ENGINES = {}, {}, {}, []
+STATE_KEYS = ("w", "b", "m_w", "v_w", "m_b", "v_b")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def close_engines():
+    yield
+    import torch
+    torch.cuda.synchronize()
+    for eng in ENGINES:
+        eng.close()
+    del ENGINES[:]
+    RIGS.clear()
+    TWINS.clear()
+
+
+# ---- a plan's data: weights, the four images, truths, frames -----------------------------------------------------------------------------
+class Rig(object):
+    def __init__(self, sid):
+        import torch
+        pl = S.PLANS[sid]
+        row = P.PLANS[pl["pid"]]
+        self.sid, self.net = sid, row["net"]
+        cls, anchors, names, (h, w) = P.NETS[self.net]
+        rng = np.random.RandomState(45)
+        self.x8 = rng.randint(0, 256, size=(S.N_IMAGES, h, w, 3)).astype(np.uint8)
+        self.xf = (self.x8 / 255.).astype(np.float32)
+        self.weights = calibrated(pl["pid"])
+        self.max_batch = S.plan_kw(sid)["max_batch"]
+        self.xd, self.x8d = torch.from_numpy(self.xf).cuda(), torch.from_numpy(self.x8).cuda()
+        gt, counts = yeval.pack_gts(S.TRUTHS, S.MAX_GT)
+        self.gt_dev = torch.from_numpy(np.ascontiguousarray(gt).view(np.uint8).reshape(S.N_IMAGES, -1)).cuda()
+        self.gc_dev = torch.from_numpy(counts).cuda()
+        self.frames = [torch.from_numpy(rng.randint(0, 256, size=s + (3,)).astype(np.uint8)).cuda() for s in S.FRAME_SIZES]
+        self.big = {}
+        self.dummy = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")     # arguments of refused calls: never read or written
+        if pl["train"]:
+            cout, cin = ytrain.head_counts(P.create_network(self.net))[:2]
+            self.head = ytrain.split_head(self.weights, cout, cin)
+
+    def images(self, lo, n, u8=False):
+        """images lo .. lo + n - 1 on the device; more than the four distinct ones (the switchable plan): image i is distinct image i mod 4"""
+        import torch
+        src = self.x8d if u8 else self.xd
+        if lo + n <= S.N_IMAGES:
+            return src[lo:lo + n]
+        if (n, u8) not in self.big:
+            self.big[(n, u8)] = src[torch.arange(n, device=src.device) % S.N_IMAGES].contiguous()
+        return self.big[(n, u8)]
+
+    def gts(self, lo, n):
+        return self.gt_dev[lo:lo + n], self.gc_dev[lo:lo + n]
+
+
+@functools.lru_cache(maxsize=None)
+def calibrated(pid):
+    """the synthetic stream of the row's network with its objectness biases re-centred on the four images (synth.calibrate_model), so that
+    the detect calls find boxes to compare (control); a pure function of the row"""
+    row = P.PLANS[pid]
+    cls, anchors, names, (h, w) = P.NETS[row["net"]]
+    x8 = np.random.RandomState(45).randint(0, 256, size=(S.N_IMAGES, h, w, 3)).astype(np.uint8)
+    model = P.build_model(pid, weights=P.weights_of(row["net"]), max_batch=S.MAX_BATCH, streams=1)
+    w_ = synth.calibrate_model(model, (x8 / 255.).astype(np.float32), CALIBRATION[row["net"]] * synth.HEAD_DEFAULTS[cls.version][1])
+    model.net.engine.close()
+    w_.setflags(write=False)
+    return w_
+
+
+def rig(sid):
+    if sid not in RIGS:
+        RIGS[sid] = Rig(sid)
+    return RIGS[sid]
+
+
+def new_engine(sid, keep=True):
+    """a fresh engine of the plan with the rig's weights.  The stream count never comes from a measurement here: the one-off tuning of a
+    streams = 0 engine is switched off, the sequences call yolo_net_set_streams themselves"""
+    model = S.build_model(sid, weights=rig(sid).weights)
+    eng = model.net.engine
+    eng._streams_tuned = True
+    eng.sid = sid
+    if keep:
+        ENGINES.append(eng)
+    return eng
+
+
+# ---- running a call ------------------------------------------------------------------------------------------------------------------------
+def refuse(r, eng, what):
+    """a call the library must refuse, through the C ABI -> (status, message).  Every one of them is refused on the host before any device
+    call (api.cpp), so the buffers behind the pointers are never touched; they are large enough all the same."""
+    import torch
+    lib, h, st = eng.lib, eng.handle, eng._stream()
+    d = r.dummy.data_ptr()
+    x1 = r.images(0, 1)
+    gt, gc = r.gts(0, 1)
+    if what == "batch+1":
+        n = r.max_batch + 1
+        out = torch.empty((n,) + tuple(eng.output_shape), dtype=torch.float32, device="cuda")
+        rc = lib.yolo_net_forward(h, r.images(0, n).data_ptr(), n, out.data_ptr(), st)
+    elif what == "loss-on-v3":
+        rc = lib.yolo_net_loss(h, x1.data_ptr(), 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, d, None, d + 4096, st)
+    elif what == "loss_grad-on-v3":
+        rc = lib.yolo_v2_loss_grad(C.byref(eng.head), d, 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, d + 4096, d + 8192, d + 12288, d + 16384, st)
+    elif what == "set_streams(3)":
+        rc = lib.yolo_net_set_streams(h, 3)
+    elif what == "set_streams(1)-split-arenas":
+        rc = lib.yolo_net_set_streams(h, 1)
+    elif what in ("train-null-state", "train-two-parts"):
+        state = None if what == "train-null-state" else d + 256 - d % 256
+        rc = lib.yolo_net_train_head_step(h, x1.data_ptr(), 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, state, float(S.LR), d + 32768, st)
+    else:
+        raise ValueError(what)
+    return int(rc), (lib.yolo_last_error() or b"").decode()
+
+
+def enqueue(r, eng, call):
+    """one pure call on the current stream, nothing else: no host synchronisation, results that live in engine-held tensors cloned on the
+    stream -> {name: device tensor | host value}"""
+    import torch
+    kind = call[0]
+    if kind == S.REFUSE:
+        rc, msg = refuse(r, eng, call[1])
+        want = S.REFUSALS[call[1]]
+        assert rc == want[0] and want[1] in msg, "%r: status %d (%r), the documented refusal is status %d with %r" % (call, rc, msg, want[0], want[1])
+        return {"status": np.array([rc], np.int32)}
+    lo, n = call[1], call[2]
+    if kind in ("forward", "forward_u8", "forward_timed"):
+        x = r.images(lo, n, kind == "forward_u8")
+        # an output tensor of 0xFF (NaN): a row the pass does not write must not show up as what the allocator's recycled block held --
+        # the right logits of an earlier call, more often than not
+        out = poisoned_out(eng, n)
+        getattr(eng, kind)(x, out=out)      # (forward_timed synchronises inside the library: it reads its events)
+        return {"logits": out}
+    if kind in S.DETECT:
+        method, thr, mode = S.DETECT[kind]
+        if method == "detect_frames":
+            got = eng.detect_frames([r.frames[i % S.N_IMAGES] for i in range(lo, lo + n)], thr, S.IOU, mode, _hip.RESIZE_LETTERBOX)
+        else:
+            got = getattr(eng, method)(r.images(lo, n, method == "detect_u8"), thr, S.IOU, mode)
+        return dict(zip(("boxes", "counts", "status"), (t.clone() for t in got)))
+    if kind in ("loss", "loss_u8"):
+        images, result = getattr(eng, kind)(r.images(lo, n, kind == "loss_u8"), r.gts(lo, n))
+        return {"images": images, "result": result}
+    if kind == "loss_grad":
+        return dict(zip(("images", "result", "assign", "grad"), eng.loss_grad(r.images(lo, n), r.gts(lo, n))))
+    raise ValueError(call)
+
+
+def named_fields(raw, dtype):
+    """the bytes of a record array without its trailing pad word, which is nobody's output"""
+    rec = np.ascontiguousarray(raw).view(dtype)
+    return np.concatenate([np.ascontiguousarray(rec[k]).view(np.uint8).reshape(-1) for k in dtype.names if k != "pad_"])
+
+
+def to_host(res):
+    out = {}
+    for k, v in res.items():
+        a = v if isinstance(v, np.ndarray) else v.cpu().numpy()
+        if k == "images":
+            a = named_fields(a, yeval.LOSS_IMAGE_DTYPE)
+        elif k == "result":
+            a = named_fields(a, yeval.LOSS_RESULT_DTYPE)
+        out[k] = a
+    return out
+
+
+def state_parts(eng):
+    """the master values and the four moment arrays of the engine's training state (tests/test_gpu_train.py: state_parts)"""
+    lay = eng.train_layout
+    nw, nb = lay.cout * lay.cin * 4, lay.cout * 4
+    raw = eng._train_state.cpu().numpy()
+    return {k: raw[int(getattr(lay, k + "_offset")):int(getattr(lay, k + "_offset")) + n].copy() for k, n in zip(STATE_KEYS, (nw, nb, nw, nw, nb, nb))}
+
+
+def execute(r, eng, call):
+    """a call of either kind, synchronously -> its result on the host, None for a changing call that returns nothing"""
+    kind = call[0]
+    if not S.is_changing(call):
+        return to_host(enqueue(r, eng, call))
+    if kind in ("train", "train_u8"):
+        lo, n, t = call[1:]
+        step = eng.train_head_step_u8 if kind == "train_u8" else eng.train_head_step
+        res = to_host({"result": step(r.images(lo, n, kind == "train_u8"), r.gts(lo, n), engine.adam_lr_t(S.LR, t))})
+        res.update(state_parts(eng))
+        return res
+    if kind == "head_train_init":
+        eng.head_train_init(*r.head)
+    elif kind == "load_weights":
+        eng.load_weights(r.weights)
+    elif kind == "rebind":
+        poison_and_bind(eng, "ones")
+    elif kind == "set_streams":
+        _hip.check(eng.lib.yolo_net_set_streams(eng.handle, call[1]), "yolo_net_set_streams")
+        assert eng.num_streams == call[1]
+    else:
+        raise ValueError(call)
+    return None
+
+
+def done(eng):
+    """close an engine whose sequence is over and let go of its memory (what is still open when the module ends: close_engines)"""
+    eng.close()
+    if eng in ENGINES:
+        ENGINES.remove(eng)
+
+
+def twin(sid, key, cache=True):
+    """the result of key's call on a fresh engine that has executed only key's changing calls"""
+    if cache and (sid, key) in TWINS:
+        return TWINS[(sid, key)]
+    import torch
+    prefix, call = key
+    r = rig(sid)
+    eng = new_engine(sid, keep=False)
+    try:
+        for c in prefix:
+            execute(r, eng, c)
+        res = execute(r, eng, call)
+        torch.cuda.synchronize()
+    finally:
+        eng.close()
+    if cache:
+        TWINS[(sid, key)] = res
+    return res
+
+
+# ---- comparing -----------------------------------------------------------------------------------------------------------------------------
+def first_difference(got, want):
+    """None, or what differed first between two results of one call"""
+    assert sorted(got) == sorted(want), (sorted(got), sorted(want))
+    if "counts" in got:
+        for k in ("counts", "status"):
+            if not np.array_equal(got[k], want[k]):
+                return "%s: %s against the twin's %s" % (k, got[k].tolist(), want[k].tolist())
+        for i, n in enumerate(want["counts"]):
+            a, b = got["boxes"][i, :n].view(np.uint32), want["boxes"][i, :n].view(np.uint32)
+            if not np.array_equal(a, b):
+                rec, col = (int(v) for v in np.argwhere(a != b)[0])
+                return "image %d, record %d of %d, field %d: %r against the twin's %r" % (i, rec, n, col, got["boxes"][i, rec].tolist(), want["boxes"][i, rec].tolist())
+        return None
+    for k in sorted(want):
+        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        if a.shape != b.shape or a.dtype != b.dtype:
+            return "%s: shape / type %s %s against the twin's %s %s" % (k, a.shape, a.dtype, b.shape, b.dtype)
+        if a.tobytes() == b.tobytes():
+            continue
+        bits = {4: np.uint32, 2: np.uint16, 1: np.uint8, 8: np.uint64}[a.dtype.itemsize]
+        bad = np.argwhere(a.view(bits) != b.view(bits))
+        idx = tuple(int(v) for v in bad[0])
+        where = "(image, row, column%s) = %s" % (", channel" if a.ndim == 4 else "", idx) if a.ndim >= 3 else "element %s" % (idx,)
+        return "%s: %d of %d elements differ, first at %s: %r against the twin's %r" % (k, len(bad), a.size, where, a[idx].item(), b[idx].item())
+    return None
+
+
+def describe_failure(sid, name, seq, i, diff):
+    ran = [c for c in seq[:i] if c[0] != S.REFUSE]          # (a refused call launches nothing: the suspect is the call in front of it)
+    prev = ran[-1] if ran else None
+    changing = [c for c in seq[:i] if S.is_changing(c)]
+    return ("plan %s, sequence %s, call %d %r: the result differs from its twin's (a fresh engine that ran only %r and this call)\n  %s\n"
+            "  the call in front of it: %r%s%s\n  the last changing call in front of it: %r"
+            % (sid, name, i, seq[i], list(S.twin_key(seq, i)[0]), diff, prev,
+               " (a SPARSE detect: head rows below the threshold's logit were not written)" if prev and S.is_sparse_detect(prev) else "",
+               ", then the refused %r" % (seq[i - 1],) if i and seq[i - 1][0] == S.REFUSE else "", changing[-1] if changing else None))
+
+
+def control(sid):
+    """two fresh twins, the same call, the same bytes -- else what a sequence would show is non-determinism, not call order"""
+    if sid not in CONTROL:
+        CONTROL[sid] = None
+        kinds = S.PLANS[sid]["kinds"]
+        # (calls of the covering walk's own set, so that the cached twin of each serves the sequences as well)
+        detect = min((k for k in kinds if k in S.DETECT and S.DETECT[k][0] == "detect"), key=lambda k: S.DETECT[k][1:])     # the lowest threshold
+        for call in [(k,) + S.variants(kinds, k)[0] for k in ("forward", detect)]:
+            want = twin(sid, ((), call))
+            diff = first_difference(twin(sid, ((), call), cache=False), want)
+            if diff:
+                CONTROL[sid] = "%r: %s" % (call, diff)
+                break
+            # the fixture itself: finite, non-zero logits, and boxes to compare
+            assert "counts" not in want or int(want["counts"].sum()) > 0, "plan %s: %r finds no box: the fixture detects nothing" % (sid, call)
+            assert "logits" not in want or (np.isfinite(want["logits"]).all() and np.any(want["logits"] != 0)), (sid, call)
+    if CONTROL[sid]:
+        pytest.fail("plan %s: CONTROL failed -- two fresh engines, the same single call, different bytes.  This is non-determinism, not call "
+                    "order; the plan's sequences are not run.  %s" % (sid, CONTROL[sid]))
+
+
+def run_sequence(sid, name, seq, start=0, end=None):
+    """the calls of seq[:end] on one engine, those from `start` on compared with their twins"""
+    control(sid)
+    r = rig(sid)
+    eng = new_engine(sid)
+    boxes = 0
+    seq = seq[:end]
+    for i, call in enumerate(seq):
+        got = execute(r, eng, call)
+        if got is None or i < start:
+            continue
+        diff = first_difference(got, twin(sid, S.twin_key(seq, i)))
+        assert diff is None, describe_failure(sid, name, seq, i, diff)
+        boxes += int(got["counts"].sum()) if "counts" in got else 0
+    done(eng)
+    print("%s/%s: calls %d .. %d equal to their twins (%d twins cached for the module), %d boxes" % (sid, name, start, len(seq) - 1, len(TWINS), boxes))
+
+
+# ---- 1 - 6: one item per (plan, sequence, part) ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sid,name,part,start,end", S.ITEMS, ids=["%s/%s/%d" % it[:3] for it in S.ITEMS])
+def test_sequence(sid, name, part, start, end):
+    run_sequence(sid, name, S.sequences_of(sid)[name], start, end)
+
+
+# ---- 8: two engines of different plans alive at once, calls interleaved on one stream --------------------------------------------------------
+def test_two_engines_interleaved():
+    for sid in S.PAIR:
+        control(sid)
+    engines = {sid: new_engine(sid) for sid in S.PAIR}
+    for i, (sid, call) in enumerate(S.INTERLEAVED):
+        got = execute(rig(sid), engines[sid], call)
+        diff = first_difference(got, twin(sid, ((), call)))
+        assert diff is None, "interleaved call %d, %r on plan %s, behind %r on the other engine: %s" % (i, call, sid, S.INTERLEAVED[i - 1] if i else None, diff)
+    for eng in engines.values():
+        done(eng)
+
+
+# ---- 9: the covering walk without host synchronisation between the calls -----------------------------------------------------------------------
+@pytest.mark.parametrize("sid", S.ASYNC_PLANS)
+def test_covering_walk_enqueued_without_synchronisation(sid):
+    """every call of the walk is only enqueued (inputs, truths and frames are on the device already; results that live in the engine's
+    record buffer are cloned on the stream); ONE synchronisation at the end, then every result is compared.  forward_timed is the
+    exception by its nature: it reads its own events and so waits for the stream inside the library."""
+    import torch
+    control(sid)
+    seq = S.SEQUENCES[sid]["cover"]
+    r = rig(sid)
+    eng = new_engine(sid)
+    torch.cuda.synchronize()
+    pending = [enqueue(r, eng, call) for call in seq]
+    torch.cuda.synchronize()
+    for i, res in enumerate(pending):
+        diff = first_difference(to_host(res), twin(sid, S.twin_key(seq, i)))
+        assert diff is None, "enqueued without synchronisation: " + describe_failure(sid, "cover", seq, i, diff)
+    done(eng)
+
+
+# ---- 7: exact chains through autotune and tune_streams -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cid", sorted(S.EXACT_CHAINS))
+def test_exact_chain_through_autotune_and_tune_streams(cid):
+    """autotune and tune_streams decide by timing, so two twins may end up with different tiles: on integer data every tile and every
+    split must give the integer reference, which is what each forward of the chain is compared with"""
+    import torch
+    spec = S.EXACT_CHAINS[cid]
+    c = dict(E.CASES[E.IDS.index(cid)], B=S.EXACT_BATCH)
+    variant = spec["variant"]
+    L, d, want, kept, rep = E.reference(c, variant)             # (asserts exact_ref's preconditions for this batch)
+    x8 = (np.random.RandomState(7).randint(0, 2, size=d["x"].shape) * 255).astype(np.uint8)
+    want8 = X.check_preconditions(L, dict(d, x=(x8 / 255.).astype(np.float32)), c["dtype"], keep=set())["out"]
+    assert np.array_equal((x8 / 255.).astype(np.float32), (x8 > 0).astype(np.float32))
+    eng = engine.HipNetwork(E.build_graph(c, variant), dtype=c["dtype"], max_batch=S.EXACT_BATCH)
+    ENGINES.append(eng)
+    eng.load_weights(d["stream"])
+    names, text = E.kernel_text(eng, eng.kernel_infos())
+    assert spec["feature"] in text, (cid, names)
+    xd = torch.from_numpy(d["x"]).cuda()
+    for i, (kind, lo, n) in enumerate(S.EXACT_STEPS):
+        what = "%s step %d %s at batch %d (kernels now: %s)" % (cid, i, kind, n, [ki.name.decode() for ki in eng.kernel_infos()])
+        if kind == "autotune":
+            eng.autotune(xd[lo:lo + n])
+        elif kind == "tune_streams":
+            _hip.check(eng.lib.yolo_net_tune_streams(eng.handle, xd[lo:lo + n].data_ptr(), n, eng._stream()), "yolo_net_tune_streams")
+        elif kind == "forward_u8":
+            E.assert_equal(eng.forward_u8(x8[lo:lo + n]).cpu().numpy(), want8[lo:lo + n], what)
+        else:
+            E.assert_equal(eng.forward(xd[lo:lo + n]).cpu().numpy(), want[lo:lo + n], what)
+    done(eng)
