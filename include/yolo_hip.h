@@ -42,6 +42,9 @@
  *   yolo_net_train_head_step, yolo_net_train_head_step_u8
  *                           net/yolo.py:161-173: sess.run([optimizer, loss, ...]) of one training batch, for the detection layer alone
  *                           (+ yolo_wgrad_plan, yolo_net_head_input, yolo_net_head_train_bytes / _layout / _init / _read: no reference call site)
+ *   yolo_v3_loss, yolo_v3_loss_grad, yolo_net_loss_v3, yolo_net_loss_v3_u8 (+ yolo_v3_loss_rows)
+ *                           no reference call site: the reference binds no loss to YoloV3 (net/yolo.py:208-211); the loss of Darknet's
+ *                           [yolo] layer and its gradient with respect to the logits
  *   yolo_augment_u8         net/base.py:15-23, :100-107: seq.to_deterministic().augment_images of a resized batch, on the device
  *   yolo_augment_truths_host
  *                           net/base.py:107-111: augment_bounding_boxes(...).remove_out_of_image().cut_out_of_image()
@@ -76,7 +79,10 @@ extern "C" {
                                           yolo_net_head_input, yolo_net_head_train_bytes, yolo_net_head_train_layout, yolo_net_head_train_init,
                                           yolo_net_head_train_read, yolo_net_train_head_step, yolo_net_train_head_step_u8;
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_augment_image POD only) -- training augmentation:
-                                          yolo_augment_u8, yolo_augment_check, yolo_augment_truths_host, yolo_augment_tile */
+                                          yolo_augment_u8, yolo_augment_check, yolo_augment_truths_host, yolo_augment_tile;
+                                          added WITHIN ABI 7 in the same way (new exports only; the yolo_loss_* PODs are reused unchanged) -- the YOLOv3
+                                          loss and its gradient: yolo_v3_loss_rows, yolo_v3_loss, yolo_v3_loss_grad, yolo_net_loss_v3,
+                                          yolo_net_loss_v3_u8 */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -615,6 +621,86 @@ int yolo_loss_reduce(const yolo_loss_image *images_dev, int n_images, int n_repe
 int yolo_v2_loss_grad(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
                       int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, float *grad_dev,
                       void *stream);
+
+/* ---- YOLOv3 loss and its gradient on the device (added WITHIN ABI 7: new exports only, nothing existing changed) ------------------
+ * The loss of Darknet's [yolo] layer (forward_yolo_layer), the definition every YOLOv3 .weights file was trained with, and its gradient
+ * with respect to the logits.  The reference has no loss for YoloV3 (net/yolo.py:208-211); yolo_v2_loss*, yolo_net_loss* and
+ * yolo_net_train_head_step* keep refusing a version 3 head.  This stops at the logits: no backward pass, no step.
+ *
+ * Inputs.     logits float32 [B][R][5 + C], the layout yolo_net_forward writes for a version 3 head: rows scale by scale in head order,
+ *             inside a scale [h_s][w_s][A_s]; R = sum_s h_s * w_s * A_s.  A yolo_head_desc with version == 3, 1 <= n_scales <=
+ *             YOLO_MAX_SCALES and anchors (aw, ah) in the grid units of their scale.  Truths yolo_gt [B][max_gt] with int32 counts [B],
+ *             1 <= max_gt <= YOLO_EVAL_MAX_GT, centre / size normalised to the network input (stretch resize); `difficult` is ignored.
+ *             ignore_thresh: a double in (0, 1]; upstream cfgs use 0.7.
+ * Truth checks. As for yolo_v2_loss, with the same status bits: skipped are a truth whose centre lies outside [0, 1) in x or y -- its cell
+ *             floor(x * w_s) would lie outside the grid, at every scale alike (YOLO_LOSS_OUT_OF_GRID; x == 1.0 too, a NaN too), one with
+ *             w <= 0, h <= 0 or a NaN size (YOLO_LOSS_BAD_BOX: it now covers a ZERO size too, because the log of the size is taken), one
+ *             whose class_idx is outside [0, C) (YOLO_LOSS_BAD_CLASS).  A count outside [0, max_gt] is clamped (YOLO_LOSS_BAD_COUNT).
+ * Assignment. Per valid truth, in float64: the best anchor over ALL anchors of all scales, scales in head order and anchors in index
+ *             order, by eval_iou(0, 0, w * w_s, h * h_s, 0, 0, aw, ah) (the evaluation's IoU, net/base.py:180-192); the FIRST anchor to
+ *             reach the largest value wins (strict `<` replacement from -1).  The truth's slot is that scale, cell
+ *             (floor(y * h_s), floor(x * w_s)) and that anchor.  When several truths of an image claim one slot the LAST in list order owns
+ *             it (Darknet overwrites the box and objectness deltas in list order); the others count in n_truths, not in n_assigned.
+ * Targets of a winner row, float64, rounded ONCE to float32: tx = x * w_s - c, ty = y * h_s - r, tw = log(w * w_s / aw),
+ *             th = log(h * h_s / ah), m = 2 - w * h.
+ * Terms.      float32, every operation rounded on its own, sp(t) = fmaxf(t, 0) + log1pf(expf(-fabsf(t))), expf and log1pf CORRECTLY
+ *             rounded (evaluated in float64 and rounded once: a term does not depend on the float32 library that evaluates it):
+ *               winner row:      xy = m * (sp(t0) - tx * t0 + sp(t1) - ty * t1)      (added left to right)
+ *                                wh = m * 0.5 * ((t2 - tw)^2 + (t3 - th)^2)
+ *                                obj = sp(t4) - t4
+ *                                cls = sum_k (k == class ? sp(t[5 + k]) - t[5 + k] : sp(t[5 + k]))      (the bracket is a selection)
+ *               every other row: noobj = sp(t4), UNLESS the row is ignored; an ignored row forms no term at all.
+ * Ignore test. The row's box in float32, every operation rounded on its own: bx = (sigmoid(t0) + c) / w_s, by = (sigmoid(t1) + r) / h_s,
+ *             bw = expf(t2) * float(aw) / w_s, bh = expf(t3) * float(ah) / h_s, with the sigmoid 1 / (1 + expf(-t)) of the decode (the
+ *             decode itself keeps the size in float64; this is a restatement, the decode is untouched).  Widened to float64;
+ *             best = max over the image's VALID truths of eval_iou(box, truth) in normalised units; ignored iff best > ignore_thresh.
+ *             The comparison is strict, a NaN compares false, an image without truths ignores nothing.  Only rows that are not winners
+ *             are tested.
+ * Totals.     loss_xy = S xy / B, loss_wh = S wh / B, loss_obj = S obj / B, loss_noobj = S noobj / B, loss_class = S cls / B,
+ *             loss = the five added in this order.  yolo_loss_image / yolo_loss_result as for YOLOv2: n_assigned counts winner rows.
+ * Gradient.   G = d loss / d logits, float32 [B][R][5 + C], EVERY element written by every call; float32, every operation rounded on its
+ *             own, s(t) = 1 / (1 + expf(-t)) with the correctly rounded expf of the terms:
+ *               winner row:               G0 = m * (s(t0) - tx) / B, G1 = m * (s(t1) - ty) / B, G2 = m * (t2 - tw) / B, G3 = m * (t3 - th) / B,
+ *                                         G4 = (s(t4) - 1) / B, G[5 + k] = (s(t[5 + k]) - [k == class]) / B
+ *               not a winner, not ignored: G4 = s(t4) / B, all else +0 exactly
+ *               ignored:                  the whole row +0 exactly
+ *             This is -1 / B times Darknet's `delta`, so an optimizer fed with G takes Darknet's step.
+ * Three DELIBERATE DIFFERENCES from Darknet:
+ *   (a) the number returned is the function whose gradient G is (cross-entropies and half squares), not Darknet's printed
+ *       mag_array(delta)^2;
+ *   (b) the truth_thresh branch is not built: it never fires at the cfgs' value 1;
+ *   (c) one truth per slot: Darknet's partial class update when a slot is claimed twice is not kept.
+ * Sums.       Every float32 term is widened to float64 and added in a FIXED order: a thread's rows ascending (the class terms of a wave's
+ *             winner rows: lanes striding over the classes, a butterfly over the lanes), the lane tree, the waves in index order, the parts
+ *             of an image in index order, the images in index order.  A part is a constant number of rows (1024).  No floating-point
+ *             atomics: the same bits on every call and every device. */
+/* R and the number of partial records an image is summed through -- a function of the head alone, never of the device, because it fixes
+ * the summation order.  YOLO_ERR_ARG as below for a bad head. */
+int yolo_v3_loss_rows(const yolo_head_desc *head, int64_t *rows_per_image, int32_t *parts_per_image);
+/* The standalone entry.  parts_dev: yolo_loss_image [batch][parts], caller-owned scratch; images_dev [batch]; assign_dev int32 [batch][R],
+ * REQUIRED and wholly written by every call: a value >= 0 is the index of the truth that owns the row, -1 none, -2 ignored -- the complete
+ * description the gradient kernel needs.  Three kernels (one workgroup per image; parts x images; one workgroup), enqueued on `stream`
+ * with no host synchronisation.  YOLO_ERR_ARG, with a message that names the entry, for a null pointer, batch < 1, max_gt outside
+ * 1..YOLO_EVAL_MAX_GT, ignore_thresh outside (0, 1], a head that is not version 3 ("the head must be version 3"), n_scales or n_classes
+ * out of range, a scale with h, w or n_anchors < 1, or an image of 2^31 or more logits. */
+int yolo_v3_loss(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                 double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev,
+                 void *stream);
+/* Runs the kernels of yolo_v3_loss exactly as yolo_v3_loss does -- parts, images, result and assign hold the same bytes -- then the
+ * gradient kernel (a lane per element, no LDS, no atomics).  grad_dev: batch * R * (5 + C) floats that do not overlap logits_dev;
+ * YOLO_ERR_ARG also for a NULL grad_dev and for grad_dev == logits_dev. */
+int yolo_v3_loss_grad(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                      double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev,
+                      yolo_loss_result *result_dev, float *grad_dev, void *stream);
+/* One enqueue for a validation batch: a DENSE forward pass into the workspace logits, as yolo_net_loss does it, then the kernels of
+ * yolo_v3_loss on them with the net's head: bit-identical to yolo_net_forward[_u8] followed by yolo_v3_loss.  Checks and messages as
+ * yolo_net_forward plus those of yolo_v3_loss; a net whose head was never set is told so first (YOLO_ERR_STATE). */
+int yolo_net_loss_v3(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                     double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev,
+                     yolo_loss_result *result_dev, void *stream);
+int yolo_net_loss_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                        double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev,
+                        yolo_loss_result *result_dev, void *stream);
 
 /* ---- Training the detection layer on the device (added within ABI 7: new exports, the yolo_wgrad_plan and yolo_tensor_view PODs only) ------
  * The detection layer is the last conv of every YOLOv2 network here (net/v2.py:52-56): 1 x 1, stride 1, linear, with bias and no batch

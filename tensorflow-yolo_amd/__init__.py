@@ -7,7 +7,7 @@ shim `tensorflow_yolo_amd.py` at the repository root maps one onto the other).
 """
 from . import _hip  # noqa: F401
 from .net.base import BoundingBox  # noqa: F401
-from .net.lossfn import yolo_v2_loss  # noqa: F401
+from .net.lossfn import yolo_v2_loss, yolo_v3_loss  # noqa: F401
 from .net.yolo import Yolo, YoloV2, YoloV2Tiny, YoloV3, YoloV3SPP, YoloV3Tiny  # noqa: F401
 
-__all__ = ["Yolo", "YoloV2", "YoloV2Tiny", "YoloV3", "YoloV3SPP", "YoloV3Tiny", "BoundingBox", "yolo_v2_loss"]
+__all__ = ["Yolo", "YoloV2", "YoloV2Tiny", "YoloV3", "YoloV3SPP", "YoloV3Tiny", "BoundingBox", "yolo_v2_loss", "yolo_v3_loss"]

@@ -214,6 +214,16 @@ SIGNATURES = {
     # the gradient of the YOLOv2 loss with respect to the logits (added within ABI 7)
     "yolo_v2_loss_grad": (C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    # the YOLOv3 loss and its gradient with respect to the logits (added within ABI 7)
+    "yolo_v3_loss_rows": (C.c_int, [C.POINTER(HeadDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "yolo_v3_loss": (C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_v3_loss_grad": (C.c_int, [C.POINTER(HeadDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_net_loss_v3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_net_loss_v3_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     # training the detection layer (added within ABI 7)
     "yolo_wgrad_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(WgradPlan)]),
     "yolo_conv1x1_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,

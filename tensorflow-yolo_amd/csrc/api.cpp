@@ -732,6 +732,88 @@ int yolo_loss_reduce(const yolo_loss_image *images_dev, int n_images, int n_repe
     return YOLO_OK;
 }
 
+// ---- YOLOv3 loss (yolo_hip.h: added within ABI 7; kernels in loss3.hip, geometry and checks in loss3_host.cpp) -----------------------------
+int yolo_v3_loss_rows(const yolo_head_desc *head, int64_t *rows_per_image, int32_t *parts_per_image) {
+    if (!head || !rows_per_image || !parts_per_image) return fail(YOLO_ERR_ARG, "yolo_v3_loss_rows: null argument");
+    Loss3Geometry geo;
+    std::string err;
+    const int rc = loss3_geometry(head, &geo, err);
+    if (rc) return fail(rc, "yolo_v3_loss_rows: " + err);
+    *rows_per_image = geo.rows;
+    *parts_per_image = geo.parts;
+    return YOLO_OK;
+}
+
+static int run_loss3(const Loss3Geometry &geo, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+                     double ignore_thresh, yolo_loss_image *parts, yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad,
+                     hipStream_t s) {
+    Loss3Params p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.gt = gt; p.gt_counts = gt_counts; p.batch = batch; p.max_gt = max_gt; p.ignore_thresh = ignore_thresh; p.geo = geo;
+    p.parts = parts; p.images = images; p.assign = assign; p.result = result; p.grad = grad;
+    HIP_TRY(launch_loss3(p, s));
+    if (grad) HIP_TRY(launch_loss3_grad(p, s));
+    return YOLO_OK;
+}
+
+int yolo_v3_loss(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                 double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev,
+                 void *stream) {
+    Loss3Geometry geo;
+    std::string err;
+    const int rc = loss3_check(head, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev, result_dev,
+                               false, nullptr, &geo, err);
+    if (rc) return fail(rc, "yolo_v3_loss: " + err);
+    return run_loss3(geo, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev, result_dev, nullptr,
+                     static_cast<hipStream_t>(stream));
+}
+
+int yolo_v3_loss_grad(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                      double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev,
+                      yolo_loss_result *result_dev, float *grad_dev, void *stream) {
+    Loss3Geometry geo;
+    std::string err;
+    const int rc = loss3_check(head, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev, result_dev,
+                               true, grad_dev, &geo, err);
+    if (rc) return fail(rc, "yolo_v3_loss_grad: " + err);
+    return run_loss3(geo, logits_dev, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev, result_dev, grad_dev,
+                     static_cast<hipStream_t>(stream));
+}
+
+static int net_loss_v3_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                           double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev,
+                           yolo_loss_result *result_dev, void *stream, const char *who) {
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    std::string err;        // whether a head was set at all comes before what kind of head it is
+    int rc = check_head(&net->head, net->out_count, err);
+    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
+    Loss3Geometry geo;
+    // (the logits pointer is the workspace's: any non-null value stands in for it until check_ready has seen the net)
+    rc = loss3_check(&net->head, net, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev, result_dev, false,
+                     nullptr, &geo, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    rc = check_ready(net, in_dev.ptr, batch, who);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // a DENSE pass into the workspace logits (obj_min_logit is -inf outside detect_any: every row is written)
+    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
+    rc = run_forward(net, in_dev, batch, logits, s);
+    if (rc) return rc;
+    return run_loss3(geo, logits, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev, result_dev, nullptr, s);
+}
+int yolo_net_loss_v3(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                     double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev,
+                     yolo_loss_result *result_dev, void *stream) {
+    return net_loss_v3_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev,
+                           result_dev, stream, "yolo_net_loss_v3");
+}
+int yolo_net_loss_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                        double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev,
+                        yolo_loss_result *result_dev, void *stream) {
+    return net_loss_v3_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts_dev, images_dev, assign_dev,
+                           result_dev, stream, "yolo_net_loss_v3_u8");
+}
+
 // ---- training the detection layer (yolo_hip.h: added within ABI 7; kernels in train.hip, split and checks in train_host.cpp) ---------------
 int yolo_wgrad_plan(int64_t P, int cin, int cout, int x_dtype, struct yolo_wgrad_plan *out) {
     std::string err;

@@ -26,4 +26,16 @@ __device__ __forceinline__ double eval_iou(double x1, double y1, double w1, doub
     return inter / uni;
 }
 
+// The version 3 decode of one row in float32, every operation rounded on its own (yolo_hip.h: the ignore test of the YOLOv3 loss).  Centre as
+// decode_kernel computes it (v3.py:129); the size in float32 with the anchor rounded to float32 -- decode_kernel keeps the size in float64
+// (its anchors are np.float64), so it does not share this function: the detect tests pin its bits.
+__device__ __forceinline__ void decode_v3_f32(float t0, float t1, float t2, float t3, float c, float r, float ws, float hs, float awf, float ahf,
+                                              float &bx, float &by, float &bw, float &bh) {
+#pragma clang fp contract(off)
+    bx = (sigmoid_f32(t0) + c) / ws;
+    by = (sigmoid_f32(t1) + r) / hs;
+    bw = expf(t2) * awf / ws;
+    bh = expf(t3) * ahf / hs;
+}
+
 }  // namespace yolo

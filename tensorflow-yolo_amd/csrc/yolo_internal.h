@@ -17,6 +17,7 @@
 #include "yolo_hip.h"
 #include "train_host.h"
 #include "augment_host.h"
+#include "loss3_host.h"
 
 namespace yolo {
 
@@ -411,6 +412,23 @@ struct LossGradParams {
 hipError_t launch_loss_images(const LossParams &p, int batch, hipStream_t s);
 hipError_t launch_loss_finish(const LossFinishParams &p, hipStream_t s);
 hipError_t launch_loss_grad(const LossGradParams &p, hipStream_t s);
+
+// ---- YOLOv3 loss (loss3.hip; the geometry and the argument checks: loss3_host.h) ------------------------------------------------------
+struct Loss3Params {
+    const float *logits;       // [B][R][5 + C]
+    const yolo_gt *gt;         // [B][max_gt]
+    const int *gt_counts;
+    int batch, max_gt;
+    double ignore_thresh;
+    Loss3Geometry geo;
+    yolo_loss_image *parts;    // [B][geo.parts]
+    yolo_loss_image *images;   // [B]
+    int *assign;               // [B][R]: truth index | -1 none | -2 ignored
+    yolo_loss_result *result;
+    float *grad;               // [B][R][5 + C], every element written (loss3_grad_kernel only)
+};
+hipError_t launch_loss3(const Loss3Params &p, hipStream_t s);          // assign, terms, finish
+hipError_t launch_loss3_grad(const Loss3Params &p, hipStream_t s);     // the gradient kernel alone, on the table launch_loss3 left
 
 // ---- training the detection layer (train.hip; the launch split and the argument checks: train_host.h) ---------------------------
 constexpr int kWgradThreads = 256;

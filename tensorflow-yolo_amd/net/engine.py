@@ -49,13 +49,28 @@ def head_desc_v2(h, w, anchors, num_classes):
     return hd
 
 
-def head_desc_v3(yolos):
-    """From the yolo layers of a detection layer (reference net/v3.py:145-149)."""
+def head_desc_v3(yolos, anchors_per_scale=None, n_classes=None):
+    """From the yolo layers of a detection layer (reference net/v3.py:145-149): head_desc_v3(yolos).  Or from plain numbers, for a head
+    that belongs to no network of this package: head_desc_v3(grids, anchors_per_scale, n_classes) with grids = [(h, w), ...] in head order
+    and anchors_per_scale = [[(aw, ah), ...], ...] in the grid units of their scale."""
     hd = _hip.HeadDesc()
-    hd.version, hd.n_classes, hd.n_scales = 3, int(yolos[0].no_c), len(yolos)
-    for s, y in enumerate(yolos):
-        hd.h[s], hd.w[s], hd.n_anchors[s] = y.h, y.w, y.b
-        for i, (aw, ah) in enumerate(y.anchors):
+    if anchors_per_scale is None:
+        hd.version, hd.n_classes, hd.n_scales = 3, int(yolos[0].no_c), len(yolos)
+        for s, y in enumerate(yolos):
+            hd.h[s], hd.w[s], hd.n_anchors[s] = y.h, y.w, y.b
+            for i, (aw, ah) in enumerate(y.anchors):
+                hd.anchors[s][2 * i], hd.anchors[s][2 * i + 1] = float(aw), float(ah)
+        return hd
+    grids = [(int(h), int(w)) for h, w in yolos]
+    if n_classes is None or not 1 <= len(grids) <= _hip.MAX_SCALES or len(anchors_per_scale) != len(grids):
+        raise ValueError("head_desc_v3: expected 1..%d grids, as many anchor lists and n_classes" % _hip.MAX_SCALES)
+    hd.version, hd.n_classes, hd.n_scales = 3, int(n_classes), len(grids)
+    for s, ((h, w), anc) in enumerate(zip(grids, anchors_per_scale)):
+        anc = np.reshape(np.asarray(anc, dtype=np.float64), [-1, 2])
+        if not 1 <= len(anc) <= _hip.MAX_ANCHORS:
+            raise ValueError("head_desc_v3: scale %d: expected 1..%d anchors" % (s, _hip.MAX_ANCHORS))
+        hd.h[s], hd.w[s], hd.n_anchors[s] = h, w, len(anc)
+        for i, (aw, ah) in enumerate(anc):
             hd.anchors[s][2 * i], hd.anchors[s][2 * i + 1] = float(aw), float(ah)
     return hd
 
@@ -489,6 +504,63 @@ class HipNetwork(Plan):
         """loss_grad() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as loss_grad(float32(x / 255.))"""
         return self._loss_grad_any(x, gts, True)
 
+    # -- the YOLOv3 loss and its gradient (yolo_net_loss_v3 / yolo_net_loss_v3_u8 / yolo_v3_loss_grad) -----------------------------------------
+    def _need_v3(self):
+        if getattr(self, "head", None) is None or self.head.version != 3:
+            raise ValueError("the YOLOv3 loss is defined for version 3 heads only (loss / loss_grad serve a YOLOv2 head)")
+
+    def _loss_v3_any(self, x, gts, ignore_thresh, u8, images):
+        from . import evaluate as yeval
+        torch = self.torch
+        self._need_v3()
+        x = self.to_device_u8(x) if u8 else self.to_device(x)
+        self._tune_streams(x)
+        b = x.shape[0]
+        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
+        rows, parts = v3_loss_rows(self.head)
+        if images is None:
+            images = torch.empty((b, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        elif (images.device != self.device or images.dtype != torch.uint8 or tuple(images.shape) != (b, yeval.LOSS_IMAGE_DTYPE.itemsize)
+              or not images.is_contiguous()):
+            raise ValueError("images: expected a contiguous uint8 device tensor [%d, %d]" % (b, yeval.LOSS_IMAGE_DTYPE.itemsize))
+        scratch = torch.empty((b, parts, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        assign = torch.empty((b, rows), dtype=torch.int32, device=self.device)
+        name = "yolo_net_loss_v3_u8" if u8 else "yolo_net_loss_v3"
+        with torch.cuda.device(self.device):
+            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt), float(ignore_thresh),
+                                               scratch.data_ptr(), images.data_ptr(), assign.data_ptr(), result.data_ptr(), self._stream()), name)
+        self.u8_calls += int(u8)
+        self._loss_keep = (x, gt_dev, gc_dev, scratch)     # (alive until the next call: the work is only enqueued)
+        return images, result, assign
+
+    def loss_v3(self, x, gts, ignore_thresh=0.7, images=None):
+        """The YOLOv3 loss of a batch against its truths (the loss of Darknet's [yolo] layer; include/yolo_hip.h has the definition): a
+        dense forward pass and the loss kernels in one enqueue, no host sync.  Returns device tensors (images uint8 [B, 56], result uint8
+        [64] as loss(); assign int32 [B, R]: truth index | -1 | -2 ignored).  ValueError on a YOLOv2 head."""
+        return self._loss_v3_any(x, gts, ignore_thresh, False, images)
+
+    def loss_v3_u8(self, x, gts, ignore_thresh=0.7, images=None):
+        """loss_v3() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as loss_v3(float32(x / 255.))"""
+        return self._loss_v3_any(x, gts, ignore_thresh, True, images)
+
+    def _loss_v3_grad_any(self, x, gts, ignore_thresh, u8):
+        self._need_v3()
+        logits = (self.forward_u8 if u8 else self.forward)(x)
+        images, result, assign, grad, keep = v3_loss_grad(self.head, logits, gts, ignore_thresh)
+        self._loss_keep = (logits,) + keep         # (alive until the next call: the work is only enqueued)
+        return images, result, assign, grad
+
+    def loss_v3_grad(self, x, gts, ignore_thresh=0.7):
+        """loss_v3() and its gradient with respect to the head logits: a dense forward pass into an output tensor, then the loss kernels
+        and the gradient kernel on it, on the same stream, no host sync.  Returns device tensors (images, result, assign as loss_v3();
+        grad float32 of the logits' shape).  The gradient stops at the logits."""
+        return self._loss_v3_grad_any(x, gts, ignore_thresh, False)
+
+    def loss_v3_grad_u8(self, x, gts, ignore_thresh=0.7):
+        """loss_v3_grad() for a uint8 batch [B,H,W,C] (0..255, RGB)"""
+        return self._loss_v3_grad_any(x, gts, ignore_thresh, True)
+
     # -- training the detection layer (yolo_net_head_train_init / yolo_net_train_head_step / yolo_net_head_train_read) ------------------
     def head_train_init(self, head_w, head_b):
         """Allocate the head-training state and start it from head_w [cout, cin] (the Darknet kernel, [out][in]) and head_b [cout]: master
@@ -646,6 +718,37 @@ def v2_loss_grad(head, logits, gts):
                                                 images.data_ptr(), assign.data_ptr(), result.data_ptr(), grad.data_ptr(),
                                                 torch.cuda.current_stream(dev).cuda_stream), "yolo_v2_loss_grad")
     return images, result, assign, grad, (gt_dev, gc_dev)
+
+
+def v3_loss_rows(head):
+    """yolo_v3_loss_rows: (rows per image R, partial records per image) of a version 3 head"""
+    rows, parts = C.c_int64(0), C.c_int32(0)
+    _hip.check(_hip.lib().yolo_v3_loss_rows(C.byref(head), C.byref(rows), C.byref(parts)), "yolo_v3_loss_rows")
+    return int(rows.value), int(parts.value)
+
+
+def v3_loss_grad(head, logits, gts, ignore_thresh=0.7):
+    """yolo_v3_loss_grad on float32 device logits [B, R, 5 + C] (contiguous) with a version 3 head: the loss kernels and the gradient
+    kernel in one enqueue on the current stream, no host sync.  gts as HipNetwork.loss takes them.  Returns device tensors (images uint8
+    [B, 56], result uint8 [64], assign int32 [B, R], grad float32 of the logits' shape) and the tensors the caller keeps alive with the
+    logits until the work has run."""
+    from . import evaluate as yeval
+    torch = _torch()
+    dev, b = logits.device, logits.shape[0]
+    rows, parts = v3_loss_rows(head)
+    if logits.numel() != b * rows * (5 + head.n_classes):
+        raise ValueError("logits: expected %d x %d x %d values, got %d" % (b, rows, 5 + head.n_classes, logits.numel()))
+    gt_dev, gc_dev, max_gt = loss_gts(torch, dev, gts, b)
+    scratch = torch.empty((b, parts, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    images = torch.empty((b, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    assign = torch.empty((b, rows), dtype=torch.int32, device=dev)
+    grad = torch.empty_like(logits)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.lib().yolo_v3_loss_grad(C.byref(head), logits.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt),
+                                                float(ignore_thresh), scratch.data_ptr(), images.data_ptr(), assign.data_ptr(), result.data_ptr(),
+                                                grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "yolo_v3_loss_grad")
+    return images, result, assign, grad, (gt_dev, gc_dev, scratch)
 
 
 def check_status(status, allow_truncation=False):

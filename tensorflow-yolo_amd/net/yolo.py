@@ -189,6 +189,29 @@ class Yolo(object):
         out["grad"] = grad
         return out
 
+    def loss_v3(self, x_batch, truths, ignore_thresh=0.7):
+        """The YOLOv3 loss of one batch, forward only: the loss of Darknet's [yolo] layer (include/yolo_hip.h has the definition; the
+        reference binds no loss to YoloV3).  Arguments and the returned dict as loss(); ignore_thresh: a row whose decoded box overlaps
+        a truth by more than this pays no objectness penalty.  ValueError on a YOLOv2 network."""
+        from . import evaluate as yeval
+        eng = self.net.engine
+        if not eng.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
+        images, result, _ = (eng.loss_v3_u8 if eng.is_u8(x_batch) else eng.loss_v3)(x_batch, truths, ignore_thresh)
+        return yeval.loss_to_host(images, result)
+
+    def loss_v3_grad(self, x_batch, truths, ignore_thresh=0.7):
+        """loss_v3() and the gradient of that loss with respect to the head logits.  Returns loss_v3()'s dict plus `grad`, a float32 DEVICE
+        tensor [B, R, 5 + C].  The gradient stops at the logits: there is no backward pass through the network here."""
+        from . import evaluate as yeval
+        eng = self.net.engine
+        if not eng.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights / build(weights=...) first")
+        images, result, _, grad = (eng.loss_v3_grad_u8 if eng.is_u8(x_batch) else eng.loss_v3_grad)(x_batch, truths, ignore_thresh)
+        out = yeval.loss_to_host(images, result)
+        out["grad"] = grad
+        return out
+
     # ---- TEST mode --------------------------------------------------------------------------------
     def test(self, params):
         image_dir = params["image_dir"]
