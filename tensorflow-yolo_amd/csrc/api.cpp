@@ -72,7 +72,7 @@ int yolo_net_create(const yolo_layer_desc *layers, int n_layers, const yolo_net_
     }
     if (net->opt.force_tile > 0 && net->opt.force_tile != kMxTile + 1)        // test / tuning hook: one tile id on every conv that accepts it
         for (Kernel &k : net->kernels)
-            if (k.kind == K_CONV && k.stem < 2 && conv_tile_valid(net, k, net->opt.force_tile - 1)) k.tile = net->opt.force_tile - 1;
+            if (conv_dispatched(k) && conv_tile_valid(net, k, net->opt.force_tile - 1)) k.tile = net->opt.force_tile - 1;
     // the split-K slab is the last region of the workspace (plan.cpp reserves nothing for it): sized from the launches that can split
     net->splitk_bytes = splitk_slab_bytes(net) * (size_t)net->arenas;
     if (net->splitk_bytes) net->tail.push_back({"split-K tickets + slabs", net->splitk_off, net->splitk_bytes, net->splitk_bytes});
@@ -998,7 +998,7 @@ int yolo_net_head_train_init(yolo_net *net, void *state_dev, size_t bytes, const
     HIP_TRY(hipMemcpy(st + L.w_offset, head_w_host, nw, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(st + L.b_offset, head_b_host, nb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(st + L.m_w_offset, 0, (size_t)(L.dw_offset - L.m_w_offset)));       // the four moment arrays lie one behind the other
-    // the layer's packed form, as pack_weights (plan.cpp) writes a 1 x 1 conv without batch norm: row o at o * wrow bytes, bias as it is
+    // the layer's packed form, as pack_weights (weights.cpp) writes a 1 x 1 conv without batch norm: row o at o * wrow bytes, bias as it is
     const size_t wrow = (size_t)k->ktiles * 128;
     const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
     std::vector<unsigned char> rows((size_t)k->cout * wrow, 0);

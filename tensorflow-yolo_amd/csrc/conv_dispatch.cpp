@@ -215,7 +215,7 @@ size_t splitk_slab_bytes(const yolo_net *net) {
     size_t need = 0;
     for (size_t ki = 0; ki < net->kernels.size(); ++ki) {
         const Kernel &k = net->kernels[ki];
-        if (k.kind != K_CONV || k.stem >= 2) continue;
+        if (!conv_dispatched(k)) continue;
         for (int b = 1; b <= per; ++b) {
             ConvParams p;
             conv_shape_params(net, k, b, p);
@@ -231,7 +231,7 @@ size_t splitk_slab_bytes(const yolo_net *net) {
 bool pass_splits_k(const yolo_net *net, int batch) {
     for (size_t ki = 0; ki < net->kernels.size(); ++ki) {
         const Kernel &k = net->kernels[ki];
-        if (k.kind != K_CONV || k.stem >= 2) continue;
+        if (!conv_dispatched(k)) continue;
         ConvParams p;
         conv_shape_params(net, k, batch, p);
         if (resolve_conv(net, ki, p, k.tile, arena_slab_data_bytes(net)).ks > 1) return true;
@@ -250,19 +250,19 @@ void conv_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out) {
     out->flops = 2.0 * li.H * li.W * k.cout * k.ksize * k.ksize * k.cin;
     out->bytes = (double)k.in.H * k.in.W * k.cin * net->esize + view_elems(k.out) * view_esz(net, k.out) + (k.has_res ? view_elems(k.in2) * net->esize : 0.0);
     out->weight_bytes = (double)k.cout * k.ksize * k.ksize * k.cin * net->esize + 4.0 * k.cout;
-    if (k.stem == 3) {          // no launch of its own
+    if (k.stem == STEM_TAIL) {          // no launch of its own
         out->flops = 0; out->bytes = 0; out->weight_bytes = 0;
         snprintf(out->name, sizeof out->name, "conv_igemm<fused into conv_stem>");
         return;
     }
-    if (k.stem == 2) {
+    if (k.stem == STEM_HOST) {
         const Kernel &f = net->kernels[kernel - 1];
         out->flops += 2.0 * f.out.H * f.out.W * f.cout * 27;
         out->bytes = (double)f.in.H * f.in.W * 3 * 4 + view_elems(k.out) * view_esz(net, k.out);
         out->weight_bytes += 28.0 * f.cout * 4;
         snprintf(out->name, sizeof out->name, "conv_stem<f16,3-32-64>");
         set_symbol(out, "yolo::stem_v3_kernel(yolo::StemParams)");
-        if (kernel + 1 < (int)net->kernels.size() && net->kernels[kernel + 1].stem == 3) {
+        if (kernel + 1 < (int)net->kernels.size() && net->kernels[kernel + 1].stem == STEM_TAIL) {
             const Kernel &t3 = net->kernels[kernel + 1];
             out->flops += 2.0 * li.H * li.W * t3.cout * t3.cin;
             out->bytes += view_elems(t3.out) * view_esz(net, t3.out);

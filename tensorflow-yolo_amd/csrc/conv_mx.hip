@@ -3,7 +3,7 @@
 // Operands follow OCP MX v1.0 with e4m3fn elements and one E8M0 scale per 32 input channels:
 //   scale exponent e = floor(log2 amax) - 8 (8 = emax of e4m3), elements e4m3fn(v * 2^-e) rounded to nearest even and clamped to
 //   +-448 before the conversion; amax = 0 gives the smallest scale (byte 0) and zero elements.
-// Weights are quantized once on the host (plan.cpp: pack_weights, mx_pack); activations stay fp16 in HBM and are quantized here,
+// Weights are quantized once on the host (weights.cpp: pack_weights, mx_pack); activations stay fp16 in HBM and are quantized here,
 // one block per (pixel, 32 channels), by the same device function yolo_mx_quantize runs.
 //
 // Tiling: a workgroup owns 128 couts x 256 positions of the padded-linear grid of conv_tap.hip (one shared pad column after every
@@ -224,7 +224,7 @@ const char *conv_mx_symbol(bool fast) {
     return fast ? "void yolo::conv3x3_mx_kernel<true>(yolo::ConvParams)" : "void yolo::conv3x3_mx_kernel<false>(yolo::ConvParams)";
 }
 
-// p: the launch parameters of make_conv_params (fp16 views); p.wgt = the MX weight image of mx_pack (plan.cpp)
+// p: the launch parameters of make_conv_params (fp16 views); p.wgt = the MX weight image of mx_pack (weights.cpp)
 hipError_t launch_conv_mx(const ConvParams &p0, hipStream_t s) {
     ConvParams p = p0;
     if (p.ksize != 3 || p.stride != 1 || p.f32 || p.H != p.Ho || p.W != p.Wo || !conv_mx_fits(p.W) || p.HoWo <= 0 || (p.cin_chunks * 8) % 128)

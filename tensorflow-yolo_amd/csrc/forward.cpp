@@ -78,14 +78,14 @@ void first_info(const yolo_net *net, const Kernel &k, yolo_kernel_info *out) {
     snprintf(out->name, sizeof out->name, k.pool_fused ? "conv_first_pool<%s,%d>" : "conv_first<%s,%d>", dtype_tag(net), k.cout);
     if (k.pool_fused) { out->out_h = k.in.H; out->out_w = k.in.W; out->flops = 2.0 * k.in.H * k.in.W * k.cout * 27; }
     set_symbol(out, first_symbol(net->opt.dtype, k.cout, k.pool_fused != 0));
-    if (k.stem == 1) {
+    if (k.stem == STEM_FIRST_FOLDED) {
         out->symbol[0] = 0;          // no launch of its own: accounted for in the conv_stem kernel that follows
         out->flops = 0; out->bytes = 0; out->weight_bytes = 0;
         snprintf(out->name, sizeof out->name, "conv_first<fused into conv_stem>");
     }
 }
-// ---- the stem (K_CONV with stem == 2; its report: conv_dispatch.cpp) ------------------------------
-// the first-layer kernel in front of conv `ki` is folded into this launch, and the 1x1 64 -> 32 behind it where the plan says so (stem == 3)
+// ---- the stem (K_CONV with stem == STEM_HOST; its report: conv_dispatch.cpp) ------------------------------
+// the first-layer kernel in front of conv `ki` is folded into this launch, and the 1x1 64 -> 32 behind it where the plan says so (STEM_TAIL)
 void stem_params(const yolo_net *net, size_t ki, const Ptrs &P, StemParams &p) {
     const Kernel &f = net->kernels[ki - 1], &k = net->kernels[ki];
     memset(&p, 0, sizeof p);
@@ -98,7 +98,7 @@ void stem_params(const yolo_net *net, size_t ki, const Ptrs &P, StemParams &p) {
     p.H = f.in.H; p.W = f.in.W; p.Ho = k.out.H; p.Wo = k.out.W;
     p.out_ld = k.out.ld; p.out_img_stride = k.out.img_stride;
     p.in_img_stride = (long long)f.in.H * f.in.W * 3;
-    if (ki + 1 < net->kernels.size() && net->kernels[ki + 1].stem == 3) {      // 1x1 64->32 on the same pixels
+    if (ki + 1 < net->kernels.size() && net->kernels[ki + 1].stem == STEM_TAIL) {      // 1x1 64->32 on the same pixels
         const Kernel &t = net->kernels[ki + 1];
         p.w3 = weights_at(net, t.w_off); p.b3 = floats_at(net, t.b_off);
         p.out3 = P.view_ptr(t.out);
@@ -290,8 +290,8 @@ int run_forward_pass(const Ptrs &P, hipStream_t s, hipEvent_t *ev, long long *ob
             s = s_branch;
         }
         if (ev && hipEventRecord(ev[2 * ki], s) != hipSuccess) return fail(YOLO_ERR_HIP, "hipEventRecord failed");
-        bool no_launch = (k.kind == K_FIRST && k.stem == 1) || (k.kind == K_CONV && k.stem == 3);      // computed by the stem kernel (stem.hip)
-        if (k.kind == K_CONV && k.stem == 0 && k.fuse2_prev && fused2_done) no_launch = true, fused2_done = false;       // computed by the conv in front of it
+        bool no_launch = !has_own_launch(k);      // computed by the stem kernel (stem.hip)
+        if (k.kind == K_CONV && k.stem == STEM_NONE && k.fuse2_prev && fused2_done) no_launch = true, fused2_done = false;       // computed by the conv in front of it
         if (no_launch) {
         } else if (k.kind == K_PREP) {
             PrepParams p;
@@ -302,7 +302,7 @@ int run_forward_pass(const Ptrs &P, hipStream_t s, hipEvent_t *ev, long long *ob
             const int rc = first_params(net, k, P, p);
             if (rc) return rc;
             e = launch_first(p, dtype, s, u8);
-        } else if (k.kind == K_CONV && k.stem == 2) {
+        } else if (k.kind == K_CONV && k.stem == STEM_HOST) {
             StemParams p;
             stem_params(net, ki, P, p);
             e = launch_stem(p, batch, s, net->halves ? kStemGrid / net->parts : kStemGrid, u8);
@@ -512,7 +512,7 @@ int autotune_tiles(yolo_net *net, const NetIn in_dev, int batch, hipStream_t s) 
     HIP_TRY(hipEventCreate(&e1));
     for (size_t ki = 0; ki < net->kernels.size(); ++ki) {
         Kernel &k = net->kernels[ki];
-        if (k.kind != K_CONV || k.stem >= 2 || k.mx || !dma_eligible(net, k)) continue;      // (MX convs: one kernel, weights packed for it)
+        if (!conv_dispatched(k) || k.mx || !dma_eligible(net, k)) continue;      // (MX convs: one kernel, weights packed for it)
         ConvParams p;
         rc = conv_params(net, k, P, p);
         if (rc) break;

@@ -31,6 +31,20 @@ static inline size_t roundup_sz(size_t a, size_t b) { return (a + b - 1) / b * b
 
 namespace {
 
+// The launch-fusion rules of the planner (Planner::try_*) and the variable that switches each one off, whatever its value.  Looked up
+// at every plan_network call, never cached: tests and tools plan one net both ways in one process.
+enum Rule { R_FIRST_DIRECT, R_STEM, R_STEM_TAIL, R_FUSE2, R_FIRST_POOL, R_CONV_POOL, R_SPP_BLOCK, R_COUNT };
+const char *const kRuleOff[R_COUNT] = {
+    "YOLO_NO_FIRST_DIRECT",     // the first layer reads the float32 input itself -> prep pass + generic conv
+    "YOLO_NO_STEM",             // first layer + 3x3/2 32->64 as one kernel -> two launches
+    "YOLO_NO_STEM3",            // the 1x1 64->32 inside the stem kernel -> a launch of its own
+    "YOLO_NO_FUSE2",            // the 1x1 128->64 in the epilogue of the 3x3 in front of it -> a launch of its own
+    "YOLO_NO_FIRST_POOL",       // the 2x2/2 pool inside the first-layer kernel -> pool kernel
+    "YOLO_NO_CONV_POOL",        // the 2x2/2 pool in the conv epilogue -> pool kernel
+    "YOLO_NO_SPP_FUSE",         // the three pools of an SPP block as one kernel -> three pool launches
+};
+inline bool rule_on(Rule r) { return !getenv(kRuleOff[r]); }
+
 struct Fuse {
     int kind = 0;       // 0 none, 1 residual, 2 upsample x2, 3 reorg x2
     int layer = -1;     // the fused shortcut / upsample / reorg layer
@@ -52,6 +66,8 @@ struct Planner {
     std::vector<Copy> copies;
     std::vector<int> route_buf;
     bool first_direct = false;
+    size_t wsrc = 0, woff = 0;            // emit(): floats of the Darknet stream / bytes of the packed blob given out so far
+    double flops = 0;
     std::string err;
 
     Planner(yolo_net *n_) : net(n_), L(n_->layers), n((int)n_->layers.size()) {}
@@ -270,10 +286,10 @@ struct Planner {
     // spp_pool_kernel).  Layer i is the k1 pool, k its half-made kernel (in, out set); the two wider pools are later layers of the list.
     // Nothing is elided, so keep_all does not matter.  fp16 tensors, maps up to 32 x 32, every view 16-byte aligned; else (and under
     // YOLO_NO_SPP_FUSE) each pool is a pool_same_kernel launch of its own.
-    bool spp_block(int i, int s, Kernel &k) {
+    bool try_spp_block(int i, int s, Kernel &k) {
         const yolo_layer_desc &d = L[i].d;
         const int r = (d.ksize - 1) / 2;
-        if (net->opt.dtype != YOLO_DTYPE_F16 || (r != 1 && r != 2) || getenv("YOLO_NO_SPP_FUSE")) return false;
+        if (net->opt.dtype != YOLO_DTYPE_F16 || (r != 1 && r != 2) || !rule_on(R_SPP_BLOCK)) return false;
         if (L[i].H > kSppMaxSide || L[i].W > kSppMaxSide || !chunk_aligned(k.in) || !chunk_aligned(k.out)) return false;
         int wide[2] = {-1, -1};
         for (int j = i + 1; j < n; ++j) {
@@ -319,303 +335,341 @@ struct Planner {
         net->kernels.push_back(k);
     }
 
-    bool emit() {
-        size_t wsrc = 0;
-        size_t woff = 0;
-        double flops = 0;
-        for (int i = 0; i < n; ++i) {
-            const yolo_layer_desc &d = L[i].d;
-            char nm[64];
-            snprintf(nm, sizeof nm, "layer %d: ", i);
-            switch (d.op) {
-            case YOLO_OP_INPUT: {
-                // first layer 3x3/1 on a 3-channel input with 16|32 filters: the direct kernel of
-                // first.hip reads the caller's float32 tensor itself, so no cast/pad pass is needed
-                first_direct = n > 2 && d.c == 3 && L[1].d.op == YOLO_OP_CONV && L[1].d.src[0] == 0 && L[1].d.ksize == 3 &&
-                               L[1].d.stride == 1 && (L[1].d.filters == 16 || L[1].d.filters == 32) && sole(0, 1) &&
-                               fuse[1].kind == 0 && !has_head[1] && !has_claim[1] && !getenv("YOLO_NO_FIRST_DIRECT");
-                if (first_direct) {
-                    L[i].view = dense_view(BUF_USER_IN, d.h, d.w, d.c, d.c);
-                    L[i].view.f32 = true;
-                    L[i].materialised = true;
-                    break;
-                }
-                int cpad = roundup(d.c, epc);
-                Kernel k;
-                k.kind = K_PREP; k.layer = 0;
-                k.in = dense_view(BUF_USER_IN, d.h, d.w, d.c, d.c);
-                k.in.f32 = true;
-                View v = dense_view(new_buffer((long long)d.h * d.w * cpad, esize), d.h, d.w, d.c, cpad);
-                k.out = v;
-                k.note = "f32 NHWC -> T NHWC, channels zero-padded to a 16-byte chunk";
-                net->kernels.push_back(k);
-                L[i].view = v; L[i].materialised = true;
-                break;
-            }
-            case YOLO_OP_CONV: {
-                int s = resolve(d.src[0]);
-                if (!L[s].materialised) return fail(std::string(nm) + "source not materialised");
-                if (i == 1 && first_direct) {
-                    Kernel k;
-                    k.kind = K_FIRST; k.layer = 1; k.src_layer = 1;
-                    k.in = L[0].view;
-                    k.ksize = 3; k.stride = 1; k.cout = d.filters; k.cin = 3; k.cin_s = 3;
-                    k.leaky = d.leaky; k.batch_norm = d.batch_norm;
-                    k.out = out_view_for(1);
-                    if (has_claim[1]) k.note = "-> concat slice";
-                    k.note += " direct conv on the float32 input (no cast/pad pass)";
-                    k.w_src = wsrc;
-                    wsrc += (size_t)d.filters * 27 + (d.batch_norm ? 4 : 1) * (size_t)d.filters;
-                    k.w_off = woff; k.w_bytes = (size_t)27 * d.filters * 4;
-                    k.b_off = roundup_sz(k.w_off + k.w_bytes, 256);
-                    woff = roundup_sz(k.b_off + (size_t)d.filters * 4, 256);
-                    flops += 2.0 * L[i].H * L[i].W * d.filters * 27;
-                    net->kernels.push_back(k);
-                    L[1].view = k.out; L[1].materialised = true;
-                    break;
-                }
-                const View &in = L[s].view;
-                if (in.f32) return fail(std::string(nm) + "conv cannot read a float32 head tensor");
-                int cin = L[s].C;
-                int cin_s = roundup(cin, epc);
-                if (cin_s > in.ld - in.coff && cin_s != cin) return fail(std::string(nm) + "padded input channels exceed the view");
-                if (cin_s != cin && L[s].d.op != YOLO_OP_INPUT)
-                    return fail(std::string(nm) + "input channels must be a multiple of the 16-byte chunk");
-                int chunks = cin_s / epc;
-                Kernel k;
-                k.kind = K_CONV; k.src_layer = i;
-                k.in = in;
-                k.ksize = d.ksize; k.stride = d.stride; k.cout = d.filters; k.cin = cin; k.cin_s = cin_s;
-                k.leaky = d.leaky; k.batch_norm = d.batch_norm;
-                int taps = d.ksize * d.ksize;
-                if (chunks % 8 == 0) {
-                    k.perchunk = 0; k.cpt = chunks; k.ktiles = taps * (chunks / 8);
-                } else if (chunks == 1 || chunks == 2 || chunks == 4) {
-                    k.perchunk = 1; k.cpt = chunks; k.ktiles = (taps * chunks + 7) / 8;
-                } else {
-                    return fail(std::string(nm) + "unsupported input channel count for the implicit-GEMM tiling");
-                }
-                k.cfg = d.filters <= 32 ? CFG_N32 : d.filters <= 64 ? CFG_N64 : CFG_N128;
-                int key = i;
-                const Fuse &f = fuse[i];
-                if (f.kind) key = f.layer;
-                if (f.kind == 1) {
-                    if (!L[f.res].materialised) return fail(std::string(nm) + "residual source not materialised");
-                    k.in2 = L[f.res].view; k.has_res = 1;
-                    if (k.in2.f32) return fail(std::string(nm) + "residual cannot be a float32 head tensor");
-                    k.note = "fused: +shortcut(layer " + std::to_string(f.layer) + ")";
-                } else if (f.kind == 2) {
-                    k.outmode = OUT_UP2; k.note = "fused: upsample x2 (layer " + std::to_string(f.layer) + ")";
-                } else if (f.kind == 3) {
-                    k.outmode = OUT_REORG2; k.note = "fused: reorg x2 (layer " + std::to_string(f.layer) + ")";
-                }
-                k.layer = key;
-                if (has_head[i]) {
-                    k.head = 1;
-                    k.out = head_target[i];
-                    k.note += " -> head logits (float32, reference layout)";
-                } else {
-                    k.out = out_view_for(key);
-                }
-                if (has_claim[key]) k.note += " -> concat slice";
-                // weights
-                int cout_pad = roundup(d.filters, 128);
-                size_t wrow = (size_t)k.ktiles * 128;
-                k.w_src = wsrc;
-                wsrc += (size_t)d.filters * cin * taps + (d.batch_norm ? 4 : 1) * (size_t)d.filters;
-                k.w_off = woff; k.w_bytes = wrow * cout_pad;
-                k.b_off = roundup_sz(k.w_off + k.w_bytes, 256);
-                // (bias region padded to a multiple of 256 couts: the 256-cout tiles load the bias of their whole tile as the
-                // accumulators' initial value before they know how many of its couts exist -- conv_common.h: conv_init_acc_bias)
-                woff = roundup_sz(k.b_off + (size_t)roundup(d.filters, 256) * 4, 256);
-                flops += 2.0 * L[i].H * L[i].W * d.filters * taps * cin;
-                // Darknet-53 stem: first-layer kernel + this 3x3/2 32->64 conv as one kernel (stem.hip) when nobody else
-                // reads the 32-channel tensor (keep_all needs it in memory) and the output takes 16-byte stores
-                if (i == 2 && first_direct && !net->kernels.empty() && net->kernels.back().kind == K_FIRST && s == 1 && sole(1, 2) &&
-                    !net->opt.keep_all && net->opt.dtype == YOLO_DTYPE_F16 && d.ksize == 3 && d.stride == 2 && d.filters == 64 &&
-                    L[1].d.filters == 32 && d.leaky && L[1].d.leaky && f.kind == 0 && !has_head[i] && L[1].H % 2 == 0 && L[1].W % 2 == 0 &&
-                    view_chunk_aligned(k.out, epc) && !k.out.f32 && !getenv("YOLO_NO_STEM")) {
-                    net->kernels.back().stem = 1;
-                    k.stem = 2;
-                    k.note += " fused with the first layer (stem.hip): the 32-channel tensor stays in LDS";
-                }
-                // ... and the 1x1 64->32 conv behind the stem (Darknet-53 layer 3) is computed by the stem kernel too
-                if (i == 3 && net->kernels.size() >= 2 && net->kernels.back().stem == 2 && s == 2 && d.ksize == 1 && d.stride == 1 &&
-                    d.filters == 32 && cin == 64 && d.leaky && f.kind == 0 && !has_head[i] && !k.out.f32 &&
-                    view_chunk_aligned(k.out, epc) && k.in.ld == net->kernels.back().out.ld &&
-                    k.in.coff == net->kernels.back().out.coff && k.in.buf == net->kernels.back().out.buf && !getenv("YOLO_NO_STEM3")) {
-                    k.stem = 3;
-                    k.note += " computed inside the stem kernel (no launch)";
-                }
-                // Back-to-back 1x1 (conv_common.h: conv_epilogue_fused_1x1): a 1x1 128 -> 64 conv whose input is exactly what the 3x3
-                // conv in front of it writes, where that conv's workgroups hold all 128 couts of their positions (Darknet-53 at
-                // 152 x 152: the stride-2 conv into the stage and the first residual block's 3x3, each followed by the next block's
-                // 1x1).  Structural conditions here; whether a launch takes the fused instantiation depends on the tile its batch
-                // picks (conv_dispatch.cpp: resolve_conv), else the 1x1 runs as a launch of its own.
-                if (!net->kernels.empty() && net->opt.dtype == YOLO_DTYPE_F16 && !net->opt.keep_all && !getenv("YOLO_NO_FUSE2") &&
-                    d.ksize == 1 && d.stride == 1 && d.filters == 64 && cin == 128 && f.kind == 0 && !has_head[i] && !k.out.f32 &&
-                    view_chunk_aligned(k.out, epc)) {
-                    Kernel &c = net->kernels.back();
-                    if (c.kind == K_CONV && c.layer == s && c.stem == 0 && c.cout == 128 && c.ksize == 3 && c.cpt % 4 == 0 &&
-                        c.outmode == OUT_NORMAL && !c.head && !c.out.f32 && c.out.buf == k.in.buf && c.out.ld == k.in.ld &&
-                        c.out.coff == k.in.coff && c.out.base == k.in.base && c.out.img_stride == k.in.img_stride) {
-                        c.fuse2_next = 1;
-                        k.fuse2_prev = 1;
-                        k.note += " (computed by the conv in front of it where that launch holds all 128 channels per workgroup)";
-                    }
-                }
-                net->kernels.push_back(k);
-                L[key].view = k.out; L[key].materialised = true;
-                if (key != i) { L[i].materialised = false; }
-                break;
-            }
-            case YOLO_OP_MAXPOOL: {
-                int s = resolve(d.src[0]);
-                if (!L[s].materialised) return fail(std::string(nm) + "source not materialised");
-                // Darknet-19 / tiny-YOLO: the 2x2/2 pool right behind the first conv is taken inside the first-layer kernel
-                // (the full-resolution tensor is never written) when nobody else reads that tensor
-                if (i == 2 && s == 1 && first_direct && !net->kernels.empty() && net->kernels.back().kind == K_FIRST && sole(1, 2) &&
-                    !net->opt.keep_all && d.stride == 2 && L[1].H % 2 == 0 && L[1].W % 2 == 0 && !getenv("YOLO_NO_FIRST_POOL")) {
-                    View pv = out_view_for(i);
-                    if (!pv.f32 && view_chunk_aligned(pv, epc)) {
-                        Kernel &f = net->kernels.back();
-                        f.pool_fused = 1;
-                        f.out = pv;
-                        f.layer = i;
-                        f.note += " + fused 2x2/2 max-pool (layer 2)";
-                        L[i].view = pv; L[i].materialised = true;
-                        L[1].materialised = false;
-                        break;
-                    }
-                }
-                // conv 3x3/1 -> max-pool 2x2/2 on a wide map: the pool is taken in the conv's epilogue (conv_common.h:
-                // conv_epilogue_pool2, the CAP_POOL 2-D tap tiles only, so the conv is pinned to the one of its width) and the
-                // full-resolution tensor is never written.  Wide maps only: below ~96 columns the padded-linear tiles beat the 2-D
-                // ones by more than the pool kernel costs (r03 sweep: 52 x 52 128 -> 256 +9 us vs a 9 us pool)
-                if (!net->kernels.empty() && net->kernels.back().kind == K_CONV && net->kernels.back().layer == s &&
-                    net->kernels.back().src_layer == s && sole(s, i) && !net->opt.keep_all && d.stride == 2 && L[s].H % 2 == 0 &&
-                    L[s].W % 2 == 0 && L[s].W >= 96 && !getenv("YOLO_NO_CONV_POOL")) {
-                    Kernel &c = net->kernels.back();
-                    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-                    const int pool_tile = c.cout == 64 ? TILE_TAP2D_64x256 : c.cout == 32 ? TILE_TAP2D_32x256 : c.cout > 64 ? TILE_TAP2D_128x256 : -1;
-                    if (c.ksize == 3 && c.stride == 1 && c.outmode == OUT_NORMAL && !c.has_res && !c.head && !c.stem && !has_claim[s] &&
-                        c.cpt % 4 == 0 && c.cout % 16 == 0 && pool_tile >= 0 && (f16 || conv_tile(pool_tile).f32_ok())) {
-                        View pv = out_view_for(i);
-                        if (!pv.f32 && view_chunk_aligned(pv, epc)) {
-                            c.outmode = OUT_POOL2;
-                            c.out = pv;
-                            c.layer = i;
-                            c.tile = pool_tile;
-                            c.note += " + fused 2x2/2 max-pool (layer " + std::to_string(i) + ")";
-                            if (has_claim[i]) c.note += " -> concat slice";
-                            L[i].view = pv; L[i].materialised = true;
-                            L[s].materialised = false;
-                            break;
-                        }
-                    }
-                }
-                if (L[i].materialised) break;       // a wider pool of an SPP block: written by the block's fused kernel
-                Kernel k;
-                k.kind = K_POOL; k.layer = i; k.in = L[s].view; k.pool_stride = d.stride; k.pool_k = d.ksize;
-                if (k.in.f32) return fail(std::string(nm) + "maxpool cannot read a float32 head tensor");
-                k.out = out_view_for(i);
-                if (d.ksize != 2 && spp_block(i, s, k)) {
-                    net->kernels.push_back(k);
-                    L[i].view = k.out; L[i].materialised = true;
-                    break;
-                }
-                if (d.ksize != 2) k.note = "SAME max-pool " + std::to_string(d.ksize) + "x" + std::to_string(d.ksize) + "/1" + (has_claim[i] ? " -> concat slice" : "");
-                if (k.out.f32) {    // final layer: pool into T, then convert
-                    View t = alloc_view(L[i].H, L[i].W, L[i].C);
-                    View fin = k.out;
-                    k.out = t;
-                    net->kernels.push_back(k);
-                    add_eltwise(i, t, nullptr, fin, OUT_NORMAL, "convert final layer to float32");
-                    L[i].view = fin;
-                } else {
-                    net->kernels.push_back(k);
-                    L[i].view = k.out;
+    // a final layer produced by something that cannot write the user tensor directly: one more pass, T -> float32
+    void convert_final(int i, const View &src, const View &fin) {
+        add_eltwise(i, src, nullptr, fin, OUT_NORMAL, "convert final layer to float32");
+        L[i].view = fin;
+    }
+
+    // The weights of conv layer i: where its values stand in the Darknet stream and in the packed blob -- w_bytes of weights, the bias
+    // of bias_couts floats behind them, each region 256-byte aligned -- and its share of the FLOP total.
+    void weight_region(Kernel &k, int i, int taps, int cin, size_t w_bytes, int bias_couts) {
+        const yolo_layer_desc &d = L[i].d;
+        k.w_src = wsrc;
+        wsrc += (size_t)d.filters * cin * taps + (d.batch_norm ? 4 : 1) * (size_t)d.filters;
+        k.w_off = woff; k.w_bytes = w_bytes;
+        k.b_off = roundup_sz(k.w_off + k.w_bytes, 256);
+        woff = roundup_sz(k.b_off + (size_t)bias_couts * 4, 256);
+        flops += 2.0 * L[i].H * L[i].W * d.filters * taps * cin;
+    }
+
+    // ---- the launch-fusion rules: each tests its structural conditions and, where they hold, applies its marks and notes ----
+
+    // first layer 3x3/1 on a 3-channel input with 16|32 filters: the direct kernel of
+    // first.hip reads the caller's float32 tensor itself, so no cast/pad pass is needed
+    bool try_first_direct() {
+        const yolo_layer_desc &d = L[0].d;
+        first_direct = n > 2 && d.c == 3 && L[1].d.op == YOLO_OP_CONV && L[1].d.src[0] == 0 && L[1].d.ksize == 3 &&
+                       L[1].d.stride == 1 && (L[1].d.filters == 16 || L[1].d.filters == 32) && sole(0, 1) &&
+                       fuse[1].kind == 0 && !has_head[1] && !has_claim[1] && rule_on(R_FIRST_DIRECT);
+        if (!first_direct) return false;
+        L[0].view = dense_view(BUF_USER_IN, d.h, d.w, d.c, d.c);
+        L[0].view.f32 = true;
+        L[0].materialised = true;
+        return true;
+    }
+
+    // Darknet-53 stem: first-layer kernel + this 3x3/2 32->64 conv as one kernel (stem.hip) when nobody else
+    // reads the 32-channel tensor (keep_all needs it in memory) and the output takes 16-byte stores
+    bool try_stem(int i, int s, Kernel &k) {
+        const yolo_layer_desc &d = L[i].d;
+        if (!(i == 2 && first_direct && !net->kernels.empty() && net->kernels.back().kind == K_FIRST && s == 1 && sole(1, 2) &&
+              !net->opt.keep_all && net->opt.dtype == YOLO_DTYPE_F16 && d.ksize == 3 && d.stride == 2 && d.filters == 64 &&
+              L[1].d.filters == 32 && d.leaky && L[1].d.leaky && fuse[i].kind == 0 && !has_head[i] && L[1].H % 2 == 0 && L[1].W % 2 == 0 &&
+              view_chunk_aligned(k.out, epc) && !k.out.f32 && rule_on(R_STEM)))
+            return false;
+        net->kernels.back().stem = STEM_FIRST_FOLDED;
+        k.stem = STEM_HOST;
+        k.note += " fused with the first layer (stem.hip): the 32-channel tensor stays in LDS";
+        return true;
+    }
+
+    // ... and the 1x1 64->32 conv behind the stem (Darknet-53 layer 3) is computed by the stem kernel too
+    bool try_stem_tail(int i, int s, Kernel &k) {
+        const yolo_layer_desc &d = L[i].d;
+        if (!(i == 3 && net->kernels.size() >= 2 && net->kernels.back().stem == STEM_HOST && s == 2 && d.ksize == 1 && d.stride == 1 &&
+              d.filters == 32 && k.cin == 64 && d.leaky && fuse[i].kind == 0 && !has_head[i] && !k.out.f32 &&
+              view_chunk_aligned(k.out, epc) && k.in.ld == net->kernels.back().out.ld &&
+              k.in.coff == net->kernels.back().out.coff && k.in.buf == net->kernels.back().out.buf && rule_on(R_STEM_TAIL)))
+            return false;
+        k.stem = STEM_TAIL;
+        k.note += " computed inside the stem kernel (no launch)";
+        return true;
+    }
+
+    // Back-to-back 1x1 (conv_common.h: conv_epilogue_fused_1x1): a 1x1 128 -> 64 conv whose input is exactly what the 3x3
+    // conv in front of it writes, where that conv's workgroups hold all 128 couts of their positions (Darknet-53 at
+    // 152 x 152: the stride-2 conv into the stage and the first residual block's 3x3, each followed by the next block's
+    // 1x1).  Structural conditions here; whether a launch takes the fused instantiation depends on the tile its batch
+    // picks (conv_dispatch.cpp: resolve_conv), else the 1x1 runs as a launch of its own.
+    bool try_fuse2(int i, int s, Kernel &k) {
+        const yolo_layer_desc &d = L[i].d;
+        if (!(!net->kernels.empty() && net->opt.dtype == YOLO_DTYPE_F16 && !net->opt.keep_all && rule_on(R_FUSE2) &&
+              d.ksize == 1 && d.stride == 1 && d.filters == 64 && k.cin == 128 && fuse[i].kind == 0 && !has_head[i] && !k.out.f32 &&
+              view_chunk_aligned(k.out, epc)))
+            return false;
+        Kernel &c = net->kernels.back();
+        if (!(c.kind == K_CONV && c.layer == s && c.stem == STEM_NONE && c.cout == 128 && c.ksize == 3 && c.cpt % 4 == 0 &&
+              c.outmode == OUT_NORMAL && !c.head && !c.out.f32 && c.out.buf == k.in.buf && c.out.ld == k.in.ld &&
+              c.out.coff == k.in.coff && c.out.base == k.in.base && c.out.img_stride == k.in.img_stride))
+            return false;
+        c.fuse2_next = 1;
+        k.fuse2_prev = 1;
+        k.note += " (computed by the conv in front of it where that launch holds all 128 channels per workgroup)";
+        return true;
+    }
+
+    // Darknet-19 / tiny-YOLO: the 2x2/2 pool right behind the first conv is taken inside the first-layer kernel
+    // (the full-resolution tensor is never written) when nobody else reads that tensor
+    bool try_first_pool(int i, int s) {
+        const yolo_layer_desc &d = L[i].d;
+        if (!(i == 2 && s == 1 && first_direct && !net->kernels.empty() && net->kernels.back().kind == K_FIRST && sole(1, 2) &&
+              !net->opt.keep_all && d.stride == 2 && L[1].H % 2 == 0 && L[1].W % 2 == 0 && rule_on(R_FIRST_POOL)))
+            return false;
+        View pv = out_view_for(i);
+        if (pv.f32 || !view_chunk_aligned(pv, epc)) return false;
+        Kernel &f = net->kernels.back();
+        f.pool_fused = 1;
+        f.out = pv;
+        f.layer = i;
+        f.note += " + fused 2x2/2 max-pool (layer 2)";
+        L[i].view = pv; L[i].materialised = true;
+        L[1].materialised = false;
+        return true;
+    }
+
+    // conv 3x3/1 -> max-pool 2x2/2 on a wide map: the pool is taken in the conv's epilogue (conv_common.h:
+    // conv_epilogue_pool2, the CAP_POOL 2-D tap tiles only, so the conv is pinned to the one of its width) and the
+    // full-resolution tensor is never written.  Wide maps only: below ~96 columns the padded-linear tiles beat the 2-D
+    // ones by more than the pool kernel costs (r03 sweep: 52 x 52 128 -> 256 +9 us vs a 9 us pool)
+    bool try_conv_pool(int i, int s) {
+        const yolo_layer_desc &d = L[i].d;
+        if (!(!net->kernels.empty() && net->kernels.back().kind == K_CONV && net->kernels.back().layer == s &&
+              net->kernels.back().src_layer == s && sole(s, i) && !net->opt.keep_all && d.stride == 2 && L[s].H % 2 == 0 &&
+              L[s].W % 2 == 0 && L[s].W >= 96 && rule_on(R_CONV_POOL)))
+            return false;
+        Kernel &c = net->kernels.back();
+        const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
+        const int pool_tile = c.cout == 64 ? TILE_TAP2D_64x256 : c.cout == 32 ? TILE_TAP2D_32x256 : c.cout > 64 ? TILE_TAP2D_128x256 : -1;
+        if (!(c.ksize == 3 && c.stride == 1 && c.outmode == OUT_NORMAL && !c.has_res && !c.head && !c.stem && !has_claim[s] &&
+              c.cpt % 4 == 0 && c.cout % 16 == 0 && pool_tile >= 0 && (f16 || conv_tile(pool_tile).f32_ok())))
+            return false;
+        View pv = out_view_for(i);
+        if (pv.f32 || !view_chunk_aligned(pv, epc)) return false;
+        c.outmode = OUT_POOL2;
+        c.out = pv;
+        c.layer = i;
+        c.tile = pool_tile;
+        c.note += " + fused 2x2/2 max-pool (layer " + std::to_string(i) + ")";
+        if (has_claim[i]) c.note += " -> concat slice";
+        L[i].view = pv; L[i].materialised = true;
+        L[s].materialised = false;
+        return true;
+    }
+
+    // ---- one function per layer op: the generic lowering, plus the rules that may take its place ----
+
+    bool emit_input(int i) {
+        const yolo_layer_desc &d = L[i].d;
+        if (try_first_direct()) return true;
+        int cpad = roundup(d.c, epc);
+        Kernel k;
+        k.kind = K_PREP; k.layer = 0;
+        k.in = dense_view(BUF_USER_IN, d.h, d.w, d.c, d.c);
+        k.in.f32 = true;
+        View v = dense_view(new_buffer((long long)d.h * d.w * cpad, esize), d.h, d.w, d.c, cpad);
+        k.out = v;
+        k.note = "f32 NHWC -> T NHWC, channels zero-padded to a 16-byte chunk";
+        net->kernels.push_back(k);
+        L[i].view = v; L[i].materialised = true;
+        return true;
+    }
+
+    // layer 1 under first_direct: [27 = (kh,kw,cin)][cout] float32 weights, the bias of its couts
+    void emit_first_conv() {
+        const yolo_layer_desc &d = L[1].d;
+        Kernel k;
+        k.kind = K_FIRST; k.layer = 1; k.src_layer = 1;
+        k.in = L[0].view;
+        k.ksize = 3; k.stride = 1; k.cout = d.filters; k.cin = 3; k.cin_s = 3;
+        k.leaky = d.leaky; k.batch_norm = d.batch_norm;
+        k.out = out_view_for(1);
+        if (has_claim[1]) k.note = "-> concat slice";
+        k.note += " direct conv on the float32 input (no cast/pad pass)";
+        weight_region(k, 1, 9, 3, (size_t)27 * d.filters * 4, d.filters);
+        net->kernels.push_back(k);
+        L[1].view = k.out; L[1].materialised = true;
+    }
+
+    bool emit_conv(int i, const std::string &nm) {
+        const yolo_layer_desc &d = L[i].d;
+        int s = resolve(d.src[0]);
+        if (!L[s].materialised) return fail(nm + "source not materialised");
+        if (i == 1 && first_direct) { emit_first_conv(); return true; }
+        const View &in = L[s].view;
+        if (in.f32) return fail(nm + "conv cannot read a float32 head tensor");
+        int cin = L[s].C;
+        int cin_s = roundup(cin, epc);
+        if (cin_s > in.ld - in.coff && cin_s != cin) return fail(nm + "padded input channels exceed the view");
+        if (cin_s != cin && L[s].d.op != YOLO_OP_INPUT)
+            return fail(nm + "input channels must be a multiple of the 16-byte chunk");
+        int chunks = cin_s / epc;
+        Kernel k;
+        k.kind = K_CONV; k.src_layer = i;
+        k.in = in;
+        k.ksize = d.ksize; k.stride = d.stride; k.cout = d.filters; k.cin = cin; k.cin_s = cin_s;
+        k.leaky = d.leaky; k.batch_norm = d.batch_norm;
+        int taps = d.ksize * d.ksize;
+        if (chunks % 8 == 0) {
+            k.perchunk = 0; k.cpt = chunks; k.ktiles = taps * (chunks / 8);
+        } else if (chunks == 1 || chunks == 2 || chunks == 4) {
+            k.perchunk = 1; k.cpt = chunks; k.ktiles = (taps * chunks + 7) / 8;
+        } else {
+            return fail(nm + "unsupported input channel count for the implicit-GEMM tiling");
+        }
+        k.cfg = d.filters <= 32 ? CFG_N32 : d.filters <= 64 ? CFG_N64 : CFG_N128;
+        int key = i;
+        const Fuse &f = fuse[i];
+        if (f.kind) key = f.layer;
+        if (f.kind == 1) {
+            if (!L[f.res].materialised) return fail(nm + "residual source not materialised");
+            k.in2 = L[f.res].view; k.has_res = 1;
+            if (k.in2.f32) return fail(nm + "residual cannot be a float32 head tensor");
+            k.note = "fused: +shortcut(layer " + std::to_string(f.layer) + ")";
+        } else if (f.kind == 2) {
+            k.outmode = OUT_UP2; k.note = "fused: upsample x2 (layer " + std::to_string(f.layer) + ")";
+        } else if (f.kind == 3) {
+            k.outmode = OUT_REORG2; k.note = "fused: reorg x2 (layer " + std::to_string(f.layer) + ")";
+        }
+        k.layer = key;
+        if (has_head[i]) {
+            k.head = 1;
+            k.out = head_target[i];
+            k.note += " -> head logits (float32, reference layout)";
+        } else {
+            k.out = out_view_for(key);
+        }
+        if (has_claim[key]) k.note += " -> concat slice";
+        // [cout_pad][K] rows; the bias region padded to a multiple of 256 couts: the 256-cout tiles load the bias of their whole tile as the
+        // accumulators' initial value before they know how many of its couts exist -- conv_common.h: conv_init_acc_bias
+        weight_region(k, i, taps, cin, (size_t)k.ktiles * 128 * roundup(d.filters, 128), roundup(d.filters, 256));
+        try_stem(i, s, k);
+        try_stem_tail(i, s, k);
+        try_fuse2(i, s, k);
+        net->kernels.push_back(k);
+        L[key].view = k.out; L[key].materialised = true;
+        if (key != i) { L[i].materialised = false; }
+        return true;
+    }
+
+    bool emit_maxpool(int i, const std::string &nm) {
+        const yolo_layer_desc &d = L[i].d;
+        int s = resolve(d.src[0]);
+        if (!L[s].materialised) return fail(nm + "source not materialised");
+        if (try_first_pool(i, s) || try_conv_pool(i, s)) return true;
+        if (L[i].materialised) return true;       // a wider pool of an SPP block: written by the block's fused kernel
+        Kernel k;
+        k.kind = K_POOL; k.layer = i; k.in = L[s].view; k.pool_stride = d.stride; k.pool_k = d.ksize;
+        if (k.in.f32) return fail(nm + "maxpool cannot read a float32 head tensor");
+        k.out = out_view_for(i);
+        if (d.ksize != 2 && try_spp_block(i, s, k)) {
+            net->kernels.push_back(k);
+            L[i].view = k.out; L[i].materialised = true;
+            return true;
+        }
+        if (d.ksize != 2) k.note = "SAME max-pool " + std::to_string(d.ksize) + "x" + std::to_string(d.ksize) + "/1" + (has_claim[i] ? " -> concat slice" : "");
+        if (k.out.f32) {    // final layer: pool into T, then convert
+            const View fin = k.out;
+            k.out = alloc_view(L[i].H, L[i].W, L[i].C);
+            net->kernels.push_back(k);
+            convert_final(i, k.out, fin);
+        } else {
+            net->kernels.push_back(k);
+            L[i].view = k.out;
+        }
+        L[i].materialised = true;
+        return true;
+    }
+
+    bool emit_route(int i, const std::string &nm) {
+        const yolo_layer_desc &d = L[i].d;
+        if (d.n_src == 1) {
+            int s = resolve(d.src[0]);
+            L[i].view = L[s].view; L[i].materialised = L[s].materialised;
+            if (i == n - 1) convert_final(i, L[s].view, out_view_for(i));
+            return true;
+        }
+        View v = dense_view(route_buf[i], L[i].H, L[i].W, L[i].C, L[i].C);
+        for (const Copy &c : copies) {
+            if (c.route != i) continue;
+            if (!L[c.src].materialised) return fail(nm + "route source not materialised");
+            View o = dense_view(route_buf[i], L[c.src].H, L[c.src].W, L[c.src].C, L[i].C);
+            o.coff = c.coff;
+            add_eltwise(i, L[c.src].view, nullptr, o, OUT_NORMAL, "concat by copy (source could not write in place)");
+        }
+        L[i].view = v; L[i].materialised = true;
+        if (i == n - 1) convert_final(i, v, out_view_for(i));
+        return true;
+    }
+
+    // reorg / upsample / shortcut that no conv's epilogue produces
+    bool emit_eltwise_op(int i, const std::string &nm) {
+        const yolo_layer_desc &d = L[i].d;
+        if (L[i].fused_into >= 0) return true;    // produced by the conv's epilogue
+        int a = resolve(d.src[0]);
+        if (!L[a].materialised) return fail(nm + "source not materialised");
+        View out = out_view_for(i);
+        if (d.op == YOLO_OP_SHORTCUT) {
+            int b = resolve(d.src[1]);
+            if (!L[b].materialised) return fail(nm + "source not materialised");
+            add_eltwise(i, L[a].view, &L[b].view, out, OUT_NORMAL, "standalone shortcut add");
+        } else {
+            add_eltwise(i, L[a].view, nullptr, out, d.op == YOLO_OP_REORG ? OUT_REORG2 : OUT_UP2,
+                        d.op == YOLO_OP_REORG ? "standalone reorg" : "standalone upsample");
+        }
+        L[i].view = out; L[i].materialised = true;
+        return true;
+    }
+
+    bool emit_yolo(int i, const std::string &nm) {
+        const yolo_layer_desc &d = L[i].d;
+        int a = resolve(d.src[0]);
+        if (n - 1 > i && L[n - 1].d.op == YOLO_OP_DETECTION) {
+            bool in_det = false;
+            for (int k = 0; k < L[n - 1].d.n_src; ++k) in_det |= L[n - 1].d.src[k] == i;
+            if (in_det) {
+                if (!(L[a].d.op == YOLO_OP_CONV && has_head[a])) {
+                    if (!L[a].materialised) return fail(nm + "source not materialised");
+                    add_eltwise(i, L[a].view, nullptr, L[i].view, OUT_NORMAL, "copy head rows into the output tensor");
                 }
                 L[i].materialised = true;
-                break;
+                return true;
             }
-            case YOLO_OP_ROUTE: {
-                if (d.n_src == 1) {
-                    int s = resolve(d.src[0]);
-                    L[i].view = L[s].view; L[i].materialised = L[s].materialised;
-                    if (i == n - 1) {
-                        View fin = out_view_for(i);
-                        add_eltwise(i, L[s].view, nullptr, fin, OUT_NORMAL, "convert final layer to float32");
-                        L[i].view = fin;
-                    }
-                    break;
-                }
-                View v = dense_view(route_buf[i], L[i].H, L[i].W, L[i].C, L[i].C);
-                for (const Copy &c : copies) {
-                    if (c.route != i) continue;
-                    if (!L[c.src].materialised) return fail(std::string(nm) + "route source not materialised");
-                    View o = dense_view(route_buf[i], L[c.src].H, L[c.src].W, L[c.src].C, L[i].C);
-                    o.coff = c.coff;
-                    add_eltwise(i, L[c.src].view, nullptr, o, OUT_NORMAL, "concat by copy (source could not write in place)");
-                }
-                L[i].view = v; L[i].materialised = true;
-                if (i == n - 1) {
-                    View fin = out_view_for(i);
-                    add_eltwise(i, v, nullptr, fin, OUT_NORMAL, "convert final layer to float32");
-                    L[i].view = fin;
-                }
-                break;
-            }
+        }
+        L[i].view = L[a].view; L[i].materialised = L[a].materialised;
+        return true;
+    }
+
+    bool emit() {
+        for (int i = 0; i < n; ++i) {
+            const std::string nm = "layer " + std::to_string(i) + ": ";
+            bool ok = true;
+            switch (L[i].d.op) {
+            case YOLO_OP_INPUT: ok = emit_input(i); break;
+            case YOLO_OP_CONV: ok = emit_conv(i, nm); break;
+            case YOLO_OP_MAXPOOL: ok = emit_maxpool(i, nm); break;
+            case YOLO_OP_ROUTE: ok = emit_route(i, nm); break;
             case YOLO_OP_REORG:
             case YOLO_OP_UPSAMPLE:
-            case YOLO_OP_SHORTCUT: {
-                if (L[i].fused_into >= 0) break;    // produced by the conv's epilogue
-                int a = resolve(d.src[0]);
-                if (!L[a].materialised) return fail(std::string(nm) + "source not materialised");
-                View out = out_view_for(i);
-                if (d.op == YOLO_OP_SHORTCUT) {
-                    int b = resolve(d.src[1]);
-                    if (!L[b].materialised) return fail(std::string(nm) + "source not materialised");
-                    add_eltwise(i, L[a].view, &L[b].view, out, OUT_NORMAL, "standalone shortcut add");
-                } else {
-                    add_eltwise(i, L[a].view, nullptr, out, d.op == YOLO_OP_REORG ? OUT_REORG2 : OUT_UP2,
-                                d.op == YOLO_OP_REORG ? "standalone reorg" : "standalone upsample");
-                }
-                L[i].view = out; L[i].materialised = true;
-                break;
+            case YOLO_OP_SHORTCUT: ok = emit_eltwise_op(i, nm); break;
+            case YOLO_OP_YOLO: ok = emit_yolo(i, nm); break;
+            case YOLO_OP_DETECTION: L[i].materialised = true; break;
             }
-            case YOLO_OP_YOLO: {
-                int a = resolve(d.src[0]);
-                if (n - 1 > i && L[n - 1].d.op == YOLO_OP_DETECTION) {
-                    bool in_det = false;
-                    for (int k = 0; k < L[n - 1].d.n_src; ++k) in_det |= L[n - 1].d.src[k] == i;
-                    if (in_det) {
-                        if (!(L[a].d.op == YOLO_OP_CONV && has_head[a])) {
-                            if (!L[a].materialised) return fail(std::string(nm) + "source not materialised");
-                            add_eltwise(i, L[a].view, nullptr, L[i].view, OUT_NORMAL, "copy head rows into the output tensor");
-                        }
-                        L[i].materialised = true;
-                        break;
-                    }
-                }
-                L[i].view = L[a].view; L[i].materialised = L[a].materialised;
-                break;
-            }
-            case YOLO_OP_DETECTION:
-                L[i].materialised = true;
-                break;
-            }
+            if (!ok) return false;
         }
-        // a final layer produced by something that cannot write the user tensor directly
-        {
-            int last = n - 1;
-            if (L[last].d.op == YOLO_OP_INPUT) {
-                View fin = out_view_for(last);
-                add_eltwise(last, L[last].view, nullptr, fin, OUT_NORMAL, "convert final layer to float32");
-                L[last].view = fin;
-            }
-            if (!L[last].materialised) return fail("final layer was not materialised");
-        }
+        const int last = n - 1;
+        if (L[last].d.op == YOLO_OP_INPUT) convert_final(last, L[last].view, out_view_for(last));
+        if (!L[last].materialised) return fail("final layer was not materialised");
         net->weight_count = wsrc;
         net->weights_bytes = woff ? woff : 256;
         net->flops_per_image = flops;
@@ -680,7 +734,7 @@ struct Planner {
             const bool by_rule = want <= 0;
             if (want <= 0) {
                 int convs = 0;
-                for (const Kernel &k : K) convs += k.kind == K_CONV && k.stem < 3;
+                for (const Kernel &k : K) convs += counts_as_conv_launch(k);
                 const yolo_layer_desc &d0 = net->layers[0].d;
                 const double px_per_part = (double)(net->opt.max_batch / 2) * d0.h * d0.w;
                 want = (net->opt.dtype == YOLO_DTYPE_F16 && convs >= 40 && px_per_part >= 2.5e6) ? 2 : 1;
@@ -778,152 +832,6 @@ bool mx_eligible(const yolo_net *net, const Kernel &k) {
     if (k.stem || k.fuse2_next || k.fuse2_prev || k.head || k.outmode == OUT_POOL2 || k.in.f32) return false;
     if (!conv_mx_fits(k.in.W) || k.in.H != k.out.H || k.in.W != k.out.W) return false;
     return view_chunk_aligned(k.in, 8) && k.in.coff + k.cin <= k.in.ld;        // (k.in.base is 0: only float32 head views have one)
-}
-
-// float -> e4m3fn, round to nearest even; |x| <= 448 (the caller clamps)
-static unsigned char e4m3_rne(double x) {
-    const unsigned char sign = std::signbit(x) ? 0x80 : 0;
-    const double a = std::fabs(x);
-    if (a < 0.015625) return sign | (unsigned char)std::nearbyint(a * 512.0);      // subnormal m * 2^-9 (m = 8: the smallest normal)
-    int E;
-    const double fr = std::frexp(a, &E);        // a = fr 2^E, fr in [0.5, 1)
-    int e = E - 1, mant = (int)std::nearbyint((2.0 * fr - 1.0) * 8.0);
-    if (mant == 8) { ++e; mant = 0; }
-    return sign | (unsigned char)((e + 7) << 3) | (unsigned char)mant;
-}
-
-// the host twin of conv_mx.hip's mx_quant_block (OCP MX: e = floor(log2 amax) - 8, clamped to E8M0; elements RNE, saturated)
-unsigned char mx_quant_block_host(const float *v, unsigned char *q) {
-    float amax = 0.0f;
-    for (int i = 0; i < 32; ++i) amax = std::fmax(amax, std::fabs(v[i]));
-    if (amax == 0.0f) {
-        for (int i = 0; i < 32; ++i) q[i] = 0;
-        return 0;
-    }
-    int E;
-    (void)std::frexp(amax, &E);
-    int eb = (E - 1) - 8 + 127;
-    eb = eb < 0 ? 0 : eb > 254 ? 254 : eb;
-    const double mul = std::ldexp(1.0, 127 - eb);
-    for (int i = 0; i < 32; ++i) {
-        double x = (double)v[i] * mul;
-        x = x > 448.0 ? 448.0 : x < -448.0 ? -448.0 : x;
-        q[i] = e4m3_rne(x);
-    }
-    return (unsigned char)eb;
-}
-
-// conv_mx.hip weight image of one conv: for cout group G (32 couts), tap t, 128-channel slice s, cout tile a (0, 1) and lane l, the 32
-// e4m3 values of the MFMA A operand at ((((G * 9 + t) * S + s) * 2 + a) * 64 + l) * 32 -- row R = l & 15 = cout 32 G + 8 (R >> 2) +
-// 4 a + (R & 3); lane group g = l >> 4 holds channels 16 g .. 16 g + 15 and 64 + 16 g .. of the slice (conv_mx.hip: lane map) --, and
-// the scale byte of 32-channel block g of that row at the same fragment index behind all elements
-static void mx_pack(const Kernel &k, const float *kern, const std::vector<double> &scale, unsigned char *dst) {
-    const int S = k.cin / 128, cout_pad = (k.cout + 127) / 128 * 128;
-    unsigned char *sdst = dst + (size_t)cout_pad * 9 * k.cin;
-    float v[32];
-    unsigned char q[4][32], sc[4];
-    for (int G = 0; G < cout_pad / 32; ++G)
-        for (int t = 0; t < 9; ++t)
-            for (int s = 0; s < S; ++s)
-                for (int a = 0; a < 2; ++a)
-                    for (int R = 0; R < 16; ++R) {
-                        const int o = 32 * G + 8 * (R >> 2) + 4 * a + (R & 3);
-                        for (int b = 0; b < 4; ++b) {
-                            for (int j = 0; j < 32; ++j)
-                                v[j] = o < k.cout ? (float)((double)kern[((size_t)o * k.cin + s * 128 + 32 * b + j) * 9 + t] * scale[o]) : 0.0f;
-                            sc[b] = mx_quant_block_host(v, q[b]);
-                        }
-                        for (int g = 0; g < 4; ++g) {
-                            const size_t f = ((((size_t)G * 9 + t) * S + s) * 2 + a) * 64 + 16 * g + R;
-                            memcpy(dst + f * 32, q[g >> 1] + 16 * (g & 1), 16);
-                            memcpy(dst + f * 32 + 16, q[2 + (g >> 1)] + 16 * (g & 1), 16);
-                            sdst[f] = sc[g];
-                        }
-                    }
-}
-
-// Darknet stream -> device layout.  Order per conv (net/layers.py:53-63; net/base.py:26-46):
-// BN: beta, gamma, moving_mean, moving_variance, kernel[out][in][kh][kw]; else bias, kernel.
-// Fold: w' = w * gamma/sqrt(var+eps), b' = beta - mean*gamma/sqrt(var+eps), eps = 1e-5
-// (net/layers.py:5), computed in float64 and rounded once.
-int pack_weights(const yolo_net *net, const float *host, size_t n, std::vector<unsigned char> &blob, std::string &err) {
-    if (n != net->weight_count) {
-        err = "weight stream holds " + std::to_string(n) + " values, the layer list needs " + std::to_string(net->weight_count);
-        return YOLO_ERR_WEIGHTS;
-    }
-    blob.assign(net->weights_bytes, 0);
-    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-    for (const Kernel &k : net->kernels) {
-        if (k.kind == K_FIRST) {        // [27 = (kh,kw,cin)][cout] float32 (first.hip)
-            const float *p = host + k.w_src;
-            const float *beta = nullptr, *gamma = nullptr, *mean = nullptr, *var = nullptr, *bias = nullptr;
-            if (k.batch_norm) { beta = p; gamma = p + k.cout; mean = p + 2 * k.cout; var = p + 3 * k.cout; p += 4 * (size_t)k.cout; }
-            else { bias = p; p += k.cout; }
-            float *wdst = reinterpret_cast<float *>(blob.data() + k.w_off);
-            float *bdst = reinterpret_cast<float *>(blob.data() + k.b_off);
-            for (int o = 0; o < k.cout; ++o) {
-                double scale = 1.0;
-                if (k.batch_norm) {
-                    scale = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-                    bdst[o] = (float)((double)beta[o] - (double)mean[o] * scale);
-                } else {
-                    bdst[o] = bias[o];
-                }
-                for (int t = 0; t < 9; ++t)
-                    for (int ci = 0; ci < 3; ++ci) {
-                        float v = (float)((double)p[((size_t)o * 3 + ci) * 9 + t] * scale);
-                        if (f16) v = (float)(_Float16)v;        // same operand rounding as the MFMA path
-                        wdst[(t * 3 + ci) * k.cout + o] = v;
-                    }
-            }
-            continue;
-        }
-        if (k.kind != K_CONV) continue;
-        const int taps = k.ksize * k.ksize;
-        const float *p = host + k.w_src;
-        const float *beta = nullptr, *gamma = nullptr, *mean = nullptr, *var = nullptr, *bias = nullptr;
-        if (k.batch_norm) { beta = p; gamma = p + k.cout; mean = p + 2 * k.cout; var = p + 3 * k.cout; p += 4 * (size_t)k.cout; }
-        else { bias = p; p += k.cout; }
-        const float *kern = p;      // [out][in][kh][kw]
-        float *bdst = reinterpret_cast<float *>(blob.data() + k.b_off);
-        const size_t wrow = (size_t)k.ktiles * 128;
-        if (k.mx) {     // folded bias as below; weights folded in float64, rounded to float32, quantized to MXFP8 once
-            std::vector<double> sc((size_t)k.cout, 1.0);
-            for (int o = 0; o < k.cout; ++o) {
-                if (k.batch_norm) {
-                    sc[o] = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-                    bdst[o] = (float)((double)beta[o] - (double)mean[o] * sc[o]);
-                } else {
-                    bdst[o] = bias[o];
-                }
-            }
-            if ((size_t)(k.cout + 127) / 128 * 128 * 9 * k.cin * 33 / 32 > k.w_bytes) {
-                err = "MX weight image does not fit the conv's weight region";
-                return YOLO_ERR_PLAN;
-            }
-            mx_pack(k, kern, sc, blob.data() + k.w_off);
-            continue;
-        }
-        for (int o = 0; o < k.cout; ++o) {
-            double scale = 1.0;
-            if (k.batch_norm) {
-                scale = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-                bdst[o] = (float)((double)beta[o] - (double)mean[o] * scale);
-            } else {
-                bdst[o] = bias[o];
-            }
-            unsigned char *row = blob.data() + k.w_off + (size_t)o * wrow;
-            for (int t = 0; t < taps; ++t) {
-                for (int ci = 0; ci < k.cin; ++ci) {
-                    float v = (float)((double)kern[((size_t)o * k.cin + ci) * taps + t] * scale);
-                    size_t e = (size_t)t * k.cin_s + ci;     // (kh,kw) major, cin minor; chunk = e / epc
-                    if (f16) reinterpret_cast<_Float16 *>(row)[e] = (_Float16)v;
-                    else reinterpret_cast<float *>(row)[e] = v;
-                }
-            }
-        }
-    }
-    return YOLO_OK;
 }
 
 static const char *kind_name(int k) {

@@ -159,7 +159,7 @@ hipError_t launch_head_wgrad(const WgradParams &p, int x_dtype, hipStream_t s) {
 // One thread per element, the weights first and the bias behind them.  Every operation is float32 and rounded on its own:
 //   m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + (1 - beta2) * (g * g);  w = w - (lr_t * m) / (sqrt(v) + eps)
 // with IEEE division and square root (hipcc's default for HIP).  pack_w / pack_b, if not null, receive the element in the layout the conv
-// kernels read: row o of the 1 x 1 conv at o * pack_row elements, the plan's weight type (plan.cpp: pack_weights), float32 bias.
+// kernels read: row o of the 1 x 1 conv at o * pack_row elements, the plan's weight type (weights.cpp: pack_weights), float32 bias.
 __global__ void __launch_bounds__(kAuxBlock) adam_step_kernel(const AdamParams p) {
 #pragma clang fp contract(off)
     const float om1 = 1.f - p.beta1, om2 = 1.f - p.beta2;

@@ -505,6 +505,12 @@ size_t nms_lds_bytes(int cap);
 size_t nms_scratch_bytes(int cap);
 
 // ---- plan -----------------------------------------------------------------------------------
+enum StemRole {
+    STEM_NONE = 0,
+    STEM_FIRST_FOLDED = 1,     // K_FIRST: the first-layer kernel is fused away into the next conv (no launch)
+    STEM_HOST = 2,             // K_CONV: this 3x3/2 conv runs as stem.hip, together with the first layer in front of it
+    STEM_TAIL = 3,             // K_CONV: this 1x1 conv is computed by the stem kernel in front of it (no launch)
+};
 struct Kernel {
     int kind = 0;
     int layer = -1;            // reference layer index this kernel materialises
@@ -516,8 +522,7 @@ struct Kernel {
     int tile = -1;             // conv_dma tile id chosen by yolo_net_autotune (-1: heuristic)
     int head = 0;              // conv writes float32 head logits into the reference-layout output
     int pool_fused = 0;        // K_FIRST: the max-pool layer behind it is taken in the same kernel
-    int stem = 0;              // 1: first-layer kernel fused away into the next conv; 2: this conv runs as stem.hip with it;
-                               // 3: this 1x1 conv is computed by the stem kernel in front of it (no launch)
+    StemRole stem = STEM_NONE; // this kernel's part in the Darknet-53 stem launch (stem.hip), if any
     int fuse2_next = 0;        // the NEXT kernel is a 1x1 128 -> 64 conv on this conv's output that the fused instantiation of this launch
                                // can compute (conv_common.h: conv_epilogue_fused_1x1); whether it does is decided per launch (conv_dispatch.cpp: resolve_conv)
     int fuse2_prev = 0;        // ... and the mark on that 1x1: skipped when the conv in front of it has computed it
@@ -535,6 +540,12 @@ struct Kernel {
     View out2, out3;
     std::string note;
 };
+// this conv goes through the conv dispatch (conv_dispatch.cpp: resolve_conv) -- the stem's launch and the 1x1 it computes do not
+inline bool conv_dispatched(const Kernel &k) { return k.kind == K_CONV && k.stem != STEM_HOST && k.stem != STEM_TAIL; }
+// this kernel has a launch of its own -- the two the stem kernel computes beside its 3x3/2 conv have none
+inline bool has_own_launch(const Kernel &k) { return !(k.kind == K_FIRST && k.stem == STEM_FIRST_FOLDED) && !(k.kind == K_CONV && k.stem == STEM_TAIL); }
+// counts as a conv launch for the stream rule (plan.cpp: allocate)
+inline bool counts_as_conv_launch(const Kernel &k) { return k.kind == K_CONV && k.stem != STEM_TAIL; }
 
 struct LayerInfo {
     yolo_layer_desc d;

@@ -134,7 +134,7 @@ def trunc_f16(v):
 
 
 def folded(wd):
-    """float64 fold of plan.cpp pack_weights / forward_ref._conv_folded_fp16 -> (kernel float64 [o][i][kh][kw], bias float32)"""
+    """float64 fold of weights.cpp pack_weights / forward_ref._conv_folded_fp16 -> (kernel float64 [o][i][kh][kw], bias float32)"""
     w = wd["kernel_oihw"].astype(np.float64)
     if "gamma" in wd:
         scale = wd["gamma"].astype(np.float64) / np.sqrt(wd["var"].astype(np.float64) + 1e-5)
