@@ -45,6 +45,11 @@
  *   yolo_v3_loss, yolo_v3_loss_grad, yolo_net_loss_v3, yolo_net_loss_v3_u8 (+ yolo_v3_loss_rows)
  *                           no reference call site: the reference binds no loss to YoloV3 (net/yolo.py:208-211); the loss of Darknet's
  *                           [yolo] layer and its gradient with respect to the logits
+ *   yolo_v3_head_wgrad      no reference call site either: the gradient of that loss with respect to the kernels and biases of the convs in
+ *                           front of the [yolo] layers, from that gradient (+ yolo_v3_head_wgrad_plan)
+ *   yolo_net_train_head_step_v3, yolo_net_train_head_step_v3_u8
+ *                           net/yolo.py:161-173 for the head convs of a YOLOv3 network (+ yolo_net_head_inputs_v3,
+ *                           yolo_net_head_train_v3_bytes / _layout / _init / _read: no reference call site)
  *   yolo_augment_u8         net/base.py:15-23, :100-107: seq.to_deterministic().augment_images of a resized batch, on the device
  *   yolo_augment_truths_host
  *                           net/base.py:107-111: augment_bounding_boxes(...).remove_out_of_image().cut_out_of_image()
@@ -82,7 +87,13 @@ extern "C" {
                                           yolo_augment_u8, yolo_augment_check, yolo_augment_truths_host, yolo_augment_tile;
                                           added WITHIN ABI 7 in the same way (new exports only; the yolo_loss_* PODs are reused unchanged) -- the YOLOv3
                                           loss and its gradient: yolo_v3_loss_rows, yolo_v3_loss, yolo_v3_loss_grad, yolo_net_loss_v3,
-                                          yolo_net_loss_v3_u8 */
+                                          yolo_net_loss_v3_u8;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_v3_wgrad_plan and yolo_v3_wgrad_view PODs only) -- the
+                                          weight gradient of the YOLOv3 head convs: yolo_v3_head_wgrad_plan, yolo_v3_head_wgrad;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_head_train_v3_layout POD only) -- training the YOLOv3 head
+                                          convs: yolo_net_head_inputs_v3, yolo_net_head_train_v3_layout, yolo_net_head_train_v3_bytes,
+                                          yolo_net_head_train_v3_init, yolo_net_head_train_v3_read, yolo_net_train_head_step_v3,
+                                          yolo_net_train_head_step_v3_u8 */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -625,7 +636,8 @@ int yolo_v2_loss_grad(const yolo_head_desc *head, const float *logits_dev, int b
 /* ---- YOLOv3 loss and its gradient on the device (added WITHIN ABI 7: new exports only, nothing existing changed) ------------------
  * The loss of Darknet's [yolo] layer (forward_yolo_layer), the definition every YOLOv3 .weights file was trained with, and its gradient
  * with respect to the logits.  The reference has no loss for YoloV3 (net/yolo.py:208-211); yolo_v2_loss*, yolo_net_loss* and
- * yolo_net_train_head_step* keep refusing a version 3 head.  This stops at the logits: no backward pass, no step.
+ * yolo_net_train_head_step* keep refusing a version 3 head.  This stops at the logits; the weight gradient of the head convs from G is
+ * yolo_v3_head_wgrad below.
  *
  * Inputs.     logits float32 [B][R][5 + C], the layout yolo_net_forward writes for a version 3 head: rows scale by scale in head order,
  *             inside a scale [h_s][w_s][A_s]; R = sum_s h_s * w_s * A_s.  A yolo_head_desc with version == 3, 1 <= n_scales <=
@@ -791,6 +803,111 @@ int yolo_net_train_head_step(yolo_net *net, const float *in_dev, int batch, cons
                              void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 int yolo_net_train_head_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
                                 void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+
+/* ---- The weight gradient of the YOLOv3 head convs (added within ABI 7: new exports, the yolo_v3_wgrad_plan and yolo_v3_wgrad_view PODs) ------
+ * The head convs of a YOLOv3 network are the convs in front of its [yolo] layers, one per scale: 1 x 1, stride 1, linear, with bias and no
+ * batch norm, cout_s = A_s * (5 + C).  This is their backward pass with respect to kernel and bias, from the gradient G of
+ * yolo_v3_loss_grad.  The entries that run a whole training step on a net: "Training the YOLOv3 head convs on a net" below.
+ *
+ * Definition.  For scale s with P_s = batch * h_s * w_s positions, position p = (image n, cell q = row * w_s + column):
+ *       dW_s[o][c] = S_p G_s[p][o] * X_s[p][c]          db_s[o] = S_p G_s[p][o]          o = a * (5 + C) + k
+ *   G_s[p][o] is element k of row row0_s + q * A_s + a of image n of G ([B][R][5 + C], rows scale by scale; row0_s = the rows of the scales
+ *   in front).  X_s is the conv's input, a strided NHWC view as for yolo_conv1x1_wgrad: element (n, q, c) at n * image_stride + q * ld +
+ *   coff + c from x_dev, fp16 or float32, cin % 8 == 0.
+ *   The sums run over exactly those (p, o) that the assign table (assign_dev of yolo_v3_loss_grad: >= 0 winner, -1 none, -2 ignored) does
+ *   NOT declare a structural zero.  What remains: k == 4 for every row; every k of a row whose table entry is >= 0.  A structural zero
+ *   forms no product and is never read -- a DELIBERATE DIFFERENCE from a dense G^T X: a non-finite X at a position without a winner
+ *   reaches only the objectness rows o = a * (5 + C) + 4, and what G holds in its structural zeros does not matter.  A table entry >= max_gt
+ *   names no truth: its row counts as one without a winner.  The table must name a truth at most once per image (yolo_v3_loss_grad does).
+ * Objectness part (k == 4).  One pass over X_s: X widened to float32 (exact), float32 products and sums on the vector ALU (six flops per
+ *   two bytes of X: the matrix cores have nothing to add), column 4 of G read with 4-byte loads.  The positions of a scale are split into
+ *   n_chunks chunks of positions_per_chunk; a chunk is summed in ascending position order into a float32 slab of the scratch, a second
+ *   kernel adds the slabs in chunk order, reduce_tile_chunks of them staged at a time.  All scales run in one launch.
+ * Winner part (k != 4).  slot[n][j] = the row truth j of image n owns, or -1, built from the table; then a workgroup per (scale, anchor,
+ *   win_tile_rows elements k, win_tile_cin channels) walks the slots in order, `threads` of them at a time, compacts the winner rows of its scale and anchor in that
+ *   order, and adds per element the terms G[row][k] * X[position][c], images ascending, then truth index ascending, into one float32
+ *   sum.  A row of dW_s and an element of db_s without a term is +0.
+ * Every element of every dW_s and db_s is written by every call; nothing depends on what scratch (slot included), dW or db held before.
+ * No floating-point atomics: two calls return the same bits.  Against exact arithmetic, per element, with T <= P_s terms:
+ *   |dW - exact| <= (T + 2) 2^-24 S |G| |X|.
+ * yolo_v3_head_wgrad_plan (host only: the sizing call for the scratch, and the hook the tests size their cases from): cin[s] the input
+ * channels of scale s.  Scale s: positions = P_s, threads_per_chunk = cin_s / channels_per_thread threads walk one chunk, chunk k holds
+ * the positions [k * positions_per_chunk, min(P_s, (k + 1) * positions_per_chunk)); its slab of n_chunks * (A_s * cin_s + 8) floats lies at
+ * slab_offset[s] of the scratch; the winner part runs win_workgroups[s] = A_s * ceil((5 + C) / win_tile_rows) * ceil(cin_s / win_tile_cin) workgroups.  slot
+ * (int32 [batch][max_gt], reserved for max_gt = YOLO_EVAL_MAX_GT) lies at slot_offset.  Every part is 256-byte aligned.  YOLO_ERR_ARG for a
+ * null pointer, a dtype that is not F16 / F32, batch < 1, a head that is not version 3 ("the head must be version 3") or otherwise
+ * refused by yolo_v3_loss_rows, cin % 8 != 0, P_s above 2^30, cout_s * (cin_s + 1) beyond 31 bits. */
+struct yolo_v3_wgrad_plan {
+    int32_t n_scales, threads, channels_per_thread, min_chunk, win_tile_cin, win_tile_rows, reduce_tile_chunks, pad_;
+    int32_t positions[YOLO_MAX_SCALES], positions_per_chunk[YOLO_MAX_SCALES], n_chunks[YOLO_MAX_SCALES], threads_per_chunk[YOLO_MAX_SCALES];
+    int32_t obj_workgroups[YOLO_MAX_SCALES], win_workgroups[YOLO_MAX_SCALES];
+    uint64_t slab_offset[YOLO_MAX_SCALES], slab_bytes[YOLO_MAX_SCALES];
+    uint64_t slot_offset, slot_bytes, scratch_bytes;
+};
+int yolo_v3_head_wgrad_plan(const yolo_head_desc *head, const int32_t *cin, int batch, int x_dtype, struct yolo_v3_wgrad_plan *out);
+/* The input of one head conv: a device pointer and the view's strides in elements (yolo_tensor_view with a pointer for the offset). */
+struct yolo_v3_wgrad_view {
+    const void *x_dev;
+    int64_t image_stride;
+    int32_t ld, coff;
+    int32_t dtype;          /* YOLO_DTYPE_F16 | YOLO_DTYPE_F32 */
+    int32_t cin;
+};
+/* The standalone entry.  views[n_scales] in head order; g_dev float32 [batch][R][5 + C] and assign_dev int32 [batch][R] as
+ * yolo_v3_loss_grad left them; dw_dev[s] float32 [cout_s][cin_s], db_dev[s] float32 [cout_s]; scratch_dev 16-byte aligned, at least
+ * yolo_v3_head_wgrad_plan's scratch_bytes.  Four kernels, enqueued on `stream` with no host synchronisation.  YOLO_ERR_ARG, with a
+ * message that names the entry (and the scale), for what the plan refuses and for a null pointer, max_gt outside 1..YOLO_EVAL_MAX_GT, a
+ * view whose channels do not fit ld or whose images overlap, a pointer not aligned to its element type, a scratch that is too small. */
+int yolo_v3_head_wgrad(const yolo_head_desc *head, const struct yolo_v3_wgrad_view *views, int batch, const float *g_dev,
+                       const int32_t *assign_dev, int max_gt, float *const *dw_dev, float *const *db_dev, void *scratch_dev,
+                       size_t scratch_bytes, void *stream);
+
+/* ---- Training the YOLOv3 head convs on a net (added within ABI 7: new exports, the yolo_head_train_v3_layout POD only) ------
+ * What the entries of "Training the detection layer" are for a YOLOv2 network, for the head convs of a version 3 network (YOLOv3,
+ * YOLOv3-SPP, YOLOv3-tiny): every head conv's kernel and bias receive Adam updates from the YOLOv3 loss, everything in front of them is
+ * frozen and its batch norms run on their stored statistics.  The older entries keep refusing a version 3 network.  The optimiser is
+ * the reference's Adam (net/v2.py:205), not Darknet's SGD with momentum.
+ *
+ * yolo_net_head_inputs_v3: where the input of every head conv lives in the bound workspace after a dense forward, in head order
+ * (yolo_tensor_view as for yolo_net_head_input); *n receives the number of scales.  A head conv is a conv kernel of the plan that writes
+ * the logits: 1 x 1, stride 1, linear, with bias and no batch norm.  The entry VERIFIES from the plan's buffer lifetimes that each input
+ * is still intact behind the last kernel of the pass: no kernel behind the head conv writes its buffer, and no buffer that shares bytes
+ * with it is alive later (the planner keeps the buffers of a branch tail to the end of the pass, and the last head is the last kernel).
+ * YOLO_ERR_STATE with a message that names the scale when the plan reuses a head's input; the refusals of yolo_net_head_input for a net
+ * that runs several stream parts ("call yolo_net_set_streams(net, 1)"), a fused-away input or cin % 8 != 0; YOLO_ERR_ARG for a net whose
+ * head is not version 3 or whose head convs do not match its head.
+ *
+ * State (caller-owned device memory, every part 256-byte aligned): per scale the float32 master W_s [cout_s][cin_s] and b_s, their four
+ * moment arrays, dW_s and db_s; one G for a full batch; the assign table, the part and image records of the v3 loss; the scratch of
+ * yolo_v3_head_wgrad (slot inside it), sized for the largest split of any batch up to max_batch.  bias_src[s]: the position, in floats,
+ * of conv s's bias in the Darknet stream -- its cout_s biases stand there, its cout_s * cin_s kernel values behind them -- so that a
+ * caller can cut the heads out of a .weights stream and put them back.  _init (synchronous; weights loaded first) copies w_host[s]
+ * [cout_s][cin_s] and b_host[s] into the masters AND, packed, into the net's device weights, and zeroes the moments; _read copies the
+ * masters back (synchronous). */
+typedef struct yolo_head_train_v3_layout {
+    int32_t n_scales, pad_;
+    int32_t cin[YOLO_MAX_SCALES], cout[YOLO_MAX_SCALES];
+    uint64_t w_offset[YOLO_MAX_SCALES], b_offset[YOLO_MAX_SCALES], m_w_offset[YOLO_MAX_SCALES], v_w_offset[YOLO_MAX_SCALES];
+    uint64_t m_b_offset[YOLO_MAX_SCALES], v_b_offset[YOLO_MAX_SCALES], dw_offset[YOLO_MAX_SCALES], db_offset[YOLO_MAX_SCALES];
+    uint64_t bias_src[YOLO_MAX_SCALES];
+    uint64_t grad_offset, assign_offset, parts_offset, images_offset, scratch_offset, scratch_bytes, total_bytes;
+} yolo_head_train_v3_layout;
+int yolo_net_head_inputs_v3(const yolo_net *net, yolo_tensor_view *out, int32_t *n);
+int yolo_net_head_train_v3_layout(const yolo_net *net, yolo_head_train_v3_layout *out);
+size_t yolo_net_head_train_v3_bytes(const yolo_net *net);
+int yolo_net_head_train_v3_init(yolo_net *net, void *state_dev, size_t bytes, const float *const *w_host, const float *const *b_host);
+int yolo_net_head_train_v3_read(yolo_net *net, const void *state_dev, float *const *w_host, float *const *b_host);
+/* ONE enqueue with no host synchronisation for a training step on the head convs: a dense forward pass into the workspace logits, the
+ * kernels of yolo_v3_loss_grad on them, yolo_v3_head_wgrad on the views of yolo_net_head_inputs_v3, and per scale the Adam update of
+ * yolo_adam_step (beta1 = 0.9, beta2 = 0.999, eps = 1e-8) on the masters -- which in the same pass writes the conv's packed form into the
+ * net's device weights, exactly the bytes yolo_net_load_weights would have produced from the master values (an MXFP8 plan keeps its head
+ * convs fp16).  result_dev receives the yolo_loss_result of the weights BEFORE the update.  Bit-identical to yolo_net_forward[_u8] ->
+ * yolo_v3_loss_grad -> yolo_v3_head_wgrad -> yolo_adam_step per scale on the same buffers.  Checks and messages as yolo_net_loss_v3 plus
+ * those of yolo_net_head_inputs_v3; a null state is YOLO_ERR_ARG ("null state"). */
+int yolo_net_train_head_step_v3(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+int yolo_net_train_head_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                                   int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 
 /* ---- Training augmentation on the device: flips, blur, dropout, noise, shift (added within ABI 7: new exports, one new POD) ------
  * The reference trains through an imgaug pipeline (net/base.py:15-23): Fliplr(0.5), Flipud(0.5), GaussianBlur((0, 3.0)), Dropout(0.02),

@@ -126,6 +126,30 @@ class HeadTrainLayout(C.Structure):
                                           "total_bytes")] + [("cin", C.c_int32), ("cout", C.c_int32)]
 
 
+class HeadTrainV3Layout(C.Structure):
+    """yolo_head_train_v3_layout: byte offsets of the parts of the YOLOv3 head-training state, per scale where the part is per conv"""
+    _fields_ = ([("n_scales", C.c_int32), ("pad_", C.c_int32), ("cin", C.c_int32 * MAX_SCALES), ("cout", C.c_int32 * MAX_SCALES)] +
+                [(n, C.c_uint64 * MAX_SCALES) for n in ("w_offset", "b_offset", "m_w_offset", "v_w_offset", "m_b_offset", "v_b_offset",
+                                                        "dw_offset", "db_offset", "bias_src")] +
+                [(n, C.c_uint64) for n in ("grad_offset", "assign_offset", "parts_offset", "images_offset", "scratch_offset",
+                                           "scratch_bytes", "total_bytes")])
+
+
+class V3WgradPlan(C.Structure):
+    """yolo_v3_wgrad_plan: how the weight gradient of the YOLOv3 head convs is split (per scale: chunks of positions, slabs; slot; scratch)"""
+    _fields_ = ([(n, C.c_int32) for n in ("n_scales", "threads", "channels_per_thread", "min_chunk", "win_tile_cin", "win_tile_rows", "reduce_tile_chunks", "pad_")] +
+                [(n, C.c_int32 * MAX_SCALES) for n in ("positions", "positions_per_chunk", "n_chunks", "threads_per_chunk", "obj_workgroups",
+                                                       "win_workgroups")] +
+                [(n, C.c_uint64 * MAX_SCALES) for n in ("slab_offset", "slab_bytes")] +
+                [(n, C.c_uint64) for n in ("slot_offset", "slot_bytes", "scratch_bytes")])
+
+
+class V3WgradView(C.Structure):
+    """yolo_v3_wgrad_view: the input of one head conv, a strided NHWC view behind a device pointer"""
+    _fields_ = [("x_dev", C.c_void_p), ("image_stride", C.c_int64), ("ld", C.c_int32), ("coff", C.c_int32), ("dtype", C.c_int32),
+                ("cin", C.c_int32)]
+
+
 class AugmentImage(C.Structure):
     """yolo_augment_image: how one image of a training batch is augmented (net/augment.py draws it)"""
     _fields_ = [("enabled", C.c_int32), ("flip_lr", C.c_int32), ("flip_ud", C.c_int32), ("radius", C.c_int32), ("taps", C.c_uint16 * 10),
@@ -238,6 +262,20 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p]),
     "yolo_net_train_head_step_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                               C.c_void_p, C.c_void_p]),
+    # the weight gradient of the YOLOv3 head convs (added within ABI 7)
+    "yolo_v3_head_wgrad_plan": (C.c_int, [C.POINTER(HeadDesc), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(V3WgradPlan)]),
+    "yolo_v3_head_wgrad": (C.c_int, [C.POINTER(HeadDesc), C.POINTER(V3WgradView), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]),
+    # training the YOLOv3 head convs on a net (added within ABI 7)
+    "yolo_net_head_inputs_v3": (C.c_int, [C.c_void_p, C.POINTER(TensorView), C.POINTER(C.c_int32)]),
+    "yolo_net_head_train_v3_layout": (C.c_int, [C.c_void_p, C.POINTER(HeadTrainV3Layout)]),
+    "yolo_net_head_train_v3_bytes": (C.c_size_t, [C.c_void_p]),
+    "yolo_net_head_train_v3_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "yolo_net_head_train_v3_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "yolo_net_train_head_step_v3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                              C.c_float, C.c_void_p, C.c_void_p]),
+    "yolo_net_train_head_step_v3_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                                 C.c_float, C.c_void_p, C.c_void_p]),
     # training augmentation (added within ABI 7)
     "yolo_augment_check": (C.c_int, [C.POINTER(AugmentImage), C.c_int, C.c_int]),
     "yolo_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(AugmentImage), C.c_void_p]),
@@ -308,6 +346,20 @@ def wgrad_plan(P, cin, cout, x_dtype=DTYPE_F16):
     pl = WgradPlan()
     check(lib().yolo_wgrad_plan(int(P), int(cin), int(cout), int(x_dtype), C.byref(pl)), "yolo_wgrad_plan")
     return {name: int(getattr(pl, name)) for name, _ in WgradPlan._fields_ if name != "pad_"}
+
+
+def v3_head_wgrad_plan(head, cins, batch, x_dtype=DTYPE_F16):
+    """yolo_v3_head_wgrad_plan as a dict (host only): scalars as ints, per-scale fields as lists of n_scales ints"""
+    pl = V3WgradPlan()
+    arr = (C.c_int32 * MAX_SCALES)(*[int(c) for c in cins])
+    check(lib().yolo_v3_head_wgrad_plan(C.byref(head), arr, int(batch), int(x_dtype), C.byref(pl)), "yolo_v3_head_wgrad_plan")
+    out = {}
+    for name, kind in V3WgradPlan._fields_:
+        if name == "pad_":
+            continue
+        v = getattr(pl, name)
+        out[name] = int(v) if kind in (C.c_int32, C.c_uint64) else [int(x) for x in v[:pl.n_scales]]
+    return out
 
 
 def augment_tile():

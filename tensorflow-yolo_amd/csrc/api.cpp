@@ -857,6 +857,36 @@ int yolo_adam_step(float *w, float *b, float *m_w, float *v_w, float *m_b, float
     return YOLO_OK;
 }
 
+// ---- the weight gradient of the YOLOv3 head convs (yolo_hip.h: added within ABI 7; kernels in train3.hip, split and checks in train3_host.cpp)
+int yolo_v3_head_wgrad_plan(const yolo_head_desc *head, const int32_t *cin, int batch, int x_dtype, struct yolo_v3_wgrad_plan *out) {
+    std::string err;
+    Wgrad3Geometry geo;
+    const int rc = wgrad3_plan(head, cin, batch, x_dtype, out, &geo, err);
+    return rc ? fail(rc, "yolo_v3_head_wgrad_plan: " + err) : YOLO_OK;
+}
+
+static int run_wgrad3(const Wgrad3Geometry &geo, const struct yolo_v3_wgrad_plan &pl, int batch, const float *g, const int32_t *assign, int max_gt,
+                      void *scratch, hipStream_t s) {
+    Wgrad3Params p;
+    memset(&p, 0, sizeof p);
+    static_cast<Wgrad3Geometry &>(p) = geo;
+    p.g = g; p.assign = assign; p.batch = batch; p.max_gt = max_gt;
+    p.slot = reinterpret_cast<int *>(static_cast<unsigned char *>(scratch) + pl.slot_offset);
+    HIP_TRY(launch_head3_wgrad(p, s));
+    return YOLO_OK;
+}
+
+int yolo_v3_head_wgrad(const yolo_head_desc *head, const struct yolo_v3_wgrad_view *views, int batch, const float *g_dev,
+                       const int32_t *assign_dev, int max_gt, float *const *dw_dev, float *const *db_dev, void *scratch_dev,
+                       size_t scratch_bytes, void *stream) {
+    std::string err;
+    struct yolo_v3_wgrad_plan pl;
+    Wgrad3Geometry geo;
+    const int rc = wgrad3_check(head, views, batch, g_dev, assign_dev, max_gt, dw_dev, db_dev, scratch_dev, scratch_bytes, &pl, &geo, err);
+    if (rc) return fail(rc, "yolo_v3_head_wgrad: " + err);
+    return run_wgrad3(geo, pl, batch, g_dev, assign_dev, max_gt, scratch_dev, static_cast<hipStream_t>(stream));
+}
+
 // ---- training augmentation (augment_host.cpp: checks, records, truths; augment.hip: the kernel)
 int yolo_augment_check(const yolo_augment_image *params, int h, int w) {
     std::string err;
@@ -1082,6 +1112,258 @@ int yolo_net_train_head_step(yolo_net *net, const float *in_dev, int batch, cons
 int yolo_net_train_head_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
                                 void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
     return train_head_step_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, state_dev, lr_t, result_dev, stream, "yolo_net_train_head_step_u8");
+}
+
+// ---- training the YOLOv3 head convs on a net (yolo_hip.h: added within ABI 7) -------------------------------------------------------------
+// The head convs of a version 3 net in head order, each the 1 x 1 / stride 1 linear conv with bias that writes its scale of the logits from
+// a tensor of the workspace that is still intact behind the last kernel of the pass.  The message says what is in the way.
+static int head_convs_v3(const yolo_net *net, const Kernel *out[YOLO_MAX_SCALES], const char *who) {
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    std::string err;
+    int rc = check_head(&net->head, net->out_count, err);
+    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
+    if (net->head.version != 3)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 3 (yolo_net_train_head_step trains the detection layer of a YOLOv2 network)");
+    const std::vector<Kernel> &K = net->kernels;
+    std::vector<int> heads;
+    for (int i = 0; i < (int)K.size(); ++i)
+        if (K[i].kind == K_CONV && K[i].head) heads.push_back(i);
+    std::sort(heads.begin(), heads.end(), [&](int a, int b) { return K[a].out.base < K[b].out.base; });       // head order = the order of the rows
+    if ((int)heads.size() != net->head.n_scales)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": the plan has " + std::to_string(heads.size()) + " head convs for " + std::to_string(net->head.n_scales) + " scales");
+    const int width = 5 + net->head.n_classes;
+    for (int s = 0; s < net->head.n_scales; ++s) {
+        const int ki = heads[s];
+        const Kernel &k = K[ki];
+        const std::string at = std::string(who) + ": scale " + std::to_string(s) + ": ";
+        if (k.ksize != 1 || k.stride != 1 || k.leaky || k.batch_norm || k.out.buf != BUF_USER_OUT || !k.out.f32 || k.has_res || k.outmode != OUT_NORMAL ||
+            k.cout != net->head.n_anchors[s] * width || k.in.H != net->head.h[s] || k.in.W != net->head.w[s])
+            return fail(YOLO_ERR_ARG, at + "the head conv must be a 1 x 1 / stride 1 linear conv with bias and no batch norm that writes this scale of the logits");
+        if (k.stem || k.fuse2_prev || k.mx || k.in.buf < 0 || k.in.f32 || k.in.base)
+            return fail(YOLO_ERR_STATE, at + "the plan has fused the head conv's input away");
+        if (k.cin % 8 || k.cin_s != k.cin) return fail(YOLO_ERR_ARG, at + "the head conv's input channels must be a multiple of 8");
+        // intact behind the last kernel: nothing behind the head conv writes its input's buffer, and no buffer alive later shares its bytes
+        const Buffer &b = net->buffers[k.in.buf];
+        for (int j = ki + 1; j < (int)K.size(); ++j)
+            for (const View *v : {&K[j].out, &K[j].out2, &K[j].out3})
+                if (v->buf == k.in.buf)
+                    return fail(YOLO_ERR_STATE, at + "the plan reuses the head conv's input: kernel " + std::to_string(j) + " writes its buffer behind the head conv");
+        for (size_t q = 0; q < net->buffers.size(); ++q) {
+            const Buffer &o = net->buffers[q];
+            if ((int)q == k.in.buf || o.last < 0 || !o.bytes || !b.bytes) continue;
+            const bool shares = o.offset < b.offset + b.bytes && b.offset < o.offset + o.bytes;
+            if (shares && o.last >= b.first)
+                return fail(YOLO_ERR_STATE, at + "the plan reuses the head conv's input: buffer " + std::to_string(q) + " shares its bytes and is alive behind it");
+        }
+        out[s] = &k;
+    }
+    if (net->parts != 1)
+        return fail(YOLO_ERR_STATE, std::string(who) + ": this net runs a batch as " + std::to_string(net->parts) +
+                                        " stream parts, each in its own arena; call yolo_net_set_streams(net, 1)");
+    return YOLO_OK;
+}
+
+static int net_x_dtype(const yolo_net *net) { return net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32; }
+
+int yolo_net_head_inputs_v3(const yolo_net *net, yolo_tensor_view *out, int32_t *n) {
+    const Kernel *ks[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = head_convs_v3(net, ks, "yolo_net_head_inputs_v3");
+    if (rc) return rc;
+    if (!out || !n) return fail(YOLO_ERR_ARG, "yolo_net_head_inputs_v3: null argument");
+    *n = net->head.n_scales;
+    for (int s = 0; s < net->head.n_scales; ++s) {
+        const Kernel *k = ks[s];
+        memset(&out[s], 0, sizeof out[s]);
+        out[s].offset = net->buffers[k->in.buf].offset;
+        out[s].image_stride = k->in.img_stride;
+        out[s].ld = k->in.ld; out[s].coff = k->in.coff;
+        out[s].dtype = net_x_dtype(net);
+        out[s].cin = k->cin; out[s].h = k->in.H; out[s].w = k->in.W;
+    }
+    return YOLO_OK;
+}
+
+static int head_train_v3_layout(const yolo_net *net, const Kernel *ks[YOLO_MAX_SCALES], yolo_head_train_v3_layout *L, const char *who) {
+    int rc = head_convs_v3(net, ks, who);
+    if (rc) return rc;
+    std::string err;
+    Loss3Geometry lg;
+    rc = loss3_geometry(&net->head, &lg, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    const size_t mb = (size_t)net->opt.max_batch;
+    size_t off = 0;
+    auto part = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return (uint64_t)at; };
+    memset(L, 0, sizeof *L);
+    L->n_scales = net->head.n_scales;
+    int32_t cin[YOLO_MAX_SCALES] = {0, 0, 0, 0};
+    for (int s = 0; s < L->n_scales; ++s) {
+        const Kernel *k = ks[s];
+        const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
+        L->cin[s] = cin[s] = k->cin; L->cout[s] = k->cout;
+        L->bias_src[s] = k->w_src;
+        L->w_offset[s] = part(nw); L->b_offset[s] = part(nb);
+        L->m_w_offset[s] = part(nw); L->v_w_offset[s] = part(nw); L->m_b_offset[s] = part(nb); L->v_b_offset[s] = part(nb);
+        L->dw_offset[s] = part(nw); L->db_offset[s] = part(nb);
+    }
+    L->grad_offset = part(mb * net->out_count * 4);
+    L->assign_offset = part(mb * (size_t)lg.rows * 4);
+    L->parts_offset = part(mb * (size_t)lg.parts * sizeof(yolo_loss_image));
+    L->images_offset = part(mb * sizeof(yolo_loss_image));
+    // the slabs of a smaller batch may be laid out otherwise: the scratch is sized for the largest split of any batch up to max_batch
+    uint64_t need = 0;
+    for (size_t b = 1; b <= mb; ++b) {
+        struct yolo_v3_wgrad_plan q;
+        Wgrad3Geometry g;
+        rc = wgrad3_plan(&net->head, cin, (int)b, YOLO_DTYPE_F32, &q, &g, err);
+        if (rc) return fail(rc, std::string(who) + ": " + err);
+        if (q.scratch_bytes > need) need = q.scratch_bytes;
+    }
+    L->scratch_bytes = need;
+    L->scratch_offset = part((size_t)need);
+    L->total_bytes = off;
+    return YOLO_OK;
+}
+
+int yolo_net_head_train_v3_layout(const yolo_net *net, yolo_head_train_v3_layout *out) {
+    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_head_train_v3_layout: null argument");
+    const Kernel *ks[YOLO_MAX_SCALES];
+    return head_train_v3_layout(net, ks, out, "yolo_net_head_train_v3_layout");
+}
+
+size_t yolo_net_head_train_v3_bytes(const yolo_net *net) {
+    yolo_head_train_v3_layout L;
+    const Kernel *ks[YOLO_MAX_SCALES];
+    if (head_train_v3_layout(net, ks, &L, "yolo_net_head_train_v3_bytes")) return 0;
+    return (size_t)L.total_bytes;
+}
+
+int yolo_net_head_train_v3_init(yolo_net *net, void *state_dev, size_t bytes, const float *const *w_host, const float *const *b_host) {
+    const char *who = "yolo_net_head_train_v3_init";
+    if (!net || !state_dev || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    yolo_head_train_v3_layout L;
+    const Kernel *ks[YOLO_MAX_SCALES];
+    int rc = head_train_v3_layout(net, ks, &L, who);
+    if (rc) return rc;
+    for (int s = 0; s < L.n_scales; ++s)
+        if (!w_host[s] || !b_host[s]) return fail(YOLO_ERR_ARG, std::string(who) + ": scale " + std::to_string(s) + ": null argument");
+    if (bytes < L.total_bytes) return fail(YOLO_ERR_ARG, std::string(who) + ": state too small (yolo_net_head_train_v3_bytes)");
+    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
+    if (!net->weights_loaded || !net->dev_weights) return fail(YOLO_ERR_STATE, std::string(who) + ": weights not loaded");
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
+    HIP_TRY(hipDeviceSynchronize());
+    for (int s = 0; s < L.n_scales; ++s) {
+        const Kernel *k = ks[s];
+        const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
+        HIP_TRY(hipMemcpy(st + L.w_offset[s], w_host[s], nw, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(st + L.b_offset[s], b_host[s], nb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(st + L.m_w_offset[s], 0, nw));
+        HIP_TRY(hipMemset(st + L.v_w_offset[s], 0, nw));
+        HIP_TRY(hipMemset(st + L.m_b_offset[s], 0, nb));
+        HIP_TRY(hipMemset(st + L.v_b_offset[s], 0, nb));
+        // the conv's packed form, as pack_weights (weights.cpp) writes a 1 x 1 conv without batch norm: row o at o * wrow bytes, bias as it is
+        const size_t wrow = (size_t)k->ktiles * 128;
+        std::vector<unsigned char> rows((size_t)k->cout * wrow, 0);
+        for (int o = 0; o < k->cout; ++o)
+            for (int c = 0; c < k->cin; ++c) {
+                const float v = w_host[s][(size_t)o * k->cin + c];
+                if (f16) reinterpret_cast<_Float16 *>(rows.data() + (size_t)o * wrow)[c] = (_Float16)v;
+                else reinterpret_cast<float *>(rows.data() + (size_t)o * wrow)[c] = v;
+            }
+        HIP_TRY(hipMemcpy(net->dev_weights + k->w_off, rows.data(), rows.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(net->dev_weights + k->b_off, b_host[s], nb, hipMemcpyHostToDevice));
+    }
+    return YOLO_OK;
+}
+
+int yolo_net_head_train_v3_read(yolo_net *net, const void *state_dev, float *const *w_host, float *const *b_host) {
+    const char *who = "yolo_net_head_train_v3_read";
+    if (!net || !state_dev || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    yolo_head_train_v3_layout L;
+    const Kernel *ks[YOLO_MAX_SCALES];
+    int rc = head_train_v3_layout(net, ks, &L, who);
+    if (rc) return rc;
+    for (int s = 0; s < L.n_scales; ++s)
+        if (!w_host[s] || !b_host[s]) return fail(YOLO_ERR_ARG, std::string(who) + ": scale " + std::to_string(s) + ": null argument");
+    const unsigned char *st = static_cast<const unsigned char *>(state_dev);
+    HIP_TRY(hipDeviceSynchronize());
+    for (int s = 0; s < L.n_scales; ++s) {
+        HIP_TRY(hipMemcpy(w_host[s], st + L.w_offset[s], (size_t)L.cout[s] * L.cin[s] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b_host[s], st + L.b_offset[s], (size_t)L.cout[s] * 4, hipMemcpyDeviceToHost));
+    }
+    return YOLO_OK;
+}
+
+static int train_head_step_v3_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                  double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream, const char *who) {
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    yolo_head_train_v3_layout L;
+    const Kernel *ks[YOLO_MAX_SCALES];
+    int rc = head_train_v3_layout(net, ks, &L, who);
+    if (rc) return rc;
+    if (!state_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null state (yolo_net_head_train_v3_init)");
+    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    yolo_loss_image *parts = reinterpret_cast<yolo_loss_image *>(st + L.parts_offset);
+    yolo_loss_image *images = reinterpret_cast<yolo_loss_image *>(st + L.images_offset);
+    int32_t *assign = reinterpret_cast<int32_t *>(st + L.assign_offset);
+    float *grad = reinterpret_cast<float *>(st + L.grad_offset);
+    Loss3Geometry lg;
+    std::string err;
+    // (the logits pointer is the workspace's: any non-null value that is not the gradient stands in for it until check_ready has seen the net)
+    rc = loss3_check(&net->head, net, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts, images, assign, result_dev, true, grad, &lg, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    rc = check_ready(net, in_dev.ptr, batch, who);
+    if (rc) return rc;
+    if (!(lr_t == lr_t)) return fail(YOLO_ERR_ARG, std::string(who) + ": lr_t is NaN");
+    yolo_v3_wgrad_view views[YOLO_MAX_SCALES];
+    float *dw[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr}, *db[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
+    memset(views, 0, sizeof views);
+    for (int s = 0; s < L.n_scales; ++s) {
+        const Kernel *k = ks[s];
+        views[s].x_dev = net->dev_ws + net->buffers[k->in.buf].offset;
+        views[s].image_stride = k->in.img_stride; views[s].ld = k->in.ld; views[s].coff = k->in.coff;
+        views[s].dtype = net_x_dtype(net); views[s].cin = k->cin;
+        dw[s] = reinterpret_cast<float *>(st + L.dw_offset[s]); db[s] = reinterpret_cast<float *>(st + L.db_offset[s]);
+    }
+    struct yolo_v3_wgrad_plan pl;
+    Wgrad3Geometry geo;
+    rc = wgrad3_check(&net->head, views, batch, grad, assign, max_gt, dw, db, st + L.scratch_offset, (size_t)L.scratch_bytes, &pl, &geo, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
+    rc = run_forward(net, in_dev, batch, logits, s);        // dense: obj_min_logit is -inf outside detect_any
+    if (rc) return rc;
+    rc = run_loss3(lg, logits, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts, images, assign, result_dev, grad, s);
+    if (rc) return rc;
+    rc = run_wgrad3(geo, pl, batch, grad, assign, max_gt, st + L.scratch_offset, s);
+    if (rc) return rc;
+    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
+    for (int i = 0; i < L.n_scales; ++i) {
+        const Kernel *k = ks[i];
+        AdamParams p;
+        memset(&p, 0, sizeof p);
+        p.w = reinterpret_cast<float *>(st + L.w_offset[i]); p.b = reinterpret_cast<float *>(st + L.b_offset[i]);
+        p.m_w = reinterpret_cast<float *>(st + L.m_w_offset[i]); p.v_w = reinterpret_cast<float *>(st + L.v_w_offset[i]);
+        p.m_b = reinterpret_cast<float *>(st + L.m_b_offset[i]); p.v_b = reinterpret_cast<float *>(st + L.v_b_offset[i]);
+        p.dw = dw[i]; p.db = db[i]; p.n_w = (long long)k->cout * k->cin; p.n_b = k->cout;
+        p.lr_t = lr_t; p.beta1 = 0.9f; p.beta2 = 0.999f; p.eps = 1e-8f;        // tf.train.AdamOptimizer's defaults (net/v2.py:205)
+        p.pack_w = net->dev_weights + k->w_off; p.pack_b = reinterpret_cast<float *>(net->dev_weights + k->b_off);
+        p.pack_cin = k->cin; p.pack_f16 = f16;
+        p.pack_row = (int)((size_t)k->ktiles * 128 / (f16 ? 2 : 4));
+        HIP_TRY(launch_adam_step(p, s));
+    }
+    return YOLO_OK;
+}
+int yolo_net_train_head_step_v3(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
+    return train_head_step_v3_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
+                                  "yolo_net_train_head_step_v3");
+}
+int yolo_net_train_head_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                                   int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
+    return train_head_step_v3_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
+                                  "yolo_net_train_head_step_v3_u8");
 }
 
 int yolo_u8_unit_table(float *out256) {

@@ -16,6 +16,7 @@
 
 #include "yolo_hip.h"
 #include "train_host.h"
+#include "train3_host.h"
 #include "augment_host.h"
 #include "loss3_host.h"
 
@@ -453,6 +454,15 @@ struct AdamParams {
 };
 hipError_t launch_head_wgrad(const WgradParams &p, int x_dtype, hipStream_t s);     // both kernels
 hipError_t launch_adam_step(const AdamParams &p, hipStream_t s);
+
+// ---- the weight gradient of the YOLOv3 head convs (train3.hip; the split and the argument checks: train3_host.h) -------------------------
+struct Wgrad3Params : Wgrad3Geometry {
+    const float *g;            // [B][R][5 + C]
+    const int *assign;         // [B][R]: truth index | -1 none | -2 ignored (yolo_v3_loss_grad)
+    int *slot;                 // [B][max_gt]: the row a truth owns or -1; written by head3_slot_kernel
+    int batch, max_gt;
+};
+hipError_t launch_head3_wgrad(const Wgrad3Params &p, hipStream_t s);   // all four kernels
 
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);

@@ -154,6 +154,20 @@ class Plan(object):
         _hip.check(self.lib.yolo_net_head_train_layout(self.handle, C.byref(lay)), "yolo_net_head_train_layout")
         return lay
 
+    def head_inputs_v3(self):
+        """yolo_net_head_inputs_v3: where the input of every head conv lives in the workspace after a dense forward, in head order (a list of
+        _hip.TensorView; host only)"""
+        views = (_hip.TensorView * _hip.MAX_SCALES)()
+        n = C.c_int32(0)
+        _hip.check(self.lib.yolo_net_head_inputs_v3(self.handle, views, C.byref(n)), "yolo_net_head_inputs_v3")
+        return [views[s] for s in range(n.value)]
+
+    def head_train_layout_v3(self):
+        """yolo_net_head_train_v3_layout: byte offsets of the parts of the YOLOv3 head-training state (a _hip.HeadTrainV3Layout; host only)"""
+        lay = _hip.HeadTrainV3Layout()
+        _hip.check(self.lib.yolo_net_head_train_v3_layout(self.handle, C.byref(lay)), "yolo_net_head_train_v3_layout")
+        return lay
+
     def describe(self):
         n = self.lib.yolo_net_describe(self.handle, None, 0)
         buf = C.create_string_buffer(n)
@@ -622,6 +636,74 @@ class HipNetwork(Plan):
                        "yolo_net_head_train_read")
         return w, b
 
+    # -- training the YOLOv3 head convs (yolo_net_head_inputs_v3 / yolo_net_head_train_v3_* / yolo_net_train_head_step_v3) ----------------
+    def head_train_init_v3(self, head_ws, head_bs):
+        """Allocate the YOLOv3 head-training state and start it from head_ws[s] [cout_s, cin_s] (the Darknet kernels, [out][in]) and
+        head_bs[s] [cout_s], in head order: master values, zeroed moments, and the convs packed into the device weights.  Synchronous.  A
+        net whose streams = 0 rule runs two halves is set to one pass first (each part has its own arena)."""
+        torch = self.torch
+        if not self.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights first")
+        if self._auto_streams and self.num_streams != 1:
+            _hip.check(self.lib.yolo_net_set_streams(self.handle, 1), "yolo_net_set_streams")
+        self._streams_tuned = True
+        lay = self.head_train_layout_v3()
+        if len(head_ws) != lay.n_scales or len(head_bs) != lay.n_scales:
+            raise ValueError("expected %d head kernels and biases, one per scale" % lay.n_scales)
+        ws = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in head_ws]
+        bs = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in head_bs]
+        for s in range(lay.n_scales):
+            if ws[s].size != lay.cout[s] * lay.cin[s] or bs[s].size != lay.cout[s]:
+                raise ValueError("scale %d: expected a head kernel of %d x %d values and %d biases, got %d and %d"
+                                 % (s, lay.cout[s], lay.cin[s], lay.cout[s], ws[s].size, bs[s].size))
+        wp = (C.c_void_p * _hip.MAX_SCALES)(*[w.ctypes.data for w in ws])
+        bp = (C.c_void_p * _hip.MAX_SCALES)(*[b.ctypes.data for b in bs])
+        with torch.cuda.device(self.device):
+            self._train_state_v3 = torch.empty(int(lay.total_bytes), dtype=torch.uint8, device=self.device)
+            _hip.check(self.lib.yolo_net_head_train_v3_init(self.handle, self._train_state_v3.data_ptr(), self._train_state_v3.numel(), wp, bp),
+                       "yolo_net_head_train_v3_init")
+        self.train_layout_v3 = lay
+        return self._train_state_v3
+
+    def _train_head_step_v3_any(self, x, gts, lr_t, ignore_thresh, u8, result):
+        from . import evaluate as yeval
+        torch = self.torch
+        if getattr(self, "_train_state_v3", None) is None:
+            raise RuntimeError("train_head_step_v3 follows head_train_init_v3")
+        x = self.to_device_u8(x) if u8 else self.to_device(x)
+        b = x.shape[0]
+        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
+        if result is None:
+            result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        name = "yolo_net_train_head_step_v3_u8" if u8 else "yolo_net_train_head_step_v3"
+        with torch.cuda.device(self.device):
+            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt), float(ignore_thresh),
+                                               self._train_state_v3.data_ptr(), float(lr_t), result.data_ptr(), self._stream()), name)
+        self.u8_calls += int(u8)
+        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
+        return result
+
+    def train_head_step_v3(self, x, gts, lr_t, ignore_thresh=0.7, result=None):
+        """One training step of the head convs of a YOLOv3 network in one enqueue, no host sync (include/yolo_hip.h:
+        yolo_net_train_head_step_v3): dense forward, the YOLOv3 loss and its gradient, the sparse weight gradient, Adam update and re-pack
+        per scale.  lr_t: adam_lr_t(lr, step).  Returns the device record (uint8 [64] = yolo_loss_result) of the loss BEFORE the update."""
+        return self._train_head_step_v3_any(x, gts, lr_t, ignore_thresh, False, result)
+
+    def train_head_step_v3_u8(self, x, gts, lr_t, ignore_thresh=0.7, result=None):
+        """train_head_step_v3() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as train_head_step_v3(float32(x / 255.))"""
+        return self._train_head_step_v3_any(x, gts, lr_t, ignore_thresh, True, result)
+
+    def head_train_read_v3(self):
+        """The master values of the head convs (synchronous): ([kernel float32 [cout_s, cin_s]], [bias float32 [cout_s]]) in head order"""
+        lay = self.train_layout_v3
+        ws = [np.empty((lay.cout[s], lay.cin[s]), dtype=np.float32) for s in range(lay.n_scales)]
+        bs = [np.empty(lay.cout[s], dtype=np.float32) for s in range(lay.n_scales)]
+        wp = (C.c_void_p * _hip.MAX_SCALES)(*[w.ctypes.data for w in ws])
+        bp = (C.c_void_p * _hip.MAX_SCALES)(*[b.ctypes.data for b in bs])
+        with self.torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_head_train_v3_read(self.handle, self._train_state_v3.data_ptr(), wp, bp), "yolo_net_head_train_v3_read")
+        return ws, bs
+
     def forward_timed_u8(self, x, out=None):
         """forward_timed() for a uint8 batch: the input kernel's entry is the time of its uint8 twin."""
         torch = self.torch
@@ -749,6 +831,47 @@ def v3_loss_grad(head, logits, gts, ignore_thresh=0.7):
                                                 float(ignore_thresh), scratch.data_ptr(), images.data_ptr(), assign.data_ptr(), result.data_ptr(),
                                                 grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "yolo_v3_loss_grad")
     return images, result, assign, grad, (gt_dev, gc_dev, scratch)
+
+
+def v3_head_wgrad(head, xs, grad, assign, max_gt, scratch=None, out=None):
+    """yolo_v3_head_wgrad: the weight gradient of the head convs of a version 3 head from the gradient and the table of v3_loss_grad
+    (float32 [B, R, 5 + C] and int32 [B, R] device tensors), one enqueue on the current stream, no host sync.  xs: per scale, in head
+    order, the conv's input -- a contiguous fp16 / float32 device tensor [B, h_s, w_s, cin_s], or (flat tensor, ld, coff, image_stride,
+    cin) for a strided view of it (element (n, q, c) at n * image_stride + q * ld + coff + c).  scratch: a uint8 device tensor to run in
+    (tests pre-fill it), else one is allocated; out: ([dW_s], [db_s]) to write into.  Returns ([dW_s float32 [cout_s, cin_s]], [db_s
+    float32 [cout_s]], scratch); the caller keeps the inputs alive until the work has run."""
+    torch = _torch()
+    dev, b, ns = grad.device, grad.shape[0], head.n_scales
+    if len(xs) != ns:
+        raise ValueError("v3_head_wgrad: expected %d inputs, one per scale, got %d" % (ns, len(xs)))
+    views = (_hip.V3WgradView * _hip.MAX_SCALES)()
+    for s, x in enumerate(xs):
+        if isinstance(x, (tuple, list)):
+            t, ld, coff, image_stride, cin = x
+        else:
+            if not x.is_contiguous() or x.dim() != 4 or x.shape[0] != b or tuple(x.shape[1:3]) != (head.h[s], head.w[s]):
+                raise ValueError("v3_head_wgrad: scale %d: expected a contiguous [%d, %d, %d, cin] tensor" % (s, b, head.h[s], head.w[s]))
+            t, cin = x, x.shape[3]
+            ld, coff, image_stride = cin, 0, head.h[s] * head.w[s] * cin
+        if t.dtype not in (torch.float16, torch.float32):
+            raise ValueError("v3_head_wgrad: scale %d: the input must be fp16 or float32" % s)
+        views[s].x_dev, views[s].image_stride, views[s].ld, views[s].coff = t.data_ptr(), int(image_stride), int(ld), int(coff)
+        views[s].dtype, views[s].cin = (_hip.DTYPE_F16 if t.dtype == torch.float16 else _hip.DTYPE_F32), int(cin)
+    cins = [views[s].cin for s in range(ns)]
+    pl = _hip.v3_head_wgrad_plan(head, cins, b, views[0].dtype)
+    with torch.cuda.device(dev):
+        if scratch is None:
+            scratch = torch.empty(pl["scratch_bytes"], dtype=torch.uint8, device=dev)
+        if out is None:
+            couts = [head.n_anchors[s] * (5 + head.n_classes) for s in range(ns)]
+            out = ([torch.empty((couts[s], cins[s]), dtype=torch.float32, device=dev) for s in range(ns)],
+                   [torch.empty(couts[s], dtype=torch.float32, device=dev) for s in range(ns)])
+        dws = (C.c_void_p * _hip.MAX_SCALES)(*[t.data_ptr() for t in out[0]])
+        dbs = (C.c_void_p * _hip.MAX_SCALES)(*[t.data_ptr() for t in out[1]])
+        _hip.check(_hip.lib().yolo_v3_head_wgrad(C.byref(head), views, b, grad.data_ptr(), assign.data_ptr(), int(max_gt), dws, dbs,
+                                                 scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                   "yolo_v3_head_wgrad")
+    return out[0], out[1], scratch
 
 
 def check_status(status, allow_truncation=False):

@@ -1,6 +1,8 @@
 """`--mode train` for the detection layer: the reference's loop (net/yolo.py:98-195) around yolo_net_train_head_step.
 
-Runs only when [TRAIN] has `train_layers = head`.  Two deliberate differences from the reference (include/yolo_hip.h):
+Runs only when [TRAIN] has `train_layers = head` (a v2 network) or `train_layers = heads` (a v3 network: the convs in front of its
+[yolo] layers, trained with the YOLOv3 loss through yolo_net_train_head_step_v3; `ignore_thresh`, default 0.7, is its ignore threshold and
+`pretrained_classes = N` lets a file trained for N classes start a fine-tune for another number).  Two deliberate differences from the reference (include/yolo_hip.h):
 only the last conv's kernel and bias receive updates, and the backbone's batch norms run on their stored statistics -- a fine-tune of the
 detection layer on a frozen, pretrained backbone.  Batching is the reference's (net/v2.py:209-219: the last batch is padded with the
 first annotations, the list is shuffled per epoch), the console lines are its strings, the validation loss is its number (the
@@ -25,14 +27,22 @@ from . import base, engine, v3
 NOT_SUPPORTED = "train mode is not supported by the HIP inference backend"
 
 
-def train_option(params):
-    """The [TRAIN] key `train_layers`: absent -> False (train keeps raising), `head` -> True, anything else raises ValueError."""
+def train_layers(params):
+    """The [TRAIN] key `train_layers`: absent -> None, `head` (the detection layer of a v2 network) or `heads` (the detection convs of a v3
+    network) -> that word, anything else raises ValueError."""
     raw = params.get("train_layers")
     if raw is None:
-        return False
-    if str(raw).strip().lower() != "head":
-        raise ValueError("train_layers must be head (the detection layer on a frozen backbone), got %r" % (raw,))
-    return True
+        return None
+    word = str(raw).strip().lower()
+    if word not in ("head", "heads"):
+        raise ValueError("train_layers must be head (the detection layer on a frozen backbone) or, for a v3 network, heads (its detection "
+                         "convs), got %r" % (raw,))
+    return word
+
+
+def train_option(params):
+    """The [TRAIN] key `train_layers`: absent -> False (train keeps raising), `head` or `heads` -> True, anything else raises ValueError."""
+    return train_layers(params) is not None
 
 
 def augment_option(params):
@@ -48,9 +58,17 @@ def augment_option(params):
 def check_params(params, version):
     """What the head training refuses, before a network is built: a v3 network (the reference binds no loss to YoloV3,
     net/yolo.py:208-211), any augmentation without `augment = device`, and with it a probability outside [0, 1].
+    `train_layers = heads` is the other way round: a v3 network only, a v2 network is a ValueError.
     -> the augmentation probability that will run (0.0: none)"""
-    if not str(version).startswith("v2"):
-        raise NotImplementedError(NOT_SUPPORTED + " for %s networks: the reference has a loss for YOLOv2 only" % version)
+    if train_layers(params) == "heads":
+        if not str(version).startswith("v3"):
+            raise ValueError("train_layers = heads trains the detection convs of a v3 network; a %s network takes train_layers = head" % version)
+        ignore = float(params.get("ignore_thresh", 0.7))
+        if not 0 < ignore <= 1:
+            raise ValueError("ignore_thresh must be in (0, 1] (got %s)" % params.get("ignore_thresh"))
+    elif not str(version).startswith("v2"):
+        raise NotImplementedError(NOT_SUPPORTED + " for %s networks: the reference has a loss for YOLOv2 only"
+                                  " (train_layers = heads trains the detection convs of a v3 network)" % version)
     prob = float(params.get("augment_probability", 0))
     if not augment_option(params):
         if prob != 0:
@@ -118,6 +136,70 @@ def initial_stream(body, net, seed):
     raise ValueError("weight file holds {} values, the network needs {} ({} without the detection layer)".format(len(body), need, need - n_head))
 
 
+def head_convs_v3(net):
+    """The detection convs of a v3 layer list, in head order: [(position of the conv's bias in the Darknet stream, cout, cin)].  A
+    detection conv is the conv in front of a yolo layer: its cout biases stand at the position, its kernel [cout][cin] behind them."""
+    from .layers import conv2d_bn_act, yolo_layer
+    out, pos = [], 0
+    for i, l in enumerate(net):
+        if not isinstance(l, conv2d_bn_act):
+            continue
+        if i + 1 < len(net) and isinstance(net[i + 1], yolo_layer):
+            if l.batch_norm or l.ksize != 1 or l.weight_count() != l.filters * (l.in_channels + 1):
+                raise ValueError("the conv in front of a yolo layer is not a 1 x 1 conv with bias")
+            out.append((pos, l.filters, l.in_channels))
+        pos += l.weight_count()
+    if not out:
+        raise ValueError("the network has no yolo layers")
+    return out
+
+
+def split_heads(body, heads):
+    """([kernel [cout, cin]], [bias [cout]]) of the detection convs `heads` (head_convs_v3) in a Darknet stream"""
+    body = np.asarray(body, dtype=np.float32)
+    return ([body[pos + cout:pos + cout * (cin + 1)].reshape(cout, cin).copy() for pos, cout, cin in heads],
+            [body[pos:pos + cout].copy() for pos, cout, cin in heads])
+
+
+def replace_heads(body, heads, ws, bs):
+    """a copy of the stream with the floats of the detection convs replaced at their positions"""
+    out = np.array(body, dtype=np.float32, copy=True)
+    for (pos, cout, cin), w, b in zip(heads, ws, bs):
+        out[pos:pos + cout] = np.asarray(b, dtype=np.float32).reshape(cout)
+        out[pos + cout:pos + cout * (cin + 1)] = np.asarray(w, dtype=np.float32).reshape(cout * cin)
+    return out
+
+
+def initial_stream_v3(body, net, pretrained_net, seed):
+    """The stream a `heads` training starts from.  A stream of exactly the net's length is used as it is.  With pretrained_net -- the same
+    network built for the [TRAIN] key `pretrained_classes` = N classes -- a stream of THAT network's length keeps every float outside
+    the detection convs, and the detection convs get seeded N(0, 0.02) kernels and zero biases: how an 80-class file starts a 3-class
+    fine-tune.  Any other length raises with the lengths in the message.  -> (stream, whether the heads were drawn)"""
+    heads = head_convs_v3(net)
+    need = sum(l.weight_count() for l in net if hasattr(l, "weight_count"))
+    body = np.asarray(body, dtype=np.float32)
+    if len(body) == need:
+        return body, False
+    other = None
+    if pretrained_net is not None:
+        old = head_convs_v3(pretrained_net)
+        other = sum(l.weight_count() for l in pretrained_net if hasattr(l, "weight_count"))
+        if len(body) == other:
+            out = np.zeros(need, dtype=np.float32)
+            src = dst = 0
+            for (p_old, co_old, ci_old), (p_new, co_new, ci_new) in zip(old, heads):        # the floats between the detection convs
+                out[dst:dst + (p_old - src)] = body[src:p_old]
+                assert dst + (p_old - src) == p_new and ci_old == ci_new
+                src, dst = p_old + co_old * (ci_old + 1), p_new + co_new * (ci_new + 1)
+            out[dst:] = body[src:]
+            rng = np.random.RandomState(seed)
+            ws = [rng.normal(0.0, 0.02, size=(cout, cin)).astype(np.float32) for _, cout, cin in heads]
+            return replace_heads(out, heads, ws, [np.zeros(cout, dtype=np.float32) for _, cout, _ in heads]), True
+    raise ValueError("weight file holds {} values, the network needs {}{}".format(
+        len(body), need, " ({} with pretrained_classes = the file's class count)".format(other) if other is not None
+        else " (no pretrained_classes key: a file trained for another number of classes needs it)"))
+
+
 def checkpoint_path(checkpoint_dir, prefix, step):
     return os.path.join(checkpoint_dir, "{}-{}.weights".format(prefix, step))
 
@@ -176,10 +258,29 @@ def validation_loss(eng, annotations, batch_size):
     return float(rec["loss"]) / nb
 
 
+def validation_loss_v3(eng, annotations, batch_size, ignore_thresh):
+    """validation_loss for a v3 network: the per-image partials of HipNetwork.loss_v3_u8, added and weighted the same way"""
+    from . import evaluate as yeval
+    torch = eng.torch
+    n = len(annotations)
+    bs, nb, pad = yeval.loss_batches(n, batch_size)
+    images = torch.empty((n, yeval.LOSS_IMAGE_DTYPE.itemsize), dtype=torch.uint8, device=eng.device)
+    for start in range(0, n, bs):
+        x, truths = batch_to_device(eng, annotations[start:start + bs])
+        eng.loss_v3_u8(x, truths, ignore_thresh, images=images[start:start + len(truths)])
+    total = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=eng.device)
+    with torch.cuda.device(eng.device):
+        _hip.check(eng.lib.yolo_loss_reduce(images.data_ptr(), n, pad, bs, total.data_ptr(), eng._stream()), "yolo_loss_reduce")
+    rec = total.cpu().numpy().view(yeval.LOSS_RESULT_DTYPE)[0]
+    return float(rec["loss"]) / nb
+
+
 def train_head(model, params):
-    """Yolo.train with `train_layers = head`"""
+    """Yolo.train with `train_layers = head` (a v2 network) or `heads` (a v3 network): one loop, the entries of the version"""
     from . import evaluate as yeval
     augment_prob = check_params(params, model.version)
+    v3_heads = train_layers(params) == "heads"
+    ignore_thresh = float(params.get("ignore_thresh", 0.7))
     batch_size = int(params["batch_size"])
     learning_rate = float(params["learning_rate"])
     checkpoint_prefix, checkpoint_dir = params["checkpoint_prefix"], params["checkpoint_dir"]
@@ -200,20 +301,41 @@ def train_head(model, params):
 
     model.build(anchors, class_names, input_shape, dtype=params.get("dtype", "fp32"), max_batch=batch_size, streams=1)
     net, eng = model.net, model.net.engine
-    cout, cin, _, _ = head_counts(net)
-    header, pretrained = base.read_darknet_weights(params["pretrained_weights_path"], "v2")
+    file_version = "v3" if v3_heads else "v2"
+    if v3_heads:
+        heads = head_convs_v3(net)
+    else:
+        cout, cin, _, _ = head_counts(net)
+    header, pretrained = base.read_darknet_weights(params["pretrained_weights_path"], file_version)
     step, path = latest_checkpoint(checkpoint_dir, checkpoint_prefix)
     if step < 0:
-        body, drawn = initial_stream(pretrained, net, seed)
+        if v3_heads:
+            old = None
+            if params.get("pretrained_classes") is not None:
+                names = ["c%d" % i for i in range(int(params["pretrained_classes"]))]
+                old = type(model).create_network(anchors, names, False, input_shape=tuple(input_shape))
+            body, drawn = initial_stream_v3(pretrained, net, old, seed)
+        else:
+            body, drawn = initial_stream(pretrained, net, seed)
         v3.attach_weights(net, body)
         print("Pre-trained weights loaded." + (" Detection layer drawn from N(0, 0.02), seed {}.".format(seed) if drawn else ""))
         step = 0
         write_checkpoint(checkpoint_path(checkpoint_dir, checkpoint_prefix, step), header, body)
     else:
-        header, body = base.read_darknet_weights(path, "v2")
+        header, body = base.read_darknet_weights(path, file_version)
         v3.attach_weights(net, body)
         print("Checkpoint restored. step:{}".format(step))
-    eng.head_train_init(*split_head(body, cout, cin))       # (the moments are not part of a .weights file: they start at zero)
+    # (the moments are not part of a .weights file: they start at zero)
+    if v3_heads:
+        eng.head_train_init_v3(*split_heads(body, heads))
+        read_stream = lambda: replace_heads(body, heads, *eng.head_train_read_v3())
+        step_u8 = lambda x, truths, lr_t, result: eng.train_head_step_v3_u8(x, truths, lr_t, ignore_thresh, result=result)
+        val_loss = lambda: validation_loss_v3(eng, val_annotations, batch_size, ignore_thresh)
+    else:
+        eng.head_train_init(*split_head(body, cout, cin))
+        read_stream = lambda: replace_head(body, *eng.head_train_read())
+        step_u8 = lambda x, truths, lr_t, result: eng.train_head_step_u8(x, truths, lr_t, result=result)
+        val_loss = lambda: validation_loss(eng, val_annotations, batch_size)
 
     rng = random.Random(seed)
     augment = None
@@ -232,17 +354,16 @@ def train_head(model, params):
                 break
             updates += 1
             x, truths = batch_to_device(eng, batch, augment)
-            eng.train_head_step_u8(x, truths, engine.adam_lr_t(learning_rate, updates), result=result)
+            step_u8(x, truths, engine.adam_lr_t(learning_rate, updates), result)
             train_loss = np.float32(result.cpu().numpy().view(yeval.LOSS_RESULT_DTYPE)[0]["loss"])
             train_loss_mva = train_loss_mva * 0.9 + train_loss * 0.1 if train_loss_mva is not None else train_loss
             print("step {} ({}/{}): {} (moving average: {})".format(step, epoch, epochs, train_loss, train_loss_mva))
             if step > 0 and step % checkpoint_step == 0:
-                w, b = eng.head_train_read()
-                write_checkpoint(checkpoint_path(checkpoint_dir, checkpoint_prefix, step), header, replace_head(body, w, b))
+                write_checkpoint(checkpoint_path(checkpoint_dir, checkpoint_prefix, step), header, read_stream())
                 if val_annotations:
-                    print("validation loss: {}".format(validation_loss(eng, val_annotations, batch_size)))
+                    print("validation loss: {}".format(val_loss()))
                 else:
                     print("no validation annotations: validation skipped")
         print("Epoch ({}/{}) completed.".format(epoch, epochs))
-    model.trained_head = eng.head_train_read()
+    model.trained_head = eng.head_train_read_v3() if v3_heads else eng.head_train_read()
     print("Done")

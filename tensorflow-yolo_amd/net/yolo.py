@@ -30,7 +30,8 @@ class Yolo(object):
     # ---- out of scope for an inference backend (train: but for the detection layer) -----------------
     def train(self, params):
         """The reference's loop (net/yolo.py:98-195) for the detection layer on a frozen backbone, only when [TRAIN] has
-        `train_layers = head` (net/train.py); without the key train mode is what it was: not supported."""
+        `train_layers = head` (a v2 network) or `train_layers = heads` (the detection convs of a v3 network) (net/train.py); without the
+        key train mode is what it was: not supported."""
         from . import train as ytrain
         if not ytrain.train_option(params):
             raise NotImplementedError("train mode is not supported by the HIP inference backend")
