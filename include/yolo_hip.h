@@ -50,6 +50,9 @@
  *   yolo_net_train_head_step_v3, yolo_net_train_head_step_v3_u8
  *                           net/yolo.py:161-173 for the head convs of a YOLOv3 network (+ yolo_net_head_inputs_v3,
  *                           yolo_net_head_train_v3_bytes / _layout / _init / _read: no reference call site)
+ *   yolo_conv1x1_dgrad, yolo_conv3x3_wgrad (+ yolo_conv3x3_wgrad_plan)
+ *                           tf.gradients of net/v2.py:188 with respect to the detection layer's input (through the leaky ReLU in front of
+ *                           it) and, from that, to the kernel and beta of the 3 x 3 conv of net/v2.py:62: standalone operators
  *   yolo_augment_u8         net/base.py:15-23, :100-107: seq.to_deterministic().augment_images of a resized batch, on the device
  *   yolo_augment_truths_host
  *                           net/base.py:107-111: augment_bounding_boxes(...).remove_out_of_image().cut_out_of_image()
@@ -93,7 +96,14 @@ extern "C" {
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_head_train_v3_layout POD only) -- training the YOLOv3 head
                                           convs: yolo_net_head_inputs_v3, yolo_net_head_train_v3_layout, yolo_net_head_train_v3_bytes,
                                           yolo_net_head_train_v3_init, yolo_net_head_train_v3_read, yolo_net_train_head_step_v3,
-                                          yolo_net_train_head_step_v3_u8 */
+                                          yolo_net_train_head_step_v3_u8;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_conv3x3_wgrad_plan POD only) -- the two operators a
+                                          backward pass behind the detection layer is built from: yolo_conv1x1_dgrad, yolo_conv3x3_wgrad_plan,
+                                          yolo_conv3x3_wgrad;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_tail_train_layout POD only) -- training the last 3 x 3
+                                          block and the detection layer of a YOLOv2 net: yolo_net_tail_inputs, yolo_net_tail_train_layout,
+                                          yolo_net_tail_train_bytes, yolo_net_tail_train_init, yolo_net_tail_train_read, yolo_net_train_tail_step,
+                                          yolo_net_train_tail_step_u8 */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -722,8 +732,10 @@ int yolo_net_loss_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const y
  *   (a) only the last conv's kernel and bias receive updates; the reference's minimize() updates every variable of the graph;
  *   (b) the backbone's batch norms run on their stored statistics (the inference pass); the reference builds its training graph with
  *       is_training = True, normalises with batch statistics and updates the moving averages.
- * What a fine-tune of a pretrained, frozen backbone does.  The input gradient dX, and with it everything in front of the last conv, is
- * not here.
+ * What a fine-tune of a pretrained, frozen backbone does.  The step entries of THIS section stop at the last conv's kernel and bias.  The
+ * input gradient dX of the last conv and the weight gradient of the 3 x 3 conv in front of it are yolo_conv1x1_dgrad and yolo_conv3x3_wgrad
+ * ("The data gradient of the detection layer and the weight gradient of a 3 x 3 conv" below); yolo_net_train_tail_step ("Training the tail
+ * of a YOLOv2 net") runs a step on both layers.  Everything in front of that block is not here.
  *
  * Weight gradient.  dW[o][c] = S_p G[p][o] * X[p][c] and db[o] = S_p G[p][o], p over the P = batch * positions_per_image positions.
  *   G   float32 [P][cout], dense: the gradient in the logits' layout (yolo_v2_loss_grad).
@@ -908,6 +920,120 @@ int yolo_net_train_head_step_v3(yolo_net *net, const float *in_dev, int batch, c
                                 double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 int yolo_net_train_head_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
                                    int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+
+/* ---- The data gradient of the detection layer and the weight gradient of a 3 x 3 conv (added within ABI 7: new exports, the
+ *      yolo_conv3x3_wgrad_plan POD only) ------
+ * The two operators every backward pass behind the detection layer is built from, as standalone device ops.  The block they are written
+ * for is the 3 x 3 / batch norm / leaky conv in front of the detection layer of a YOLOv2 network (net/v2.py:62):
+ *       u = conv3x3_same(W3, X3);   z = s (.) u + b';   Y = leaky_0.1(z);   L = W Y + b        s[o] = gamma / sqrt(var + 1e-5)
+ * with b'[o] = beta - mean * s (weights.cpp: fold_batch_norm) and G = dloss / dL from yolo_v2_loss_grad.  DELIBERATE DIFFERENCES from the
+ * reference's training, beside (a) and (b) of head training above: with these operators only the block's kernel and beta and the head's
+ * kernel and bias can receive gradients; gamma and the moving statistics stay frozen (the block runs on its stored statistics, (b)).
+ * yolo_net_train_tail_step ("Training the tail of a YOLOv2 net" below) runs them on a net.
+ *
+ * Data gradient, with the activation's backward fused.  For p over the P = batch * positions_per_image positions and c < cin:
+ *       D[p][c] = (S_o G[p][o] * W[o][c]) * (Y[p][c] > 0 ? 1 : slope)              o ascending from 0
+ *   G   float32 [P][cout], dense.  cout is any value >= 1; the kernel pads the reduction with zeros and never reads past a row.
+ *   W   float32 [cout][cin], dense: the float32 MASTER kernel of the head, NOT the fp16 packed copy the forward pass reads -- nothing
+ *       is narrowed, as in yolo_conv1x1_wgrad.  cin % 8 == 0.
+ *   Y   the block's stored output, a strided NHWC view as for yolo_conv1x1_wgrad (element (n, q, c) at n * image_stride + q * ld + coff +
+ *       c from y_dev), fp16 or float32; the branch is decided by the STORED value: +0, -0, negatives (and NaN) take slope.  y_dev may
+ *       be null: then the factor is 1 everywhere and y_dtype, ld, coff and image_stride are not looked at.
+ *   Arithmetic: products and sums on the float32-input matrix cores (v_mfma_f32_32x32x2_f32: a float32 fmaf chain from +0, o ascending);
+ *   the factor is ONE float32 multiply, rounded once (a multiply by 1 is exact).  D is float32, dense [P][cin]; every element is written
+ *   (16-byte stores), nothing depends on what D held.  One kernel, enqueued on `stream` with no host synchronisation.
+ *   YOLO_ERR_ARG for a null g / w / d, cin % 8 != 0, cout < 1, P outside 1 .. 2^30, cout * cin past 31 bits, w_dev or d_dev not 16-byte
+ *   aligned, a Y view whose channels do not fit ld or whose images overlap, a y_dtype that is not F16 / F32. */
+int yolo_conv1x1_dgrad(const float *g_dev, int cout, const float *w_dev, int cin, const void *y_dev, int y_dtype, int ld, int coff,
+                       int64_t image_stride, int positions_per_image, int batch, float slope, float *d_dev, void *stream);
+
+/* 3 x 3 weight gradient, stride 1, SAME zero padding.  For position p = (image n, row r, column x) of an h x w map, tap t = 3 ky + kx:
+ *       R[o][t][c] = S_p D[p][o] * X3[n, r + ky - 1, x + kx - 1][c]        db[o] = S_p D[p][o]        dW3[o][t][c] = s32[o] * R[o][t][c]
+ *   A tap that falls outside the image contributes nothing and is never read.  The scale is ONE float32 multiply, applied in the reduce;
+ *   with a null scale_dev dW3 = R.  dbeta = db (never scaled).
+ *   D    float32 [P][cout], dense, P = batch * h * w (yolo_conv1x1_dgrad's output for the block above).
+ *   X3   the conv's input, a strided NHWC view as for yolo_conv1x1_wgrad with positions_per_image = h * w, fp16 or float32; cin % 8 == 0.
+ *   dW3  float32 [cout][9][cin]: the K order of the packed rows.  The conversion to and from the Darknet stream's [out][in][kh][kw] is the
+ *        caller's.  db float32 [cout].
+ *   Arithmetic as yolo_conv1x1_wgrad: X3 widened to float32 (exact), products and sums on the float32-input matrix cores, positions
+ *   ascending inside a chunk (a masked tap enters as a product with +0), chunks added in chunk order by a second kernel.  No
+ *   floating-point atomics: two calls return the same bits.  Every element of dW3 and db is written by every call; nothing depends on what
+ *   scratch, dW3 or db held before.  Against exact arithmetic, per element, |dW3 - exact| <= (P + 3) 2^-24 |s| S_p |D| |X3| for any split.
+ * yolo_conv3x3_wgrad_plan (host only: the sizing call for the scratch, and the hook the tests size their cases from -- a changed split
+ * shows there): tiles_cout x tiles_cin workgroup tiles of tile_cout couts x (9 taps x tile_cin channels) of dW3; a workgroup walks its
+ * chunk tile_positions positions at a time and holds, per stage, the halo_rows = tile_positions + 2 w + 2 positions
+ * [first - w - 1, first + tile_positions + w + 1) of its tile_cin channels in LDS ONCE, from which all nine taps are served.  Chunk k holds the
+ * positions [k * positions_per_chunk, min(P, (k + 1) * positions_per_chunk)); scratch_bytes = n_chunks * cout * (9 cin + 1) * 4.
+ * YOLO_ERR_ARG for h, w, batch < 1, w > 80 (the halo of a wider map does not fit LDS), P past 2^30, cin % 8 != 0, cout < 1,
+ * cout * (9 cin + 1) past 31 bits, a dtype that is not F16 / F32. */
+struct yolo_conv3x3_wgrad_plan {
+    int32_t tile_cout, tile_cin, tile_positions;
+    int32_t tiles_cout, tiles_cin;
+    int32_t positions_per_chunk, n_chunks, halo_rows;
+    uint64_t scratch_bytes;
+};
+int yolo_conv3x3_wgrad_plan(int h, int w, int batch, int cin, int cout, int x_dtype, struct yolo_conv3x3_wgrad_plan *out);
+/* scratch_dev at least yolo_conv3x3_wgrad_plan's scratch_bytes; scale_dev float32 [cout] or null.  Two kernels, enqueued on `stream` with
+ * no host synchronisation.  YOLO_ERR_ARG for what the plan refuses, a null pointer (scale_dev excepted), a pointer not aligned to its
+ * element type, a view whose channels do not fit ld or whose images overlap, a scratch that is too small. */
+int yolo_conv3x3_wgrad(const void *x_dev, int x_dtype, int ld, int coff, int64_t image_stride, int h, int w, int batch, int cin,
+                       const float *d_dev, int cout, const float *scale_dev, float *dw_dev, float *db_dev, void *scratch_dev,
+                       size_t scratch_bytes, void *stream);
+
+/* ---- Training the tail of a YOLOv2 net: the last 3 x 3 block and the detection layer (added within ABI 7: new exports, the
+ *      yolo_tail_train_layout POD only) ------
+ * The tail is the 3 x 3 / stride 1 / batch norm / leaky conv whose output the detection layer reads (net/v2.py:62 in the full network, the
+ * second 1024-wide conv in tiny-YOLOv2) plus the detection layer.  What is updated: the block's kernel W3 and beta, the head's kernel and
+ * bias.  gamma and the moving statistics stay frozen; the block, like the backbone, runs on its stored statistics (difference (b) above).
+ *
+ * yolo_net_tail_inputs: where the block's input X3 and the head's input Y (the view of yolo_net_head_input) live in the bound workspace
+ * after a dense forward.  Succeeds only when the last kernel is the detection layer (the checks of yolo_net_head_input) and the kernel that
+ * writes its input is a 3 x 3 / stride 1 conv with batch norm and leaky ReLU that writes exactly that view; YOLO_ERR_ARG, naming what is in
+ * the way, for a network that has no such block (a v3 net, a 1 x 1 or stride-2 conv, a conv with a residual, an input that no single conv
+ * writes); YOLO_ERR_STATE for a plan that runs the block as an MXFP8 conv, fused it with a neighbour (pool / reorg / upsample in its
+ * epilogue, a back-to-back 1 x 1, the stem), keeps its input outside the workspace or reuses that input's bytes behind it, or runs the
+ * batch in several stream parts. */
+int yolo_net_tail_inputs(const yolo_net *net, yolo_tensor_view *block_in, yolo_tensor_view *head_in);
+
+/* Caller-owned device state of the tail training, every part 256-byte aligned: the head's parts as in yolo_head_train_layout; for the
+ * block the float32 master W3 [cout3][9][cin3] (tap t = 3 ky + kx: the K order of the packed rows) and beta [cout3], their four moment
+ * arrays, dW3 and dbeta; scale64 (float64 [cout3] = gamma / sqrt(var + 1e-5), computed ONCE on the host at init exactly as the weight
+ * loader folds batch norm), scale32 (its float32 rounding: the s32 of yolo_conv3x3_wgrad) and mean; D [max_batch * h * w][cout3]; G, the
+ * winner table, the per-image records; one scratch that the two weight gradients use one after the other.  cin == cout3.
+ * block_src / head_src: the first float of the block (its beta) and of the head (its bias) in the Darknet stream.
+ * yolo_net_tail_train_init (synchronous; weights loaded first): block_host is the block's piece of the Darknet stream -- beta, gamma,
+ * moving mean, moving variance [cout3 each], then the kernel [out][in][kh][kw] --, head_w_host [cout][cin] and head_b_host [cout] the
+ * head's.  Converts the kernel to [o][t][c], fills the masters, zeroes the moments and writes both layers' packed forms into the net's
+ * device weights.  yolo_net_tail_train_read: synchronous copy of the master values back, the block's kernel converted to
+ * [out][in][kh][kw] again. */
+typedef struct yolo_tail_train_layout {
+    uint64_t w_offset, b_offset, m_w_offset, v_w_offset, m_b_offset, v_b_offset, dw_offset, db_offset;
+    uint64_t w3_offset, beta_offset, m_w3_offset, v_w3_offset, m_beta_offset, v_beta_offset, dw3_offset, dbeta_offset;
+    uint64_t scale64_offset, scale32_offset, mean_offset;
+    uint64_t d_offset, grad_offset, assign_offset, images_offset, scratch_offset, scratch_bytes, total_bytes;
+    uint64_t block_src, head_src;
+    int32_t cin, cout, cin3, cout3;
+} yolo_tail_train_layout;
+int yolo_net_tail_train_layout(const yolo_net *net, yolo_tail_train_layout *out);
+size_t yolo_net_tail_train_bytes(const yolo_net *net);
+int yolo_net_tail_train_init(yolo_net *net, void *state_dev, size_t bytes, const float *block_host, const float *head_w_host,
+                             const float *head_b_host);
+int yolo_net_tail_train_read(yolo_net *net, const void *state_dev, float *block_kernel_host, float *beta_host, float *w_host, float *b_host);
+/* ONE enqueue with no host synchronisation for a step of net/yolo.py:161-173 on the tail, in this order: a dense forward pass; the kernels
+ * of yolo_v2_loss_grad; the head's weight gradient (yolo_conv1x1_wgrad on Y); yolo_conv1x1_dgrad from the head's master kernel BEFORE its
+ * update, with Y and slope 0.1; yolo_conv3x3_wgrad on X3 with scale32; the Adam update and re-pack of the head (as
+ * yolo_net_train_head_step); the Adam update of W3 and beta, which in the same pass writes the block's packed form,
+ *       pack[o][t * cin3 + c] = T((double)W3[o][t][c] * scale64[o])          b'[o] = (float)((double)beta[o] - (double)mean[o] * scale64[o])
+ * (T the plan's weight type, ONE rounding from the float64 product): exactly the bytes yolo_net_load_weights produces from the stream
+ * rebuilt with yolo_net_tail_train_read.  (The loader writes T((float)(product)); for T = fp16 its host compiler folds the two truncations
+ * into one, so its bytes are the once-rounded ones -- rounding to float32 first differs in about one element of 30 000, which the tests
+ * found; for T = float32 the two forms are the same.)  result_dev receives the yolo_loss_result of the weights BEFORE the update.  Bit-identical to the standalone
+ * entries called one after the other on the same buffers (yolo_adam_step for both updates).  Checks and messages as
+ * yolo_net_train_head_step plus those of yolo_net_tail_inputs. */
+int yolo_net_train_tail_step(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                             void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+int yolo_net_train_tail_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 
 /* ---- Training augmentation on the device: flips, blur, dropout, noise, shift (added within ABI 7: new exports, one new POD) ------
  * The reference trains through an imgaug pipeline (net/base.py:15-23): Fliplr(0.5), Flipud(0.5), GaussianBlur((0, 3.0)), Dropout(0.02),

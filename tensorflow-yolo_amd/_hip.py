@@ -113,6 +113,13 @@ class WgradPlan(C.Structure):
                 ("scratch_bytes", C.c_uint64)]
 
 
+class Conv3x3WgradPlan(C.Structure):
+    """yolo_conv3x3_wgrad_plan: how a 3 x 3 weight-gradient call is split (tiles of dW3, chunks of positions, the halo in LDS, scratch)"""
+    _fields_ = [("tile_cout", C.c_int32), ("tile_cin", C.c_int32), ("tile_positions", C.c_int32), ("tiles_cout", C.c_int32),
+                ("tiles_cin", C.c_int32), ("positions_per_chunk", C.c_int32), ("n_chunks", C.c_int32), ("halo_rows", C.c_int32),
+                ("scratch_bytes", C.c_uint64)]
+
+
 class TensorView(C.Structure):
     """yolo_tensor_view: a strided NHWC tensor inside the bound workspace"""
     _fields_ = [("offset", C.c_uint64), ("image_stride", C.c_int64), ("ld", C.c_int32), ("coff", C.c_int32), ("dtype", C.c_int32),
@@ -124,6 +131,15 @@ class HeadTrainLayout(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("w_offset", "b_offset", "m_w_offset", "v_w_offset", "m_b_offset", "v_b_offset", "dw_offset",
                                           "db_offset", "grad_offset", "assign_offset", "images_offset", "scratch_offset", "scratch_bytes",
                                           "total_bytes")] + [("cin", C.c_int32), ("cout", C.c_int32)]
+
+
+class TailTrainLayout(C.Structure):
+    """yolo_tail_train_layout: byte offsets of the parts of the tail-training state (the head's parts, then the 3 x 3 block's)"""
+    _fields_ = [(n, C.c_uint64) for n in ("w_offset", "b_offset", "m_w_offset", "v_w_offset", "m_b_offset", "v_b_offset", "dw_offset",
+                                          "db_offset", "w3_offset", "beta_offset", "m_w3_offset", "v_w3_offset", "m_beta_offset",
+                                          "v_beta_offset", "dw3_offset", "dbeta_offset", "scale64_offset", "scale32_offset", "mean_offset",
+                                          "d_offset", "grad_offset", "assign_offset", "images_offset", "scratch_offset", "scratch_bytes",
+                                          "total_bytes", "block_src", "head_src")] + [(n, C.c_int32) for n in ("cin", "cout", "cin3", "cout3")]
 
 
 class HeadTrainV3Layout(C.Structure):
@@ -276,6 +292,22 @@ SIGNATURES = {
                                               C.c_float, C.c_void_p, C.c_void_p]),
     "yolo_net_train_head_step_v3_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                                                  C.c_float, C.c_void_p, C.c_void_p]),
+    # the data gradient of the detection layer and the weight gradient of a 3 x 3 conv (added within ABI 7)
+    "yolo_conv1x1_dgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                     C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "yolo_conv3x3_wgrad_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Conv3x3WgradPlan)]),
+    "yolo_conv3x3_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # training the tail of a YOLOv2 net (added within ABI 7)
+    "yolo_net_tail_inputs": (C.c_int, [C.c_void_p, C.POINTER(TensorView), C.POINTER(TensorView)]),
+    "yolo_net_tail_train_layout": (C.c_int, [C.c_void_p, C.POINTER(TailTrainLayout)]),
+    "yolo_net_tail_train_bytes": (C.c_size_t, [C.c_void_p]),
+    "yolo_net_tail_train_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_net_tail_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_net_train_tail_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                           C.c_void_p, C.c_void_p]),
+    "yolo_net_train_tail_step_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                              C.c_void_p, C.c_void_p]),
     # training augmentation (added within ABI 7)
     "yolo_augment_check": (C.c_int, [C.POINTER(AugmentImage), C.c_int, C.c_int]),
     "yolo_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(AugmentImage), C.c_void_p]),
@@ -346,6 +378,13 @@ def wgrad_plan(P, cin, cout, x_dtype=DTYPE_F16):
     pl = WgradPlan()
     check(lib().yolo_wgrad_plan(int(P), int(cin), int(cout), int(x_dtype), C.byref(pl)), "yolo_wgrad_plan")
     return {name: int(getattr(pl, name)) for name, _ in WgradPlan._fields_ if name != "pad_"}
+
+
+def conv3x3_wgrad_plan(h, w, batch, cin, cout, x_dtype=DTYPE_F16):
+    """yolo_conv3x3_wgrad_plan as a dict (host only)"""
+    pl = Conv3x3WgradPlan()
+    check(lib().yolo_conv3x3_wgrad_plan(int(h), int(w), int(batch), int(cin), int(cout), int(x_dtype), C.byref(pl)), "yolo_conv3x3_wgrad_plan")
+    return {name: int(getattr(pl, name)) for name, _ in Conv3x3WgradPlan._fields_}
 
 
 def v3_head_wgrad_plan(head, cins, batch, x_dtype=DTYPE_F16):

@@ -1,0 +1,33 @@
+// Host side of the data gradient of the detection layer and of the 3 x 3 weight gradient (include/yolo_hip.h: yolo_conv1x1_dgrad,
+// yolo_conv3x3_wgrad_plan, yolo_conv3x3_wgrad): how a 3 x 3 weight-gradient launch is split, its scratch layout and every argument check
+// in front of a launch.  No HIP here: train_tail_host.cpp compiles as plain C++, so that train_tail_host_check.cpp (a program with its
+// own main) runs it under AddressSanitizer + UndefinedBehaviorSanitizer on a CPU (`make san-tail`).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string>
+
+#include "yolo_hip.h"
+
+namespace yolo {
+
+// conv3x3_wgrad_kernel (train_tail.hip): a workgroup owns kTailTileCout couts x (9 taps x kTailTileCin channels) of dW3 and walks its
+// chunk of positions kTailTilePos at a time, with the kTailTilePos + 2 w + 2 halo positions of its channels in LDS
+constexpr int kTailTileCout = 64, kTailTileCin = 64, kTailTilePos = 32;
+constexpr int kTailTargetGrid = 512;        // workgroups a launch aims at: two per CU
+constexpr int kTailMinChunk = 32;           // positions a chunk holds at least
+constexpr int kTailMaxW = 80;               // (kTailTilePos + 2 w + 2) rows of kTailTileCin floats + the D tile stay inside 64 KiB of LDS
+// conv1x1_dgrad_kernel: a workgroup owns kDgradTileCin channels x kDgradTilePos positions of D and walks cout kDgradTileK at a time
+constexpr int kDgradTileCin = 128, kDgradTilePos = 64, kDgradTileK = 16;
+
+// 0 or a YOLO_ERR_* code with the message in err
+int wgrad3x3_plan(int h, int w, int batch, int cin, int cout, int x_dtype, struct yolo_conv3x3_wgrad_plan *out, std::string &err);
+// every check of yolo_conv3x3_wgrad that needs no device; the pointers are never followed.  Fills plan.
+int wgrad3x3_check(const void *x_dev, int x_dtype, int ld, int coff, long long image_stride, int h, int w, int batch, int cin,
+                   const void *d_dev, int cout, const void *scale_dev, const void *dw_dev, const void *db_dev, const void *scratch_dev,
+                   size_t scratch_bytes, struct yolo_conv3x3_wgrad_plan *plan, std::string &err);
+// every check of yolo_conv1x1_dgrad that needs no device; *tiles = the workgroups of the launch
+int dgrad_check(const void *g_dev, int cout, const void *w_dev, int cin, const void *y_dev, int y_dtype, int ld, int coff,
+                long long image_stride, int positions_per_image, int batch, float slope, const void *d_dev, long long *tiles, std::string &err);
+
+}  // namespace yolo

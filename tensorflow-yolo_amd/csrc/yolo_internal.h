@@ -17,6 +17,7 @@
 #include "yolo_hip.h"
 #include "train_host.h"
 #include "train3_host.h"
+#include "train_tail_host.h"
 #include "augment_host.h"
 #include "loss3_host.h"
 
@@ -463,6 +464,37 @@ struct Wgrad3Params : Wgrad3Geometry {
     int batch, max_gt;
 };
 hipError_t launch_head3_wgrad(const Wgrad3Params &p, hipStream_t s);   // all four kernels
+
+// ---- the data gradient of the detection layer and the 3 x 3 weight gradient (train_tail.hip; the split and the checks: train_tail_host.h) ----
+struct DgradParams {
+    const float *g;            // [P][cout]
+    const float *w;            // [cout][cin], the float32 master kernel
+    const void *y;             // element 0 of the view's buffer (fp16 or float32) or null: no activation factor
+    float *d;                  // [P][cin]
+    int P, cin, cout, ld, coff, ppi;
+    long long img_stride;
+    int tiles_cin;
+    float slope;
+};
+struct Wgrad3x3Params {
+    const void *x;             // element 0 of the view's buffer: fp16 or float32
+    const float *d;            // [P][cout]
+    const float *scale;        // [cout] or null
+    float *slab;               // [n_chunks][cout * 9 * cin + cout]
+    float *dw, *db;            // [cout][9][cin], [cout]
+    int P, cin, cout, ld, coff, h, w, ppi;
+    long long img_stride;
+    int ppc, n_chunks, tiles_cout, tiles_cin, halo_rows;       // yolo_conv3x3_wgrad_plan
+    int slab_stride;           // cout * (9 * cin + 1)
+};
+struct TailAdamParams {
+    AdamParams a;              // w = W3 [cout3][9 * cin3], b = beta; pack_cin = 9 * cin3; pack_w, pack_b, pack_row as for the head
+    const double *scale64;     // [cout3]: the batch-norm fold's scale
+    const float *mean;         // [cout3]
+};
+hipError_t launch_tail_adam(const TailAdamParams &p, hipStream_t s);
+hipError_t launch_conv1x1_dgrad(const DgradParams &p, int y_dtype, long long tiles, hipStream_t s);
+hipError_t launch_conv3x3_wgrad(const Wgrad3x3Params &p, int x_dtype, hipStream_t s);      // both kernels
 
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);

@@ -154,6 +154,19 @@ class Plan(object):
         _hip.check(self.lib.yolo_net_head_train_layout(self.handle, C.byref(lay)), "yolo_net_head_train_layout")
         return lay
 
+    def tail_inputs(self):
+        """yolo_net_tail_inputs: where the input of the 3 x 3 block behind the detection layer and the detection layer's input live in the
+        workspace after a dense forward (two _hip.TensorView; host only)"""
+        block_in, head_in = _hip.TensorView(), _hip.TensorView()
+        _hip.check(self.lib.yolo_net_tail_inputs(self.handle, C.byref(block_in), C.byref(head_in)), "yolo_net_tail_inputs")
+        return block_in, head_in
+
+    def tail_train_layout(self):
+        """yolo_net_tail_train_layout: byte offsets of the parts of the tail-training state (a _hip.TailTrainLayout; host only)"""
+        lay = _hip.TailTrainLayout()
+        _hip.check(self.lib.yolo_net_tail_train_layout(self.handle, C.byref(lay)), "yolo_net_tail_train_layout")
+        return lay
+
     def head_inputs_v3(self):
         """yolo_net_head_inputs_v3: where the input of every head conv lives in the workspace after a dense forward, in head order (a list of
         _hip.TensorView; host only)"""
@@ -636,6 +649,74 @@ class HipNetwork(Plan):
                        "yolo_net_head_train_read")
         return w, b
 
+    # -- training the tail of a YOLOv2 net (yolo_net_tail_train_init / yolo_net_train_tail_step / yolo_net_tail_train_read) -------------
+    def tail_train_init(self, block, head_w, head_b):
+        """Allocate the tail-training state and start it from `block` -- the 3 x 3 block's piece of the Darknet stream: beta, gamma, moving
+        mean, moving variance [cout3 each], then the kernel [out][in][kh][kw] --, head_w [cout, cin] and head_b [cout]: master values,
+        zeroed moments, the fold's scale, and both layers packed into the device weights.  Synchronous.  A net whose streams = 0 rule runs
+        two halves is set to one pass first (each part has its own arena)."""
+        torch = self.torch
+        if not self.weights_loaded:
+            raise RuntimeError("no weights loaded: call load_weights first")
+        if self._auto_streams and self.num_streams != 1:
+            _hip.check(self.lib.yolo_net_set_streams(self.handle, 1), "yolo_net_set_streams")
+        self._streams_tuned = True
+        lay = self.tail_train_layout()
+        blk = np.ascontiguousarray(block, dtype=np.float32).reshape(-1)
+        w = np.ascontiguousarray(head_w, dtype=np.float32).reshape(-1)
+        b = np.ascontiguousarray(head_b, dtype=np.float32).reshape(-1)
+        if blk.size != lay.cout3 * (4 + 9 * lay.cin3) or w.size != lay.cout * lay.cin or b.size != lay.cout:
+            raise ValueError("expected a block of %d values, a head kernel of %d x %d values and %d biases, got %d, %d and %d"
+                             % (lay.cout3 * (4 + 9 * lay.cin3), lay.cout, lay.cin, lay.cout, blk.size, w.size, b.size))
+        with torch.cuda.device(self.device):
+            self._tail_state = torch.empty(int(lay.total_bytes), dtype=torch.uint8, device=self.device)
+            _hip.check(self.lib.yolo_net_tail_train_init(self.handle, self._tail_state.data_ptr(), self._tail_state.numel(), blk.ctypes.data,
+                                                         w.ctypes.data, b.ctypes.data), "yolo_net_tail_train_init")
+        self.tail_layout = lay
+        return self._tail_state
+
+    def _train_tail_step_any(self, x, gts, lr_t, u8, result):
+        from . import evaluate as yeval
+        torch = self.torch
+        if getattr(self, "_tail_state", None) is None:
+            raise RuntimeError("train_tail_step follows tail_train_init")
+        x = self.to_device_u8(x) if u8 else self.to_device(x)
+        b = x.shape[0]
+        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
+        if result is None:
+            result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        name = "yolo_net_train_tail_step_u8" if u8 else "yolo_net_train_tail_step"
+        with torch.cuda.device(self.device):
+            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt),
+                                               self._tail_state.data_ptr(), float(lr_t), result.data_ptr(), self._stream()), name)
+        self.u8_calls += int(u8)
+        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
+        return result
+
+    def train_tail_step(self, x, gts, lr_t, result=None):
+        """One training step of the last 3 x 3 block and the detection layer in one enqueue, no host sync (include/yolo_hip.h:
+        yolo_net_train_tail_step): dense forward, loss and its gradient, the head's weight gradient, the data gradient, the block's weight
+        gradient, Adam update and re-pack of both layers.  lr_t: adam_lr_t(lr, step).  Returns the device record (uint8 [64] =
+        yolo_loss_result) of the loss BEFORE the update; `result`: a caller's tensor to write it into."""
+        return self._train_tail_step_any(x, gts, lr_t, False, result)
+
+    def train_tail_step_u8(self, x, gts, lr_t, result=None):
+        """train_tail_step() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as train_tail_step(float32(x / 255.))"""
+        return self._train_tail_step_any(x, gts, lr_t, True, result)
+
+    def tail_train_read(self):
+        """The master values of the tail (synchronous): (block kernel float32 [cout3, cin3, 3, 3] as the Darknet stream holds it, beta
+        [cout3], head kernel [cout, cin], head bias [cout])"""
+        lay = self.tail_layout
+        k3 = np.empty((lay.cout3, lay.cin3, 3, 3), dtype=np.float32)
+        beta = np.empty(lay.cout3, dtype=np.float32)
+        w = np.empty((lay.cout, lay.cin), dtype=np.float32)
+        b = np.empty(lay.cout, dtype=np.float32)
+        with self.torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_tail_train_read(self.handle, self._tail_state.data_ptr(), k3.ctypes.data, beta.ctypes.data,
+                                                         w.ctypes.data, b.ctypes.data), "yolo_net_tail_train_read")
+        return k3, beta, w, b
+
     # -- training the YOLOv3 head convs (yolo_net_head_inputs_v3 / yolo_net_head_train_v3_* / yolo_net_train_head_step_v3) ----------------
     def head_train_init_v3(self, head_ws, head_bs):
         """Allocate the YOLOv3 head-training state and start it from head_ws[s] [cout_s, cin_s] (the Darknet kernels, [out][in]) and
@@ -871,6 +952,75 @@ def v3_head_wgrad(head, xs, grad, assign, max_gt, scratch=None, out=None):
         _hip.check(_hip.lib().yolo_v3_head_wgrad(C.byref(head), views, b, grad.data_ptr(), assign.data_ptr(), int(max_gt), dws, dbs,
                                                  scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream),
                    "yolo_v3_head_wgrad")
+    return out[0], out[1], scratch
+
+
+def _nhwc_view(torch, x, who):
+    """a contiguous fp16 / float32 [B, h, w, c] device tensor, or (flat tensor, ld, coff, image_stride, (B, h, w, c)) for a strided view of
+    one (element (n, q, c) at n * image_stride + q * ld + coff + c) -> (tensor, dtype code, ld, coff, image_stride, (B, h, w, c))"""
+    if isinstance(x, (tuple, list)):
+        t, ld, coff, image_stride, shape = x
+    else:
+        if x.dim() != 4 or not x.is_contiguous():
+            raise ValueError("%s: expected a contiguous [B, h, w, c] tensor or a view tuple" % who)
+        t, shape = x, tuple(x.shape)
+        ld, coff, image_stride = shape[3], 0, shape[1] * shape[2] * shape[3]
+    if t.dtype not in (torch.float16, torch.float32):
+        raise ValueError("%s: the view must be fp16 or float32" % who)
+    return t, (_hip.DTYPE_F16 if t.dtype == torch.float16 else _hip.DTYPE_F32), int(ld), int(coff), int(image_stride), tuple(int(v) for v in shape)
+
+
+def conv1x1_dgrad(grad, weight, y=None, slope=0.1, out=None):
+    """yolo_conv1x1_dgrad: D[p][c] = (sum_o G[p][o] W[o][c]) * (Y[p][c] > 0 ? 1 : slope), one enqueue on the current stream, no host sync.
+    grad: float32 device tensor [B, h, w, cout] (or [P, cout] when y is None); weight: the float32 MASTER kernel [cout, cin]; y: the stored
+    output of the block in front -- as _nhwc_view takes it -- or None for no activation factor; out: a float32 [P, cin] tensor to write into
+    (tests pre-fill it).  Returns D float32 [P, cin]; the caller keeps the inputs alive until the work has run."""
+    torch = _torch()
+    dev = grad.device
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    if grad.dtype != torch.float32 or weight.dtype != torch.float32 or not grad.is_contiguous() or not weight.is_contiguous() or grad.shape[-1] != cout:
+        raise ValueError("conv1x1_dgrad: expected contiguous float32 grad [..., %d] and weight [%d, %d]" % (cout, cout, cin))
+    P = grad.numel() // cout
+    if y is None:
+        yt, ydt, ld, coff, istride, ppi, b = None, 0, 0, 0, 0, P, 1
+    else:
+        yt, ydt, ld, coff, istride, shape = _nhwc_view(torch, y, "conv1x1_dgrad")
+        b, ppi = shape[0], shape[1] * shape[2]
+        if b * ppi != P or shape[3] != cin:
+            raise ValueError("conv1x1_dgrad: y is %r, expected %d positions of %d channels" % (shape, P, cin))
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((P, cin), dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().yolo_conv1x1_dgrad(grad.data_ptr(), cout, weight.data_ptr(), cin, yt.data_ptr() if yt is not None else None, ydt,
+                                                 ld, coff, istride, ppi, b, float(slope), out.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "yolo_conv1x1_dgrad")
+    return out
+
+
+def conv3x3_wgrad(x, d, scale=None, scratch=None, out=None):
+    """yolo_conv3x3_wgrad: the gradient of a 3 x 3 / stride 1 / SAME conv with respect to its kernel and bias, from the gradient D of its
+    output, one enqueue on the current stream, no host sync.  x: the conv's input as _nhwc_view takes it; d: float32 device tensor
+    [B * h * w, cout] (contiguous); scale: float32 [cout] (the fold's scale: dW3 = scale * R) or None; scratch: a uint8 device tensor to run
+    in (tests pre-fill it), else one is allocated; out: (dW3, db) to write into.  Returns (dW3 float32 [cout, 9, cin], db float32 [cout],
+    scratch); the caller keeps the inputs alive until the work has run."""
+    torch = _torch()
+    dev = d.device
+    xt, xdt, ld, coff, istride, (b, h, w, cin) = _nhwc_view(torch, x, "conv3x3_wgrad")
+    if d.dtype != torch.float32 or not d.is_contiguous() or d.dim() != 2 or d.shape[0] != b * h * w:
+        raise ValueError("conv3x3_wgrad: expected a contiguous float32 gradient [%d, cout]" % (b * h * w))
+    cout = int(d.shape[1])
+    if scale is not None and (scale.dtype != torch.float32 or not scale.is_contiguous() or scale.numel() != cout):
+        raise ValueError("conv3x3_wgrad: expected a contiguous float32 scale [%d]" % cout)
+    pl = _hip.conv3x3_wgrad_plan(h, w, b, cin, cout, xdt)
+    with torch.cuda.device(dev):
+        if scratch is None:
+            scratch = torch.empty(pl["scratch_bytes"], dtype=torch.uint8, device=dev)
+        if out is None:
+            out = (torch.empty((cout, 9, cin), dtype=torch.float32, device=dev), torch.empty(cout, dtype=torch.float32, device=dev))
+        _hip.check(_hip.lib().yolo_conv3x3_wgrad(xt.data_ptr(), xdt, ld, coff, istride, h, w, b, cin, d.data_ptr(), cout,
+                                                 scale.data_ptr() if scale is not None else None, out[0].data_ptr(), out[1].data_ptr(),
+                                                 scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                   "yolo_conv3x3_wgrad")
     return out[0], out[1], scratch
 
 

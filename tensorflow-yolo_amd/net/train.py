@@ -1,6 +1,8 @@
 """`--mode train` for the detection layer: the reference's loop (net/yolo.py:98-195) around yolo_net_train_head_step.
 
-Runs only when [TRAIN] has `train_layers = head` (a v2 network) or `train_layers = heads` (a v3 network: the convs in front of its
+Runs only when [TRAIN] has `train_layers = head` (a v2 network), `train_layers = tail` (a v2 network: the last 3 x 3 block -- its kernel
+and beta; gamma and the moving statistics stay frozen -- and the detection layer, through yolo_net_train_tail_step; checkpoints replace the
+block's kernel and beta and the head at their stream positions) or `train_layers = heads` (a v3 network: the convs in front of its
 [yolo] layers, trained with the YOLOv3 loss through yolo_net_train_head_step_v3; `ignore_thresh`, default 0.7, is its ignore threshold and
 `pretrained_classes = N` lets a file trained for N classes start a fine-tune for another number).  Two deliberate differences from the reference (include/yolo_hip.h):
 only the last conv's kernel and bias receive updates, and the backbone's batch norms run on their stored statistics -- a fine-tune of the
@@ -28,15 +30,15 @@ NOT_SUPPORTED = "train mode is not supported by the HIP inference backend"
 
 
 def train_layers(params):
-    """The [TRAIN] key `train_layers`: absent -> None, `head` (the detection layer of a v2 network) or `heads` (the detection convs of a v3
-    network) -> that word, anything else raises ValueError."""
+    """The [TRAIN] key `train_layers`: absent -> None, `head` (the detection layer of a v2 network), `tail` (its last 3 x 3 block and the
+    detection layer) or `heads` (the detection convs of a v3 network) -> that word, anything else raises ValueError."""
     raw = params.get("train_layers")
     if raw is None:
         return None
     word = str(raw).strip().lower()
-    if word not in ("head", "heads"):
-        raise ValueError("train_layers must be head (the detection layer on a frozen backbone) or, for a v3 network, heads (its detection "
-                         "convs), got %r" % (raw,))
+    if word not in ("head", "heads", "tail"):
+        raise ValueError("train_layers must be head (the detection layer on a frozen backbone), tail (the last 3 x 3 block and the detection "
+                         "layer of a v2 network) or, for a v3 network, heads (its detection convs), got %r" % (raw,))
     return word
 
 
@@ -66,6 +68,9 @@ def check_params(params, version):
         ignore = float(params.get("ignore_thresh", 0.7))
         if not 0 < ignore <= 1:
             raise ValueError("ignore_thresh must be in (0, 1] (got %s)" % params.get("ignore_thresh"))
+    elif train_layers(params) == "tail" and not str(version).startswith("v2"):
+        raise ValueError("train_layers = tail trains the last 3 x 3 block and the detection layer of a v2 network; a %s network takes "
+                         "train_layers = heads" % version)
     elif not str(version).startswith("v2"):
         raise NotImplementedError(NOT_SUPPORTED + " for %s networks: the reference has a loss for YOLOv2 only"
                                   " (train_layers = heads trains the detection convs of a v3 network)" % version)
@@ -120,6 +125,40 @@ def replace_head(body, w, b):
     n_head = cout * (cin + 1)
     out[len(out) - n_head:len(out) - n_head + cout] = np.asarray(b, dtype=np.float32)
     out[len(out) - cout * cin:] = np.asarray(w, dtype=np.float32).reshape(-1)
+    return out
+
+
+def tail_counts(net):
+    """(cout3, cin3, position of the block's first float in the Darknet stream, floats of the block) of a v2 layer list: the block is the
+    conv in front of the detection layer, 3 x 3 with batch norm -- beta, gamma, moving mean, moving variance [cout3 each], then the kernel
+    [out][in][kh][kw] (net/layers.py:53-63)"""
+    from .layers import conv2d_bn_act
+    convs = [l for l in net if isinstance(l, conv2d_bn_act)]
+    if len(convs) < 2:
+        raise ValueError("the network has no conv in front of the detection layer")
+    _, _, n_head, need = head_counts(net)
+    blk = convs[-2]
+    cout3, cin3 = int(blk.filters), int(blk.in_channels)
+    if not blk.batch_norm or blk.ksize != 3 or blk.weight_count() != cout3 * (4 + 9 * cin3):
+        raise ValueError("the conv in front of the detection layer is not a 3 x 3 conv with batch norm")
+    return cout3, cin3, need - n_head - blk.weight_count(), blk.weight_count()
+
+
+def split_tail(body, net):
+    """(the block's piece of the stream, head kernel [cout, cin], head bias [cout]) of a v2 Darknet stream"""
+    cout, cin, _, _ = head_counts(net)
+    _, _, pos, n_block = tail_counts(net)
+    w, b = split_head(body, cout, cin)
+    return np.asarray(body[pos:pos + n_block], dtype=np.float32).copy(), w, b
+
+
+def replace_tail(body, net, kernel3, beta, w, b):
+    """a copy of the stream with the block's kernel ([cout3, cin3, 3, 3], the stream's order) and beta and the head's floats replaced at
+    their positions; gamma and the moving statistics stay as they are"""
+    cout3, cin3, pos, _ = tail_counts(net)
+    out = replace_head(body, w, b)
+    out[pos:pos + cout3] = np.asarray(beta, dtype=np.float32).reshape(cout3)
+    out[pos + 4 * cout3:pos + 4 * cout3 + cout3 * cin3 * 9] = np.asarray(kernel3, dtype=np.float32).reshape(cout3 * cin3 * 9)
     return out
 
 
@@ -276,10 +315,11 @@ def validation_loss_v3(eng, annotations, batch_size, ignore_thresh):
 
 
 def train_head(model, params):
-    """Yolo.train with `train_layers = head` (a v2 network) or `heads` (a v3 network): one loop, the entries of the version"""
+    """Yolo.train with `train_layers = head` or `tail` (a v2 network) or `heads` (a v3 network): one loop, the entries of the version"""
     from . import evaluate as yeval
     augment_prob = check_params(params, model.version)
     v3_heads = train_layers(params) == "heads"
+    tail = train_layers(params) == "tail"
     ignore_thresh = float(params.get("ignore_thresh", 0.7))
     batch_size = int(params["batch_size"])
     learning_rate = float(params["learning_rate"])
@@ -331,6 +371,11 @@ def train_head(model, params):
         read_stream = lambda: replace_heads(body, heads, *eng.head_train_read_v3())
         step_u8 = lambda x, truths, lr_t, result: eng.train_head_step_v3_u8(x, truths, lr_t, ignore_thresh, result=result)
         val_loss = lambda: validation_loss_v3(eng, val_annotations, batch_size, ignore_thresh)
+    elif tail:
+        eng.tail_train_init(*split_tail(body, net))
+        read_stream = lambda: replace_tail(body, net, *eng.tail_train_read())
+        step_u8 = lambda x, truths, lr_t, result: eng.train_tail_step_u8(x, truths, lr_t, result=result)
+        val_loss = lambda: validation_loss(eng, val_annotations, batch_size)
     else:
         eng.head_train_init(*split_head(body, cout, cin))
         read_stream = lambda: replace_head(body, *eng.head_train_read())
@@ -365,5 +410,9 @@ def train_head(model, params):
                 else:
                     print("no validation annotations: validation skipped")
         print("Epoch ({}/{}) completed.".format(epoch, epochs))
-    model.trained_head = eng.head_train_read_v3() if v3_heads else eng.head_train_read()
+    if tail:
+        model.trained_tail = eng.tail_train_read()
+        model.trained_head = model.trained_tail[2:]
+    else:
+        model.trained_head = eng.head_train_read_v3() if v3_heads else eng.head_train_read()
     print("Done")
