@@ -2,17 +2,20 @@
 
 The rule under test: the result of call i of a sequence equals, bit for bit, the result of the same call on a TWIN -- an engine built the
 same way that has executed only the CHANGING calls in front of i, in order, and then this call.  PURE calls (forward, forward_u8,
-forward_timed, detect / detect_u8 at 0.5, 0.05 and 0.9999 in both NMS modes, detect_frames, loss, loss_u8, loss_grad, a refused call) must
-leave nothing behind that a later call can observe; changing calls (a train step, head_train_init, load_weights, a re-bind onto a poisoned
-buffer, set_streams, autotune, tune_streams) are what a twin replays.  twin_key(sequence, i) is the key a twin's result is cached under.
+forward_timed, detect / detect_u8 at 0.5, 0.05 and 0.9999 in both NMS modes, detect_frames, loss, loss_u8, loss_grad, loss_v3, loss_v3_u8,
+loss_v3_grad, a refused call) must leave nothing behind that a later call can observe; changing calls (a train step of any of the three
+families -- the YOLOv2 head, the YOLOv3 head convs, the YOLOv2 tail --, their inits, load_weights, a re-bind onto a poisoned buffer,
+set_streams, autotune, tune_streams) are what a twin replays.  twin_key(sequence, i) is the key a twin's result is cached under.
 
 A call is a tuple: (kind, lo, n) runs on images lo .. lo + n - 1 of the plan's four distinct images, ("refuse", what) is a call the library
-must refuse (REFUSALS), a changing call is (kind, ...) of CHANGING.  Every list below is a constant: the walks are generated at import by
-a fixed algorithm and a fixed seed, nothing is drawn while the tests run.
+must refuse (REFUSALS), a changing call is (kind, ...) of CHANGING; a train step is (kind, lo, n, t), Adam's step t = 1, 2, ...  Every list
+below is a constant: the walks are generated at import by a fixed algorithm and a fixed seed, nothing is drawn while the tests run.
 
-Two claims are built into twin_key and are therefore asserted by every comparison behind them: yolo_net_load_weights of the ORIGINAL
-stream takes the net back to the bytes of a net that never trained, and yolo_net_head_train_init starts the training state again (a
-train step behind it equals the first step)."""
+A twin need not replay a changing call whose every effect is gone: twin_key drops it (the rules are in its docstring, EFFECTS is what they
+are computed from, tests/test_sequences_cpu.py proves them on a model of its own).  Every drop is a claim, asserted by every comparison
+behind it: yolo_net_load_weights of the ORIGINAL stream takes the net back to the bytes of a net that never trained; an init of a family
+starts that family's training state again and packs its layers as load_weights does (a step behind it equals the first step), whatever a
+step of ANOTHER family on the same net had packed there."""
 import functools
 import random
 
@@ -32,23 +35,39 @@ DETECT = {"detect@0.5": ("detect", 0.5, _hip.NMS_AGNOSTIC), "detect@0.5/per-clas
           "detect_u8@0.5": ("detect_u8", 0.5, _hip.NMS_AGNOSTIC), "detect_frames@0.5": ("detect_frames", 0.5, _hip.NMS_AGNOSTIC)}
 FORWARD = ("forward", "forward_u8", "forward_timed")
 LOSS = ("loss", "loss_u8", "loss_grad")
+LOSS_V3 = ("loss_v3", "loss_v3_u8", "loss_v3_grad")
+# ignore_thresh of every YOLOv3 loss call and train step of the table.  Not the engine's default of 0.7: on the calibrated synthetic weights
+# no row of the four images overlaps a truth by more than 0.5 on YOLOv3 fp16 and mxfp8 (0.7, 0.6: no ignored row on any plan; 0.5: one
+# on YOLOv3-SPP and YOLOv3-tiny, none on the other two), and a loss without an ignored row (-2 in `assign`) leaves that branch unrun.  At
+# 0.4: 1 (fp16), 3 (mxfp8), 1 (SPP), 4 (tiny) ignored rows and 6 truth rows; the control of tests/test_gpu_sequences.py asserts both kinds.
+IGNORE_THRESH = 0.4
 REFUSE = "refuse"
-CHANGING = ("train", "train_u8", "head_train_init", "load_weights", "rebind", "set_streams", "autotune", "tune_streams")
-V3_KINDS = FORWARD + tuple(DETECT) + (REFUSE,)
+# the three training families: the YOLOv2 detection layer, the head convs of a YOLOv3 network, the last 3 x 3 block and the detection layer
+# of a YOLOv2 network.  family -> (init kind, step kind, uint8 step kind)
+FAMILIES = {"head": ("head_train_init", "train", "train_u8"),
+            "v3": ("head_train_v3_init", "train_v3", "train_v3_u8"),
+            "tail": ("tail_train_init", "train_tail", "train_tail_u8")}
+INITS = {f[0]: name for name, f in FAMILIES.items()}                        # init kind -> family
+STEPS = {k: name for name, f in FAMILIES.items() for k in f[1:]}            # step kind -> family
+CHANGING = ("train", "train_u8", "head_train_init", "load_weights", "rebind", "set_streams", "autotune", "tune_streams",
+            "head_train_v3_init", "train_v3", "train_v3_u8", "tail_train_init", "train_tail", "train_tail_u8")
+V3_KINDS = FORWARD + tuple(DETECT) + LOSS_V3 + (REFUSE,)
 V2_KINDS = FORWARD + tuple(DETECT) + LOSS + (REFUSE,)
 SWITCH_KINDS = ("forward", "forward_u8", "forward_timed", "detect@0.5", "detect@0.05/per-class", "detect@0.9999", REFUSE)
 
-# what -> (status code, a part of yolo_last_error): include/yolo_hip.h, csrc/api.cpp
+# what -> (status code, a part of yolo_last_error): include/yolo_hip.h, csrc/api.cpp, csrc/loss3_host.cpp
 ERR_ARG, ERR_STATE = 1, 5
 REFUSALS = {"batch+1": (ERR_ARG, "batch outside 1..max_batch"),
             "loss-on-v3": (ERR_ARG, "the head must be version 2"),
             "loss_grad-on-v3": (ERR_ARG, "the head must be version 2"),
+            "loss_v3-on-v2": (ERR_ARG, "the head must be version 3"),
             "set_streams(3)": (ERR_STATE, "yolo_net_set_streams"),
             "train-null-state": (ERR_ARG, "null state"),
             "train-two-parts": (ERR_STATE, "call yolo_net_set_streams(net, 1)"),
+            "train_v3-two-parts": (ERR_STATE, "call yolo_net_set_streams(net, 1)"),
             "set_streams(1)-split-arenas": (ERR_STATE, "part(s) only")}
 V3_REFUSALS = ("batch+1", "loss-on-v3", "set_streams(3)", "loss_grad-on-v3")
-V2_REFUSALS = ("batch+1", "set_streams(3)", "train-null-state")
+V2_REFUSALS = ("batch+1", "set_streams(3)", "train-null-state", "loss_v3-on-v2")
 
 # truths of the four images (x, y, w, h, class): one image has none
 TRUTHS = [[(0.3, 0.4, 0.2, 0.5, 1), (0.8, 0.2, 0.3, 0.3, 2)], [], [(0.5, 0.5, 0.6, 0.4, 7)],
@@ -56,6 +75,12 @@ TRUTHS = [[(0.3, 0.4, 0.2, 0.5, 1), (0.8, 0.2, 0.3, 0.3, 2)], [], [(0.5, 0.5, 0.
 MAX_GT = 3
 FRAME_SIZES = ((120, 90), (75, 200), (64, 64), (50, 131))     # detect_frames: frame i of the plan's four, letterboxed
 LR = 1e-3
+TAIL_LR = 1e-4      # tests/test_gpu_train_tail.py: the block's weights all move by lr in Adam's first step, at 1e-3 the second step's logits overflow exp()
+
+
+def step_lr(kind):
+    """the learning rate of a train step of the table"""
+    return TAIL_LR if STEPS[kind] == "tail" else LR
 
 
 def is_changing(call):
@@ -76,18 +101,69 @@ def batch_of(call):
     return call[2] if call[0] != REFUSE and len(call) >= 3 else None
 
 
+# What a changing call reads and writes of the state a net and its engine carry between calls, as the drop rules of twin_key see it.  A
+# write replaces the whole of what it names.  PACKED: the regions of the device weights a family's init and steps re-pack.
+PACKED = {"head": ("packed head",), "v3": ("packed v3 heads",), "tail": ("packed head", "packed block")}
+STATE = {"head": "head state", "v3": "v3 state", "tail": "tail state"}
+NET = ("packed head", "packed block", "packed v3 heads", "workspace", "streams", "tiles")     # what every call that runs the net reads
+
+
+def effects(call):
+    """(what the changing call reads, what it writes)"""
+    kind = call[0]
+    if kind == "load_weights":
+        return set(), {"packed head", "packed block", "packed v3 heads"}
+    if kind in INITS:
+        return set(), {STATE[INITS[kind]]} | set(PACKED[INITS[kind]])
+    if kind in STEPS:       # forward through all packed weights, the family's state updated, its layers re-packed from it
+        return set(NET) | {STATE[STEPS[kind]]}, {STATE[STEPS[kind]]} | set(PACKED[STEPS[kind]])
+    # a re-bind, a stream count, tuned tiles: each is the history of its own piece of state (the very thing a sequence is about), so it
+    # reads what it writes and is never dropped
+    if kind == "rebind":
+        return {"workspace"}, {"workspace"}
+    if kind == "set_streams":
+        return {"streams"}, {"streams"}
+    if kind == "autotune":
+        return set(NET), {"tiles"}
+    if kind == "tune_streams":
+        return set(NET), {"streams"}
+    raise ValueError(call)
+
+
+def observes(call):
+    """what the result of a call may depend on: the net; for a train step its family's training state as well.  No call but a step of
+    its family reads a training state (a pure call has no access to one)."""
+    return set(NET) | (effects(call)[0] if is_changing(call) else set())
+
+
 def twin_key(sequence, i):
-    """(the changing calls a twin executes first, in order; the call itself).  load_weights of the original stream drops every training
-    call in front of it (and itself: the net is as it was loaded); head_train_init drops the training calls in front of it."""
-    prefix = []
-    for c in sequence[:i]:
-        if not is_changing(c):
-            continue
-        if c[0] in ("load_weights", "head_train_init"):
-            prefix = [p for p in prefix if p[0] not in ("train", "train_u8", "head_train_init")]
-        if c[0] != "load_weights":
-            prefix.append(c)
-    return tuple(prefix), sequence[i]
+    """(the changing calls a twin executes first, in order; the call itself).
+
+    Replaying every changing call in front of i is always a correct twin.  A call is dropped only when everything it wrote has since been
+    overwritten and no retained call in between read it -- dead-store elimination, backwards from what call i observes (observes), over
+    effects:
+      * a train step, or an init, is dropped behind a later init of its family or a load_weights that overwrite all it wrote, unless a
+        retained step in between (of any family: each runs the whole net) read it.  With two training states on one net both are
+        followed: tail_train_init re-packs the head that a head-only step packed, so that step is dropped where nothing read it, while a
+        tail step that ran on the head-only step's weights keeps it;
+      * load_weights does not reset a training state.  A step behind it with no init of its family in between reads the state the
+        earlier steps left, and they are retained (the table has no such step: tests/test_sequences_cpu.py);
+      * load_weights itself is dropped where no train step is retained in front of it: an init packs what load_weights packs, the net
+        is as it was loaded;
+      * rebind, set_streams, autotune and tune_streams are never dropped."""
+    calls = [c for c in sequence[:i] if is_changing(c)]
+    while True:
+        live, kept = observes(sequence[i]), []
+        for c in reversed(calls):
+            reads, writes = effects(c)
+            if writes & live:
+                kept.append(c)
+                live = (live - writes) | reads
+        kept.reverse()
+        kept = [c for j, c in enumerate(kept) if c[0] != "load_weights" or any(p[0] in STEPS for p in kept[:j])]
+        if kept == calls:
+            return tuple(calls), sequence[i]
+        calls = kept
 
 
 # ---- plans -------------------------------------------------------------------------------------------------------------------------------
@@ -116,12 +192,13 @@ def switch_max_batch(net="v3", dtype="fp16"):
 PLANS = {}      # id -> dict(pid = row of poison_cases.PLANS, more = engine options over that row's, kinds, refusals, train, streams)
 
 
-def _plan(sid, pid, kinds, refusals, train=False, streams=1, max_batch=MAX_BATCH):
-    PLANS[sid] = dict(pid=pid, more={"streams": streams, "max_batch": max_batch}, kinds=kinds, refusals=refusals, train=train, streams=streams)
+def _plan(sid, pid, kinds, refusals, train=(), streams=1, max_batch=MAX_BATCH):
+    """train: the families (FAMILIES) the plan's sequences train, the first one the plan's own"""
+    PLANS[sid] = dict(pid=pid, more={"streams": streams, "max_batch": max_batch}, kinds=kinds, refusals=refusals, train=tuple(train), streams=streams)
 
 
-_plan("v2-fp16", "v2-fp16-plan", V2_KINDS, V2_REFUSALS, train=True)
-_plan("v2-fp32", "v2-fp32-plan", V2_KINDS, V2_REFUSALS, train=True)
+_plan("v2-fp16", "v2-fp16-plan", V2_KINDS, V2_REFUSALS, train=("head",))
+_plan("v2-fp32", "v2-fp32-plan", V2_KINDS, V2_REFUSALS, train=("head",))
 _plan("v2-tiny-fp16", "v2-tiny-fp16-plan", V2_KINDS, V2_REFUSALS)
 _plan("v3-fp16", "v3-fp16-plan", V3_KINDS, V3_REFUSALS)
 _plan("v3-mxfp8", "v3-mxfp8-plan", V3_KINDS, V3_REFUSALS)
@@ -129,10 +206,24 @@ _plan("v3-spp-fp16", "v3-spp-fp16-plan", V3_KINDS, V3_REFUSALS)
 _plan("v3-tiny-fp32", "v3-tiny-fp32-plan", V3_KINDS, V3_REFUSALS)
 # streams = 0 at the smallest max_batch where the rule plans two full arenas: the plan yolo_net_set_streams can switch (max_batch: None
 # until asked for -- plan_kw -- since finding it plans the network a dozen times)
-_plan("v3-fp16-switch", "v3-fp16-plan", SWITCH_KINDS, ("batch+1", "set_streams(3)"), streams=0, max_batch=None)
+_plan("v3-fp16-switch", "v3-fp16-plan", SWITCH_KINDS, ("batch+1", "set_streams(3)", "train_v3-two-parts"), train=("v3",), streams=0, max_batch=None)
 # YOLOv2 is never given two arenas by the rule (fewer than 40 conv launches), so its two-part plan is one with streams = 2: split arenas,
-# which yolo_net_set_streams cannot switch.  The train step is refused there; that it is accepted after set_streams(1) cannot be shown.
+# which yolo_net_set_streams cannot switch.  The train step is refused there; that it is accepted after set_streams(1) cannot be shown
+# on a YOLOv2 plan (v3-fp16-switch shows it for the YOLOv3 step).
 _plan("v2-fp16-two-parts", "v2-fp16-plan", ("forward", "detect@0.5", "loss", REFUSE), ("train-two-parts", "set_streams(1)-split-arenas"), streams=2)
+# Training plans, over rows the table has already (a plan id of its own each: the cap on twin keys is per plan id).  The head convs of
+# the MXFP8 plan are fp16 convs and trainable; yolo_net_tail_inputs accepts the three YOLOv2 rows at 160 x 160 (test_sequences_cpu.py).
+TRAIN_V3 = ("v3-fp16-train", "v3-tiny-fp32-train", "v3-mxfp8-train")
+TRAIN_TAIL = ("v2-fp16-tail", "v2-fp32-tail", "v2-tiny-fp16-tail")
+for _sid in TRAIN_V3:
+    _plan(_sid, _sid[:-len("-train")] + "-plan", V3_KINDS, V3_REFUSALS, train=("v3",))
+for _sid in TRAIN_TAIL:
+    _plan(_sid, _sid[:-len("-tail")] + "-plan", V2_KINDS, V2_REFUSALS, train=("tail",))
+# Two training states on one net, head-only and tail: the `head-and-tail` sequence of the tail rows, under ids of its own -- with the four
+# training sequences a tail plan has 99 twin keys, this one needs 37 more, and the cap is 112.
+HEAD_AND_TAIL = tuple(s + "-and-head" for s in TRAIN_TAIL)
+for _sid in HEAD_AND_TAIL:
+    _plan(_sid, PLANS[_sid[:-len("-and-head")]]["pid"], V2_KINDS, V2_REFUSALS, train=("tail", "head"))
 
 
 def plan_kw(sid):
@@ -222,13 +313,17 @@ def _next(sid, kind, prev, other_images=False, small=False):
 def named_prologue(sid):
     """the leaks the issue names, each at a batch size different from its predecessor's: detect at 0.5 -> forward (obj_min_logit);
     detect at 0.5 -> detect at 0.05 on OTHER images (rows the first did not write); 0.9999 <-> 0.5; loss -> detect -> loss_grad;
-    forward_timed -> detect (obj_valid, halves)"""
+    forward_timed -> detect (obj_valid, halves); on a YOLOv3 plan loss_v3 -> detect at 0.5 -> loss_v3_grad (rows the sparse detect left
+    unwritten in front of a dense pass), detect at 0.5 -> loss_v3 on OTHER images, forward_timed -> loss_v3_u8"""
     kinds = PLANS[sid]["kinds"]
     chain = [("detect@0.5", False), ("forward", False), ("detect@0.5", "small"), ("detect@0.05", True), ("detect@0.9999", False), ("detect@0.5", False),
              ("detect@0.9999", False)]
     if "loss" in kinds:
         chain += [("loss", False), ("detect@0.5", False), ("loss_grad", False)]
     chain += [("forward_timed", False), ("detect@0.5", False)]
+    if "loss_v3" in kinds:
+        chain += [("loss_v3", False), ("detect@0.5", False), ("loss_v3_grad", False), ("detect@0.5", "small"), ("loss_v3", True), ("forward_timed", False),
+                  ("loss_v3_u8", False)]
     out = [("detect@0.5",) + variants(kinds, "detect@0.5")[0]]
     for kind, other in chain[1:]:
         out.append(_next(sid, kind, out[-1], other is True, other == "small"))
@@ -268,14 +363,30 @@ MAIN = ("v2-fp16", "v2-fp32", "v2-tiny-fp16", "v3-fp16", "v3-mxfp8", "v3-spp-fp1
 for _sid in MAIN:
     SEQUENCES[_sid] = {"cover": cover_walk(_sid), "random": random_walk(_sid)}
 
-# 3. training (YOLOv2 fp16 and fp32), in three items so that none builds more than one round of twins
+# 3. training, every family with its own init and step, in three sequences so that no item builds more than one round of twins
+def training_sequences(sid, family):
+    init, step, step_u8 = FAMILIES[family]
+    start = [(init,), (step, 0, 3, 1)]
+    return {"train-1": start + each_pure(sid, 0),
+            "train-2": start + [("forward", 0, 2), (step, 0, 4, 2)] + each_pure(sid, 1),
+            "train-u8-load-init": (start + [("detect@0.5", 0, 2), (step_u8, 1, 2, 2)] + each_pure(sid, 0)
+                                   + [("load_weights",)] + each_pure(sid, 0) + each_pure(sid, 1)       # back to the untrained twins
+                                   + [(init,), (step, 0, 3, 1)] + each_pure(sid, 0))}                  # the first step again
+
+
 for _sid in ("v2-fp16", "v2-fp32"):
-    _start = [("head_train_init",), ("train", 0, 3, 1)]
-    SEQUENCES[_sid]["train-1"] = _start + each_pure(_sid, 0)
-    SEQUENCES[_sid]["train-2"] = _start + [("forward", 0, 2), ("train", 0, 4, 2)] + each_pure(_sid, 1)
-    SEQUENCES[_sid]["train-u8-load-init"] = (_start + [("detect@0.5", 0, 2), ("train_u8", 1, 2, 2)] + each_pure(_sid, 0)
-                                             + [("load_weights",)] + each_pure(_sid, 0) + each_pure(_sid, 1)       # back to the untrained twins
-                                             + [("head_train_init",), ("train", 0, 3, 1)] + each_pure(_sid, 0))    # the first step again
+    SEQUENCES[_sid].update(training_sequences(_sid, "head"))
+# 3b. the YOLOv3 head convs and the YOLOv2 tail; rebind-train: nothing the second step reads out of the workspace (the head convs' inputs,
+# the block's input, split-K slabs, ticket counters, the logits) may survive from the first -- the workspace is 0xFF in between
+for _sid in TRAIN_V3 + TRAIN_TAIL:
+    _init, _step, _ = FAMILIES[PLANS[_sid]["train"][0]]
+    SEQUENCES[_sid] = training_sequences(_sid, PLANS[_sid]["train"][0])
+    SEQUENCES[_sid]["rebind-train"] = [(_init,), (_step, 0, 3, 1), ("rebind",), (_step, 1, 3, 2)] + each_pure(_sid, 1)
+# 3c. two training states on one net, both packing the head: a head-only step, a tail step on the head it packed, a head-only step on the
+# block the tail step packed; then head_train_init again, behind which the head-only step is the first step on the TAIL-trained block
+for _sid in HEAD_AND_TAIL:
+    SEQUENCES[_sid] = {"head-and-tail": [("head_train_init",), ("train", 0, 3, 1), ("tail_train_init",), ("train_tail", 0, 2, 1), ("train", 0, 4, 2)]
+                       + each_pure(_sid, 0) + [("head_train_init",), ("train", 0, 3, 1)] + each_pure(_sid, 1)}
 
 # 5. a re-bind onto an 0xFF-filled buffer in the middle of a walk
 for _sid in ("v2-fp16", "v3-fp16", "v3-tiny-fp32"):
@@ -296,15 +407,29 @@ def switch_sequence(mb):
     return [("set_streams", 2)] + body + [("set_streams", 1)] + body + [("set_streams", 2)] + body
 
 
+def switch_body(mb):
+    """every pure kind of the switchable plan: the full batch and one image more than half of it as two parts, 4, 2 and 3 images as one"""
+    return switch_sequence(mb)[1:10]
+
+
+def switch_train_sequence(mb):
+    """the train step of the YOLOv3 head convs on the plan yolo_net_set_streams can switch: refused at two parts (each part has its own
+    arena: which one would the head convs' inputs be read from), accepted after set_streams(1); back at two parts both arenas see the
+    trained heads; refused again; a second step after the next switch.  yolo_net_set_streams changes which arena a head input lives in."""
+    refused = (REFUSE, "train_v3-two-parts")
+    return ([("set_streams", 2), ("forward", 0, mb), refused, ("set_streams", 1), ("head_train_v3_init",), ("train_v3", 0, 4, 1), ("set_streams", 2),
+             ("detect@0.5", 0, mb)] + switch_body(mb) + [refused, ("set_streams", 1), ("train_v3", 0, 3, 2)] + switch_body(mb))     # (a body begins with the full batch)
+
+
 SEQUENCES["v2-fp16-two-parts"] = {"refused-train": [("forward", 0, 4), (REFUSE, "train-two-parts"), ("forward", 0, 4), ("detect@0.5", 0, 3),
                                                     (REFUSE, "set_streams(1)-split-arenas"), ("detect@0.5", 0, 3), ("loss", 0, 4), (REFUSE, "train-two-parts"),
                                                     ("loss", 0, 4), ("forward", 0, 1)]}
-ALL_PLANS = MAIN + ("v3-fp16-switch", "v2-fp16-two-parts")
+ALL_PLANS = MAIN + ("v3-fp16-switch", "v2-fp16-two-parts") + TRAIN_V3 + TRAIN_TAIL + HEAD_AND_TAIL
 
 
 def sequences_of(sid):
     if sid == "v3-fp16-switch" and sid not in SEQUENCES:        # (planned a dozen times to find its max_batch: when first asked for)
-        SEQUENCES[sid] = {"switch": switch_sequence(switch_max_batch())}
+        SEQUENCES[sid] = {"switch": switch_sequence(switch_max_batch()), "switch-train": switch_train_sequence(switch_max_batch())}
     return SEQUENCES[sid]
 
 
@@ -314,15 +439,31 @@ def sequences_of(sid):
 TWINS_PER_ITEM = 8
 
 
+def builds_twin(call):
+    """a call whose result is compared with a twin's: a pure call, a train step (the other changing calls return nothing)"""
+    return is_pure(call) or call[0] in STEPS
+
+
+def control_engines(sid):
+    """the engines the plan's first item builds for the controls that came with the YOLOv3 loss and the training families, beyond the twins
+    its sequences cache: the second twin of each controlled call (tests/test_gpu_sequences.py: control) -- a loss_v3 call on a YOLOv3
+    plan; on a training plan id a forward, a detect and the first step as well, and for head-and-tail the forward behind that step, which
+    is no call of the sequence.  They count against the first item's twins, so that it costs what any other item costs."""
+    kinds = PLANS[sid]["kinds"]
+    if sid in TRAIN_V3 + TRAIN_TAIL + HEAD_AND_TAIL:
+        return 3 + ("loss_v3" in kinds) + (sid in HEAD_AND_TAIL)
+    return int("loss_v3" in kinds)
+
+
 def items():
     out = []
     for sid in ALL_PLANS:
         met = set()
-        for name, seq in sequences_of(sid).items():
-            start, new, part = 0, 0, 1
+        for k, (name, seq) in enumerate(sequences_of(sid).items()):
+            start, new, part = 0, control_engines(sid) if k == 0 else 0, 1
             for i in range(len(seq)):
                 key = twin_key(seq, i)
-                fresh = key not in met and not (is_changing(seq[i]) and seq[i][0] not in ("train", "train_u8"))
+                fresh = key not in met and builds_twin(seq[i])
                 if fresh and new == TWINS_PER_ITEM:
                     out.append((sid, name, part, start, i))
                     start, new, part = i, 0, part + 1
@@ -340,8 +481,16 @@ PAIR = ("v3-fp16", "v2-tiny-fp16")
 INTERLEAVED = [(PAIR[i % 2], c) for i, c in enumerate(
     x for pair in zip(SEQUENCES[PAIR[0]]["random"][:12], SEQUENCES[PAIR[1]]["random"][:12]) for x in pair)]
 
-# 9. the covering walk without any host synchronisation between the calls
-ASYNC_PLANS = ("v2-fp16", "v3-fp16")
+# 8b. ... and two engines that both TRAIN, a YOLOv2 tail and the YOLOv3 head convs: (plan, call), each engine's calls the start of its
+# train-2 sequence (init, step, forward, step, pure kinds), so that every twin is one of that sequence's
+PAIR_TRAIN = ("v2-tiny-fp16-tail", "v3-tiny-fp32-train")
+INTERLEAVED_TRAIN_CALLS = 12
+INTERLEAVED_TRAIN = [(PAIR_TRAIN[i % 2], c) for i, c in enumerate(
+    x for pair in zip(SEQUENCES[PAIR_TRAIN[0]]["train-2"][:INTERLEAVED_TRAIN_CALLS], SEQUENCES[PAIR_TRAIN[1]]["train-2"][:INTERLEAVED_TRAIN_CALLS]) for x in pair)]
+
+# 9. the covering walk without any host synchronisation between the calls (the plans that have one), and the train-2 sequence of one
+# plan of each training family (the plans that train)
+ASYNC_PLANS = ("v2-fp16", "v3-fp16", "v3-tiny-fp32-train", "v2-tiny-fp16-tail")
 
 # 7. exact chains (tests/test_gpu_exact.py's list; integer data: every tile and every split must give the integer reference), each run as
 # forward (1 image) -> autotune -> forward (3) -> tune_streams -> forward (2) -> forward_u8 -> forward (3) at max_batch 3

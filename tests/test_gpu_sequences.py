@@ -1,22 +1,33 @@
 """GPU: a net's answers must not depend on the calls before them.
 
 A yolo_net carries state from one call to the next -- on the host (obj_min_logit, obj_valid, cand_clean, side_ok, parts / halves, the
-tiles autotune chose, the head's packed weights) and on the device (split-K ticket counters, candidate counters, the logits region with
-rows a sparse detect did not write, the compact objectness array, split-K slabs, the lifetime-packed arenas, the fork / join events).
-Every other GPU test asks its question of a freshly built engine.  Here whole sequences of calls run on ONE engine (tests/sequence_cases.py
-has the table and the rule, tests/test_sequences_cpu.py its properties), and the result of every call is compared, bit for bit, with the
-result of the same call on a TWIN: a fresh engine that has executed only the changing calls in front of it.  Twins are cached per module
-by sequence_cases.twin_key; every twin is closed as soon as its one result is on the host, every other engine when the module ends.
+tiles autotune chose) and on the device (the packed weights of the layers a train step re-packs, split-K ticket counters, candidate
+counters, the logits region with rows a sparse detect did not write, the compact objectness array, split-K slabs, the lifetime-packed
+arenas a train step reads activations out of, the fork / join events); an engine adds up to three training states (the YOLOv2 head, the
+YOLOv3 head convs, the YOLOv2 tail) and torch.empty scratch, assign and parts tensors per call.  Every other GPU test asks its question of
+a freshly built engine.  Here whole sequences of calls run on ONE engine (tests/sequence_cases.py has the table and the rule,
+tests/test_sequences_cpu.py its properties), and the result of every call is compared, bit for bit, with the result of the same call on a
+TWIN: a fresh engine that has executed only the changing calls in front of it that still matter (sequence_cases.twin_key).  Twins are
+cached per module by that key (the largest ones, the states of tail steps, only while memory allows: an evicted twin is built again);
+every twin is closed as soon as its one result is on the host, every other engine when the module ends.
 
 What is compared: logits and gradients as bytes; counts, status and the first counts[n] records of every image of a detect; the named
-fields of the loss records; the result and the six state arrays of a train step; the status code and message of a refused call.
+fields of the loss records (`images`, `result`) of the YOLOv2 and the YOLOv3 loss, `assign` and `grad` as bytes; of a YOLOv2 head step the
+result and the six state arrays; of a YOLOv3 head step the result and per scale s the masters w[s], b[s], the moments m_w[s], v_w[s],
+m_b[s], v_b[s] and the gradients dw[s], db[s] of the engine's state; of a tail step the result and the sixteen parts of the tail state
+(TAIL_PARTS: the head's eight and the block's eight); the status code and message of a refused call.  There is no tolerance anywhere.
 
-A control comes first, per plan: two fresh twins making the same call give the same bytes.  If it fails the finding is NON-DETERMINISM,
-not call order, and the plan's sequences stop there.
+Controls come first, per plan: two fresh twins making the same call give the same bytes -- a forward and a detect, a loss_v3 call where
+the plan has one, the first train step where the plan's sequences train.  If one fails the finding is NON-DETERMINISM, not call order,
+and the plan's sequences stop there.  The controls also hold the fixture to exercising the code: boxes are found, loss_v3 assigns truth
+rows and ignores rows, the first step's weight gradients are non-zero on every scale and the forward behind it differs from the untrained one.
 
 How to read a failure: it names the plan and the sequence, the index and the call, the call in front of it (and whether that was a sparse
-detect: head rows below the threshold's logit not written) and the last changing call, and the first differing (image, row, column) or
-record.  The call in front is the suspect; the state it may have left is listed in DESIGN.md section 5, "Call order"."""
+detect: head rows below the threshold's logit not written) and the last changing call, the changing calls the twin replayed, and the
+first differing (image, row, column), record or state array (`m_w[1]`: the first moment of the kernel of scale 1).  The call in front is
+the suspect; the state it may have left is listed in DESIGN.md section 5, "Call order".  A state array that differs while `result` does not
+points at the state (an init that did not start it again, a part another family's step wrote); `result` or `dw` differing points at the
+forward behind the step: packed weights, or what the step read out of the workspace."""
 import ctypes as C
 import functools
 
@@ -36,6 +47,10 @@ pytestmark = pytest.mark.gpu
 CALIBRATION = {"v2": 1, "v2-tiny": 1, "v3": 8, "v3-spp": 8, "v3-tiny": 10}        # x synth.HEAD_DEFAULTS' fraction, as the detect tests of these sizes use
 RIGS, TWINS, CONTROL, ENGINES = {}, {}, {}, []
 STATE_KEYS = ("w", "b", "m_w", "v_w", "m_b", "v_b")
+V3_STATE_KEYS = STATE_KEYS + ("dw", "db")
+TAIL_PARTS = ("w", "b", "m_w", "v_w", "m_b", "v_b", "dw", "db", "w3", "beta", "m_w3", "v_w3", "m_beta", "v_beta", "dw3", "dbeta")     # tests/test_gpu_train_tail.py
+TWIN_CACHE_BYTES = 1 << 30      # of cached LARGE twin results; what goes over it: the oldest of OTHER plans are dropped (and built again if asked for)
+LARGE_RESULT_BYTES = 32 << 20   # the state of a tail step (150 - 200 MB); the logits of the switchable plan's full batch (105 MB)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -70,9 +85,15 @@ class Rig(object):
         self.frames = [torch.from_numpy(rng.randint(0, 256, size=s + (3,)).astype(np.uint8)).cuda() for s in S.FRAME_SIZES]
         self.big = {}
         self.dummy = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")     # arguments of refused calls: never read or written
-        if pl["train"]:
-            cout, cin = ytrain.head_counts(P.create_network(self.net))[:2]
+        # what the inits of the plan's training families start from: the layers' own values in the rig's stream
+        layers = P.create_network(self.net) if pl["train"] else None
+        if "head" in pl["train"]:
+            cout, cin = ytrain.head_counts(layers)[:2]
             self.head = ytrain.split_head(self.weights, cout, cin)
+        if "tail" in pl["train"]:
+            self.tail = ytrain.split_tail(self.weights, layers)
+        if "v3" in pl["train"]:
+            self.heads_v3 = ytrain.split_heads(self.weights, ytrain.head_convs_v3(layers))
 
     def images(self, lo, n, u8=False):
         """images lo .. lo + n - 1 on the device; more than the four distinct ones (the switchable plan): image i is distinct image i mod 4"""
@@ -144,16 +165,23 @@ def refuse(r, eng, what):
     elif what in ("train-null-state", "train-two-parts"):
         state = None if what == "train-null-state" else d + 256 - d % 256
         rc = lib.yolo_net_train_head_step(h, x1.data_ptr(), 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, state, float(S.LR), d + 32768, st)
+    elif what == "loss_v3-on-v2":       # (net_loss_v3_any: the head's version is looked at before the net is, nothing is launched)
+        rc = lib.yolo_net_loss_v3(h, x1.data_ptr(), 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, S.IGNORE_THRESH, d, d + 4096, d + 8192, d + 12288, st)
+    elif what == "train_v3-two-parts":  # (head_convs_v3, the first thing the step does: refused whether or not a state exists)
+        rc = lib.yolo_net_train_head_step_v3(h, x1.data_ptr(), 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, S.IGNORE_THRESH, d + 256 - d % 256, float(S.LR),
+                                             d + 32768, st)
     else:
         raise ValueError(what)
     return int(rc), (lib.yolo_last_error() or b"").decode()
 
 
 def enqueue(r, eng, call):
-    """one pure call on the current stream, nothing else: no host synchronisation, results that live in engine-held tensors cloned on the
-    stream -> {name: device tensor | host value}"""
+    """one pure call or one train step on the current stream, nothing else: no host synchronisation, results that live in engine-held
+    tensors (records, a training state) cloned on the stream -> {name: device tensor | host value}"""
     import torch
     kind = call[0]
+    if kind in S.STEPS:
+        return enqueue_step(r, eng, call)
     if kind == S.REFUSE:
         rc, msg = refuse(r, eng, call[1])
         want = S.REFUSALS[call[1]]
@@ -179,7 +207,50 @@ def enqueue(r, eng, call):
         return {"images": images, "result": result}
     if kind == "loss_grad":
         return dict(zip(("images", "result", "assign", "grad"), eng.loss_grad(r.images(lo, n), r.gts(lo, n))))
+    if kind in ("loss_v3", "loss_v3_u8"):
+        return dict(zip(("images", "result", "assign"), getattr(eng, kind)(r.images(lo, n, kind == "loss_v3_u8"), r.gts(lo, n), S.IGNORE_THRESH)))
+    if kind == "loss_v3_grad":
+        return dict(zip(("images", "result", "assign", "grad"), eng.loss_v3_grad(r.images(lo, n), r.gts(lo, n), S.IGNORE_THRESH)))
     raise ValueError(call)
+
+
+def state_slices(eng, family):
+    """{name: (the engine's state tensor of the family, byte offset, bytes)} of the parts of a training state that a step is compared on"""
+    if family == "head":
+        lay = eng.train_layout
+        nw, nb = lay.cout * lay.cin * 4, lay.cout * 4
+        return {k: (eng._train_state, int(getattr(lay, k + "_offset")), n) for k, n in zip(STATE_KEYS, (nw, nb, nw, nw, nb, nb))}
+    if family == "v3":
+        lay = eng.train_layout_v3
+        out = {}
+        for s in range(lay.n_scales):
+            nw, nb = lay.cout[s] * lay.cin[s] * 4, lay.cout[s] * 4
+            for k, n in zip(V3_STATE_KEYS, (nw, nb, nw, nw, nb, nb, nw, nb)):
+                out["%s[%d]" % (k, s)] = (eng._train_state_v3, int(getattr(lay, k + "_offset")[s]), n)
+        return out
+    lay = eng.tail_layout
+    nw, nb, nw3, nb3 = lay.cout * lay.cin * 4, lay.cout * 4, lay.cout3 * 9 * lay.cin3 * 4, lay.cout3 * 4
+    return {k: (eng._tail_state, int(getattr(lay, k + "_offset")), n) for k, n in zip(TAIL_PARTS, (nw, nb, nw, nw, nb, nb, nw, nb, nw3, nb3, nw3, nw3, nb3, nb3, nw3, nb3))}
+
+
+def enqueue_step(r, eng, call):
+    """a train step of any family into a result tensor of the test's, and clones of the state's parts behind it on the stream"""
+    import torch
+    kind, lo, n, t = call
+    family, u8 = S.STEPS[kind], kind.endswith("_u8")
+    x, gts, lr_t = r.images(lo, n, u8), r.gts(lo, n), engine.adam_lr_t(S.step_lr(kind), t)
+    result = torch.full((yeval.LOSS_RESULT_DTYPE.itemsize,), 0xFF, dtype=torch.uint8, device="cuda")
+    if family == "head":
+        (eng.train_head_step_u8 if u8 else eng.train_head_step)(x, gts, lr_t, result=result)
+    elif family == "v3":
+        (eng.train_head_step_v3_u8 if u8 else eng.train_head_step_v3)(x, gts, lr_t, S.IGNORE_THRESH, result=result)
+    else:
+        (eng.train_tail_step_u8 if u8 else eng.train_tail_step)(x, gts, lr_t, result=result)
+    res = {"result": result}
+    for k, (state, at, nbytes) in state_slices(eng, family).items():
+        part = state[at:at + nbytes].clone()
+        res[k] = part if family == "head" else part.view(torch.float32)     # (the head family's parts stay the bytes they have always been here)
+    return res
 
 
 def named_fields(raw, dtype):
@@ -200,27 +271,18 @@ def to_host(res):
     return out
 
 
-def state_parts(eng):
-    """the master values and the four moment arrays of the engine's training state (tests/test_gpu_train.py: state_parts)"""
-    lay = eng.train_layout
-    nw, nb = lay.cout * lay.cin * 4, lay.cout * 4
-    raw = eng._train_state.cpu().numpy()
-    return {k: raw[int(getattr(lay, k + "_offset")):int(getattr(lay, k + "_offset")) + n].copy() for k, n in zip(STATE_KEYS, (nw, nb, nw, nw, nb, nb))}
-
-
-def execute(r, eng, call):
-    """a call of either kind, synchronously -> its result on the host, None for a changing call that returns nothing"""
+def issue(r, eng, call):
+    """a call of either kind, as the engine issues it -> enqueue's device results, None for a changing call that returns nothing (the inits
+    and load_weights are synchronous by nature: the library waits for the device before it copies)"""
     kind = call[0]
-    if not S.is_changing(call):
-        return to_host(enqueue(r, eng, call))
-    if kind in ("train", "train_u8"):
-        lo, n, t = call[1:]
-        step = eng.train_head_step_u8 if kind == "train_u8" else eng.train_head_step
-        res = to_host({"result": step(r.images(lo, n, kind == "train_u8"), r.gts(lo, n), engine.adam_lr_t(S.LR, t))})
-        res.update(state_parts(eng))
-        return res
+    if S.builds_twin(call):
+        return enqueue(r, eng, call)
     if kind == "head_train_init":
         eng.head_train_init(*r.head)
+    elif kind == "tail_train_init":
+        eng.tail_train_init(*r.tail)
+    elif kind == "head_train_v3_init":
+        eng.head_train_init_v3(*r.heads_v3)
     elif kind == "load_weights":
         eng.load_weights(r.weights)
     elif kind == "rebind":
@@ -231,6 +293,17 @@ def execute(r, eng, call):
     else:
         raise ValueError(call)
     return None
+
+
+def execute(r, eng, call, fetch=True):
+    """a call of either kind, synchronously -> its result on the host, None for a changing call that returns nothing (fetch = False: for
+    any call; the device has finished it all the same)"""
+    import torch
+    res = issue(r, eng, call)
+    if res is None or not fetch:
+        torch.cuda.synchronize()
+        return None
+    return to_host(res)
 
 
 def done(eng):
@@ -250,14 +323,25 @@ def twin(sid, key, cache=True):
     eng = new_engine(sid, keep=False)
     try:
         for c in prefix:
-            execute(r, eng, c)
+            execute(r, eng, c, fetch=False)
         res = execute(r, eng, call)
         torch.cuda.synchronize()
     finally:
         eng.close()
     if cache:
         TWINS[(sid, key)] = res
+        # the states of the tail steps are hundreds of megabytes each: over the budget the oldest LARGE results of other plans go
+        large = [k for k, v in TWINS.items() if result_bytes(v) > LARGE_RESULT_BYTES]
+        held = sum(result_bytes(TWINS[k]) for k in large)
+        for old in [k for k in large if k[0] != sid]:
+            if held <= TWIN_CACHE_BYTES:
+                break
+            held -= result_bytes(TWINS.pop(old))
     return res
+
+
+def result_bytes(res):
+    return sum(v.nbytes for v in res.values()) if res else 0
 
 
 # ---- comparing -----------------------------------------------------------------------------------------------------------------------------
@@ -306,15 +390,36 @@ def control(sid):
         kinds = S.PLANS[sid]["kinds"]
         # (calls of the covering walk's own set, so that the cached twin of each serves the sequences as well)
         detect = min((k for k in kinds if k in S.DETECT and S.DETECT[k][0] == "detect"), key=lambda k: S.DETECT[k][1:])     # the lowest threshold
-        for call in [(k,) + S.variants(kinds, k)[0] for k in ("forward", detect)]:
-            want = twin(sid, ((), call))
-            diff = first_difference(twin(sid, ((), call), cache=False), want)
+        first = next(iter(S.sequences_of(sid).values()))
+        trains = sid in S.TRAIN_V3 + S.TRAIN_TAIL + S.HEAD_AND_TAIL         # (the plans that came with the three training families)
+        keys = [((), (k,) + S.variants(kinds, k)[0]) for k in ("forward", detect) + (("loss_v3",) if "loss_v3" in kinds else ())]
+        if trains:
+            assert first[0][0] in S.INITS and first[1][0] in S.STEPS and first[1][3] == 1, first[:2]
+            keys.append(((first[0],), first[1]))         # the first training step
+        for key in keys:
+            call = key[1]
+            want = twin(sid, key)
+            diff = first_difference(twin(sid, key, cache=False), want)
             if diff:
-                CONTROL[sid] = "%r: %s" % (call, diff)
+                CONTROL[sid] = "%r behind %r: %s" % (call, list(key[0]), diff)
                 break
             # the fixture itself: finite, non-zero logits, and boxes to compare
             assert "counts" not in want or int(want["counts"].sum()) > 0, "plan %s: %r finds no box: the fixture detects nothing" % (sid, call)
             assert "logits" not in want or (np.isfinite(want["logits"]).all() and np.any(want["logits"] != 0)), (sid, call)
+            if call[0] == "loss_v3":        # ... truth rows and ignored rows in the loss
+                assert (want["assign"] >= 0).any() and (want["assign"] == -2).any(), (
+                    "plan %s: %r at ignore_thresh %r assigns %d truth rows and ignores %d rows: the fixture leaves a branch of the loss unrun"
+                    % (sid, call, S.IGNORE_THRESH, int((want["assign"] >= 0).sum()), int((want["assign"] == -2).sum())))
+            if call[0] in S.STEPS:          # ... a weight gradient on every scale / layer, and a forward that sees the update
+                grads = [k for k in want if k.startswith("dw")]
+                assert grads or S.STEPS[call[0]] == "head", sorted(want)
+                for k in grads:
+                    assert np.isfinite(want[k]).all() and np.any(want[k] != 0), "plan %s: %r leaves %s zero or not finite: the fixture trains nothing there" % (sid, call, k)
+                fwd = S.each_pure(sid, 0)[0]
+                assert fwd[0] == "forward"
+                trained, untrained = twin(sid, (key[0] + (call,), fwd)), twin(sid, ((), fwd))
+                assert np.isfinite(trained["logits"]).all() and first_difference(trained, untrained) is not None, (
+                    "plan %s: the forward behind %r equals the untrained twin's: the step changed nothing a forward sees" % (sid, call))
     if CONTROL[sid]:
         pytest.fail("plan %s: CONTROL failed -- two fresh engines, the same single call, different bytes.  This is non-determinism, not call "
                     "order; the plan's sequences are not run.  %s" % (sid, CONTROL[sid]))
@@ -328,8 +433,8 @@ def run_sequence(sid, name, seq, start=0, end=None):
     boxes = 0
     seq = seq[:end]
     for i, call in enumerate(seq):
-        got = execute(r, eng, call)
-        if got is None or i < start:
+        got = execute(r, eng, call, fetch=i >= start)      # (a part's calls in front of its start are another part's to compare)
+        if got is None:
             continue
         diff = first_difference(got, twin(sid, S.twin_key(seq, i)))
         assert diff is None, describe_failure(sid, name, seq, i, diff)
@@ -357,8 +462,27 @@ def test_two_engines_interleaved():
         done(eng)
 
 
+def test_two_training_engines_interleaved():
+    """a YOLOv2 tail and the YOLOv3 head convs training side by side: init, step, forward, step and pure calls of each, alternating on one
+    stream; every result equals its twin's in the engine's OWN sequence (the other engine's calls are nobody's changing calls)"""
+    own = {sid: [c for s, c in S.INTERLEAVED_TRAIN if s == sid] for sid in S.PAIR_TRAIN}
+    for sid in S.PAIR_TRAIN:
+        control(sid)
+    engines = {sid: new_engine(sid) for sid in S.PAIR_TRAIN}
+    at = dict.fromkeys(S.PAIR_TRAIN, 0)
+    for i, (sid, call) in enumerate(S.INTERLEAVED_TRAIN):
+        got = execute(rig(sid), engines[sid], call)
+        at[sid] += 1
+        if got is None:
+            continue
+        diff = first_difference(got, twin(sid, S.twin_key(own[sid], at[sid] - 1)))
+        assert diff is None, "interleaved call %d, %r on plan %s, behind %r on the other engine: %s" % (i, call, sid, S.INTERLEAVED_TRAIN[i - 1] if i else None, diff)
+    for eng in engines.values():
+        done(eng)
+
+
 # ---- 9: the covering walk without host synchronisation between the calls -----------------------------------------------------------------------
-@pytest.mark.parametrize("sid", S.ASYNC_PLANS)
+@pytest.mark.parametrize("sid", [s for s in S.ASYNC_PLANS if "cover" in S.SEQUENCES[s]])
 def test_covering_walk_enqueued_without_synchronisation(sid):
     """every call of the walk is only enqueued (inputs, truths and frames are on the device already; results that live in the engine's
     record buffer are cloned on the stream); ONE synchronisation at the end, then every result is compared.  forward_timed is the
@@ -374,6 +498,59 @@ def test_covering_walk_enqueued_without_synchronisation(sid):
     for i, res in enumerate(pending):
         diff = first_difference(to_host(res), twin(sid, S.twin_key(seq, i)))
         assert diff is None, "enqueued without synchronisation: " + describe_failure(sid, "cover", seq, i, diff)
+    done(eng)
+
+
+@pytest.mark.parametrize("sid", [s for s in S.ASYNC_PLANS if "train-2" in S.SEQUENCES[s]])
+def test_train_2_enqueued_without_synchronisation(sid):
+    """init (synchronous by nature), step, forward, step, every pure kind: the steps write their records into tensors of the test's, the
+    parts of the training state are cloned on the stream behind each step; ONE synchronisation at the end, then every result is compared.
+    Each step's forward, loss, weight gradient and update are ordered against the calls around them by the stream alone."""
+    import torch
+    control(sid)
+    seq = S.SEQUENCES[sid]["train-2"]
+    r = rig(sid)
+    eng = new_engine(sid)
+    torch.cuda.synchronize()
+    pending = [issue(r, eng, call) for call in seq]
+    torch.cuda.synchronize()
+    assert sum(c[0] in S.STEPS for c in seq) == 2 and all((res is None) == (not S.builds_twin(c)) for c, res in zip(seq, pending))
+    for i, res in enumerate(pending):
+        if res is not None:
+            diff = first_difference(to_host(res), twin(sid, S.twin_key(seq, i)))
+            assert diff is None, "enqueued without synchronisation: " + describe_failure(sid, "train-2", seq, i, diff)
+    done(eng)
+
+
+# ---- the harness itself: a flipped bit of a training state is found and named ------------------------------------------------------------------
+def test_a_flipped_bit_of_the_first_moment_is_found_and_named():
+    """Nothing in the library is mutated.  Behind a correct train_v3 step on a sequence engine, one bit of one word of m_w of scale 1 is
+    flipped in the engine's state tensor: the next step's comparison must fail and name m_w of that scale; with the state and the packed
+    weights as they were in front of that step and the bit flipped back, the comparison passes again."""
+    import torch
+    sid = "v3-tiny-fp32-train"
+    control(sid)
+    seq = S.SEQUENCES[sid]["train-2"]
+    steps = [i for i, c in enumerate(seq) if c[0] in S.STEPS]
+    r = rig(sid)
+    eng = new_engine(sid)
+    for i in range(steps[1]):
+        got = execute(r, eng, seq[i])
+        assert got is None or first_difference(got, twin(sid, S.twin_key(seq, i))) is None, describe_failure(sid, "train-2", seq, i, "before the flip")
+    state, at, nbytes = state_slices(eng, "v3")["m_w[1]"]
+    words = state[at:at + nbytes].view(torch.int32)
+    word = int(torch.nonzero(words)[0])             # a moment the first step moved
+    flip = lambda: words[word:word + 1].bitwise_xor_(1 << 22)       # the top bit of the mantissa
+    flip()
+    kept_state, kept_weights = state.clone(), eng._weights.clone()
+    want = twin(sid, S.twin_key(seq, steps[1]))
+    diff = first_difference(execute(r, eng, seq[steps[1]]), want)
+    assert diff is not None and diff.startswith("m_w[1]: "), "a flipped bit of m_w[1] (word %d) in front of %r was not found, or not named: %r" % (word, seq[steps[1]], diff)
+    state.copy_(kept_state)
+    eng._weights.copy_(kept_weights)
+    flip()
+    diff = first_difference(execute(r, eng, seq[steps[1]]), want)
+    assert diff is None, "with the bit flipped back: " + describe_failure(sid, "train-2", seq, steps[1], diff)
     done(eng)
 
 

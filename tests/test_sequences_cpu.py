@@ -2,9 +2,12 @@
 ordered pair of a plan's pure kinds adjacent somewhere, every pure kind compared in every state a twin is built in, batch sizes that rise
 and fall, constant random walks -- and its plans are planned as it says: the switchable plan with two full arenas at the smallest
 max_batch that gives them, the others with the stream count they name, the exact chains with the kernels they are in the table for.  The
-number of twins a plan needs (one engine built per key) stays under the cap written in the table."""
+number of twins a plan needs (one engine built per key) stays under the cap written in the table.  The changing calls a twin does NOT
+replay (sequence_cases.twin_key drops them) are held against a model of this file's own of what every changing call reads and writes:
+the reduced prefix of every index of every sequence reaches the state of the full one."""
 import ctypes as C
 
+import numpy as np
 import pytest
 
 import poison_cases as P
@@ -28,19 +31,42 @@ def test_calls_are_well_formed(sid):
             if c[0] == S.REFUSE:
                 assert c[1] in pl["refusals"] and c[1] in S.REFUSALS, (sid, name, c)
             elif S.is_changing(c):
-                assert c[0] in S.CHANGING and (pl["train"] or c[0] not in ("train", "train_u8", "head_train_init", "load_weights")), (sid, name, c)
+                family = S.INITS.get(c[0]) or S.STEPS.get(c[0])         # a training call: of a family the plan trains
+                assert c[0] in S.CHANGING and (family is None or family in pl["train"]) and (pl["train"] or c[0] != "load_weights"), (sid, name, c)
+                if c[0] in S.STEPS:
+                    assert len(c) == 4 and 1 <= c[2] <= min(mb, S.N_IMAGES) and 0 <= c[1] and c[1] + c[2] <= S.N_IMAGES and c[3] in (1, 2), (sid, name, c)
             else:
                 assert c[0] in pl["kinds"], (sid, name, c)
                 lo, n = c[1], c[2]
                 assert 1 <= n <= mb and (n > S.N_IMAGES or (0 <= lo and lo + n <= S.N_IMAGES)), (sid, name, c)
-    assert set(pl["kinds"]) <= set(S.FORWARD) | set(S.DETECT) | set(S.LOSS) | {S.REFUSE}
+    assert set(pl["kinds"]) <= set(S.FORWARD) | set(S.DETECT) | set(S.LOSS) | set(S.LOSS_V3) | {S.REFUSE}
     if "loss" in pl["kinds"]:
-        assert P.PLANS[pl["pid"]]["net"].startswith("v2")
+        assert P.PLANS[pl["pid"]]["net"].startswith("v2") and not set(S.LOSS_V3) & set(pl["kinds"])
+    if "loss_v3" in pl["kinds"]:
+        assert P.PLANS[pl["pid"]]["net"].startswith("v3") and set(S.LOSS_V3) <= set(pl["kinds"])
+    assert set(pl["train"]) <= set(S.FAMILIES) and all((f == "v3") == P.PLANS[pl["pid"]]["net"].startswith("v3") for f in pl["train"])
     assert max(t[4] for img in S.TRUTHS for t in img) < 20 and max(len(img) for img in S.TRUTHS) <= S.MAX_GT and [] in S.TRUTHS
 
 
 def test_pure_and_changing_calls_are_the_issue_s():
-    assert set(S.CHANGING) == {"train", "train_u8", "head_train_init", "load_weights", "rebind", "set_streams", "autotune", "tune_streams"}
+    assert set(S.CHANGING) == {"train", "train_u8", "head_train_init", "load_weights", "rebind", "set_streams", "autotune", "tune_streams",
+                               "head_train_v3_init", "train_v3", "train_v3_u8", "tail_train_init", "train_tail", "train_tail_u8"}
+    assert S.FAMILIES == {"head": ("head_train_init", "train", "train_u8"), "v3": ("head_train_v3_init", "train_v3", "train_v3_u8"),
+                          "tail": ("tail_train_init", "train_tail", "train_tail_u8")}
+    assert set(S.INITS) | set(S.STEPS) <= set(S.CHANGING) and len(S.INITS) == 3 and len(S.STEPS) == 6
+    assert S.LOSS_V3 == ("loss_v3", "loss_v3_u8", "loss_v3_grad") and 0.0 < S.IGNORE_THRESH <= 1.0
+    # the four YOLOv3 plans have the three v3 loss kinds, the v2 plans the refusal of the v3 loss; the refusals of the v2 loss stay
+    for sid in ("v3-fp16", "v3-mxfp8", "v3-spp-fp16", "v3-tiny-fp32"):
+        assert set(S.LOSS_V3) <= set(S.PLANS[sid]["kinds"]) and {"loss-on-v3", "loss_grad-on-v3"} <= set(S.PLANS[sid]["refusals"])
+    for sid in ("v2-fp16", "v2-fp32", "v2-tiny-fp16") + S.TRAIN_TAIL + S.HEAD_AND_TAIL:
+        assert "loss_v3-on-v2" in S.PLANS[sid]["refusals"] and set(S.LOSS) <= set(S.PLANS[sid]["kinds"])
+    assert S.REFUSALS["loss_v3-on-v2"] == (S.ERR_ARG, "the head must be version 3")
+    assert S.REFUSALS["train_v3-two-parts"] == (S.ERR_STATE, "call yolo_net_set_streams(net, 1)")
+    # the learning rates: the head families at the table's, the tail at the one its own GPU test uses (and for its reason)
+    import test_gpu_sequences as G
+    import test_gpu_train_tail as TT
+    assert S.step_lr("train") == S.step_lr("train_v3_u8") == S.LR == 1e-3 and S.step_lr("train_tail") == S.step_lr("train_tail_u8") == TT.LR == 1e-4
+    assert G.TAIL_PARTS == TT.TAIL_PARTS and len(G.TAIL_PARTS) == 16 and G.V3_STATE_KEYS == ("w", "b", "m_w", "v_w", "m_b", "v_b", "dw", "db")
     thresholds = {(m, t) for m, t, _ in S.DETECT.values()}
     assert {("detect", 0.5), ("detect", 0.05), ("detect", 0.9999), ("detect_u8", 0.5), ("detect_frames", 0.5)} <= thresholds
     for t in (0.5, 0.05, 0.9999):       # both NMS modes
@@ -48,7 +74,7 @@ def test_pure_and_changing_calls_are_the_issue_s():
     assert S.is_sparse_detect(("detect@0.5", 0, 1)) and S.is_sparse_detect(("detect@0.05/per-class", 0, 1))
     assert not S.is_sparse_detect(("detect@0.9999", 0, 1)) and not S.is_sparse_detect(("forward", 0, 1))       # inside 1e-4 of 1: the dense branch
     assert 1.0 - 0.9999 <= 1e-4 + 1e-12
-    assert set(S.V2_KINDS) == set(S.V3_KINDS) | set(S.LOSS)
+    assert set(S.V2_KINDS) - set(S.LOSS) == set(S.V3_KINDS) - set(S.LOSS_V3) and set(S.LOSS) <= set(S.V2_KINDS) and set(S.LOSS_V3) <= set(S.V3_KINDS)
 
 
 # ---- the walks -----------------------------------------------------------------------------------------------------------------------------
@@ -96,6 +122,15 @@ def test_the_named_leaks_are_in_the_covering_walk(sid):
     assert adjacent("forward_timed", "detect@0.5")                        # obj_valid, halves
     if "loss" in S.PLANS[sid]["kinds"]:
         assert any(a[0] == "loss" and b[0].startswith("detect") and c[0] == "loss_grad" for a, b, c in zip(walk, walk[1:], walk[2:]))
+    if "loss_v3" in S.PLANS[sid]["kinds"]:
+        # loss_v3 -> a SPARSE detect -> loss_v3_grad, each at a batch size different from its predecessor's
+        assert any(a[0] == "loss_v3" and b[0] == "detect@0.5" and S.is_sparse_detect(b) and c[0] == "loss_v3_grad" and a[2] != b[2] != c[2]
+                   for a, b, c in zip(walk, walk[1:], walk[2:]))
+        # rows the sparse detect did not write (more images than it had: batch slots it never touched), images it did not see
+        assert any(x[0] == "detect@0.5" and y[0] == "loss_v3" and y[2] > x[2] and not (x[1] <= y[1] and y[1] + y[2] <= x[1] + x[2]) for x, y in zip(walk, walk[1:]))
+        assert adjacent("forward_timed", "loss_v3_u8")
+    else:
+        assert not set(S.LOSS_V3) & {c[0] for c in walk}
 
 
 @pytest.mark.parametrize("sid", S.ALL_PLANS)
@@ -111,7 +146,10 @@ def test_random_walks_regenerate_identically():
         a, b = S.random_walk(sid), S.random_walk(sid)
         assert a == b == S.SEQUENCES[sid]["random"] and len(a) == 24 and all(S.is_pure(c) for c in a), sid
         assert a != S.random_walk(sid, seed=1)
-    assert S.SEQUENCES["v3-fp16"]["random"][:3] == [("detect@0.05", 1, 3), ("detect_frames@0.5", 0, 3), ("detect@0.9999/per-class", 0, 1)]     # seed 0, written out
+    # seed 0, written out (drawn from the plan's calls, the three v3 loss kinds among them)
+    assert S.SEQUENCES["v3-fp16"]["random"][:3] == [("detect_frames@0.5", 0, 1), ("detect@0.5", 3, 1), ("detect_u8@0.5", 0, 3)]
+    for sid in ("v3-fp16", "v3-mxfp8", "v3-spp-fp16", "v3-tiny-fp32"):
+        assert set(S.LOSS_V3) <= {c[0] for c in S.all_calls(sid)}
 
 
 @pytest.mark.parametrize("sid", S.ALL_PLANS)
@@ -140,13 +178,119 @@ def test_twin_keys():
     assert S.twin_key(seq, 7) == S.twin_key(seq, 0)                                     # load_weights: the untrained twin
     assert S.twin_key(seq, 10) == ((("rebind",), ("head_train_init",)), ("train", 0, 3, 1))       # the first step again, on a re-bound workspace
     # in the table: the pure calls behind load_weights have the keys of the untrained twins, the step behind the second init the key of the first
-    for sid in ("v2-fp16", "v2-fp32"):
+    for sid in ("v2-fp16", "v2-fp32") + S.TRAIN_V3 + S.TRAIN_TAIL:
+        init, step, step_u8 = S.FAMILIES[S.PLANS[sid]["train"][0]]
         s = S.SEQUENCES[sid]["train-u8-load-init"]
         i = s.index(("load_weights",))
         assert all(S.twin_key(s, j)[0] == () for j in range(i + 1, i + 1 + 2 * len(S.PLANS[sid]["kinds"])))
-        j = len(s) - 1 - s[::-1].index(("train", 0, 3, 1))
-        assert j > i and S.twin_key(s, j) == S.twin_key(s, 1)
-        assert any(c[0] == "train_u8" for c in s)
+        j = len(s) - 1 - s[::-1].index((step, 0, 3, 1))
+        assert j > i and S.twin_key(s, j) == S.twin_key(s, 1) == (((init,),), (step, 0, 3, 1))
+        assert any(c[0] == step_u8 for c in s)
+    # two training states on one net.  tail_train_init re-packs the head, so the tail step does not see the head-only step in front of it;
+    # the second head-only step reads the state the first left and the block the tail step packed: everything is replayed for it ...
+    s = S.SEQUENCES["v2-fp16-tail-and-head"]["head-and-tail"]
+    start = (("head_train_init",), ("train", 0, 3, 1), ("tail_train_init",), ("train_tail", 0, 2, 1), ("train", 0, 4, 2))
+    assert tuple(s[:5]) == start and all(S.twin_key(s, j)[0] == start[:j] for j in (0, 1, 2, 4, 5))
+    assert S.twin_key(s, 3) == ((("tail_train_init",),), ("train_tail", 0, 2, 1))
+    # ... and behind the second head_train_init, which overwrites all that is left of the two head-only steps, neither they nor the
+    # first init are replayed: the step is the first step on the tail-trained block
+    j = 5 + s[5:].index(("head_train_init",))
+    assert S.twin_key(s, j + 1) == ((("tail_train_init",), ("train_tail", 0, 2, 1), ("head_train_init",)), ("train", 0, 3, 1))
+    assert S.twin_key(s, len(s) - 1)[0] == (("tail_train_init",), ("train_tail", 0, 2, 1), ("head_train_init",), ("train", 0, 3, 1))
+    # a tail step that DID run on a head-only step's head (no tail_train_init in between) keeps that step behind a later head_train_init
+    s = [("tail_train_init",), ("head_train_init",), ("train", 0, 3, 1), ("train_tail", 0, 2, 1), ("head_train_init",), ("forward", 0, 1)]
+    assert S.twin_key(s, 5)[0] == tuple(s[:5])
+    # load_weights does not reset a training state: a step behind it without an init keeps the steps in front of it, and load_weights
+    s = [("head_train_v3_init",), ("train_v3", 0, 3, 1), ("load_weights",), ("train_v3", 0, 4, 2), ("forward", 0, 1)]
+    assert S.twin_key(s, 3)[0] == tuple(s[:3]) and S.twin_key(s, 4)[0] == tuple(s[:4])
+    # rebind and set_streams are never dropped, whatever is dropped around them
+    s = [("set_streams", 2), ("head_train_v3_init",), ("train_v3", 0, 3, 1), ("rebind",), ("set_streams", 1), ("load_weights",), ("forward", 0, 1)]
+    assert S.twin_key(s, 6)[0] == (("set_streams", 2), ("rebind",), ("set_streams", 1))
+
+
+# ---- the drop rules of twin_key, against a model of what the changing calls do -------------------------------------------------------------
+# The model is this file's own (sequence_cases.effects is not used): each piece of state holds a VALUE, a term built from the call that wrote
+# it and the values that call read.  Two prefixes that end in equal terms have put the net into the same state as far as the model goes.
+PIECES = ("packed head", "packed block", "packed v3 heads", "head state", "tail state", "v3 state", "workspace", "streams", "tiles")
+MODEL_STATE = {"head": "head state", "tail": "tail state", "v3": "v3 state"}
+MODEL_PACKS = {"head": ("packed head",), "tail": ("packed head", "packed block"), "v3": ("packed v3 heads",)}
+
+
+def model_net(st):
+    """what a pass through the net can see: every packed region, the workspace binding, the stream count, the tiles"""
+    return tuple(st[k] for k in ("packed head", "packed block", "packed v3 heads", "workspace", "streams", "tiles"))
+
+
+def model_run(calls):
+    st = dict.fromkeys(PIECES, "as built")
+    st.update({"packed head": "as loaded", "packed block": "as loaded", "packed v3 heads": "as loaded", "head state": None, "tail state": None, "v3 state": None})
+    for c in calls:
+        kind = c[0]
+        if kind == "load_weights":                  # the original stream: every packed region as it was loaded; no training state is touched
+            st.update({"packed head": "as loaded", "packed block": "as loaded", "packed v3 heads": "as loaded"})
+        elif kind in S.INITS:                       # masters from the original stream, zeroed moments; the family's layers packed from the masters
+            st[MODEL_STATE[S.INITS[kind]]] = "started"
+            st.update(dict.fromkeys(MODEL_PACKS[S.INITS[kind]], "as loaded"))
+        elif kind in S.STEPS:                       # forward through the net as it is, the state moved, the family's layers packed from the new masters
+            family = S.STEPS[kind]
+            assert st[MODEL_STATE[family]] is not None, "a step without its init: %r" % (c,)
+            st[MODEL_STATE[family]] = ("step", c, st[MODEL_STATE[family]], model_net(st))
+            st.update({k: ("packed from", k, st[MODEL_STATE[family]]) for k in MODEL_PACKS[family]})
+        elif kind == "rebind":
+            st["workspace"] = ("re-bound", st["workspace"])
+        elif kind in ("set_streams", "tune_streams"):
+            st["streams"] = (c, st["streams"])
+        elif kind == "autotune":
+            st["tiles"] = (c, st["tiles"])
+        else:
+            raise ValueError(c)
+    return st
+
+
+def model_result(calls, call):
+    """what the call returns, and the state it leaves, behind `calls`: a pure call sees the net; a step its family's state as well and
+    leaves a new one; an init, a load or a switch returns nothing"""
+    st = model_run(calls)
+    if S.is_pure(call):
+        return ("result", call, model_net(st))
+    after = model_run(list(calls) + [call])
+    return ("result", call, model_net(after)) + ((after[MODEL_STATE[S.STEPS[call[0]]]],) if call[0] in S.STEPS else ())
+
+
+@pytest.mark.parametrize("sid", S.ALL_PLANS)
+def test_the_reduced_prefix_reaches_the_state_of_the_full_prefix(sid):
+    """for every index of every sequence: the calls twin_key keeps are a subsequence of the changing calls in front of the index, and in
+    the model they give the call the same result, and leave the same net, as all of them do.  And the table never steps a family without
+    an init of that family between the step and the last load_weights in front of it (load_weights does not reset a training state)."""
+    dropped = 0
+    for name, seq in all_sequences(sid).items():
+        for i, call in enumerate(seq):
+            full = [c for c in seq[:i] if S.is_changing(c)]
+            kept = list(S.twin_key(seq, i)[0])
+            it = iter(full)
+            assert all(any(c == f for f in it) for c in kept), (sid, name, i, kept)            # a subsequence, in order
+            assert model_result(kept, call) == model_result(full, call), (sid, name, i, call, kept)
+            dropped += len(full) - len(kept)
+            if call[0] in S.STEPS:
+                family = S.STEPS[call[0]]
+                behind_load = full[max((j for j, c in enumerate(full) if c[0] == "load_weights"), default=-1) + 1:]
+                assert any(c[0] in S.INITS and S.INITS[c[0]] == family for c in behind_load), (sid, name, i, call)
+    if any("train-u8-load-init" in n or "head-and-tail" in n for n in all_sequences(sid)):
+        assert dropped > 0, sid
+
+
+def test_the_model_tells_a_wrong_drop_from_a_right_one():
+    """the proof above is worth what the model can refute"""
+    init, step = ("tail_train_init",), ("train_tail", 0, 3, 1)
+    head = [("head_train_init",), ("train", 0, 3, 1)]
+    fwd = ("forward", 0, 1)
+    assert model_result(head + [init, step], fwd) == model_result([init, step], fwd)                 # tail_train_init re-packs the head
+    assert model_result([init] + head + [step], fwd) != model_result([init, step], fwd)             # ... a head-only step behind it is seen
+    assert model_result([init, step, ("load_weights",)], fwd) == model_result([], fwd)
+    assert model_result([init, step, ("load_weights",)], step) != model_result([init], step)        # the state outlives load_weights
+    assert model_result([init, step, ("load_weights",), init], step) == model_result([init], step)
+    assert model_result([("rebind",)], fwd) != model_result([], fwd) and model_result([("set_streams", 2), ("set_streams", 1)], fwd) != model_result([("set_streams", 1)], fwd)
+    assert model_result([("head_train_v3_init",), ("train_v3", 0, 3, 1)], ("train_v3", 0, 4, 2)) != model_result([("head_train_v3_init",)], ("train_v3", 0, 4, 2))
 
 
 @pytest.mark.parametrize("sid", S.ALL_PLANS)
@@ -170,9 +314,10 @@ def test_items():
         assert all(a[2] == b[1] and a[1] < a[2] for a, b in zip(ps, ps[1:])), (sid, name, ps)
     for sid, name, part, start, end in S.ITEMS:      # ... and none has more than TWINS_PER_ITEM twins to build
         seq = all_sequences(sid)[name]
-        keys = {S.twin_key(seq, i) for i in range(start, end) if not (S.is_changing(seq[i]) and seq[i][0] not in ("train", "train_u8"))}
+        keys = {S.twin_key(seq, i) for i in range(start, end) if S.is_pure(seq[i]) or seq[i][0] in S.STEPS}
+        first = sid not in met          # the plan's first item builds the second twins of the newer controls as well
         new = keys - met.setdefault(sid, set())
-        assert len(new) <= S.TWINS_PER_ITEM, (sid, name, part, len(new))
+        assert len(new) + (S.control_engines(sid) if first else 0) <= S.TWINS_PER_ITEM, (sid, name, part, len(new))
         met[sid] |= keys
     for sid in S.MAIN:
         assert {"cover", "random", "refusals"} <= set(S.SEQUENCES[sid])
@@ -189,16 +334,72 @@ def test_items():
     assert all(a[0] != b[0] for a, b in zip(S.INTERLEAVED, S.INTERLEAVED[1:]))
     for sid, c in S.INTERLEAVED:
         assert ((), c) in S.twin_keys(sid)
-    assert set(S.ASYNC_PLANS) == {"v2-fp16", "v3-fp16"}
+    # the covering walks as before, and the train-2 sequence of one plan of each training family
+    assert set(S.ASYNC_PLANS) == {"v2-fp16", "v3-fp16", "v3-tiny-fp32-train", "v2-tiny-fp16-tail"}
+    assert {s for s in S.ASYNC_PLANS if "cover" in S.SEQUENCES[s]} == {"v2-fp16", "v3-fp16"}
+    assert sorted(S.PLANS[s]["train"][0] for s in S.ASYNC_PLANS if "train-2" in S.SEQUENCES[s]) == ["head", "tail", "v3"]
+    # the training sequences of every training plan, and what they are made of
+    for sid in S.TRAIN_V3 + S.TRAIN_TAIL:
+        init, step, step_u8 = S.FAMILIES[S.PLANS[sid]["train"][0]]
+        seqs, pure0, pure1 = S.SEQUENCES[sid], S.each_pure(sid, 0), S.each_pure(sid, 1)
+        assert set(seqs) == {"train-1", "train-2", "train-u8-load-init", "rebind-train"}
+        assert [c[0] for c in pure0] == list(S.PLANS[sid]["kinds"]) == [c[0] for c in pure1]
+        assert seqs["train-1"] == [(init,), (step, 0, 3, 1)] + pure0
+        assert seqs["train-2"] == [(init,), (step, 0, 3, 1), ("forward", 0, 2), (step, 0, 4, 2)] + pure1
+        assert seqs["train-u8-load-init"] == ([(init,), (step, 0, 3, 1), ("detect@0.5", 0, 2), (step_u8, 1, 2, 2)] + pure0 + [("load_weights",)] + pure0 + pure1
+                                              + [(init,), (step, 0, 3, 1)] + pure0)
+        assert S.is_sparse_detect(("detect@0.5", 0, 2))
+        s = seqs["rebind-train"]
+        assert s[:3] == [(init,), (step, 0, 3, 1), ("rebind",)] and s[3][0] == step and s[3][3] == 2 and s[4:] == pure1
+    for sid in S.HEAD_AND_TAIL:
+        assert S.SEQUENCES[sid] == {"head-and-tail": [("head_train_init",), ("train", 0, 3, 1), ("tail_train_init",), ("train_tail", 0, 2, 1), ("train", 0, 4, 2)]
+                                    + S.each_pure(sid, 0) + [("head_train_init",), ("train", 0, 3, 1)] + S.each_pure(sid, 1)}
+    # the second interleaved pair: both engines train, calls alternate, each engine's calls are the start of its train-2 sequence
+    assert S.PAIR_TRAIN == ("v2-tiny-fp16-tail", "v3-tiny-fp32-train") and all(a[0] != b[0] for a, b in zip(S.INTERLEAVED_TRAIN, S.INTERLEAVED_TRAIN[1:]))
+    for sid in S.PAIR_TRAIN:
+        own = [c for s, c in S.INTERLEAVED_TRAIN if s == sid]
+        assert own == S.SEQUENCES[sid]["train-2"][:len(own)] and sum(c[0] in S.STEPS for c in own) == 2 and sum(S.is_pure(c) for c in own) >= 8
 
 
 # ---- the plans -----------------------------------------------------------------------------------------------------------------------------
 def test_the_plans_are_the_issue_s():
     rows = {sid: (P.PLANS[pl["pid"]]["net"], P.PLANS[pl["pid"]]["dtype"]) for sid, pl in S.PLANS.items()}
     assert {rows[s] for s in S.MAIN} == {("v2", "fp16"), ("v2", "fp32"), ("v2-tiny", "fp16"), ("v3", "fp16"), ("v3", "mxfp8"), ("v3-spp", "fp16"), ("v3-tiny", "fp32")}
-    assert {s for s in S.PLANS if S.PLANS[s]["train"]} == {"v2-fp16", "v2-fp32"}
-    for sid in S.MAIN:
+    assert {s: S.PLANS[s]["train"] for s in S.PLANS if S.PLANS[s]["train"]} == dict(
+        [("v2-fp16", ("head",)), ("v2-fp32", ("head",)), ("v3-fp16-switch", ("v3",))] + [(s, ("v3",)) for s in S.TRAIN_V3] + [(s, ("tail",)) for s in S.TRAIN_TAIL]
+        + [(s, ("tail", "head")) for s in S.HEAD_AND_TAIL])
+    assert S.TRAIN_V3 == ("v3-fp16-train", "v3-tiny-fp32-train", "v3-mxfp8-train") and S.TRAIN_TAIL == ("v2-fp16-tail", "v2-fp32-tail", "v2-tiny-fp16-tail")
+    assert [S.PLANS[s]["pid"] for s in S.TRAIN_V3 + S.TRAIN_TAIL] == ["v3-fp16-plan", "v3-tiny-fp32-plan", "v3-mxfp8-plan", "v2-fp16-plan", "v2-fp32-plan",
+                                                                     "v2-tiny-fp16-plan"]
+    assert [S.PLANS[s]["pid"] for s in S.HEAD_AND_TAIL] == [S.PLANS[s]["pid"] for s in S.TRAIN_TAIL]
+    for sid in S.TRAIN_V3:          # their pure kinds are the plan's ordinary ones
+        assert S.PLANS[sid]["kinds"] == S.V3_KINDS == S.PLANS["v3-fp16"]["kinds"]
+    for sid in S.TRAIN_TAIL + S.HEAD_AND_TAIL:
+        assert S.PLANS[sid]["kinds"] == S.V2_KINDS == S.PLANS["v2-fp16"]["kinds"]
+    for sid in S.MAIN + S.TRAIN_V3 + S.TRAIN_TAIL + S.HEAD_AND_TAIL:
         assert S.PLANS[sid]["more"] == {"streams": 1, "max_batch": 4} and not P.PLANS[S.PLANS[sid]["pid"]]["keep_all"]
+
+
+@pytest.mark.parametrize("sid", S.TRAIN_V3 + S.TRAIN_TAIL + S.HEAD_AND_TAIL)
+def test_the_library_accepts_the_training_plans(sid):
+    """the entry points that refuse a plan they cannot train (a fused-away input, an MXFP8 conv, a reused buffer) accept these, and the
+    activations a step reads out of the workspace lie inside it"""
+    p = S.plan_only(sid)
+    assert p.num_streams == 1 and p.max_batch == S.MAX_BATCH
+    views = []
+    if "v3" in S.PLANS[sid]["train"]:
+        lay, views = p.head_train_layout_v3(), p.head_inputs_v3()
+        assert lay.n_scales == len(views) == p.head.n_scales >= 2 and lay.total_bytes > 0        # (the mutation test flips a bit of scale 1)
+    if "tail" in S.PLANS[sid]["train"]:
+        cls, anchors, names, _ = P.NETS[P.PLANS[S.PLANS[sid]["pid"]]["net"]]
+        h, w, _ = p.output_shape            # (a model sets the YOLOv2 head when it builds its engine)
+        p.set_head(engine.head_desc_v2(h, w, np.reshape(anchors, [-1, 2]), len(names)))
+        lay, views = p.tail_train_layout(), list(p.tail_inputs())
+        assert lay.total_bytes > 0 and (views[1].cin, views[0].cin) == (lay.cin, lay.cin3)
+    if "head" in S.PLANS[sid]["train"]:
+        assert p.head_train_layout().total_bytes > 0 and p.head_input().offset == views[1].offset
+    for v in views:
+        assert 0 <= v.offset and v.offset + S.MAX_BATCH * v.image_stride * (2 if v.dtype == _hip.DTYPE_F16 else 4) <= p.workspace_bytes, (sid, v.offset)
 
 
 @pytest.mark.parametrize("sid", S.MAIN + ("v2-fp16-two-parts",))
@@ -237,6 +438,24 @@ def test_the_switchable_plan_has_two_full_arenas_at_the_smallest_max_batch():
     assert ns == {mb, mb // 2 + 1, 4, 2, 3} and 2 * 4 <= mb < 2 * (mb // 2 + 1)
     seq = S.sequences_of("v3-fp16-switch")["switch"]
     assert [c for c in seq if S.is_changing(c)] == [("set_streams", 2), ("set_streams", 1), ("set_streams", 2)] and S.is_changing(seq[0])
+    # the YOLOv3 train step on this plan: refused at two parts, accepted after set_streams(1), seen by both arenas, refused again, a second step
+    seq = S.sequences_of("v3-fp16-switch")["switch-train"]
+    refused = (S.REFUSE, "train_v3-two-parts")
+    assert seq[:7] == [("set_streams", 2), ("forward", 0, mb), refused, ("set_streams", 1), ("head_train_v3_init",), ("train_v3", 0, 4, 1), ("set_streams", 2)]
+    assert seq[7:9] == [("detect@0.5", 0, mb), ("forward", 0, mb)] and S.is_sparse_detect(seq[7])
+    assert [c for c in seq if S.is_changing(c)] == [("set_streams", 2), ("set_streams", 1), ("head_train_v3_init",), ("train_v3", 0, 4, 1), ("set_streams", 2),
+                                                    ("set_streams", 1), ("train_v3", 0, 3, 2)]
+    j = len(seq) - 1 - seq[::-1].index(("set_streams", 1))
+    assert seq[j - 1] == refused and seq[j + 1] == ("train_v3", 0, 3, 2) and seq[j + 2] == ("forward", 0, mb)
+    streams = 0
+    for c in seq:           # the refusal only ever at two parts, the steps only at one
+        streams = c[1] if c[0] == "set_streams" else streams
+        assert (c != refused or streams == 2) and (c[0] not in S.STEPS or streams == 1), c
+    assert S.twin_key(seq, len(seq) - 1)[0] == tuple(c for c in seq if S.is_changing(c))
+    lay = p.head_train_layout_v3()          # at one part (the loop above left it there) the layout is accepted ...
+    assert lay.n_scales == 3
+    assert p.lib.yolo_net_set_streams(p.handle, 2) == 0 and p.lib.yolo_net_head_train_v3_layout(p.handle, C.byref(lay)) == S.REFUSALS["train_v3-two-parts"][0]
+    assert S.REFUSALS["train_v3-two-parts"][1] in p.lib.yolo_last_error().decode()      # ... at two parts it is refused with the documented message
 
 
 def test_yolov2_is_never_given_two_full_arenas():
