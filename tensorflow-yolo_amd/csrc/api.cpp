@@ -1,5 +1,6 @@
 // C ABI of libyolo_hip.so (declared in include/yolo_hip.h): argument and state checks, then one call into the planner (plan.cpp), the
-// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame, the evaluation, the loss, the head-training and the augmentation entries live here whole.  No exceptions cross the boundary.
+// forward engine (forward.cpp) or a launcher.  Decode + NMS, the frame, the evaluation, the loss and the augmentation entries live here
+// whole; the training entries are train_api.cpp.  No exceptions cross the boundary.
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -101,18 +102,6 @@ int yolo_net_head_desc(const yolo_net *net, yolo_head_desc *out) {
     return YOLO_OK;
 }
 
-static int check_head(const yolo_head_desc *h, size_t out_count, std::string &err) {
-    if (h->version != 2 && h->version != 3) { err = "head version must be 2 or 3"; return YOLO_ERR_ARG; }
-    if (h->n_scales < 1 || h->n_scales > YOLO_MAX_SCALES || h->n_classes < 1) { err = "bad head geometry"; return YOLO_ERR_ARG; }
-    size_t rows = 0;
-    for (int s = 0; s < h->n_scales; ++s) {
-        if (h->n_anchors[s] < 1 || h->n_anchors[s] > YOLO_MAX_ANCHORS || h->h[s] < 1 || h->w[s] < 1) { err = "bad head scale"; return YOLO_ERR_ARG; }
-        rows += (size_t)h->h[s] * h->w[s] * h->n_anchors[s];
-    }
-    if (out_count && rows * (5 + h->n_classes) != out_count) { err = "head geometry does not match the network output size"; return YOLO_ERR_ARG; }
-    return YOLO_OK;
-}
-
 int yolo_net_set_head(yolo_net *net, const yolo_head_desc *head) {
     if (!net || !head) return fail(YOLO_ERR_ARG, "yolo_net_set_head: null argument");
     std::string err;
@@ -180,7 +169,20 @@ int yolo_net_bind_workspace(yolo_net *net, void *ws, size_t bytes) {
 
 }  // extern "C"
 
-namespace {
+// ---- the checks and launch lists that the training entries (train_api.cpp) share with the entries here: declared in yolo_internal.h
+namespace yolo {
+
+int check_head(const yolo_head_desc *h, size_t out_count, std::string &err) {
+    if (h->version != 2 && h->version != 3) { err = "head version must be 2 or 3"; return YOLO_ERR_ARG; }
+    if (h->n_scales < 1 || h->n_scales > YOLO_MAX_SCALES || h->n_classes < 1) { err = "bad head geometry"; return YOLO_ERR_ARG; }
+    size_t rows = 0;
+    for (int s = 0; s < h->n_scales; ++s) {
+        if (h->n_anchors[s] < 1 || h->n_anchors[s] > YOLO_MAX_ANCHORS || h->h[s] < 1 || h->w[s] < 1) { err = "bad head scale"; return YOLO_ERR_ARG; }
+        rows += (size_t)h->h[s] * h->w[s] * h->n_anchors[s];
+    }
+    if (out_count && rows * (5 + h->n_classes) != out_count) { err = "head geometry does not match the network output size"; return YOLO_ERR_ARG; }
+    return YOLO_OK;
+}
 
 int check_ready(yolo_net *net, const void *in, int batch, const char *who) {
     if (!net || !in) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
@@ -189,6 +191,67 @@ int check_ready(yolo_net *net, const void *in, int batch, const char *who) {
     if (!net->dev_ws) return fail(YOLO_ERR_STATE, std::string(who) + ": workspace not bound");
     return YOLO_OK;
 }
+
+// every check here is made on the host, before any device call
+int check_loss_args(const yolo_head_desc *head, const void *gt_dev, const void *gt_counts_dev, int max_gt, const void *images_dev,
+                    const void *result_dev, const char *who) {
+    if (!head || !gt_dev || !gt_counts_dev || !images_dev || !result_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (max_gt < 1 || max_gt > YOLO_EVAL_MAX_GT) return fail(YOLO_ERR_ARG, std::string(who) + ": max_gt must be 1.." + std::to_string(YOLO_EVAL_MAX_GT));
+    if (head->version != 2 || head->n_scales != 1)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 2 with one scale (the reference has a loss for YOLOv2 only)");
+    std::string err;
+    int rc = check_head(head, 0, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    if ((long long)head->h[0] * head->w[0] > YOLO_LOSS_MAX_CELLS)
+        return fail(YOLO_ERR_ARG, std::string(who) + ": h * w must be at most " + std::to_string(YOLO_LOSS_MAX_CELLS));
+    return YOLO_OK;
+}
+
+static int run_loss(const yolo_head_desc &h, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+                    yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, hipStream_t s) {
+    LossParams p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.gt = gt; p.gt_counts = gt_counts; p.max_gt = max_gt;
+    p.h = h.h[0]; p.w = h.w[0]; p.na = h.n_anchors[0]; p.n_classes = h.n_classes;
+    for (int a = 0; a < p.na; ++a) {
+        p.aw[a] = h.anchors[0][2 * a]; p.ah[a] = h.anchors[0][2 * a + 1];
+        p.awf[a] = (float)p.aw[a]; p.ahf[a] = (float)p.ah[a];
+    }
+    p.images = images; p.assign = assign;
+    HIP_TRY(launch_loss_images(p, batch, s));
+    HIP_TRY(launch_loss_finish(LossFinishParams{images, batch, 0, batch, result}, s));
+    return YOLO_OK;
+}
+
+// the kernels of yolo_v2_loss_grad: the two of run_loss, then the gradient kernel on the winner table they left
+int run_loss_grad(const yolo_head_desc &h, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+                  yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad, hipStream_t s) {
+    int rc = run_loss(h, logits, batch, gt, gt_counts, max_gt, images, assign, result, s);
+    if (rc) return rc;
+    LossGradParams p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.gt = gt; p.assign = assign; p.grad = grad; p.batch = batch; p.max_gt = max_gt;
+    p.h = h.h[0]; p.w = h.w[0]; p.na = h.n_anchors[0]; p.n_classes = h.n_classes;
+    for (int a = 0; a < p.na; ++a) { p.awf[a] = (float)h.anchors[0][2 * a]; p.ahf[a] = (float)h.anchors[0][2 * a + 1]; }
+    HIP_TRY(launch_loss_grad(p, s));
+    return YOLO_OK;
+}
+
+int run_loss3(const Loss3Geometry &geo, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+              double ignore_thresh, yolo_loss_image *parts, yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad,
+              hipStream_t s) {
+    Loss3Params p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.gt = gt; p.gt_counts = gt_counts; p.batch = batch; p.max_gt = max_gt; p.ignore_thresh = ignore_thresh; p.geo = geo;
+    p.parts = parts; p.images = images; p.assign = assign; p.result = result; p.grad = grad;
+    HIP_TRY(launch_loss3(p, s));
+    if (grad) HIP_TRY(launch_loss3_grad(p, s));
+    return YOLO_OK;
+}
+
+}  // namespace yolo
+
+namespace {
 
 void fill_decode(const yolo_head_desc &h, DecodeParams &dp) {
     dp.version = h.version;
@@ -372,7 +435,6 @@ int yolo_net_read_layer(yolo_net *net, int layer, int batch, float *host_out, si
     return YOLO_OK;
 }
 
-static size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 // scratch of the standalone decode + NMS: candidates at 0 | counters | NMS slabs
 struct DecodeScratch {
     size_t counters, slabs, total;
@@ -632,51 +694,6 @@ int yolo_eval_finish(const yolo_eval_desc *desc, void *state_dev, void *result_d
 }
 
 // ---- YOLOv2 loss (yolo_hip.h: added within ABI 7; kernels in loss.hip) -----------------------------------------------------------------
-// every check here is made on the host, before any device call
-static int check_loss_args(const yolo_head_desc *head, const void *gt_dev, const void *gt_counts_dev, int max_gt, const void *images_dev,
-                           const void *result_dev, const char *who) {
-    if (!head || !gt_dev || !gt_counts_dev || !images_dev || !result_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    if (max_gt < 1 || max_gt > YOLO_EVAL_MAX_GT) return fail(YOLO_ERR_ARG, std::string(who) + ": max_gt must be 1.." + std::to_string(YOLO_EVAL_MAX_GT));
-    if (head->version != 2 || head->n_scales != 1)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 2 with one scale (the reference has a loss for YOLOv2 only)");
-    std::string err;
-    int rc = check_head(head, 0, err);
-    if (rc) return fail(rc, std::string(who) + ": " + err);
-    if ((long long)head->h[0] * head->w[0] > YOLO_LOSS_MAX_CELLS)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": h * w must be at most " + std::to_string(YOLO_LOSS_MAX_CELLS));
-    return YOLO_OK;
-}
-
-static int run_loss(const yolo_head_desc &h, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
-                    yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, hipStream_t s) {
-    LossParams p;
-    memset(&p, 0, sizeof p);
-    p.logits = logits; p.gt = gt; p.gt_counts = gt_counts; p.max_gt = max_gt;
-    p.h = h.h[0]; p.w = h.w[0]; p.na = h.n_anchors[0]; p.n_classes = h.n_classes;
-    for (int a = 0; a < p.na; ++a) {
-        p.aw[a] = h.anchors[0][2 * a]; p.ah[a] = h.anchors[0][2 * a + 1];
-        p.awf[a] = (float)p.aw[a]; p.ahf[a] = (float)p.ah[a];
-    }
-    p.images = images; p.assign = assign;
-    HIP_TRY(launch_loss_images(p, batch, s));
-    HIP_TRY(launch_loss_finish(LossFinishParams{images, batch, 0, batch, result}, s));
-    return YOLO_OK;
-}
-
-// the kernels of yolo_v2_loss_grad: the two of run_loss, then the gradient kernel on the winner table they left
-static int run_loss_grad(const yolo_head_desc &h, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
-                         yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad, hipStream_t s) {
-    int rc = run_loss(h, logits, batch, gt, gt_counts, max_gt, images, assign, result, s);
-    if (rc) return rc;
-    LossGradParams p;
-    memset(&p, 0, sizeof p);
-    p.logits = logits; p.gt = gt; p.assign = assign; p.grad = grad; p.batch = batch; p.max_gt = max_gt;
-    p.h = h.h[0]; p.w = h.w[0]; p.na = h.n_anchors[0]; p.n_classes = h.n_classes;
-    for (int a = 0; a < p.na; ++a) { p.awf[a] = (float)h.anchors[0][2 * a]; p.ahf[a] = (float)h.anchors[0][2 * a + 1]; }
-    HIP_TRY(launch_loss_grad(p, s));
-    return YOLO_OK;
-}
-
 int yolo_v2_loss(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
                  int max_gt, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev, void *stream) {
     if (!logits_dev) return fail(YOLO_ERR_ARG, "yolo_v2_loss: null argument");
@@ -744,18 +761,6 @@ int yolo_v3_loss_rows(const yolo_head_desc *head, int64_t *rows_per_image, int32
     return YOLO_OK;
 }
 
-static int run_loss3(const Loss3Geometry &geo, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
-                     double ignore_thresh, yolo_loss_image *parts, yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad,
-                     hipStream_t s) {
-    Loss3Params p;
-    memset(&p, 0, sizeof p);
-    p.logits = logits; p.gt = gt; p.gt_counts = gt_counts; p.batch = batch; p.max_gt = max_gt; p.ignore_thresh = ignore_thresh; p.geo = geo;
-    p.parts = parts; p.images = images; p.assign = assign; p.result = result; p.grad = grad;
-    HIP_TRY(launch_loss3(p, s));
-    if (grad) HIP_TRY(launch_loss3_grad(p, s));
-    return YOLO_OK;
-}
-
 int yolo_v3_loss(const yolo_head_desc *head, const float *logits_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
                  double ignore_thresh, yolo_loss_image *parts_dev, yolo_loss_image *images_dev, int32_t *assign_dev, yolo_loss_result *result_dev,
                  void *stream) {
@@ -814,134 +819,6 @@ int yolo_net_loss_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const y
                            result_dev, stream, "yolo_net_loss_v3_u8");
 }
 
-// ---- training the detection layer (yolo_hip.h: added within ABI 7; kernels in train.hip, split and checks in train_host.cpp) ---------------
-int yolo_wgrad_plan(int64_t P, int cin, int cout, int x_dtype, struct yolo_wgrad_plan *out) {
-    std::string err;
-    const int rc = wgrad_plan(P, cin, cout, x_dtype, out, err);
-    return rc ? fail(rc, "yolo_wgrad_plan: " + err) : YOLO_OK;
-}
-
-static int run_wgrad(const void *x, int x_dtype, int ld, int coff, long long image_stride, int ppi, int batch, int cin, const float *g, int cout,
-                     float *dw, float *db, void *scratch, const struct yolo_wgrad_plan &pl, hipStream_t s) {
-    WgradParams p;
-    memset(&p, 0, sizeof p);
-    p.x = x; p.g = g; p.slab = static_cast<float *>(scratch); p.dw = dw; p.db = db;
-    p.P = ppi * batch; p.cin = cin; p.cout = cout; p.ld = ld; p.coff = coff; p.ppi = ppi; p.img_stride = image_stride;
-    p.ppc = pl.positions_per_chunk; p.n_chunks = pl.n_chunks; p.tiles_cout = pl.tiles_cout; p.tiles_cin = pl.tiles_cin;
-    p.slab_stride = cout * (cin + 1);
-    HIP_TRY(launch_head_wgrad(p, x_dtype, s));
-    return YOLO_OK;
-}
-
-int yolo_conv1x1_wgrad(const void *x_dev, int x_dtype, int ld, int coff, int64_t image_stride, int positions_per_image, int batch, int cin,
-                       const float *g_dev, int cout, float *dw_dev, float *db_dev, void *scratch_dev, size_t scratch_bytes, void *stream) {
-    std::string err;
-    struct yolo_wgrad_plan pl;
-    const int rc = wgrad_check(x_dev, x_dtype, ld, coff, image_stride, positions_per_image, batch, cin, g_dev, cout, dw_dev, db_dev, scratch_dev,
-                               scratch_bytes, &pl, err);
-    if (rc) return fail(rc, "yolo_conv1x1_wgrad: " + err);
-    return run_wgrad(x_dev, x_dtype, ld, coff, image_stride, positions_per_image, batch, cin, g_dev, cout, dw_dev, db_dev, scratch_dev, pl,
-                     static_cast<hipStream_t>(stream));
-}
-
-int yolo_adam_step(float *w, float *b, float *m_w, float *v_w, float *m_b, float *v_b, const float *dw, const float *db, int64_t n_w,
-                   int64_t n_b, float lr_t, float beta1, float beta2, float eps, void *stream) {
-    std::string err;
-    const int rc = adam_check(w, b, m_w, v_w, m_b, v_b, dw, db, n_w, n_b, lr_t, beta1, beta2, eps, err);
-    if (rc) return fail(rc, "yolo_adam_step: " + err);
-    AdamParams p;
-    memset(&p, 0, sizeof p);
-    p.w = w; p.b = b; p.m_w = m_w; p.v_w = v_w; p.m_b = m_b; p.v_b = v_b; p.dw = dw; p.db = db; p.n_w = n_w; p.n_b = n_b;
-    p.lr_t = lr_t; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
-    HIP_TRY(launch_adam_step(p, static_cast<hipStream_t>(stream)));
-    return YOLO_OK;
-}
-
-// ---- the data gradient of the detection layer and the 3 x 3 weight gradient (yolo_hip.h: added within ABI 7; kernels in train_tail.hip, split
-//      and checks in train_tail_host.cpp)
-static int run_dgrad(const float *g, int cout, const float *w, int cin, const void *y, int y_dtype, int ld, int coff, long long image_stride, int ppi,
-                     int batch, float slope, float *d, long long tiles, hipStream_t s) {
-    DgradParams p;
-    memset(&p, 0, sizeof p);
-    p.g = g; p.w = w; p.y = y; p.d = d;
-    p.P = ppi * batch; p.cin = cin; p.cout = cout; p.ppi = ppi;
-    if (y) { p.ld = ld; p.coff = coff; p.img_stride = image_stride; }
-    p.tiles_cin = (cin + kDgradTileCin - 1) / kDgradTileCin;
-    p.slope = slope;
-    HIP_TRY(launch_conv1x1_dgrad(p, y_dtype, tiles, s));
-    return YOLO_OK;
-}
-
-int yolo_conv1x1_dgrad(const float *g_dev, int cout, const float *w_dev, int cin, const void *y_dev, int y_dtype, int ld, int coff,
-                       int64_t image_stride, int positions_per_image, int batch, float slope, float *d_dev, void *stream) {
-    std::string err;
-    long long tiles = 0;
-    const int rc = dgrad_check(g_dev, cout, w_dev, cin, y_dev, y_dtype, ld, coff, image_stride, positions_per_image, batch, slope, d_dev, &tiles, err);
-    if (rc) return fail(rc, "yolo_conv1x1_dgrad: " + err);
-    return run_dgrad(g_dev, cout, w_dev, cin, y_dev, y_dtype, ld, coff, image_stride, positions_per_image, batch, slope, d_dev, tiles,
-                     static_cast<hipStream_t>(stream));
-}
-
-int yolo_conv3x3_wgrad_plan(int h, int w, int batch, int cin, int cout, int x_dtype, struct yolo_conv3x3_wgrad_plan *out) {
-    std::string err;
-    const int rc = wgrad3x3_plan(h, w, batch, cin, cout, x_dtype, out, err);
-    return rc ? fail(rc, "yolo_conv3x3_wgrad_plan: " + err) : YOLO_OK;
-}
-
-static int run_wgrad3x3(const void *x, int x_dtype, int ld, int coff, long long image_stride, int h, int w, int batch, int cin, const float *d, int cout,
-                        const float *scale, float *dw, float *db, void *scratch, const struct yolo_conv3x3_wgrad_plan &pl, hipStream_t s) {
-    Wgrad3x3Params p;
-    memset(&p, 0, sizeof p);
-    p.x = x; p.d = d; p.scale = scale; p.slab = static_cast<float *>(scratch); p.dw = dw; p.db = db;
-    p.P = h * w * batch; p.cin = cin; p.cout = cout; p.ld = ld; p.coff = coff; p.h = h; p.w = w; p.ppi = h * w; p.img_stride = image_stride;
-    p.ppc = pl.positions_per_chunk; p.n_chunks = pl.n_chunks; p.tiles_cout = pl.tiles_cout; p.tiles_cin = pl.tiles_cin; p.halo_rows = pl.halo_rows;
-    p.slab_stride = cout * (9 * cin + 1);
-    HIP_TRY(launch_conv3x3_wgrad(p, x_dtype, s));
-    return YOLO_OK;
-}
-
-int yolo_conv3x3_wgrad(const void *x_dev, int x_dtype, int ld, int coff, int64_t image_stride, int h, int w, int batch, int cin,
-                       const float *d_dev, int cout, const float *scale_dev, float *dw_dev, float *db_dev, void *scratch_dev,
-                       size_t scratch_bytes, void *stream) {
-    std::string err;
-    struct yolo_conv3x3_wgrad_plan pl;
-    const int rc = wgrad3x3_check(x_dev, x_dtype, ld, coff, image_stride, h, w, batch, cin, d_dev, cout, scale_dev, dw_dev, db_dev, scratch_dev,
-                                  scratch_bytes, &pl, err);
-    if (rc) return fail(rc, "yolo_conv3x3_wgrad: " + err);
-    return run_wgrad3x3(x_dev, x_dtype, ld, coff, image_stride, h, w, batch, cin, d_dev, cout, scale_dev, dw_dev, db_dev, scratch_dev, pl,
-                        static_cast<hipStream_t>(stream));
-}
-
-// ---- the weight gradient of the YOLOv3 head convs (yolo_hip.h: added within ABI 7; kernels in train3.hip, split and checks in train3_host.cpp)
-int yolo_v3_head_wgrad_plan(const yolo_head_desc *head, const int32_t *cin, int batch, int x_dtype, struct yolo_v3_wgrad_plan *out) {
-    std::string err;
-    Wgrad3Geometry geo;
-    const int rc = wgrad3_plan(head, cin, batch, x_dtype, out, &geo, err);
-    return rc ? fail(rc, "yolo_v3_head_wgrad_plan: " + err) : YOLO_OK;
-}
-
-static int run_wgrad3(const Wgrad3Geometry &geo, const struct yolo_v3_wgrad_plan &pl, int batch, const float *g, const int32_t *assign, int max_gt,
-                      void *scratch, hipStream_t s) {
-    Wgrad3Params p;
-    memset(&p, 0, sizeof p);
-    static_cast<Wgrad3Geometry &>(p) = geo;
-    p.g = g; p.assign = assign; p.batch = batch; p.max_gt = max_gt;
-    p.slot = reinterpret_cast<int *>(static_cast<unsigned char *>(scratch) + pl.slot_offset);
-    HIP_TRY(launch_head3_wgrad(p, s));
-    return YOLO_OK;
-}
-
-int yolo_v3_head_wgrad(const yolo_head_desc *head, const struct yolo_v3_wgrad_view *views, int batch, const float *g_dev,
-                       const int32_t *assign_dev, int max_gt, float *const *dw_dev, float *const *db_dev, void *scratch_dev,
-                       size_t scratch_bytes, void *stream) {
-    std::string err;
-    struct yolo_v3_wgrad_plan pl;
-    Wgrad3Geometry geo;
-    const int rc = wgrad3_check(head, views, batch, g_dev, assign_dev, max_gt, dw_dev, db_dev, scratch_dev, scratch_bytes, &pl, &geo, err);
-    if (rc) return fail(rc, "yolo_v3_head_wgrad: " + err);
-    return run_wgrad3(geo, pl, batch, g_dev, assign_dev, max_gt, scratch_dev, static_cast<hipStream_t>(stream));
-}
-
 // ---- training augmentation (augment_host.cpp: checks, records, truths; augment.hip: the kernel)
 int yolo_augment_check(const yolo_augment_image *params, int h, int w) {
     std::string err;
@@ -981,738 +858,6 @@ int yolo_augment_tile(int32_t *rows, int32_t *cols, int32_t *images_per_launch) 
     if (cols) *cols = kAugTileCols;
     if (images_per_launch) *images_per_launch = kAugPerLaunch;
     return YOLO_OK;
-}
-
-// The detection layer of a net: the last kernel of the plan, if it is the 1 x 1 / stride 1 linear conv with bias that writes the logits
-// from a tensor of the workspace (plan.cpp; net/v2.py:52-56).  The message says what is in the way.
-static int head_conv(const yolo_net *net, const Kernel **out, const char *who) {
-    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    if (net->kernels.empty()) return fail(YOLO_ERR_ARG, std::string(who) + ": the plan has no kernels");
-    const Kernel &k = net->kernels.back();
-    if (k.kind != K_CONV || k.ksize != 1 || k.stride != 1 || k.leaky || k.batch_norm || k.out.buf != BUF_USER_OUT || !k.out.f32 || k.has_res || k.outmode != OUT_NORMAL)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": the last kernel of the plan must be the detection layer, a 1 x 1 / stride 1 linear conv with "
-                                                     "bias and no batch norm that writes the logits (the YOLOv2 networks; v3 heads are not trained)");
-    if (k.stem || k.fuse2_prev || k.mx || k.in.buf < 0 || k.in.f32 || k.in.base)
-        return fail(YOLO_ERR_STATE, std::string(who) + ": the plan has fused the detection layer's input away");
-    if (k.cin % 8 || k.cin_s != k.cin) return fail(YOLO_ERR_ARG, std::string(who) + ": the detection layer's input channels must be a multiple of 8");
-    if (net->parts != 1)
-        return fail(YOLO_ERR_STATE, std::string(who) + ": this net runs a batch as " + std::to_string(net->parts) +
-                                        " stream parts, each in its own arena; call yolo_net_set_streams(net, 1)");
-    *out = &k;
-    return YOLO_OK;
-}
-
-int yolo_net_head_input(const yolo_net *net, yolo_tensor_view *out) {
-    const Kernel *k = nullptr;
-    int rc = head_conv(net, &k, "yolo_net_head_input");
-    if (rc) return rc;
-    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_head_input: null argument");
-    memset(out, 0, sizeof *out);
-    out->offset = net->buffers[k->in.buf].offset;
-    out->image_stride = k->in.img_stride;
-    out->ld = k->in.ld; out->coff = k->in.coff;
-    out->dtype = net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32;
-    out->cin = k->cin; out->h = k->in.H; out->w = k->in.W;
-    return YOLO_OK;
-}
-
-static int head_train_layout(const yolo_net *net, const Kernel **kout, yolo_head_train_layout *L, struct yolo_wgrad_plan *pl, const char *who) {
-    const Kernel *k = nullptr;
-    int rc = head_conv(net, &k, who);
-    if (rc) return rc;
-    std::string err;
-    rc = check_head(&net->head, net->out_count, err);
-    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
-    if (net->head.version != 2 || net->head.n_scales != 1)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 2 with one scale (the reference has a loss for YOLOv2 only)");
-    const size_t mb = (size_t)net->opt.max_batch, hw = (size_t)k->in.H * k->in.W;
-    rc = wgrad_plan((long long)(mb * hw), k->cin, k->cout, net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32, pl, err);
-    if (rc) return fail(rc, std::string(who) + ": " + err);
-    const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
-    size_t off = 0;
-    auto part = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return (uint64_t)at; };
-    memset(L, 0, sizeof *L);
-    L->w_offset = part(nw); L->b_offset = part(nb);
-    L->m_w_offset = part(nw); L->v_w_offset = part(nw); L->m_b_offset = part(nb); L->v_b_offset = part(nb);
-    L->dw_offset = part(nw); L->db_offset = part(nb);
-    L->grad_offset = part(mb * net->out_count * 4);
-    L->assign_offset = part(mb * hw * 4);
-    L->images_offset = part(mb * sizeof(yolo_loss_image));
-    // a smaller batch never needs more chunks than the full one at the same tile counts, but its chunks may be laid out otherwise:
-    // the scratch is sized for the largest split of any batch up to max_batch
-    uint64_t need = pl->scratch_bytes;
-    for (size_t b = 1; b < mb; ++b) {
-        struct yolo_wgrad_plan q;
-        if (wgrad_plan((long long)(b * hw), k->cin, k->cout, YOLO_DTYPE_F32, &q, err) == YOLO_OK && q.scratch_bytes > need) need = q.scratch_bytes;
-    }
-    L->scratch_bytes = need;
-    L->scratch_offset = part((size_t)need);
-    L->total_bytes = off;
-    L->cin = k->cin; L->cout = k->cout;
-    if (kout) *kout = k;
-    return YOLO_OK;
-}
-
-int yolo_net_head_train_layout(const yolo_net *net, yolo_head_train_layout *out) {
-    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_head_train_layout: null argument");
-    struct yolo_wgrad_plan pl;
-    return head_train_layout(net, nullptr, out, &pl, "yolo_net_head_train_layout");
-}
-
-size_t yolo_net_head_train_bytes(const yolo_net *net) {
-    yolo_head_train_layout L;
-    struct yolo_wgrad_plan pl;
-    if (head_train_layout(net, nullptr, &L, &pl, "yolo_net_head_train_bytes")) return 0;
-    return (size_t)L.total_bytes;
-}
-
-int yolo_net_head_train_init(yolo_net *net, void *state_dev, size_t bytes, const float *head_w_host, const float *head_b_host) {
-    const char *who = "yolo_net_head_train_init";
-    if (!net || !state_dev || !head_w_host || !head_b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_head_train_layout L;
-    struct yolo_wgrad_plan pl;
-    const Kernel *k = nullptr;
-    int rc = head_train_layout(net, &k, &L, &pl, who);
-    if (rc) return rc;
-    if (bytes < L.total_bytes) return fail(YOLO_ERR_ARG, std::string(who) + ": state too small (yolo_net_head_train_bytes)");
-    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
-    if (!net->weights_loaded || !net->dev_weights) return fail(YOLO_ERR_STATE, std::string(who) + ": weights not loaded");
-    unsigned char *st = static_cast<unsigned char *>(state_dev);
-    const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(st + L.w_offset, head_w_host, nw, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st + L.b_offset, head_b_host, nb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(st + L.m_w_offset, 0, (size_t)(L.dw_offset - L.m_w_offset)));       // the four moment arrays lie one behind the other
-    // the layer's packed form, as pack_weights (weights.cpp) writes a 1 x 1 conv without batch norm: row o at o * wrow bytes, bias as it is
-    const size_t wrow = (size_t)k->ktiles * 128;
-    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-    std::vector<unsigned char> rows((size_t)k->cout * wrow, 0);
-    for (int o = 0; o < k->cout; ++o)
-        for (int c = 0; c < k->cin; ++c) {
-            const float v = head_w_host[(size_t)o * k->cin + c];
-            if (f16) reinterpret_cast<_Float16 *>(rows.data() + (size_t)o * wrow)[c] = (_Float16)v;
-            else reinterpret_cast<float *>(rows.data() + (size_t)o * wrow)[c] = v;
-        }
-    HIP_TRY(hipMemcpy(net->dev_weights + k->w_off, rows.data(), rows.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(net->dev_weights + k->b_off, head_b_host, nb, hipMemcpyHostToDevice));
-    return YOLO_OK;
-}
-
-int yolo_net_head_train_read(yolo_net *net, const void *state_dev, float *w_host, float *b_host) {
-    const char *who = "yolo_net_head_train_read";
-    if (!net || !state_dev || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_head_train_layout L;
-    struct yolo_wgrad_plan pl;
-    const Kernel *k = nullptr;
-    int rc = head_train_layout(net, &k, &L, &pl, who);
-    if (rc) return rc;
-    const unsigned char *st = static_cast<const unsigned char *>(state_dev);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(w_host, st + L.w_offset, (size_t)k->cout * k->cin * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b_host, st + L.b_offset, (size_t)k->cout * 4, hipMemcpyDeviceToHost));
-    return YOLO_OK;
-}
-
-static int train_head_step_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                               void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream, const char *who) {
-    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_head_train_layout L;
-    struct yolo_wgrad_plan pl;
-    const Kernel *k = nullptr;
-    int rc = head_train_layout(net, &k, &L, &pl, who);
-    if (rc) return rc;
-    if (!state_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null state (yolo_net_head_train_init)");
-    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
-    unsigned char *st = static_cast<unsigned char *>(state_dev);
-    yolo_loss_image *images = reinterpret_cast<yolo_loss_image *>(st + L.images_offset);
-    rc = check_loss_args(&net->head, gt_dev, gt_counts_dev, max_gt, images, result_dev, who);
-    if (rc) return rc;
-    if (batch < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": batch must be at least 1");
-    rc = check_ready(net, in_dev.ptr, batch, who);
-    if (rc) return rc;
-    if (!(lr_t == lr_t)) return fail(YOLO_ERR_ARG, std::string(who) + ": lr_t is NaN");
-    const int ppi = k->in.H * k->in.W;
-    const int x_dtype = net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32;
-    std::string err;
-    rc = wgrad_plan((long long)ppi * batch, k->cin, k->cout, x_dtype, &pl, err);
-    if (rc || pl.scratch_bytes > L.scratch_bytes) return fail(YOLO_ERR_ARG, std::string(who) + ": " + (rc ? err : std::string("weight-gradient scratch too small")));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
-    float *grad = reinterpret_cast<float *>(st + L.grad_offset);
-    float *dw = reinterpret_cast<float *>(st + L.dw_offset), *db = reinterpret_cast<float *>(st + L.db_offset);
-    rc = run_forward(net, in_dev, batch, logits, s);        // dense: obj_min_logit is -inf outside detect_any
-    if (rc) return rc;
-    rc = run_loss_grad(net->head, logits, batch, gt_dev, gt_counts_dev, max_gt, images, reinterpret_cast<int32_t *>(st + L.assign_offset), result_dev, grad, s);
-    if (rc) return rc;
-    rc = run_wgrad(net->dev_ws + net->buffers[k->in.buf].offset, x_dtype, k->in.ld, k->in.coff, k->in.img_stride, ppi, batch, k->cin, grad, k->cout,
-                   dw, db, st + L.scratch_offset, pl, s);
-    if (rc) return rc;
-    AdamParams p;
-    memset(&p, 0, sizeof p);
-    p.w = reinterpret_cast<float *>(st + L.w_offset); p.b = reinterpret_cast<float *>(st + L.b_offset);
-    p.m_w = reinterpret_cast<float *>(st + L.m_w_offset); p.v_w = reinterpret_cast<float *>(st + L.v_w_offset);
-    p.m_b = reinterpret_cast<float *>(st + L.m_b_offset); p.v_b = reinterpret_cast<float *>(st + L.v_b_offset);
-    p.dw = dw; p.db = db; p.n_w = (long long)k->cout * k->cin; p.n_b = k->cout;
-    p.lr_t = lr_t; p.beta1 = 0.9f; p.beta2 = 0.999f; p.eps = 1e-8f;        // tf.train.AdamOptimizer's defaults (net/v2.py:205)
-    p.pack_w = net->dev_weights + k->w_off; p.pack_b = reinterpret_cast<float *>(net->dev_weights + k->b_off);
-    p.pack_cin = k->cin; p.pack_f16 = x_dtype == YOLO_DTYPE_F16;
-    p.pack_row = (int)((size_t)k->ktiles * 128 / (p.pack_f16 ? 2 : 4));
-    HIP_TRY(launch_adam_step(p, s));
-    return YOLO_OK;
-}
-int yolo_net_train_head_step(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                             void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
-    return train_head_step_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, state_dev, lr_t, result_dev, stream, "yolo_net_train_head_step");
-}
-int yolo_net_train_head_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                                void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
-    return train_head_step_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, state_dev, lr_t, result_dev, stream, "yolo_net_train_head_step_u8");
-}
-
-// ---- training the tail of a YOLOv2 net (yolo_hip.h: added within ABI 7; kernels in train.hip and train_tail.hip) ---------------------------
-// The block behind the detection layer: the one kernel that writes the detection layer's input, if it is a 3 x 3 / stride 1 conv with batch
-// norm and leaky ReLU that the plan runs on its own, from a tensor of the workspace that is still intact behind the last kernel of the
-// pass.  The message says what is in the way.
-static int tail_convs(const yolo_net *net, const Kernel **block, const Kernel **head, const char *who) {
-    const Kernel *k = nullptr;
-    int rc = head_conv(net, &k, who);
-    if (rc) return rc;
-    const std::vector<Kernel> &K = net->kernels;
-    const int last = (int)K.size() - 1;
-    if (k->out.base || (size_t)k->cout * k->in.H * k->in.W != net->out_count)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": the last kernel writes one scale of several: a v3 network has no tail of this kind (its detection convs are "
-                                                     "trained with yolo_net_train_head_step_v3, train_layers = heads)");
-    int bi = -1, writers = 0;
-    for (int j = 0; j < last; ++j)
-        for (const View *v : {&K[j].out, &K[j].out2, &K[j].out3})
-            if (v->buf == k->in.buf) { bi = j; ++writers; }
-    const std::string at = std::string(who) + ": ";
-    if (writers != 1)
-        return fail(YOLO_ERR_ARG, at + "the detection layer's input is written by " + std::to_string(writers) + " kernels (a concatenation or the network input): "
-                                       "there is no single 3 x 3 block behind the detection layer");
-    const Kernel &b = K[bi];
-    if (b.kind != K_CONV || b.out.buf != k->in.buf)
-        return fail(YOLO_ERR_ARG, at + "the detection layer's input is not written by a conv (kernel " + std::to_string(bi) + ")");
-    if (b.ksize != 3 || b.stride != 1) return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer must be 3 x 3 / stride 1 (1 x 1 and stride-2 blocks are not trained)");
-    if (!b.batch_norm || !b.leaky) return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer must have batch norm and a leaky ReLU");
-    if (b.has_res) return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer carries a residual (a shortcut is fused into it): its output is not the block's alone");
-    if (b.mx) return fail(YOLO_ERR_STATE, at + "the plan runs the conv behind the detection layer as an MXFP8 conv: its packed weights are block-scaled fp8 (use an fp16 or fp32 plan)");
-    if (b.outmode != OUT_NORMAL) return fail(YOLO_ERR_STATE, at + "the plan has fused a pool, reorg or upsample into the conv behind the detection layer");
-    if (b.stem != STEM_NONE || b.fuse2_next || b.fuse2_prev) return fail(YOLO_ERR_STATE, at + "the plan has fused the conv behind the detection layer with a neighbour");
-    if (b.out.coff != k->in.coff || b.out.ld != k->in.ld || b.out.img_stride != k->in.img_stride || b.out.base != k->in.base || b.cout != k->cin ||
-        b.out.H != k->in.H || b.out.W != k->in.W || b.out.f32)
-        return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer does not write exactly the detection layer's input");
-    if (b.in.buf < 0 || b.in.f32 || b.in.base) return fail(YOLO_ERR_STATE, at + "the input of the conv behind the detection layer is not a tensor of the workspace");
-    if (b.cin % 8 || b.cin_s != b.cin) return fail(YOLO_ERR_ARG, at + "the input channels of the conv behind the detection layer must be a multiple of 8");
-    if (b.in.W > kTailMaxW) return fail(YOLO_ERR_ARG, at + "the feature map of the conv behind the detection layer is wider than " + std::to_string(kTailMaxW));
-    // intact behind the last kernel: nothing behind the block writes its input's buffer, and no buffer alive later shares its bytes
-    const Buffer &bb = net->buffers[b.in.buf];
-    for (int j = bi; j <= last; ++j)
-        for (const View *v : {&K[j].out, &K[j].out2, &K[j].out3})
-            if (v->buf == b.in.buf)
-                return fail(YOLO_ERR_STATE, at + "the plan reuses the block's input: kernel " + std::to_string(j) + " writes its buffer");
-    for (size_t q = 0; q < net->buffers.size(); ++q) {
-        const Buffer &o = net->buffers[q];
-        if ((int)q == b.in.buf || o.last < 0 || !o.bytes || !bb.bytes) continue;
-        const bool shares = o.offset < bb.offset + bb.bytes && bb.offset < o.offset + o.bytes;
-        if (shares && o.last >= bb.first)
-            return fail(YOLO_ERR_STATE, at + "the plan reuses the block's input: buffer " + std::to_string(q) + " shares its bytes and is alive behind it");
-    }
-    *block = &b;
-    *head = k;
-    return YOLO_OK;
-}
-
-static void fill_view(const yolo_net *net, const Kernel *k, yolo_tensor_view *out) {
-    memset(out, 0, sizeof *out);
-    out->offset = net->buffers[k->in.buf].offset;
-    out->image_stride = k->in.img_stride;
-    out->ld = k->in.ld; out->coff = k->in.coff;
-    out->dtype = net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32;
-    out->cin = k->cin; out->h = k->in.H; out->w = k->in.W;
-}
-
-int yolo_net_tail_inputs(const yolo_net *net, yolo_tensor_view *block_in, yolo_tensor_view *head_in) {
-    const Kernel *b = nullptr, *k = nullptr;
-    int rc = tail_convs(net, &b, &k, "yolo_net_tail_inputs");
-    if (rc) return rc;
-    if (!block_in || !head_in) return fail(YOLO_ERR_ARG, "yolo_net_tail_inputs: null argument");
-    fill_view(net, b, block_in);
-    fill_view(net, k, head_in);
-    return YOLO_OK;
-}
-
-static int tail_train_layout(const yolo_net *net, const Kernel **bout, const Kernel **kout, yolo_tail_train_layout *L, const char *who) {
-    const Kernel *b = nullptr, *k = nullptr;
-    int rc = tail_convs(net, &b, &k, who);
-    if (rc) return rc;
-    std::string err;
-    rc = check_head(&net->head, net->out_count, err);
-    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
-    if (net->head.version != 2 || net->head.n_scales != 1)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 2 with one scale (the reference has a loss for YOLOv2 only)");
-    const size_t mb = (size_t)net->opt.max_batch, hw = (size_t)k->in.H * k->in.W;
-    const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
-    const size_t nw3 = (size_t)b->cout * 9 * b->cin * 4, nb3 = (size_t)b->cout * 4;
-    size_t off = 0;
-    auto part = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return (uint64_t)at; };
-    memset(L, 0, sizeof *L);
-    L->w_offset = part(nw); L->b_offset = part(nb);
-    L->m_w_offset = part(nw); L->v_w_offset = part(nw); L->m_b_offset = part(nb); L->v_b_offset = part(nb);
-    L->dw_offset = part(nw); L->db_offset = part(nb);
-    L->w3_offset = part(nw3); L->beta_offset = part(nb3);
-    L->m_w3_offset = part(nw3); L->v_w3_offset = part(nw3); L->m_beta_offset = part(nb3); L->v_beta_offset = part(nb3);
-    L->dw3_offset = part(nw3); L->dbeta_offset = part(nb3);
-    L->scale64_offset = part((size_t)b->cout * 8); L->scale32_offset = part(nb3); L->mean_offset = part(nb3);
-    L->d_offset = part(mb * hw * (size_t)b->cout * 4);
-    L->grad_offset = part(mb * net->out_count * 4);
-    L->assign_offset = part(mb * hw * 4);
-    L->images_offset = part(mb * sizeof(yolo_loss_image));
-    // one scratch for both weight gradients, which run one after the other: the largest split of either, of any batch up to max_batch
-    uint64_t need = 0;
-    for (size_t n = 1; n <= mb; ++n) {
-        struct yolo_wgrad_plan q;
-        struct yolo_conv3x3_wgrad_plan q3;
-        rc = wgrad_plan((long long)(n * hw), k->cin, k->cout, YOLO_DTYPE_F32, &q, err);
-        if (!rc) rc = wgrad3x3_plan(b->in.H, b->in.W, (int)n, b->cin, b->cout, YOLO_DTYPE_F32, &q3, err);
-        if (rc) return fail(rc, std::string(who) + ": " + err);
-        if (q.scratch_bytes > need) need = q.scratch_bytes;
-        if (q3.scratch_bytes > need) need = q3.scratch_bytes;
-    }
-    L->scratch_bytes = need;
-    L->scratch_offset = part((size_t)need);
-    L->total_bytes = off;
-    L->block_src = b->w_src; L->head_src = k->w_src;
-    L->cin = k->cin; L->cout = k->cout; L->cin3 = b->cin; L->cout3 = b->cout;
-    if (bout) *bout = b;
-    if (kout) *kout = k;
-    return YOLO_OK;
-}
-
-int yolo_net_tail_train_layout(const yolo_net *net, yolo_tail_train_layout *out) {
-    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_tail_train_layout: null argument");
-    return tail_train_layout(net, nullptr, nullptr, out, "yolo_net_tail_train_layout");
-}
-
-size_t yolo_net_tail_train_bytes(const yolo_net *net) {
-    yolo_tail_train_layout L;
-    if (tail_train_layout(net, nullptr, nullptr, &L, "yolo_net_tail_train_bytes")) return 0;
-    return (size_t)L.total_bytes;
-}
-
-int yolo_net_tail_train_init(yolo_net *net, void *state_dev, size_t bytes, const float *block_host, const float *head_w_host,
-                             const float *head_b_host) {
-    const char *who = "yolo_net_tail_train_init";
-    if (!net || !state_dev || !block_host || !head_w_host || !head_b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_tail_train_layout L;
-    const Kernel *b = nullptr, *k = nullptr;
-    int rc = tail_train_layout(net, &b, &k, &L, who);
-    if (rc) return rc;
-    if (bytes < L.total_bytes) return fail(YOLO_ERR_ARG, std::string(who) + ": state too small (yolo_net_tail_train_bytes)");
-    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
-    if (!net->weights_loaded || !net->dev_weights) return fail(YOLO_ERR_STATE, std::string(who) + ": weights not loaded");
-    unsigned char *st = static_cast<unsigned char *>(state_dev);
-    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-    const int c3 = b->cout, ci3 = b->cin;
-    const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4, nb3 = (size_t)c3 * 4;
-    // the block: beta, gamma, mean, var, kernel[out][in][kh][kw] (net/layers.py:53-63); the fold as weights.cpp: fold_batch_norm
-    const float *beta = block_host, *gamma = block_host + c3, *mean = block_host + 2 * (size_t)c3, *var = block_host + 3 * (size_t)c3;
-    const float *kern = block_host + 4 * (size_t)c3;
-    std::vector<double> scale64((size_t)c3);
-    std::vector<float> scale32((size_t)c3), bfold((size_t)c3), w3((size_t)c3 * 9 * ci3);
-    for (int o = 0; o < c3; ++o) {
-        scale64[o] = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-        scale32[o] = (float)scale64[o];
-        bfold[o] = (float)((double)beta[o] - (double)mean[o] * scale64[o]);
-    }
-    const size_t wrow3 = (size_t)b->ktiles * 128;
-    std::vector<unsigned char> rows3((size_t)c3 * wrow3, 0);
-    for (int o = 0; o < c3; ++o)
-        for (int t = 0; t < 9; ++t)
-            for (int c = 0; c < ci3; ++c) {
-                const float w = kern[((size_t)o * ci3 + c) * 9 + t];
-                w3[((size_t)o * 9 + t) * ci3 + c] = w;
-                // (fp16: one rounding from the float64 product, which is what pack_weights' (_Float16)(float) compiles to on the host)
-                const double v = (double)w * scale64[o];
-                const size_t e = (size_t)t * b->cin_s + c;
-                if (f16) reinterpret_cast<_Float16 *>(rows3.data() + (size_t)o * wrow3)[e] = (_Float16)v;
-                else reinterpret_cast<float *>(rows3.data() + (size_t)o * wrow3)[e] = (float)v;
-            }
-    if (rows3.size() > b->w_bytes) return fail(YOLO_ERR_PLAN, std::string(who) + ": the block's packed rows do not fit its weight region");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(st + L.w_offset, head_w_host, nw, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st + L.b_offset, head_b_host, nb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(st + L.m_w_offset, 0, (size_t)(L.dw_offset - L.m_w_offset)));       // the four moment arrays lie one behind the other
-    HIP_TRY(hipMemcpy(st + L.w3_offset, w3.data(), w3.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st + L.beta_offset, beta, nb3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(st + L.m_w3_offset, 0, (size_t)(L.dw3_offset - L.m_w3_offset)));
-    HIP_TRY(hipMemcpy(st + L.scale64_offset, scale64.data(), (size_t)c3 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st + L.scale32_offset, scale32.data(), nb3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st + L.mean_offset, mean, nb3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(net->dev_weights + b->w_off, rows3.data(), rows3.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(net->dev_weights + b->b_off, bfold.data(), nb3, hipMemcpyHostToDevice));
-    // the head's packed form, as yolo_net_head_train_init writes it
-    const size_t wrow = (size_t)k->ktiles * 128;
-    std::vector<unsigned char> rows((size_t)k->cout * wrow, 0);
-    for (int o = 0; o < k->cout; ++o)
-        for (int c = 0; c < k->cin; ++c) {
-            const float v = head_w_host[(size_t)o * k->cin + c];
-            if (f16) reinterpret_cast<_Float16 *>(rows.data() + (size_t)o * wrow)[c] = (_Float16)v;
-            else reinterpret_cast<float *>(rows.data() + (size_t)o * wrow)[c] = v;
-        }
-    HIP_TRY(hipMemcpy(net->dev_weights + k->w_off, rows.data(), rows.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(net->dev_weights + k->b_off, head_b_host, nb, hipMemcpyHostToDevice));
-    return YOLO_OK;
-}
-
-int yolo_net_tail_train_read(yolo_net *net, const void *state_dev, float *block_kernel_host, float *beta_host, float *w_host, float *b_host) {
-    const char *who = "yolo_net_tail_train_read";
-    if (!net || !state_dev || !block_kernel_host || !beta_host || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_tail_train_layout L;
-    const Kernel *b = nullptr, *k = nullptr;
-    int rc = tail_train_layout(net, &b, &k, &L, who);
-    if (rc) return rc;
-    const unsigned char *st = static_cast<const unsigned char *>(state_dev);
-    std::vector<float> w3((size_t)b->cout * 9 * b->cin);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(w3.data(), st + L.w3_offset, w3.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(beta_host, st + L.beta_offset, (size_t)b->cout * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(w_host, st + L.w_offset, (size_t)k->cout * k->cin * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b_host, st + L.b_offset, (size_t)k->cout * 4, hipMemcpyDeviceToHost));
-    for (int o = 0; o < b->cout; ++o)
-        for (int t = 0; t < 9; ++t)
-            for (int c = 0; c < b->cin; ++c) block_kernel_host[((size_t)o * b->cin + c) * 9 + t] = w3[((size_t)o * 9 + t) * b->cin + c];
-    return YOLO_OK;
-}
-
-static int train_tail_step_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                               void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream, const char *who) {
-    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_tail_train_layout L;
-    const Kernel *b = nullptr, *k = nullptr;
-    int rc = tail_train_layout(net, &b, &k, &L, who);
-    if (rc) return rc;
-    if (!state_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null state (yolo_net_tail_train_init)");
-    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
-    unsigned char *st = static_cast<unsigned char *>(state_dev);
-    yolo_loss_image *images = reinterpret_cast<yolo_loss_image *>(st + L.images_offset);
-    rc = check_loss_args(&net->head, gt_dev, gt_counts_dev, max_gt, images, result_dev, who);
-    if (rc) return rc;
-    if (batch < 1) return fail(YOLO_ERR_ARG, std::string(who) + ": batch must be at least 1");
-    rc = check_ready(net, in_dev.ptr, batch, who);
-    if (rc) return rc;
-    if (!(lr_t == lr_t)) return fail(YOLO_ERR_ARG, std::string(who) + ": lr_t is NaN");
-    const int ppi = k->in.H * k->in.W;
-    const int x_dtype = net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32;
-    auto f32 = [&](uint64_t o) { return reinterpret_cast<float *>(st + o); };
-    float *grad = f32(L.grad_offset), *d = f32(L.d_offset);
-    const void *y = net->dev_ws + net->buffers[k->in.buf].offset, *x3 = net->dev_ws + net->buffers[b->in.buf].offset;
-    std::string err;
-    struct yolo_wgrad_plan pl;
-    struct yolo_conv3x3_wgrad_plan pl3;
-    long long tiles = 0;
-    rc = wgrad_check(y, x_dtype, k->in.ld, k->in.coff, k->in.img_stride, ppi, batch, k->cin, grad, k->cout, f32(L.dw_offset), f32(L.db_offset),
-                     st + L.scratch_offset, (size_t)L.scratch_bytes, &pl, err);
-    if (!rc) rc = dgrad_check(grad, k->cout, f32(L.w_offset), k->cin, y, x_dtype, k->in.ld, k->in.coff, k->in.img_stride, ppi, batch, 0.1f, d, &tiles, err);
-    if (!rc) rc = wgrad3x3_check(x3, x_dtype, b->in.ld, b->in.coff, b->in.img_stride, b->in.H, b->in.W, batch, b->cin, d, b->cout, f32(L.scale32_offset),
-                                 f32(L.dw3_offset), f32(L.dbeta_offset), st + L.scratch_offset, (size_t)L.scratch_bytes, &pl3, err);
-    if (rc) return fail(rc, std::string(who) + ": " + err);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
-    rc = run_forward(net, in_dev, batch, logits, s);        // dense: obj_min_logit is -inf outside detect_any
-    if (rc) return rc;
-    rc = run_loss_grad(net->head, logits, batch, gt_dev, gt_counts_dev, max_gt, images, reinterpret_cast<int32_t *>(st + L.assign_offset), result_dev, grad, s);
-    if (rc) return rc;
-    rc = run_wgrad(y, x_dtype, k->in.ld, k->in.coff, k->in.img_stride, ppi, batch, k->cin, grad, k->cout, f32(L.dw_offset), f32(L.db_offset),
-                   st + L.scratch_offset, pl, s);
-    if (rc) return rc;
-    // the data gradient from the head's master kernel BEFORE its update, through the leaky ReLU's derivative at the stored Y
-    rc = run_dgrad(grad, k->cout, f32(L.w_offset), k->cin, y, x_dtype, k->in.ld, k->in.coff, k->in.img_stride, ppi, batch, 0.1f, d, tiles, s);
-    if (rc) return rc;
-    rc = run_wgrad3x3(x3, x_dtype, b->in.ld, b->in.coff, b->in.img_stride, b->in.H, b->in.W, batch, b->cin, d, b->cout, f32(L.scale32_offset),
-                      f32(L.dw3_offset), f32(L.dbeta_offset), st + L.scratch_offset, pl3, s);
-    if (rc) return rc;
-    AdamParams p;
-    memset(&p, 0, sizeof p);
-    p.w = f32(L.w_offset); p.b = f32(L.b_offset); p.m_w = f32(L.m_w_offset); p.v_w = f32(L.v_w_offset); p.m_b = f32(L.m_b_offset); p.v_b = f32(L.v_b_offset);
-    p.dw = f32(L.dw_offset); p.db = f32(L.db_offset); p.n_w = (long long)k->cout * k->cin; p.n_b = k->cout;
-    p.lr_t = lr_t; p.beta1 = 0.9f; p.beta2 = 0.999f; p.eps = 1e-8f;        // tf.train.AdamOptimizer's defaults (net/v2.py:205)
-    p.pack_w = net->dev_weights + k->w_off; p.pack_b = reinterpret_cast<float *>(net->dev_weights + k->b_off);
-    p.pack_cin = k->cin; p.pack_f16 = x_dtype == YOLO_DTYPE_F16;
-    p.pack_row = (int)((size_t)k->ktiles * 128 / (p.pack_f16 ? 2 : 4));
-    HIP_TRY(launch_adam_step(p, s));
-    TailAdamParams q;
-    memset(&q, 0, sizeof q);
-    q.a = p;
-    q.a.w = f32(L.w3_offset); q.a.b = f32(L.beta_offset); q.a.m_w = f32(L.m_w3_offset); q.a.v_w = f32(L.v_w3_offset);
-    q.a.m_b = f32(L.m_beta_offset); q.a.v_b = f32(L.v_beta_offset); q.a.dw = f32(L.dw3_offset); q.a.db = f32(L.dbeta_offset);
-    q.a.n_w = (long long)b->cout * 9 * b->cin; q.a.n_b = b->cout;
-    q.a.pack_w = net->dev_weights + b->w_off; q.a.pack_b = reinterpret_cast<float *>(net->dev_weights + b->b_off);
-    q.a.pack_cin = 9 * b->cin;                              // (cin_s == cin: element t * cin + c of a master row is element t * cin_s + c of the packed row)
-    q.a.pack_row = (int)((size_t)b->ktiles * 128 / (p.pack_f16 ? 2 : 4));
-    q.scale64 = reinterpret_cast<const double *>(st + L.scale64_offset); q.mean = f32(L.mean_offset);
-    HIP_TRY(launch_tail_adam(q, s));
-    return YOLO_OK;
-}
-int yolo_net_train_tail_step(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                             void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
-    return train_tail_step_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, state_dev, lr_t, result_dev, stream, "yolo_net_train_tail_step");
-}
-int yolo_net_train_tail_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                                void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
-    return train_tail_step_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, state_dev, lr_t, result_dev, stream, "yolo_net_train_tail_step_u8");
-}
-
-// ---- training the YOLOv3 head convs on a net (yolo_hip.h: added within ABI 7) -------------------------------------------------------------
-// The head convs of a version 3 net in head order, each the 1 x 1 / stride 1 linear conv with bias that writes its scale of the logits from
-// a tensor of the workspace that is still intact behind the last kernel of the pass.  The message says what is in the way.
-static int head_convs_v3(const yolo_net *net, const Kernel *out[YOLO_MAX_SCALES], const char *who) {
-    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    std::string err;
-    int rc = check_head(&net->head, net->out_count, err);
-    if (rc) return fail(YOLO_ERR_STATE, std::string(who) + ": head geometry not set (" + err + "); call yolo_net_set_head");
-    if (net->head.version != 3)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": the head must be version 3 (yolo_net_train_head_step trains the detection layer of a YOLOv2 network)");
-    const std::vector<Kernel> &K = net->kernels;
-    std::vector<int> heads;
-    for (int i = 0; i < (int)K.size(); ++i)
-        if (K[i].kind == K_CONV && K[i].head) heads.push_back(i);
-    std::sort(heads.begin(), heads.end(), [&](int a, int b) { return K[a].out.base < K[b].out.base; });       // head order = the order of the rows
-    if ((int)heads.size() != net->head.n_scales)
-        return fail(YOLO_ERR_ARG, std::string(who) + ": the plan has " + std::to_string(heads.size()) + " head convs for " + std::to_string(net->head.n_scales) + " scales");
-    const int width = 5 + net->head.n_classes;
-    for (int s = 0; s < net->head.n_scales; ++s) {
-        const int ki = heads[s];
-        const Kernel &k = K[ki];
-        const std::string at = std::string(who) + ": scale " + std::to_string(s) + ": ";
-        if (k.ksize != 1 || k.stride != 1 || k.leaky || k.batch_norm || k.out.buf != BUF_USER_OUT || !k.out.f32 || k.has_res || k.outmode != OUT_NORMAL ||
-            k.cout != net->head.n_anchors[s] * width || k.in.H != net->head.h[s] || k.in.W != net->head.w[s])
-            return fail(YOLO_ERR_ARG, at + "the head conv must be a 1 x 1 / stride 1 linear conv with bias and no batch norm that writes this scale of the logits");
-        if (k.stem || k.fuse2_prev || k.mx || k.in.buf < 0 || k.in.f32 || k.in.base)
-            return fail(YOLO_ERR_STATE, at + "the plan has fused the head conv's input away");
-        if (k.cin % 8 || k.cin_s != k.cin) return fail(YOLO_ERR_ARG, at + "the head conv's input channels must be a multiple of 8");
-        // intact behind the last kernel: nothing behind the head conv writes its input's buffer, and no buffer alive later shares its bytes
-        const Buffer &b = net->buffers[k.in.buf];
-        for (int j = ki + 1; j < (int)K.size(); ++j)
-            for (const View *v : {&K[j].out, &K[j].out2, &K[j].out3})
-                if (v->buf == k.in.buf)
-                    return fail(YOLO_ERR_STATE, at + "the plan reuses the head conv's input: kernel " + std::to_string(j) + " writes its buffer behind the head conv");
-        for (size_t q = 0; q < net->buffers.size(); ++q) {
-            const Buffer &o = net->buffers[q];
-            if ((int)q == k.in.buf || o.last < 0 || !o.bytes || !b.bytes) continue;
-            const bool shares = o.offset < b.offset + b.bytes && b.offset < o.offset + o.bytes;
-            if (shares && o.last >= b.first)
-                return fail(YOLO_ERR_STATE, at + "the plan reuses the head conv's input: buffer " + std::to_string(q) + " shares its bytes and is alive behind it");
-        }
-        out[s] = &k;
-    }
-    if (net->parts != 1)
-        return fail(YOLO_ERR_STATE, std::string(who) + ": this net runs a batch as " + std::to_string(net->parts) +
-                                        " stream parts, each in its own arena; call yolo_net_set_streams(net, 1)");
-    return YOLO_OK;
-}
-
-static int net_x_dtype(const yolo_net *net) { return net->opt.dtype == YOLO_DTYPE_F16 ? YOLO_DTYPE_F16 : YOLO_DTYPE_F32; }
-
-int yolo_net_head_inputs_v3(const yolo_net *net, yolo_tensor_view *out, int32_t *n) {
-    const Kernel *ks[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
-    int rc = head_convs_v3(net, ks, "yolo_net_head_inputs_v3");
-    if (rc) return rc;
-    if (!out || !n) return fail(YOLO_ERR_ARG, "yolo_net_head_inputs_v3: null argument");
-    *n = net->head.n_scales;
-    for (int s = 0; s < net->head.n_scales; ++s) {
-        const Kernel *k = ks[s];
-        memset(&out[s], 0, sizeof out[s]);
-        out[s].offset = net->buffers[k->in.buf].offset;
-        out[s].image_stride = k->in.img_stride;
-        out[s].ld = k->in.ld; out[s].coff = k->in.coff;
-        out[s].dtype = net_x_dtype(net);
-        out[s].cin = k->cin; out[s].h = k->in.H; out[s].w = k->in.W;
-    }
-    return YOLO_OK;
-}
-
-static int head_train_v3_layout(const yolo_net *net, const Kernel *ks[YOLO_MAX_SCALES], yolo_head_train_v3_layout *L, const char *who) {
-    int rc = head_convs_v3(net, ks, who);
-    if (rc) return rc;
-    std::string err;
-    Loss3Geometry lg;
-    rc = loss3_geometry(&net->head, &lg, err);
-    if (rc) return fail(rc, std::string(who) + ": " + err);
-    const size_t mb = (size_t)net->opt.max_batch;
-    size_t off = 0;
-    auto part = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return (uint64_t)at; };
-    memset(L, 0, sizeof *L);
-    L->n_scales = net->head.n_scales;
-    int32_t cin[YOLO_MAX_SCALES] = {0, 0, 0, 0};
-    for (int s = 0; s < L->n_scales; ++s) {
-        const Kernel *k = ks[s];
-        const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
-        L->cin[s] = cin[s] = k->cin; L->cout[s] = k->cout;
-        L->bias_src[s] = k->w_src;
-        L->w_offset[s] = part(nw); L->b_offset[s] = part(nb);
-        L->m_w_offset[s] = part(nw); L->v_w_offset[s] = part(nw); L->m_b_offset[s] = part(nb); L->v_b_offset[s] = part(nb);
-        L->dw_offset[s] = part(nw); L->db_offset[s] = part(nb);
-    }
-    L->grad_offset = part(mb * net->out_count * 4);
-    L->assign_offset = part(mb * (size_t)lg.rows * 4);
-    L->parts_offset = part(mb * (size_t)lg.parts * sizeof(yolo_loss_image));
-    L->images_offset = part(mb * sizeof(yolo_loss_image));
-    // the slabs of a smaller batch may be laid out otherwise: the scratch is sized for the largest split of any batch up to max_batch
-    uint64_t need = 0;
-    for (size_t b = 1; b <= mb; ++b) {
-        struct yolo_v3_wgrad_plan q;
-        Wgrad3Geometry g;
-        rc = wgrad3_plan(&net->head, cin, (int)b, YOLO_DTYPE_F32, &q, &g, err);
-        if (rc) return fail(rc, std::string(who) + ": " + err);
-        if (q.scratch_bytes > need) need = q.scratch_bytes;
-    }
-    L->scratch_bytes = need;
-    L->scratch_offset = part((size_t)need);
-    L->total_bytes = off;
-    return YOLO_OK;
-}
-
-int yolo_net_head_train_v3_layout(const yolo_net *net, yolo_head_train_v3_layout *out) {
-    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_head_train_v3_layout: null argument");
-    const Kernel *ks[YOLO_MAX_SCALES];
-    return head_train_v3_layout(net, ks, out, "yolo_net_head_train_v3_layout");
-}
-
-size_t yolo_net_head_train_v3_bytes(const yolo_net *net) {
-    yolo_head_train_v3_layout L;
-    const Kernel *ks[YOLO_MAX_SCALES];
-    if (head_train_v3_layout(net, ks, &L, "yolo_net_head_train_v3_bytes")) return 0;
-    return (size_t)L.total_bytes;
-}
-
-int yolo_net_head_train_v3_init(yolo_net *net, void *state_dev, size_t bytes, const float *const *w_host, const float *const *b_host) {
-    const char *who = "yolo_net_head_train_v3_init";
-    if (!net || !state_dev || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_head_train_v3_layout L;
-    const Kernel *ks[YOLO_MAX_SCALES];
-    int rc = head_train_v3_layout(net, ks, &L, who);
-    if (rc) return rc;
-    for (int s = 0; s < L.n_scales; ++s)
-        if (!w_host[s] || !b_host[s]) return fail(YOLO_ERR_ARG, std::string(who) + ": scale " + std::to_string(s) + ": null argument");
-    if (bytes < L.total_bytes) return fail(YOLO_ERR_ARG, std::string(who) + ": state too small (yolo_net_head_train_v3_bytes)");
-    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
-    if (!net->weights_loaded || !net->dev_weights) return fail(YOLO_ERR_STATE, std::string(who) + ": weights not loaded");
-    unsigned char *st = static_cast<unsigned char *>(state_dev);
-    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-    HIP_TRY(hipDeviceSynchronize());
-    for (int s = 0; s < L.n_scales; ++s) {
-        const Kernel *k = ks[s];
-        const size_t nw = (size_t)k->cout * k->cin * 4, nb = (size_t)k->cout * 4;
-        HIP_TRY(hipMemcpy(st + L.w_offset[s], w_host[s], nw, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(st + L.b_offset[s], b_host[s], nb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(st + L.m_w_offset[s], 0, nw));
-        HIP_TRY(hipMemset(st + L.v_w_offset[s], 0, nw));
-        HIP_TRY(hipMemset(st + L.m_b_offset[s], 0, nb));
-        HIP_TRY(hipMemset(st + L.v_b_offset[s], 0, nb));
-        // the conv's packed form, as pack_weights (weights.cpp) writes a 1 x 1 conv without batch norm: row o at o * wrow bytes, bias as it is
-        const size_t wrow = (size_t)k->ktiles * 128;
-        std::vector<unsigned char> rows((size_t)k->cout * wrow, 0);
-        for (int o = 0; o < k->cout; ++o)
-            for (int c = 0; c < k->cin; ++c) {
-                const float v = w_host[s][(size_t)o * k->cin + c];
-                if (f16) reinterpret_cast<_Float16 *>(rows.data() + (size_t)o * wrow)[c] = (_Float16)v;
-                else reinterpret_cast<float *>(rows.data() + (size_t)o * wrow)[c] = v;
-            }
-        HIP_TRY(hipMemcpy(net->dev_weights + k->w_off, rows.data(), rows.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(net->dev_weights + k->b_off, b_host[s], nb, hipMemcpyHostToDevice));
-    }
-    return YOLO_OK;
-}
-
-int yolo_net_head_train_v3_read(yolo_net *net, const void *state_dev, float *const *w_host, float *const *b_host) {
-    const char *who = "yolo_net_head_train_v3_read";
-    if (!net || !state_dev || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_head_train_v3_layout L;
-    const Kernel *ks[YOLO_MAX_SCALES];
-    int rc = head_train_v3_layout(net, ks, &L, who);
-    if (rc) return rc;
-    for (int s = 0; s < L.n_scales; ++s)
-        if (!w_host[s] || !b_host[s]) return fail(YOLO_ERR_ARG, std::string(who) + ": scale " + std::to_string(s) + ": null argument");
-    const unsigned char *st = static_cast<const unsigned char *>(state_dev);
-    HIP_TRY(hipDeviceSynchronize());
-    for (int s = 0; s < L.n_scales; ++s) {
-        HIP_TRY(hipMemcpy(w_host[s], st + L.w_offset[s], (size_t)L.cout[s] * L.cin[s] * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(b_host[s], st + L.b_offset[s], (size_t)L.cout[s] * 4, hipMemcpyDeviceToHost));
-    }
-    return YOLO_OK;
-}
-
-static int train_head_step_v3_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                                  double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream, const char *who) {
-    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
-    yolo_head_train_v3_layout L;
-    const Kernel *ks[YOLO_MAX_SCALES];
-    int rc = head_train_v3_layout(net, ks, &L, who);
-    if (rc) return rc;
-    if (!state_dev) return fail(YOLO_ERR_ARG, std::string(who) + ": null state (yolo_net_head_train_v3_init)");
-    if ((uintptr_t)state_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the state must be 256-byte aligned");
-    unsigned char *st = static_cast<unsigned char *>(state_dev);
-    yolo_loss_image *parts = reinterpret_cast<yolo_loss_image *>(st + L.parts_offset);
-    yolo_loss_image *images = reinterpret_cast<yolo_loss_image *>(st + L.images_offset);
-    int32_t *assign = reinterpret_cast<int32_t *>(st + L.assign_offset);
-    float *grad = reinterpret_cast<float *>(st + L.grad_offset);
-    Loss3Geometry lg;
-    std::string err;
-    // (the logits pointer is the workspace's: any non-null value that is not the gradient stands in for it until check_ready has seen the net)
-    rc = loss3_check(&net->head, net, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts, images, assign, result_dev, true, grad, &lg, err);
-    if (rc) return fail(rc, std::string(who) + ": " + err);
-    rc = check_ready(net, in_dev.ptr, batch, who);
-    if (rc) return rc;
-    if (!(lr_t == lr_t)) return fail(YOLO_ERR_ARG, std::string(who) + ": lr_t is NaN");
-    yolo_v3_wgrad_view views[YOLO_MAX_SCALES];
-    float *dw[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr}, *db[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
-    memset(views, 0, sizeof views);
-    for (int s = 0; s < L.n_scales; ++s) {
-        const Kernel *k = ks[s];
-        views[s].x_dev = net->dev_ws + net->buffers[k->in.buf].offset;
-        views[s].image_stride = k->in.img_stride; views[s].ld = k->in.ld; views[s].coff = k->in.coff;
-        views[s].dtype = net_x_dtype(net); views[s].cin = k->cin;
-        dw[s] = reinterpret_cast<float *>(st + L.dw_offset[s]); db[s] = reinterpret_cast<float *>(st + L.db_offset[s]);
-    }
-    struct yolo_v3_wgrad_plan pl;
-    Wgrad3Geometry geo;
-    rc = wgrad3_check(&net->head, views, batch, grad, assign, max_gt, dw, db, st + L.scratch_offset, (size_t)L.scratch_bytes, &pl, &geo, err);
-    if (rc) return fail(rc, std::string(who) + ": " + err);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
-    rc = run_forward(net, in_dev, batch, logits, s);        // dense: obj_min_logit is -inf outside detect_any
-    if (rc) return rc;
-    rc = run_loss3(lg, logits, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts, images, assign, result_dev, grad, s);
-    if (rc) return rc;
-    rc = run_wgrad3(geo, pl, batch, grad, assign, max_gt, st + L.scratch_offset, s);
-    if (rc) return rc;
-    const bool f16 = net->opt.dtype == YOLO_DTYPE_F16;
-    for (int i = 0; i < L.n_scales; ++i) {
-        const Kernel *k = ks[i];
-        AdamParams p;
-        memset(&p, 0, sizeof p);
-        p.w = reinterpret_cast<float *>(st + L.w_offset[i]); p.b = reinterpret_cast<float *>(st + L.b_offset[i]);
-        p.m_w = reinterpret_cast<float *>(st + L.m_w_offset[i]); p.v_w = reinterpret_cast<float *>(st + L.v_w_offset[i]);
-        p.m_b = reinterpret_cast<float *>(st + L.m_b_offset[i]); p.v_b = reinterpret_cast<float *>(st + L.v_b_offset[i]);
-        p.dw = dw[i]; p.db = db[i]; p.n_w = (long long)k->cout * k->cin; p.n_b = k->cout;
-        p.lr_t = lr_t; p.beta1 = 0.9f; p.beta2 = 0.999f; p.eps = 1e-8f;        // tf.train.AdamOptimizer's defaults (net/v2.py:205)
-        p.pack_w = net->dev_weights + k->w_off; p.pack_b = reinterpret_cast<float *>(net->dev_weights + k->b_off);
-        p.pack_cin = k->cin; p.pack_f16 = f16;
-        p.pack_row = (int)((size_t)k->ktiles * 128 / (f16 ? 2 : 4));
-        HIP_TRY(launch_adam_step(p, s));
-    }
-    return YOLO_OK;
-}
-int yolo_net_train_head_step_v3(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
-                                double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
-    return train_head_step_v3_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
-                                  "yolo_net_train_head_step_v3");
-}
-int yolo_net_train_head_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
-                                   int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
-    return train_head_step_v3_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
-                                  "yolo_net_train_head_step_v3_u8");
 }
 
 int yolo_u8_unit_table(float *out256) {

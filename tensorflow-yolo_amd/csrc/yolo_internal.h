@@ -714,7 +714,7 @@ struct NetIn {
     bool u8;
     NetIn at(size_t elems) const { return NetIn{static_cast<const unsigned char *>(ptr) + elems * (u8 ? 1 : 4), u8}; }
 };
-// Every entry below expects a checked call (api.cpp: check_ready) and leaves its message in set_error.  (Hidden: what moved out of
+// Every entry below expects a checked call (check_ready) and leaves its message in set_error.  (Hidden: what moved out of
 // api.cpp's anonymous namespace adds nothing to the symbols the library exports.)
 #pragma GCC visibility push(hidden)
 int run_forward(yolo_net *net, NetIn in_dev, int batch, float *out_dev, hipStream_t s);
@@ -725,5 +725,18 @@ bool all_heads_write_objectness(yolo_net *net, NetIn in_dev, float *out_dev, int
 int zero_pair_counters(yolo_net *net);
 void destroy_streams(yolo_net *net);
 void aux_kernel_info(const yolo_net *net, int kernel, yolo_kernel_info *out);              // yolo_net_kernel_info of every kind but K_CONV
+
+// ---- shared with the training entries (api.cpp defines them, train_api.cpp calls them too) -------------------------------------
+int check_head(const yolo_head_desc *h, size_t out_count, std::string &err);               // a set head, matching out_count floats per image if that is not 0
+int check_ready(yolo_net *net, const void *in, int batch, const char *who);                // batch, weights, workspace
+int check_loss_args(const yolo_head_desc *head, const void *gt_dev, const void *gt_counts_dev, int max_gt, const void *images_dev,
+                    const void *result_dev, const char *who);                              // the arguments of a YOLOv2 loss call
+int run_loss_grad(const yolo_head_desc &h, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+                  yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad, hipStream_t s);
+int run_loss3(const Loss3Geometry &geo, const float *logits, int batch, const yolo_gt *gt, const int32_t *gt_counts, int max_gt,
+              double ignore_thresh, yolo_loss_image *parts, yolo_loss_image *images, int32_t *assign, yolo_loss_result *result, float *grad,
+              hipStream_t s);                                                               // grad null: the loss alone
 #pragma GCC visibility pop
+// every part of a scratch or state arena starts at a 256-byte boundary
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 }  // namespace yolo

@@ -588,17 +588,46 @@ class HipNetwork(Plan):
         """loss_v3_grad() for a uint8 batch [B,H,W,C] (0..255, RGB)"""
         return self._loss_v3_grad_any(x, gts, ignore_thresh, True)
 
-    # -- training the detection layer (yolo_net_head_train_init / yolo_net_train_head_step / yolo_net_head_train_read) ------------------
-    def head_train_init(self, head_w, head_b):
-        """Allocate the head-training state and start it from head_w [cout, cin] (the Darknet kernel, [out][in]) and head_b [cout]: master
-        values, zeroed moments, and the layer packed into the device weights.  Synchronous.  A net whose streams = 0 rule runs two halves is
-        set to one pass first (each part has its own arena)."""
-        torch = self.torch
+    # -- what the three training paths share ------------------------------------------------------------------------------------------------
+    _TRAIN_ORDER = {"_train_state": "train_head_step follows head_train_init", "_tail_state": "train_tail_step follows tail_train_init",
+                    "_train_state_v3": "train_head_step_v3 follows head_train_init_v3"}
+
+    def _train_begin(self):
+        """The opening of every *_train_init*: weights are loaded, and a net whose streams = 0 rule runs two halves is set to one pass (each
+        part has its own arena; the stream measurement of the first full batch is off from here on).  Returns torch."""
         if not self.weights_loaded:
             raise RuntimeError("no weights loaded: call load_weights first")
         if self._auto_streams and self.num_streams != 1:
             _hip.check(self.lib.yolo_net_set_streams(self.handle, 1), "yolo_net_set_streams")
         self._streams_tuned = True
+        return self.torch
+
+    def _train_step(self, name, state, x, gts, lr_t, u8, result, *extra):
+        """One yolo_net_train_*_step[_u8] call: `name` the float32 entry, `state` the attribute its *_train_init* left the state in,
+        `extra` what the entry takes between max_gt and the state"""
+        from . import evaluate as yeval
+        torch = self.torch
+        if getattr(self, state, None) is None:
+            raise RuntimeError(self._TRAIN_ORDER[state])
+        x = self.to_device_u8(x) if u8 else self.to_device(x)
+        b = x.shape[0]
+        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
+        if result is None:
+            result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        name += "_u8" if u8 else ""
+        with torch.cuda.device(self.device):
+            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt), *extra,
+                                               getattr(self, state).data_ptr(), float(lr_t), result.data_ptr(), self._stream()), name)
+        self.u8_calls += int(u8)
+        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
+        return result
+
+    # -- training the detection layer (yolo_net_head_train_init / yolo_net_train_head_step / yolo_net_head_train_read) ------------------
+    def head_train_init(self, head_w, head_b):
+        """Allocate the head-training state and start it from head_w [cout, cin] (the Darknet kernel, [out][in]) and head_b [cout]: master
+        values, zeroed moments, and the layer packed into the device weights.  Synchronous.  A net whose streams = 0 rule runs two halves is
+        set to one pass first (each part has its own arena)."""
+        torch = self._train_begin()
         lay = self.head_train_layout()
         w = np.ascontiguousarray(head_w, dtype=np.float32).reshape(-1)
         b = np.ascontiguousarray(head_b, dtype=np.float32).reshape(-1)
@@ -611,33 +640,15 @@ class HipNetwork(Plan):
         self.train_layout = lay
         return self._train_state
 
-    def _train_head_step_any(self, x, gts, lr_t, u8, result):
-        from . import evaluate as yeval
-        torch = self.torch
-        if getattr(self, "_train_state", None) is None:
-            raise RuntimeError("train_head_step follows head_train_init")
-        x = self.to_device_u8(x) if u8 else self.to_device(x)
-        b = x.shape[0]
-        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
-        if result is None:
-            result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        name = "yolo_net_train_head_step_u8" if u8 else "yolo_net_train_head_step"
-        with torch.cuda.device(self.device):
-            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt),
-                                               self._train_state.data_ptr(), float(lr_t), result.data_ptr(), self._stream()), name)
-        self.u8_calls += int(u8)
-        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
-        return result
-
     def train_head_step(self, x, gts, lr_t, result=None):
         """One training step of the detection layer in one enqueue, no host sync (include/yolo_hip.h: yolo_net_train_head_step): dense
         forward, loss and its gradient, weight gradient, Adam update and re-pack.  lr_t: adam_lr_t(lr, step).  Returns the device record
         (uint8 [64] = yolo_loss_result) of the loss BEFORE the update; `result`: a caller's tensor to write it into."""
-        return self._train_head_step_any(x, gts, lr_t, False, result)
+        return self._train_step("yolo_net_train_head_step", "_train_state", x, gts, lr_t, False, result)
 
     def train_head_step_u8(self, x, gts, lr_t, result=None):
         """train_head_step() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as train_head_step(float32(x / 255.))"""
-        return self._train_head_step_any(x, gts, lr_t, True, result)
+        return self._train_step("yolo_net_train_head_step", "_train_state", x, gts, lr_t, True, result)
 
     def head_train_read(self):
         """The master values of the detection layer (synchronous): (kernel float32 [cout, cin], bias float32 [cout])"""
@@ -655,12 +666,7 @@ class HipNetwork(Plan):
         mean, moving variance [cout3 each], then the kernel [out][in][kh][kw] --, head_w [cout, cin] and head_b [cout]: master values,
         zeroed moments, the fold's scale, and both layers packed into the device weights.  Synchronous.  A net whose streams = 0 rule runs
         two halves is set to one pass first (each part has its own arena)."""
-        torch = self.torch
-        if not self.weights_loaded:
-            raise RuntimeError("no weights loaded: call load_weights first")
-        if self._auto_streams and self.num_streams != 1:
-            _hip.check(self.lib.yolo_net_set_streams(self.handle, 1), "yolo_net_set_streams")
-        self._streams_tuned = True
+        torch = self._train_begin()
         lay = self.tail_train_layout()
         blk = np.ascontiguousarray(block, dtype=np.float32).reshape(-1)
         w = np.ascontiguousarray(head_w, dtype=np.float32).reshape(-1)
@@ -675,34 +681,16 @@ class HipNetwork(Plan):
         self.tail_layout = lay
         return self._tail_state
 
-    def _train_tail_step_any(self, x, gts, lr_t, u8, result):
-        from . import evaluate as yeval
-        torch = self.torch
-        if getattr(self, "_tail_state", None) is None:
-            raise RuntimeError("train_tail_step follows tail_train_init")
-        x = self.to_device_u8(x) if u8 else self.to_device(x)
-        b = x.shape[0]
-        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
-        if result is None:
-            result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        name = "yolo_net_train_tail_step_u8" if u8 else "yolo_net_train_tail_step"
-        with torch.cuda.device(self.device):
-            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt),
-                                               self._tail_state.data_ptr(), float(lr_t), result.data_ptr(), self._stream()), name)
-        self.u8_calls += int(u8)
-        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
-        return result
-
     def train_tail_step(self, x, gts, lr_t, result=None):
         """One training step of the last 3 x 3 block and the detection layer in one enqueue, no host sync (include/yolo_hip.h:
         yolo_net_train_tail_step): dense forward, loss and its gradient, the head's weight gradient, the data gradient, the block's weight
         gradient, Adam update and re-pack of both layers.  lr_t: adam_lr_t(lr, step).  Returns the device record (uint8 [64] =
         yolo_loss_result) of the loss BEFORE the update; `result`: a caller's tensor to write it into."""
-        return self._train_tail_step_any(x, gts, lr_t, False, result)
+        return self._train_step("yolo_net_train_tail_step", "_tail_state", x, gts, lr_t, False, result)
 
     def train_tail_step_u8(self, x, gts, lr_t, result=None):
         """train_tail_step() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as train_tail_step(float32(x / 255.))"""
-        return self._train_tail_step_any(x, gts, lr_t, True, result)
+        return self._train_step("yolo_net_train_tail_step", "_tail_state", x, gts, lr_t, True, result)
 
     def tail_train_read(self):
         """The master values of the tail (synchronous): (block kernel float32 [cout3, cin3, 3, 3] as the Darknet stream holds it, beta
@@ -722,12 +710,7 @@ class HipNetwork(Plan):
         """Allocate the YOLOv3 head-training state and start it from head_ws[s] [cout_s, cin_s] (the Darknet kernels, [out][in]) and
         head_bs[s] [cout_s], in head order: master values, zeroed moments, and the convs packed into the device weights.  Synchronous.  A
         net whose streams = 0 rule runs two halves is set to one pass first (each part has its own arena)."""
-        torch = self.torch
-        if not self.weights_loaded:
-            raise RuntimeError("no weights loaded: call load_weights first")
-        if self._auto_streams and self.num_streams != 1:
-            _hip.check(self.lib.yolo_net_set_streams(self.handle, 1), "yolo_net_set_streams")
-        self._streams_tuned = True
+        torch = self._train_begin()
         lay = self.head_train_layout_v3()
         if len(head_ws) != lay.n_scales or len(head_bs) != lay.n_scales:
             raise ValueError("expected %d head kernels and biases, one per scale" % lay.n_scales)
@@ -746,33 +729,15 @@ class HipNetwork(Plan):
         self.train_layout_v3 = lay
         return self._train_state_v3
 
-    def _train_head_step_v3_any(self, x, gts, lr_t, ignore_thresh, u8, result):
-        from . import evaluate as yeval
-        torch = self.torch
-        if getattr(self, "_train_state_v3", None) is None:
-            raise RuntimeError("train_head_step_v3 follows head_train_init_v3")
-        x = self.to_device_u8(x) if u8 else self.to_device(x)
-        b = x.shape[0]
-        gt_dev, gc_dev, max_gt = self._loss_gts(gts, b)
-        if result is None:
-            result = torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-        name = "yolo_net_train_head_step_v3_u8" if u8 else "yolo_net_train_head_step_v3"
-        with torch.cuda.device(self.device):
-            _hip.check(getattr(self.lib, name)(self.handle, x.data_ptr(), b, gt_dev.data_ptr(), gc_dev.data_ptr(), int(max_gt), float(ignore_thresh),
-                                               self._train_state_v3.data_ptr(), float(lr_t), result.data_ptr(), self._stream()), name)
-        self.u8_calls += int(u8)
-        self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
-        return result
-
     def train_head_step_v3(self, x, gts, lr_t, ignore_thresh=0.7, result=None):
         """One training step of the head convs of a YOLOv3 network in one enqueue, no host sync (include/yolo_hip.h:
         yolo_net_train_head_step_v3): dense forward, the YOLOv3 loss and its gradient, the sparse weight gradient, Adam update and re-pack
         per scale.  lr_t: adam_lr_t(lr, step).  Returns the device record (uint8 [64] = yolo_loss_result) of the loss BEFORE the update."""
-        return self._train_head_step_v3_any(x, gts, lr_t, ignore_thresh, False, result)
+        return self._train_step("yolo_net_train_head_step_v3", "_train_state_v3", x, gts, lr_t, False, result, float(ignore_thresh))
 
     def train_head_step_v3_u8(self, x, gts, lr_t, ignore_thresh=0.7, result=None):
         """train_head_step_v3() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as train_head_step_v3(float32(x / 255.))"""
-        return self._train_head_step_v3_any(x, gts, lr_t, ignore_thresh, True, result)
+        return self._train_step("yolo_net_train_head_step_v3", "_train_state_v3", x, gts, lr_t, True, result, float(ignore_thresh))
 
     def head_train_read_v3(self):
         """The master values of the head convs (synchronous): ([kernel float32 [cout_s, cin_s]], [bias float32 [cout_s]]) in head order"""

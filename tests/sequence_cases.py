@@ -55,7 +55,7 @@ V3_KINDS = FORWARD + tuple(DETECT) + LOSS_V3 + (REFUSE,)
 V2_KINDS = FORWARD + tuple(DETECT) + LOSS + (REFUSE,)
 SWITCH_KINDS = ("forward", "forward_u8", "forward_timed", "detect@0.5", "detect@0.05/per-class", "detect@0.9999", REFUSE)
 
-# what -> (status code, a part of yolo_last_error): include/yolo_hip.h, csrc/api.cpp, csrc/loss3_host.cpp
+# what -> (status code, a part of yolo_last_error): include/yolo_hip.h, csrc/api.cpp, csrc/train_api.cpp, csrc/loss3_host.cpp
 ERR_ARG, ERR_STATE = 1, 5
 REFUSALS = {"batch+1": (ERR_ARG, "batch outside 1..max_batch"),
             "loss-on-v3": (ERR_ARG, "the head must be version 2"),

@@ -6,7 +6,8 @@ Three fresh child processes, one at a time, each with YOLO_HIP_LIB set and under
 library B.  The run stops at the first child that does not exit 0.  A child (--child) runs the fixed list of small cases below --
 synthetic weights and inputs (net/synth.py), every path of the forward engine, no timing-dependent choice: no autotune, streams given
 explicitly -- and prints one SHA-256 per case over the raw bytes of the results (logits; of a detect call the boxes below each count,
-the counts and the status words; the times of forward_timed are not hashed).  The parent process compares the lists:
+the counts and the status words; the times of forward_timed are not hashed; of the three training paths the state, the device weights,
+the loss records and the arrays read back: train_cases).  The parent process compares the lists:
 
   * A against A: a case on which a library disagrees with itself is listed and left out of the second comparison.  That list must stay
     below a tenth of the cases and hold no single-stream `forward` case -- those are deterministic by design (fixed split order, no
@@ -125,8 +126,76 @@ def child():
     for per_class in (False, True):
         kept = base.non_maximum_suppression(boxes, 0.45, per_class=per_class)
         emit("nms_host 300 boxes " + ("per class" if per_class else "agnostic"), [boxes.index(b) for b in kept])
+    train_cases(emit)
     torch.cuda.synchronize()
     print("HASHES " + json.dumps(out))
+
+
+def train_cases(emit):
+    """The three training paths on the smallest nets the GPU training tests use (tests/test_gpu_train*.py), fp16 and fp32, max_batch 3:
+    *_train_init into a zeroed state, steps at batch 3, 1 (a smaller split inside a scratch sized for 3) and 3, one uint8 step.  Hashed:
+    the whole state, the device weights (the trained layers' packed rows and biases are the bytes that move), the four loss records and
+    the arrays of *_train_read."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    import spp_ref
+    import tail_cases
+    from oracle import cases
+    from tensorflow_yolo_amd import YoloV2, YoloV2Tiny, YoloV3Tiny, _hip
+    from tensorflow_yolo_amd.net import engine, synth, train as ytrain
+
+    class SmallTail(YoloV2):
+        create_network = staticmethod(tail_cases.small_tail_network)
+
+    B = 3
+    names20, names3 = ["c%d" % i for i in range(20)], ["a", "b", "c"]
+    rng = np.random.RandomState(7)
+    truths = [[(rng.uniform(0, 1), rng.uniform(0, 1), rng.uniform(0.02, 0.9), rng.uniform(0.02, 0.9), int(rng.randint(0, 3))) for _ in range(n)]
+              for n in (5, 0, 2)]       # (classes 0..2: valid for every head here; one image without a truth)
+    ptrs = lambda arrays: (C.c_void_p * _hip.MAX_SCALES)(*[a.ctypes.data for a in arrays])
+    for mode, cls, anchors, names, hw, lr in (("head", YoloV2Tiny, cases.VOC_TINY_ANCHORS, names20, (96, 160), 1e-3),
+                                              ("tail", SmallTail, cases.VOC_TINY_ANCHORS, names20, (64, 64), 1e-4),
+                                              ("heads", YoloV3Tiny, spp_ref.TINY_V3_ANCHORS, names3, (96, 160), 1e-3)):
+        layers = cls.create_network(np.reshape(anchors, [-1, 2]), names, False, input_shape=hw + (3,))
+        kw = {} if mode == "heads" else dict(head_gain=synth.HEAD_DEFAULTS["v2-tiny"][0], obj_bias=0.0)
+        weights = synth.darknet_stream(layers, seed=41, num_classes=len(names), **kw)
+        x8 = np.random.RandomState(42).randint(0, 256, size=(B,) + hw + (3,)).astype(np.uint8)
+        xf = (x8 / 255.).astype(np.float32)
+        for dtype in ("fp16", "fp32"):
+            m = cls()
+            m.build(anchors, names, hw + (3,), dtype=dtype, max_batch=B, weights=weights, streams=1)
+            eng, lib = m.net.engine, _hip.lib()
+            # init twice: the engine's own call allocates the state, the second one starts it again from zeroed bytes (the parts between
+            # the arrays and the scratch are otherwise whatever the allocator returned)
+            if mode == "head":
+                args = [np.ascontiguousarray(a, dtype=np.float32) for a in ytrain.split_head(weights, *ytrain.head_counts(m.net)[:2])]
+                st = eng.head_train_init(*args)
+                again = lambda: lib.yolo_net_head_train_init(eng.handle, st.data_ptr(), st.numel(), *[a.ctypes.data for a in args])
+                step, step_u8, read = eng.train_head_step, eng.train_head_step_u8, eng.head_train_read
+            elif mode == "tail":
+                args = [np.ascontiguousarray(a, dtype=np.float32) for a in ytrain.split_tail(weights, m.net)]
+                st = eng.tail_train_init(*args)
+                again = lambda: lib.yolo_net_tail_train_init(eng.handle, st.data_ptr(), st.numel(), *[a.ctypes.data for a in args])
+                step, step_u8, read = eng.train_tail_step, eng.train_tail_step_u8, eng.tail_train_read
+            else:
+                ws, bs = ytrain.split_heads(weights, ytrain.head_convs_v3(m.net))
+                ws, bs = [np.ascontiguousarray(a, dtype=np.float32) for a in ws], [np.ascontiguousarray(a, dtype=np.float32) for a in bs]
+                st = eng.head_train_init_v3(ws, bs)
+                again = lambda: lib.yolo_net_head_train_v3_init(eng.handle, st.data_ptr(), st.numel(), ptrs(ws), ptrs(bs))
+                step, step_u8, read = eng.train_head_step_v3, eng.train_head_step_v3_u8, lambda: sum(eng.head_train_read_v3(), [])
+            st.zero_()
+            torch.cuda.synchronize()
+            _hip.check(again(), "the second init")
+            records = [step(xf[:b], truths[:b], engine.adam_lr_t(lr, t + 1)).clone() for t, b in enumerate((3, 1, 3))]
+            records.append(step_u8(x8, truths, engine.adam_lr_t(lr, 4)).clone())
+            torch.cuda.synchronize()
+            tag = "train %s %s max3" % (mode, dtype)
+            emit(tag + " state after b3 b1 b3 u8-b3", st)
+            emit(tag + " device weights", eng._weights)
+            emit(tag + " loss records x4", *records)
+            emit(tag + " read", *read())
+            m.net.engine.close()
 
 
 def run_child(lib, timeout):
