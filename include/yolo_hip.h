@@ -53,6 +53,11 @@
  *   yolo_conv1x1_dgrad, yolo_conv3x3_wgrad (+ yolo_conv3x3_wgrad_plan)
  *                           tf.gradients of net/v2.py:188 with respect to the detection layer's input (through the leaky ReLU in front of
  *                           it) and, from that, to the kernel and beta of the 3 x 3 conv of net/v2.py:62: standalone operators
+ *   yolo_v3_head_dgrad      no reference call site: the gradient of the YOLOv3 loss with respect to the input of one head conv, through the
+ *                           leaky ReLU in front of it, from the sparse gradient in place (+ yolo_v3_head_dgrad_plan)
+ *   yolo_net_train_blocks_step_v3, yolo_net_train_blocks_step_v3_u8
+ *                           net/yolo.py:161-173 for the head convs of a YOLOv3 network and the 3 x 3 blocks behind them
+ *                           (+ yolo_net_block_inputs_v3, yolo_net_blocks_train_v3_bytes / _layout / _init / _read: no reference call site)
  *   yolo_augment_u8         net/base.py:15-23, :100-107: seq.to_deterministic().augment_images of a resized batch, on the device
  *   yolo_augment_truths_host
  *                           net/base.py:107-111: augment_bounding_boxes(...).remove_out_of_image().cut_out_of_image()
@@ -103,7 +108,13 @@ extern "C" {
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_tail_train_layout POD only) -- training the last 3 x 3
                                           block and the detection layer of a YOLOv2 net: yolo_net_tail_inputs, yolo_net_tail_train_layout,
                                           yolo_net_tail_train_bytes, yolo_net_tail_train_init, yolo_net_tail_train_read, yolo_net_train_tail_step,
-                                          yolo_net_train_tail_step_u8 */
+                                          yolo_net_train_tail_step_u8;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_v3_dgrad_plan POD only) -- the sparse data gradient of
+                                          one YOLOv3 head conv: yolo_v3_head_dgrad_plan, yolo_v3_head_dgrad;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_blocks_train_v3_layout POD only) -- training the 3 x 3
+                                          blocks behind the YOLOv3 heads: yolo_net_block_inputs_v3, yolo_net_blocks_train_v3_layout,
+                                          yolo_net_blocks_train_v3_bytes, yolo_net_blocks_train_v3_init, yolo_net_blocks_train_v3_read,
+                                          yolo_net_train_blocks_step_v3, yolo_net_train_blocks_step_v3_u8 */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -1034,6 +1045,103 @@ int yolo_net_train_tail_step(yolo_net *net, const float *in_dev, int batch, cons
                              void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 int yolo_net_train_tail_step_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
                                 void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+
+/* ---- The sparse data gradient of one YOLOv3 head conv (added within ABI 7: new exports, the yolo_v3_dgrad_plan POD only) ------
+ * The backward pass of the head conv of scale `scale` of a version 3 head with respect to its input, times the derivative of the leaky
+ * ReLU in front of it -- what yolo_conv1x1_dgrad is for the detection layer of a YOLOv2 network, from the gradient G of
+ * yolo_v3_loss_grad read IN PLACE: nothing is gathered.  It is the operator a backward pass into the 3 x 3 block behind a YOLOv3 head
+ * starts with (its output D is the D of yolo_conv3x3_wgrad).
+ *
+ * Definition.  For scale s with P_s = batch * h_s * w_s positions, position p = (image n, cell q = row * w_s + column), c < cin:
+ *       D_s[p][c] = (S_o G_s[p][o] * W_s[o][c]) * (Y_s[p][c] > 0 ? 1 : slope)          o = a * (5 + C) + k
+ *   G_s[p][o] is element k of row row0_s + q * A_s + a of image n of G ([B][R][5 + C], as for yolo_v3_head_wgrad), assign_dev the table of
+ *   yolo_v3_loss_grad.  The sum runs over exactly those (a, k) the table does NOT declare a structural zero, by the rule of
+ *   yolo_v3_head_wgrad: k == 4 for every row; every k of a row whose entry is in [0, max_gt); an entry >= max_gt counts as no winner.  A
+ *   structural zero forms no product and is never read: a NaN there changes no bit of D.
+ *   W   float32 [cout_s][cin], dense: the float32 MASTER kernel of the head conv, NOT the packed copy.  cin % 8 == 0.
+ *   Y   the stored output of the block in front, a strided NHWC view as for yolo_conv1x1_dgrad, fp16 or float32; the STORED value
+ *       decides the branch: +0, -0, negatives (and NaN) take slope.  y_dev may be null: then the factor is 1 everywhere and y_dtype, ld,
+ *       coff and image_stride are not looked at.
+ *   Arithmetic: ONE float32 fmaf chain per element on the vector ALU, from +0, over the remaining terms in ascending o (anchors ascend;
+ *   inside a winner row k runs 0 .. 4 + C, otherwise only k == 4), then ONE float32 multiply by the factor.  D is float32, dense
+ *   [P_s][cin]; every element is written by every call (16-byte stores), nothing depends on what D held.  No atomics: two calls return
+ *   the same bits.  Against exact arithmetic, with T the number of terms of the position, |D - exact| <= (T + 2) 2^-24 |factor| S |G| |W|.
+ *   One kernel, enqueued on `stream` with no host synchronisation.
+ * Kernel shape: a thread owns channels_per_thread consecutive channels of one position; the channels are cut into tiles_cin tiles of
+ *   tile_cin (the A_s objectness rows of W_s of a tile lie in lds_bytes of LDS); threads_per_position threads make a position,
+ *   positions_per_round positions one round of a workgroup, which walks `rounds` rounds: the positions_per_workgroup consecutive positions
+ *   from workgroup * positions_per_workgroup.  workgroups per channel tile; loops = rounds > 1.  (threads_per_position,
+ *   positions_per_round and rounds are a full tile's: a last tile narrower than tile_cin takes its channels / channels_per_thread
+ *   threads a position and walks the same positions in fewer rounds.)  A position with a winner row walks the
+ *   5 + C rows of that anchor out of L2: with many truths per image that walk dominates.
+ * yolo_v3_head_dgrad_plan (host only: the hook the tests size their cases from): YOLO_ERR_ARG for a null pointer, a head that is not
+ * version 3 ("the head must be version 3") or otherwise refused by yolo_v3_loss_rows, scale outside 0 .. n_scales - 1, batch < 1,
+ * cin % 8 != 0, P_s above 2^30.  yolo_v3_head_dgrad adds: a null g / assign / w / d, max_gt outside 1..YOLO_EVAL_MAX_GT, w_dev or d_dev
+ * not 16-byte aligned, a Y view whose channels do not fit ld or whose images overlap, a y_dtype that is not F16 / F32.  Every message
+ * names the entry. */
+struct yolo_v3_dgrad_plan {
+    int32_t threads, channels_per_thread, tile_cin, tiles_cin;
+    int32_t threads_per_position, positions_per_round, rounds, positions_per_workgroup;
+    int32_t workgroups, loops, positions, lds_bytes;
+};
+int yolo_v3_head_dgrad_plan(const yolo_head_desc *head, int scale, int cin, int batch, struct yolo_v3_dgrad_plan *out);
+int yolo_v3_head_dgrad(const yolo_head_desc *head, int scale, const float *g_dev, const int32_t *assign_dev, int max_gt, int batch,
+                       const float *w_dev, int cin, const void *y_dev, int y_dtype, int ld, int coff, int64_t image_stride, float slope,
+                       float *d_dev, void *stream);
+
+/* ---- Training the 3 x 3 blocks behind the YOLOv3 heads (added within ABI 7: new exports, the yolo_blocks_train_v3_layout POD only) ------
+ * What "Training the tail of a YOLOv2 net" is for a YOLOv2 network, for every scale of a version 3 network (YOLOv3, YOLOv3-SPP,
+ * YOLOv3-tiny): per scale the head conv's kernel and bias and the kernel W3 and beta of the 3 x 3 / stride 1 / batch norm / leaky conv that
+ * writes the head conv's input receive Adam updates from the YOLOv3 loss.  gamma and the moving statistics stay frozen; everything in front
+ * runs on its stored statistics.  yolo_net_tail_inputs keeps refusing a version 3 net.
+ *
+ * yolo_net_block_inputs_v3: per scale in head order, the view of the block's input X3_s and of the head conv's input Y_s in the bound
+ * workspace after a dense forward; *n receives the number of scales.  Succeeds only when yolo_net_head_inputs_v3 does and, for every
+ * scale, the one kernel that writes the head conv's input passes the checks of yolo_net_tail_inputs (3 x 3 / stride 1, batch norm and leaky
+ * ReLU, no residual, not an MXFP8 conv, no fusion with a neighbour, writes exactly the head conv's view, its input a tensor of the
+ * workspace with cin % 8 == 0 that is still intact behind the last kernel, a map at most 80 wide).  The refusal names the scale and what
+ * is in the way, with the codes of yolo_net_tail_inputs.
+ *
+ * State (caller-owned device memory, every part 256-byte aligned): per scale the eight arrays of the head conv as in
+ * yolo_head_train_v3_layout, the eight arrays of the block as in yolo_tail_train_layout (W3 [cout3][9][cin3], tap t = 3 ky + kx), scale64,
+ * scale32 and mean of the block; ONE D of max_batch * max_s(h_s w_s cout3_s) floats -- the scales run one after the other on one stream --;
+ * G, the assign table, the part and image records of the v3 loss; ONE scratch, the largest over the batches 1 .. max_batch of the
+ * yolo_v3_head_wgrad plan and every scale's yolo_conv3x3_wgrad plan.  bias_src[s] / block_src[s]: the first float of head conv s (its bias)
+ * and of block s (its beta) in the Darknet stream.
+ * _init (synchronous; weights loaded first): block_host[s] is block s's piece of the Darknet stream -- beta, gamma, moving mean, moving
+ * variance [cout3 each], then the kernel [out][in][kh][kw] --, w_host[s] [cout_s][cin_s] and b_host[s] the head conv's.  Fills the masters,
+ * zeroes the moments and writes both convs' packed forms of every scale into the net's device weights, the heads as
+ * yolo_net_head_train_v3_init, the blocks as yolo_net_tail_train_init.  _read: synchronous copy of the masters back, the blocks' kernels
+ * converted to [out][in][kh][kw] again. */
+typedef struct yolo_blocks_train_v3_layout {
+    int32_t n_scales, pad_;
+    int32_t cin[YOLO_MAX_SCALES], cout[YOLO_MAX_SCALES], cin3[YOLO_MAX_SCALES], cout3[YOLO_MAX_SCALES];
+    uint64_t w_offset[YOLO_MAX_SCALES], b_offset[YOLO_MAX_SCALES], m_w_offset[YOLO_MAX_SCALES], v_w_offset[YOLO_MAX_SCALES];
+    uint64_t m_b_offset[YOLO_MAX_SCALES], v_b_offset[YOLO_MAX_SCALES], dw_offset[YOLO_MAX_SCALES], db_offset[YOLO_MAX_SCALES];
+    uint64_t w3_offset[YOLO_MAX_SCALES], beta_offset[YOLO_MAX_SCALES], m_w3_offset[YOLO_MAX_SCALES], v_w3_offset[YOLO_MAX_SCALES];
+    uint64_t m_beta_offset[YOLO_MAX_SCALES], v_beta_offset[YOLO_MAX_SCALES], dw3_offset[YOLO_MAX_SCALES], dbeta_offset[YOLO_MAX_SCALES];
+    uint64_t scale64_offset[YOLO_MAX_SCALES], scale32_offset[YOLO_MAX_SCALES], mean_offset[YOLO_MAX_SCALES];
+    uint64_t bias_src[YOLO_MAX_SCALES], block_src[YOLO_MAX_SCALES];
+    uint64_t d_offset, grad_offset, assign_offset, parts_offset, images_offset, scratch_offset, scratch_bytes, total_bytes;
+} yolo_blocks_train_v3_layout;
+int yolo_net_block_inputs_v3(const yolo_net *net, yolo_tensor_view *block_in, yolo_tensor_view *head_in, int32_t *n);
+int yolo_net_blocks_train_v3_layout(const yolo_net *net, yolo_blocks_train_v3_layout *out);
+size_t yolo_net_blocks_train_v3_bytes(const yolo_net *net);
+int yolo_net_blocks_train_v3_init(yolo_net *net, void *state_dev, size_t bytes, const float *const *block_host, const float *const *w_host,
+                                  const float *const *b_host);
+int yolo_net_blocks_train_v3_read(yolo_net *net, const void *state_dev, float *const *block_kernel_host, float *const *beta_host,
+                                  float *const *w_host, float *const *b_host);
+/* ONE enqueue with no host synchronisation for a training step on the head convs and the blocks behind them, in this order: a dense
+ * forward pass; the kernels of yolo_v3_loss_grad; yolo_v3_head_wgrad; for s ascending, yolo_v3_head_dgrad from head conv s's master kernel
+ * BEFORE its update, with Y_s and slope 0.1, into D, then yolo_conv3x3_wgrad on X3_s with scale32_s; per scale the Adam update and re-pack
+ * of the head conv (as yolo_net_train_head_step_v3); per scale the Adam update of W3_s and beta_s with the re-pack of the block (as
+ * yolo_net_train_tail_step).  result_dev receives the yolo_loss_result of the weights BEFORE the update.  Bit-identical to the standalone
+ * entries called one after the other on the same buffers.  Checks and messages as yolo_net_train_head_step_v3 plus those of
+ * yolo_net_block_inputs_v3. */
+int yolo_net_train_blocks_step_v3(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                  double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+int yolo_net_train_blocks_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                                     int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 
 /* ---- Training augmentation on the device: flips, blur, dropout, noise, shift (added within ABI 7: new exports, one new POD) ------
  * The reference trains through an imgaug pipeline (net/base.py:15-23): Fliplr(0.5), Flipud(0.5), GaussianBlur((0, 3.0)), Dropout(0.02),

@@ -151,6 +151,17 @@ class HeadTrainV3Layout(C.Structure):
                                            "scratch_bytes", "total_bytes")])
 
 
+class BlocksTrainV3Layout(C.Structure):
+    """yolo_blocks_train_v3_layout: byte offsets of the parts of the state that trains the YOLOv3 head convs and the 3 x 3 blocks behind them"""
+    _fields_ = ([("n_scales", C.c_int32), ("pad_", C.c_int32)] + [(n, C.c_int32 * MAX_SCALES) for n in ("cin", "cout", "cin3", "cout3")] +
+                [(n, C.c_uint64 * MAX_SCALES) for n in ("w_offset", "b_offset", "m_w_offset", "v_w_offset", "m_b_offset", "v_b_offset",
+                                                        "dw_offset", "db_offset", "w3_offset", "beta_offset", "m_w3_offset", "v_w3_offset",
+                                                        "m_beta_offset", "v_beta_offset", "dw3_offset", "dbeta_offset", "scale64_offset",
+                                                        "scale32_offset", "mean_offset", "bias_src", "block_src")] +
+                [(n, C.c_uint64) for n in ("d_offset", "grad_offset", "assign_offset", "parts_offset", "images_offset", "scratch_offset",
+                                           "scratch_bytes", "total_bytes")])
+
+
 class V3WgradPlan(C.Structure):
     """yolo_v3_wgrad_plan: how the weight gradient of the YOLOv3 head convs is split (per scale: chunks of positions, slabs; slot; scratch)"""
     _fields_ = ([(n, C.c_int32) for n in ("n_scales", "threads", "channels_per_thread", "min_chunk", "win_tile_cin", "win_tile_rows", "reduce_tile_chunks", "pad_")] +
@@ -164,6 +175,13 @@ class V3WgradView(C.Structure):
     """yolo_v3_wgrad_view: the input of one head conv, a strided NHWC view behind a device pointer"""
     _fields_ = [("x_dev", C.c_void_p), ("image_stride", C.c_int64), ("ld", C.c_int32), ("coff", C.c_int32), ("dtype", C.c_int32),
                 ("cin", C.c_int32)]
+
+
+class V3DgradPlan(C.Structure):
+    """yolo_v3_dgrad_plan: how the sparse data gradient of one YOLOv3 head conv is split (channel tiles, positions per round and workgroup)"""
+    _fields_ = [(n, C.c_int32) for n in ("threads", "channels_per_thread", "tile_cin", "tiles_cin", "threads_per_position",
+                                         "positions_per_round", "rounds", "positions_per_workgroup", "workgroups", "loops", "positions",
+                                         "lds_bytes")]
 
 
 class AugmentImage(C.Structure):
@@ -308,6 +326,22 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p]),
     "yolo_net_train_tail_step_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
                                               C.c_void_p, C.c_void_p]),
+    # the sparse data gradient of one YOLOv3 head conv (added within ABI 7)
+    "yolo_v3_head_dgrad_plan": (C.c_int, [C.POINTER(HeadDesc), C.c_int, C.c_int, C.c_int, C.POINTER(V3DgradPlan)]),
+    "yolo_v3_head_dgrad": (C.c_int, [C.POINTER(HeadDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    # training the 3 x 3 blocks behind the YOLOv3 heads (added within ABI 7)
+    "yolo_net_block_inputs_v3": (C.c_int, [C.c_void_p, C.POINTER(TensorView), C.POINTER(TensorView), C.POINTER(C.c_int32)]),
+    "yolo_net_blocks_train_v3_layout": (C.c_int, [C.c_void_p, C.POINTER(BlocksTrainV3Layout)]),
+    "yolo_net_blocks_train_v3_bytes": (C.c_size_t, [C.c_void_p]),
+    "yolo_net_blocks_train_v3_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_void_p)]),
+    "yolo_net_blocks_train_v3_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_void_p)]),
+    "yolo_net_train_blocks_step_v3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                                C.c_float, C.c_void_p, C.c_void_p]),
+    "yolo_net_train_blocks_step_v3_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                                   C.c_float, C.c_void_p, C.c_void_p]),
     # training augmentation (added within ABI 7)
     "yolo_augment_check": (C.c_int, [C.POINTER(AugmentImage), C.c_int, C.c_int]),
     "yolo_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(AugmentImage), C.c_void_p]),
@@ -399,6 +433,13 @@ def v3_head_wgrad_plan(head, cins, batch, x_dtype=DTYPE_F16):
         v = getattr(pl, name)
         out[name] = int(v) if kind in (C.c_int32, C.c_uint64) else [int(x) for x in v[:pl.n_scales]]
     return out
+
+
+def head_dgrad_plan(head, scale, cin, batch):
+    """yolo_v3_head_dgrad_plan as a dict (host only)"""
+    pl = V3DgradPlan()
+    check(lib().yolo_v3_head_dgrad_plan(C.byref(head), int(scale), int(cin), int(batch), C.byref(pl)), "yolo_v3_head_dgrad_plan")
+    return {name: int(getattr(pl, name)) for name, _ in V3DgradPlan._fields_}
 
 
 def augment_tile():

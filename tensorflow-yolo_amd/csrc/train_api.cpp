@@ -1,7 +1,7 @@
 // The training half of the C ABI (declared in include/yolo_hip.h): the operators under a training step (weight gradients, data gradient,
-// Adam) and the three paths that train convs of a net on the device -- the YOLOv2 detection layer (`head`), the 3 x 3 block behind it and
-// the detection layer (`tail`), the YOLOv3 head convs (`heads`).  Each path is explicit: which convs it trains (head_conv, tail_convs,
-// head_convs_v3), its state layout, init, read, and a step that is a list of launches.  What the paths have in common is written once,
+// Adam) and the four paths that train convs of a net on the device -- the YOLOv2 detection layer (`head`), the 3 x 3 block behind it and
+// the detection layer (`tail`), the YOLOv3 head convs (`heads`), those and the 3 x 3 block behind each (`head_blocks`).  Each path is
+// explicit: which convs it trains (head_conv, tail_convs, head_convs_v3, block_convs_v3), its state layout, init, read, and a step that is a list of launches.  What the paths have in common is written once,
 // in the anonymous namespace below: the record of one trained conv, the state arena, the packing of a 1 x 1 conv, the Adam parameter
 // block, the checks of a step.  The checks and launch helpers shared with api.cpp are declared in yolo_internal.h.
 #include <algorithm>
@@ -262,44 +262,52 @@ int head_conv(const yolo_net *net, const Kernel **out, const char *who) {
     return YOLO_OK;
 }
 
-// The block behind the detection layer: the one kernel that writes the detection layer's input, if it is a 3 x 3 / stride 1 conv with batch
-// norm and leaky ReLU that the plan runs on its own, from a tensor of the workspace that is still intact behind the last kernel of the
-// pass.  The message says what is in the way.
+// The block behind a detection conv k (`noun`: "the detection layer", "the head conv"): the one kernel that writes k's input, if it is a
+// 3 x 3 / stride 1 conv with batch norm and leaky ReLU that the plan runs on its own, from a tensor of the workspace that is still intact
+// behind the last kernel of the pass.  `at` opens the message, which says what is in the way.  Shared by the YOLOv2 tail and the blocks
+// behind the YOLOv3 heads.
+int block_behind(const yolo_net *net, const Kernel *k, const std::string &at, const std::string &noun, const Kernel **block) {
+    const std::vector<Kernel> &K = net->kernels;
+    const int ki = (int)(k - K.data());
+    int bi = -1, writers = 0;
+    for (int j = 0; j < ki; ++j)
+        for (const View *v : {&K[j].out, &K[j].out2, &K[j].out3})
+            if (v->buf == k->in.buf) { bi = j; ++writers; }
+    const std::string conv = "the conv behind " + noun;
+    if (writers != 1)
+        return fail(YOLO_ERR_ARG, at + noun + "'s input is written by " + std::to_string(writers) + " kernels (a concatenation or the network input): "
+                                       "there is no single 3 x 3 block behind " + noun);
+    const Kernel &b = K[bi];
+    if (b.kind != K_CONV || b.out.buf != k->in.buf)
+        return fail(YOLO_ERR_ARG, at + noun + "'s input is not written by a conv (kernel " + std::to_string(bi) + ")");
+    if (b.ksize != 3 || b.stride != 1) return fail(YOLO_ERR_ARG, at + conv + " must be 3 x 3 / stride 1 (1 x 1 and stride-2 blocks are not trained)");
+    if (!b.batch_norm || !b.leaky) return fail(YOLO_ERR_ARG, at + conv + " must have batch norm and a leaky ReLU");
+    if (b.has_res) return fail(YOLO_ERR_ARG, at + conv + " carries a residual (a shortcut is fused into it): its output is not the block's alone");
+    if (b.mx) return fail(YOLO_ERR_STATE, at + "the plan runs " + conv + " as an MXFP8 conv: its packed weights are block-scaled fp8 (use an fp16 or fp32 plan)");
+    if (b.outmode != OUT_NORMAL) return fail(YOLO_ERR_STATE, at + "the plan has fused a pool, reorg or upsample into " + conv);
+    if (b.stem != STEM_NONE || b.fuse2_next || b.fuse2_prev) return fail(YOLO_ERR_STATE, at + "the plan has fused " + conv + " with a neighbour");
+    if (b.out.coff != k->in.coff || b.out.ld != k->in.ld || b.out.img_stride != k->in.img_stride || b.out.base != k->in.base || b.cout != k->cin ||
+        b.out.H != k->in.H || b.out.W != k->in.W || b.out.f32)
+        return fail(YOLO_ERR_ARG, at + conv + " does not write exactly " + noun + "'s input");
+    if (b.in.buf < 0 || b.in.f32 || b.in.base) return fail(YOLO_ERR_STATE, at + "the input of " + conv + " is not a tensor of the workspace");
+    if (b.cin % 8 || b.cin_s != b.cin) return fail(YOLO_ERR_ARG, at + "the input channels of " + conv + " must be a multiple of 8");
+    if (b.in.W > kTailMaxW) return fail(YOLO_ERR_ARG, at + "the feature map of " + conv + " is wider than " + std::to_string(kTailMaxW));
+    const int rc = input_intact(net, bi, b.in.buf, at + "the plan reuses the block's input: ", "");
+    if (rc) return rc;
+    *block = &b;
+    return YOLO_OK;
+}
+
+// The tail of a YOLOv2 net: the detection layer and the block behind it.
 int tail_convs(const yolo_net *net, const Kernel **block, const Kernel **head, const char *who) {
     const Kernel *k = nullptr;
     int rc = head_conv(net, &k, who);
     if (rc) return rc;
-    const std::vector<Kernel> &K = net->kernels;
-    const int last = (int)K.size() - 1;
     if (k->out.base || (size_t)k->cout * k->in.H * k->in.W != net->out_count)
         return fail(YOLO_ERR_ARG, std::string(who) + ": the last kernel writes one scale of several: a v3 network has no tail of this kind (its detection convs are "
                                                      "trained with yolo_net_train_head_step_v3, train_layers = heads)");
-    int bi = -1, writers = 0;
-    for (int j = 0; j < last; ++j)
-        for (const View *v : {&K[j].out, &K[j].out2, &K[j].out3})
-            if (v->buf == k->in.buf) { bi = j; ++writers; }
-    const std::string at = std::string(who) + ": ";
-    if (writers != 1)
-        return fail(YOLO_ERR_ARG, at + "the detection layer's input is written by " + std::to_string(writers) + " kernels (a concatenation or the network input): "
-                                       "there is no single 3 x 3 block behind the detection layer");
-    const Kernel &b = K[bi];
-    if (b.kind != K_CONV || b.out.buf != k->in.buf)
-        return fail(YOLO_ERR_ARG, at + "the detection layer's input is not written by a conv (kernel " + std::to_string(bi) + ")");
-    if (b.ksize != 3 || b.stride != 1) return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer must be 3 x 3 / stride 1 (1 x 1 and stride-2 blocks are not trained)");
-    if (!b.batch_norm || !b.leaky) return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer must have batch norm and a leaky ReLU");
-    if (b.has_res) return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer carries a residual (a shortcut is fused into it): its output is not the block's alone");
-    if (b.mx) return fail(YOLO_ERR_STATE, at + "the plan runs the conv behind the detection layer as an MXFP8 conv: its packed weights are block-scaled fp8 (use an fp16 or fp32 plan)");
-    if (b.outmode != OUT_NORMAL) return fail(YOLO_ERR_STATE, at + "the plan has fused a pool, reorg or upsample into the conv behind the detection layer");
-    if (b.stem != STEM_NONE || b.fuse2_next || b.fuse2_prev) return fail(YOLO_ERR_STATE, at + "the plan has fused the conv behind the detection layer with a neighbour");
-    if (b.out.coff != k->in.coff || b.out.ld != k->in.ld || b.out.img_stride != k->in.img_stride || b.out.base != k->in.base || b.cout != k->cin ||
-        b.out.H != k->in.H || b.out.W != k->in.W || b.out.f32)
-        return fail(YOLO_ERR_ARG, at + "the conv behind the detection layer does not write exactly the detection layer's input");
-    if (b.in.buf < 0 || b.in.f32 || b.in.base) return fail(YOLO_ERR_STATE, at + "the input of the conv behind the detection layer is not a tensor of the workspace");
-    if (b.cin % 8 || b.cin_s != b.cin) return fail(YOLO_ERR_ARG, at + "the input channels of the conv behind the detection layer must be a multiple of 8");
-    if (b.in.W > kTailMaxW) return fail(YOLO_ERR_ARG, at + "the feature map of the conv behind the detection layer is wider than " + std::to_string(kTailMaxW));
-    rc = input_intact(net, bi, b.in.buf, at + "the plan reuses the block's input: ", "");
+    rc = block_behind(net, k, std::string(who) + ": ", "the detection layer", block);
     if (rc) return rc;
-    *block = &b;
     *head = k;
     return YOLO_OK;
 }
@@ -332,10 +340,19 @@ int head_convs_v3(const yolo_net *net, const Kernel *out[YOLO_MAX_SCALES], const
     return one_part(net, who);
 }
 
+// The head convs of a version 3 net and, per scale, the block behind each (block_behind's checks).
+int block_convs_v3(const yolo_net *net, const Kernel *blocks[YOLO_MAX_SCALES], const Kernel *heads[YOLO_MAX_SCALES], const char *who) {
+    int rc = head_convs_v3(net, heads, who);
+    for (int s = 0; !rc && s < net->head.n_scales; ++s)
+        rc = block_behind(net, heads[s], std::string(who) + ": scale " + std::to_string(s) + ": ", "the head conv", &blocks[s]);
+    return rc;
+}
+
 // ---- the state of each path: the trained convs first, then what a step keeps between its launches, the scratch last ------------------------
 struct HeadTrain { TrainedConv head; yolo_head_train_layout L; };
 struct TailTrain { TrainedConv head, block; yolo_tail_train_layout L; };
 struct HeadsTrain { TrainedConv sc[YOLO_MAX_SCALES]; yolo_head_train_v3_layout L; };
+struct BlocksTrain { TrainedConv head[YOLO_MAX_SCALES], block[YOLO_MAX_SCALES]; yolo_blocks_train_v3_layout L; };
 
 int head_train_layout(const yolo_net *net, HeadTrain *t, const char *who) {
     const Kernel *k = nullptr;
@@ -417,6 +434,109 @@ int head_train_v3_layout(const yolo_net *net, HeadsTrain *t, const char *who) {
         *bytes = q.scratch_bytes;
         return r;
     });
+}
+
+int blocks_train_v3_layout(const yolo_net *net, BlocksTrain *t, const char *who) {
+    const Kernel *bs[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr}, *ks[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = block_convs_v3(net, bs, ks, who);
+    if (rc) return rc;
+    std::string err;
+    Loss3Geometry lg;
+    rc = loss3_geometry(&net->head, &lg, err);
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    const size_t mb = (size_t)net->opt.max_batch;
+    yolo_blocks_train_v3_layout *L = &t->L;
+    Arena a;
+    memset(L, 0, sizeof *L);
+    L->n_scales = net->head.n_scales;
+    size_t d_floats = 0;
+    for (int s = 0; s < L->n_scales; ++s) {
+        const Kernel *k = ks[s], *b = bs[s];
+        L->cin[s] = k->cin; L->cout[s] = k->cout; L->cin3[s] = b->cin; L->cout3[s] = b->cout;
+        L->bias_src[s] = k->w_src; L->block_src[s] = b->w_src;
+        place(t->head[s], k, a, L->w_offset[s], L->b_offset[s], L->m_w_offset[s], L->v_w_offset[s], L->m_b_offset[s], L->v_b_offset[s], L->dw_offset[s], L->db_offset[s]);
+        place(t->block[s], b, a, L->w3_offset[s], L->beta_offset[s], L->m_w3_offset[s], L->v_w3_offset[s], L->m_beta_offset[s], L->v_beta_offset[s],
+              L->dw3_offset[s], L->dbeta_offset[s]);
+        L->scale64_offset[s] = a.part((size_t)b->cout * 8); L->scale32_offset[s] = a.part((size_t)b->cout * 4); L->mean_offset[s] = a.part((size_t)b->cout * 4);
+        d_floats = std::max(d_floats, (size_t)k->in.H * k->in.W * (size_t)b->cout);
+    }
+    L->d_offset = a.part(mb * d_floats * 4);        // one D: the scales run one after the other on one stream
+    L->grad_offset = a.part(mb * net->out_count * 4);
+    L->assign_offset = a.part(mb * (size_t)lg.rows * 4);
+    L->parts_offset = a.part(mb * (size_t)lg.parts * sizeof(yolo_loss_image));
+    L->images_offset = a.part(mb * sizeof(yolo_loss_image));
+    // one scratch for the heads' weight gradient and every block's, which run one after the other
+    return place_scratch(net, L, a, who, [&](int n, uint64_t *bytes, std::string &e) {
+        struct yolo_v3_wgrad_plan q = {};
+        Wgrad3Geometry g;
+        int r = wgrad3_plan(&net->head, L->cin, n, YOLO_DTYPE_F32, &q, &g, e);
+        *bytes = q.scratch_bytes;
+        for (int s = 0; !r && s < L->n_scales; ++s) {
+            struct yolo_conv3x3_wgrad_plan q3 = {};
+            r = wgrad3x3_plan(bs[s]->in.H, bs[s]->in.W, n, bs[s]->cin, bs[s]->cout, YOLO_DTYPE_F32, &q3, e);
+            *bytes = std::max(*bytes, q3.scratch_bytes);
+        }
+        return r;
+    });
+}
+
+// ---- a 3 x 3 block's piece of the Darknet stream into a state and the device weights, and back ------------------------------------------------
+// Do a block's packed rows fit its weight region?  Asked for every block of an init BEFORE its first copy: a refused init changes nothing.
+int block_rows_fit(const Kernel *b, const std::string &who) {
+    if ((size_t)b->cout * ((size_t)b->ktiles * 128) > b->w_bytes) return fail(YOLO_ERR_PLAN, who + ": the block's packed rows do not fit its weight region");
+    return YOLO_OK;
+}
+
+// block_host: beta, gamma, mean, var [cout3 each], then the kernel [out][in][kh][kw] (net/layers.py:53-63).  The fold as weights.cpp:
+// fold_batch_norm; masters, zeroed moments, scale64 / scale32 / mean into the state, the packed rows and the folded bias into the net.
+int init_block(const yolo_net *net, const TrainedConv &blk, unsigned char *st, const float *block_host, uint64_t scale64_off, uint64_t scale32_off,
+               uint64_t mean_off, const std::string &who) {
+    const Kernel *b = blk.k;
+    const bool f16 = net_x_dtype(net) == YOLO_DTYPE_F16;
+    const int c3 = b->cout, ci3 = b->cin;
+    const size_t nb3 = (size_t)c3 * 4;
+    const float *beta = block_host, *gamma = block_host + c3, *mean = block_host + 2 * (size_t)c3, *var = block_host + 3 * (size_t)c3;
+    const float *kern = block_host + 4 * (size_t)c3;
+    std::vector<double> scale64((size_t)c3);
+    std::vector<float> scale32((size_t)c3), bfold((size_t)c3), w3((size_t)c3 * 9 * ci3);
+    for (int o = 0; o < c3; ++o) {
+        scale64[o] = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
+        scale32[o] = (float)scale64[o];
+        bfold[o] = (float)((double)beta[o] - (double)mean[o] * scale64[o]);
+    }
+    const size_t wrow3 = (size_t)b->ktiles * 128;
+    std::vector<unsigned char> rows3((size_t)c3 * wrow3, 0);
+    for (int o = 0; o < c3; ++o)
+        for (int tap = 0; tap < 9; ++tap)
+            for (int c = 0; c < ci3; ++c) {
+                const float w = kern[((size_t)o * ci3 + c) * 9 + tap];
+                w3[((size_t)o * 9 + tap) * ci3 + c] = w;
+                // (fp16: one rounding from the float64 product, which is what pack_weights' (_Float16)(float) compiles to on the host)
+                const double v = (double)w * scale64[o];
+                const size_t e = (size_t)tap * b->cin_s + c;
+                if (f16) reinterpret_cast<_Float16 *>(rows3.data() + (size_t)o * wrow3)[e] = (_Float16)v;
+                else reinterpret_cast<float *>(rows3.data() + (size_t)o * wrow3)[e] = (float)v;
+            }
+    const int rc = start_state(blk, st, w3.data(), beta);       // (the caller has asked block_rows_fit)
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(st + scale64_off, scale64.data(), (size_t)c3 * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(st + scale32_off, scale32.data(), nb3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(st + mean_off, mean, nb3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(net->dev_weights + b->w_off, rows3.data(), rows3.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(net->dev_weights + b->b_off, bfold.data(), nb3, hipMemcpyHostToDevice));
+    return YOLO_OK;
+}
+
+// the block's masters back, the kernel converted to [out][in][kh][kw]
+int read_block(const TrainedConv &blk, const unsigned char *st, float *block_kernel_host, float *beta_host) {
+    const Kernel *b = blk.k;
+    std::vector<float> w3(blk.n_w);
+    const int rc = read_state(blk, st, w3.data(), beta_host);
+    if (rc) return rc;
+    for (int o = 0; o < b->cout; ++o)
+        for (int tap = 0; tap < 9; ++tap)
+            for (int c = 0; c < b->cin; ++c) block_kernel_host[((size_t)o * b->cin + c) * 9 + tap] = w3[((size_t)o * 9 + tap) * b->cin + c];
+    return YOLO_OK;
 }
 
 // ---- the steps: checks, then a list of launches on one stream ------------------------------------------------------------------------------
@@ -545,6 +665,78 @@ int train_head_step_v3_any(yolo_net *net, const NetIn in_dev, int batch, const y
     return YOLO_OK;
 }
 
+int train_blocks_step_v3_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                             double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream, const char *who) {
+    BlocksTrain t;
+    int rc = blocks_train_v3_layout(net, &t, who);
+    if (rc) return rc;
+    const yolo_blocks_train_v3_layout &L = t.L;
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    Loss3Geometry lg;
+    std::string err;
+    rc = step_checks(net, in_dev.ptr, batch, state_dev, lr_t, "yolo_net_blocks_train_v3_init", who, [&] {
+        // (the logits pointer is the workspace's: any non-null value that is not the gradient stands in for it until check_ready has seen the net)
+        const int r = loss3_check(&net->head, net, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, st + L.parts_offset, st + L.images_offset,
+                                  st + L.assign_offset, result_dev, true, st + L.grad_offset, &lg, err);
+        return r ? fail(r, std::string(who) + ": " + err) : YOLO_OK;
+    });
+    if (rc) return rc;
+    auto f32 = [&](uint64_t o) { return reinterpret_cast<float *>(st + o); };
+    yolo_loss_image *parts = reinterpret_cast<yolo_loss_image *>(st + L.parts_offset);
+    yolo_loss_image *images = reinterpret_cast<yolo_loss_image *>(st + L.images_offset);
+    int32_t *assign = reinterpret_cast<int32_t *>(st + L.assign_offset);
+    float *grad = f32(L.grad_offset), *d = f32(L.d_offset);
+    yolo_v3_wgrad_view views[YOLO_MAX_SCALES];
+    yolo_tensor_view xv[YOLO_MAX_SCALES];
+    float *dw[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr}, *db[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
+    memset(views, 0, sizeof views);
+    for (int i = 0; i < L.n_scales; ++i) {
+        const yolo_tensor_view v = view_of(net, t.head[i].k);
+        xv[i] = view_of(net, t.block[i].k);
+        views[i].x_dev = net->dev_ws + v.offset; views[i].image_stride = v.image_stride; views[i].ld = v.ld; views[i].coff = v.coff;
+        views[i].dtype = v.dtype; views[i].cin = v.cin;
+        dw[i] = f32(t.head[i].dw); db[i] = f32(t.head[i].db);
+    }
+    struct yolo_v3_wgrad_plan pl;
+    Wgrad3Geometry geo;
+    struct yolo_v3_dgrad_plan dpl;
+    Dgrad3Params dp[YOLO_MAX_SCALES];
+    struct yolo_conv3x3_wgrad_plan pl3[YOLO_MAX_SCALES];
+    rc = wgrad3_check(&net->head, views, batch, grad, assign, max_gt, dw, db, st + L.scratch_offset, (size_t)L.scratch_bytes, &pl, &geo, err);
+    for (int i = 0; !rc && i < L.n_scales; ++i) {
+        const Kernel *b = t.block[i].k;
+        rc = dgrad3_check(&net->head, i, grad, assign, max_gt, batch, f32(t.head[i].w), views[i].cin, views[i].x_dev, views[i].dtype, views[i].ld,
+                          views[i].coff, views[i].image_stride, 0.1f, d, &dpl, &dp[i], err);
+        if (!rc) rc = wgrad3x3_check(net->dev_ws + xv[i].offset, xv[i].dtype, xv[i].ld, xv[i].coff, xv[i].image_stride, xv[i].h, xv[i].w, batch, b->cin, d,
+                                     b->cout, f32(L.scale32_offset[i]), f32(t.block[i].dw), f32(t.block[i].db), st + L.scratch_offset,
+                                     (size_t)L.scratch_bytes, &pl3[i], err);
+        if (rc) err = "scale " + std::to_string(i) + ": " + err;
+    }
+    if (rc) return fail(rc, std::string(who) + ": " + err);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
+    rc = run_forward(net, in_dev, batch, logits, s);        // dense: obj_min_logit is -inf outside detect_any
+    if (rc) return rc;
+    rc = run_loss3(lg, logits, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, parts, images, assign, result_dev, grad, s);
+    if (rc) return rc;
+    rc = run_wgrad3(geo, pl, batch, grad, assign, max_gt, st + L.scratch_offset, s);
+    if (rc) return rc;
+    for (int i = 0; i < L.n_scales; ++i) {
+        // the data gradient from the head conv's master kernel BEFORE its update, through the leaky ReLU's derivative at the stored Y_s
+        const Kernel *b = t.block[i].k;
+        HIP_TRY(launch_head3_dgrad(dp[i], s));
+        rc = run_wgrad3x3(net->dev_ws + xv[i].offset, xv[i].dtype, xv[i].ld, xv[i].coff, xv[i].image_stride, xv[i].h, xv[i].w, batch, b->cin, d, b->cout,
+                          f32(L.scale32_offset[i]), f32(t.block[i].dw), f32(t.block[i].db), st + L.scratch_offset, pl3[i], s);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < L.n_scales; ++i) HIP_TRY(launch_adam_step(adam_params(net, t.head[i], st, lr_t), s));
+    for (int i = 0; i < L.n_scales; ++i) {
+        const TailAdamParams q = {adam_params(net, t.block[i], st, lr_t), reinterpret_cast<const double *>(st + L.scale64_offset[i]), f32(L.mean_offset[i])};
+        HIP_TRY(launch_tail_adam(q, s));
+    }
+    return YOLO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -624,6 +816,25 @@ int yolo_v3_head_wgrad(const yolo_head_desc *head, const struct yolo_v3_wgrad_vi
     const int rc = wgrad3_check(head, views, batch, g_dev, assign_dev, max_gt, dw_dev, db_dev, scratch_dev, scratch_bytes, &pl, &geo, err);
     if (rc) return fail(rc, "yolo_v3_head_wgrad: " + err);
     return run_wgrad3(geo, pl, batch, g_dev, assign_dev, max_gt, scratch_dev, static_cast<hipStream_t>(stream));
+}
+
+int yolo_v3_head_dgrad_plan(const yolo_head_desc *head, int scale, int cin, int batch, struct yolo_v3_dgrad_plan *out) {
+    std::string err;
+    const int rc = dgrad3_plan(head, scale, cin, batch, out, nullptr, err);
+    return rc ? fail(rc, "yolo_v3_head_dgrad_plan: " + err) : YOLO_OK;
+}
+
+int yolo_v3_head_dgrad(const yolo_head_desc *head, int scale, const float *g_dev, const int32_t *assign_dev, int max_gt, int batch,
+                       const float *w_dev, int cin, const void *y_dev, int y_dtype, int ld, int coff, int64_t image_stride, float slope,
+                       float *d_dev, void *stream) {
+    std::string err;
+    struct yolo_v3_dgrad_plan pl;
+    Dgrad3Params p;
+    const int rc = dgrad3_check(head, scale, g_dev, assign_dev, max_gt, batch, w_dev, cin, y_dev, y_dtype, ld, coff, image_stride, slope, d_dev,
+                                &pl, &p, err);
+    if (rc) return fail(rc, "yolo_v3_head_dgrad: " + err);
+    HIP_TRY(launch_head3_dgrad(p, static_cast<hipStream_t>(stream)));
+    return YOLO_OK;
 }
 
 // ---- training the detection layer of a YOLOv2 net (yolo_hip.h: added within ABI 7) ---------------------------------------------------------
@@ -712,46 +923,14 @@ int yolo_net_tail_train_init(yolo_net *net, void *state_dev, size_t bytes, const
     TailTrain t;
     int rc = tail_train_layout(net, &t, who);
     if (!rc) rc = init_checks(net, state_dev, bytes, t.L.total_bytes, "yolo_net_tail_train_bytes", who);
+    if (!rc) rc = block_rows_fit(t.block.k, who);
     if (rc) return rc;
     const yolo_tail_train_layout &L = t.L;
-    const Kernel *b = t.block.k;
     unsigned char *st = static_cast<unsigned char *>(state_dev);
-    const bool f16 = net_x_dtype(net) == YOLO_DTYPE_F16;
-    const int c3 = b->cout, ci3 = b->cin;
-    const size_t nb3 = (size_t)c3 * 4;
-    // the block: beta, gamma, mean, var, kernel[out][in][kh][kw] (net/layers.py:53-63); the fold as weights.cpp: fold_batch_norm
-    const float *beta = block_host, *gamma = block_host + c3, *mean = block_host + 2 * (size_t)c3, *var = block_host + 3 * (size_t)c3;
-    const float *kern = block_host + 4 * (size_t)c3;
-    std::vector<double> scale64((size_t)c3);
-    std::vector<float> scale32((size_t)c3), bfold((size_t)c3), w3((size_t)c3 * 9 * ci3);
-    for (int o = 0; o < c3; ++o) {
-        scale64[o] = (double)gamma[o] / std::sqrt((double)var[o] + 1e-5);
-        scale32[o] = (float)scale64[o];
-        bfold[o] = (float)((double)beta[o] - (double)mean[o] * scale64[o]);
-    }
-    const size_t wrow3 = (size_t)b->ktiles * 128;
-    std::vector<unsigned char> rows3((size_t)c3 * wrow3, 0);
-    for (int o = 0; o < c3; ++o)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int c = 0; c < ci3; ++c) {
-                const float w = kern[((size_t)o * ci3 + c) * 9 + tap];
-                w3[((size_t)o * 9 + tap) * ci3 + c] = w;
-                // (fp16: one rounding from the float64 product, which is what pack_weights' (_Float16)(float) compiles to on the host)
-                const double v = (double)w * scale64[o];
-                const size_t e = (size_t)tap * b->cin_s + c;
-                if (f16) reinterpret_cast<_Float16 *>(rows3.data() + (size_t)o * wrow3)[e] = (_Float16)v;
-                else reinterpret_cast<float *>(rows3.data() + (size_t)o * wrow3)[e] = (float)v;
-            }
-    if (rows3.size() > b->w_bytes) return fail(YOLO_ERR_PLAN, std::string(who) + ": the block's packed rows do not fit its weight region");
     HIP_TRY(hipDeviceSynchronize());
     rc = start_state(t.head, st, head_w_host, head_b_host);
-    if (!rc) rc = start_state(t.block, st, w3.data(), beta);
+    if (!rc) rc = init_block(net, t.block, st, block_host, L.scale64_offset, L.scale32_offset, L.mean_offset, who);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(st + L.scale64_offset, scale64.data(), (size_t)c3 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st + L.scale32_offset, scale32.data(), nb3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st + L.mean_offset, mean, nb3, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(net->dev_weights + b->w_off, rows3.data(), rows3.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(net->dev_weights + b->b_off, bfold.data(), nb3, hipMemcpyHostToDevice));
     return pack_conv1x1(net, t.head.k, head_w_host, head_b_host);
 }
 
@@ -761,17 +940,11 @@ int yolo_net_tail_train_read(yolo_net *net, const void *state_dev, float *block_
     TailTrain t;
     int rc = tail_train_layout(net, &t, who);
     if (rc) return rc;
-    const Kernel *b = t.block.k;
     const unsigned char *st = static_cast<const unsigned char *>(state_dev);
-    std::vector<float> w3(t.block.n_w);
     HIP_TRY(hipDeviceSynchronize());
-    rc = read_state(t.block, st, w3.data(), beta_host);
+    rc = read_block(t.block, st, block_kernel_host, beta_host);
     if (!rc) rc = read_state(t.head, st, w_host, b_host);
-    if (rc) return rc;
-    for (int o = 0; o < b->cout; ++o)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int c = 0; c < b->cin; ++c) block_kernel_host[((size_t)o * b->cin + c) * 9 + tap] = w3[((size_t)o * 9 + tap) * b->cin + c];
-    return YOLO_OK;
+    return rc;
 }
 
 int yolo_net_train_tail_step(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
@@ -847,6 +1020,86 @@ int yolo_net_train_head_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int bat
                                    int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
     return train_head_step_v3_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
                                   "yolo_net_train_head_step_v3_u8");
+}
+
+// ---- training the 3 x 3 blocks behind the YOLOv3 heads (yolo_hip.h: added within ABI 7) ------------------------------------------------------
+int yolo_net_block_inputs_v3(const yolo_net *net, yolo_tensor_view *block_in, yolo_tensor_view *head_in, int32_t *n) {
+    const Kernel *bs[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr}, *ks[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = block_convs_v3(net, bs, ks, "yolo_net_block_inputs_v3");
+    if (rc) return rc;
+    if (!block_in || !head_in || !n) return fail(YOLO_ERR_ARG, "yolo_net_block_inputs_v3: null argument");
+    *n = net->head.n_scales;
+    for (int s = 0; s < net->head.n_scales; ++s) {
+        block_in[s] = view_of(net, bs[s]);
+        head_in[s] = view_of(net, ks[s]);
+    }
+    return YOLO_OK;
+}
+
+int yolo_net_blocks_train_v3_layout(const yolo_net *net, yolo_blocks_train_v3_layout *out) {
+    if (!out) return fail(YOLO_ERR_ARG, "yolo_net_blocks_train_v3_layout: null argument");
+    BlocksTrain t;
+    const int rc = blocks_train_v3_layout(net, &t, "yolo_net_blocks_train_v3_layout");
+    if (!rc) *out = t.L;
+    return rc;
+}
+
+size_t yolo_net_blocks_train_v3_bytes(const yolo_net *net) {
+    BlocksTrain t;
+    return blocks_train_v3_layout(net, &t, "yolo_net_blocks_train_v3_bytes") ? 0 : (size_t)t.L.total_bytes;
+}
+
+int yolo_net_blocks_train_v3_init(yolo_net *net, void *state_dev, size_t bytes, const float *const *block_host, const float *const *w_host,
+                                  const float *const *b_host) {
+    const char *who = "yolo_net_blocks_train_v3_init";
+    if (!net || !state_dev || !block_host || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    BlocksTrain t;
+    int rc = blocks_train_v3_layout(net, &t, who);
+    if (rc) return rc;
+    const yolo_blocks_train_v3_layout &L = t.L;
+    for (int s = 0; s < L.n_scales; ++s)
+        if (!block_host[s] || !w_host[s] || !b_host[s]) return fail(YOLO_ERR_ARG, std::string(who) + ": scale " + std::to_string(s) + ": null argument");
+    rc = init_checks(net, state_dev, bytes, L.total_bytes, "yolo_net_blocks_train_v3_bytes", who);
+    for (int s = 0; s < L.n_scales && !rc; ++s) rc = block_rows_fit(t.block[s].k, who);
+    if (rc) return rc;
+    unsigned char *st = static_cast<unsigned char *>(state_dev);
+    HIP_TRY(hipDeviceSynchronize());
+    for (int s = 0; s < L.n_scales && !rc; ++s) {
+        rc = start_state(t.head[s], st, w_host[s], b_host[s]);
+        if (!rc) rc = pack_conv1x1(net, t.head[s].k, w_host[s], b_host[s]);
+        if (!rc) rc = init_block(net, t.block[s], st, block_host[s], L.scale64_offset[s], L.scale32_offset[s], L.mean_offset[s], who);
+    }
+    return rc;
+}
+
+int yolo_net_blocks_train_v3_read(yolo_net *net, const void *state_dev, float *const *block_kernel_host, float *const *beta_host,
+                                  float *const *w_host, float *const *b_host) {
+    const char *who = "yolo_net_blocks_train_v3_read";
+    if (!net || !state_dev || !block_kernel_host || !beta_host || !w_host || !b_host) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    BlocksTrain t;
+    int rc = blocks_train_v3_layout(net, &t, who);
+    if (rc) return rc;
+    for (int s = 0; s < t.L.n_scales; ++s)
+        if (!block_kernel_host[s] || !beta_host[s] || !w_host[s] || !b_host[s])
+            return fail(YOLO_ERR_ARG, std::string(who) + ": scale " + std::to_string(s) + ": null argument");
+    const unsigned char *st = static_cast<const unsigned char *>(state_dev);
+    HIP_TRY(hipDeviceSynchronize());
+    for (int s = 0; s < t.L.n_scales && !rc; ++s) {
+        rc = read_block(t.block[s], st, block_kernel_host[s], beta_host[s]);
+        if (!rc) rc = read_state(t.head[s], st, w_host[s], b_host[s]);
+    }
+    return rc;
+}
+
+int yolo_net_train_blocks_step_v3(yolo_net *net, const float *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
+                                  double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
+    return train_blocks_step_v3_any(net, NetIn{in_dev, false}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
+                                    "yolo_net_train_blocks_step_v3");
+}
+int yolo_net_train_blocks_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
+                                     int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
+    return train_blocks_step_v3_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
+                                    "yolo_net_train_blocks_step_v3_u8");
 }
 
 }  // extern "C"

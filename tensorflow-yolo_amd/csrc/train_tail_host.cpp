@@ -33,7 +33,7 @@ int wgrad3x3_plan(int h, int w, int batch, int cin, int cout, int x_dtype, struc
 }
 
 // the checks of a strided NHWC view that yolo_conv1x1_wgrad makes
-static int view_check(const void *dev, int dtype, int ld, int coff, long long image_stride, long long positions_per_image, int cin, std::string &err) {
+int view_check(const void *dev, int dtype, int ld, int coff, long long image_stride, long long positions_per_image, int cin, std::string &err) {
     if (dtype != YOLO_DTYPE_F16 && dtype != YOLO_DTYPE_F32) { err = "the view's dtype must be YOLO_DTYPE_F16 or YOLO_DTYPE_F32"; return YOLO_ERR_ARG; }
     if (coff < 0 || ld < 1 || (long long)coff + cin > ld) { err = "the channels coff .. coff + cin must lie inside the pixel stride ld"; return YOLO_ERR_ARG; }
     if (image_stride < (positions_per_image - 1) * ld + coff + cin) { err = "image_stride is smaller than one image of the view"; return YOLO_ERR_ARG; }

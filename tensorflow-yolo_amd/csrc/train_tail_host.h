@@ -26,6 +26,8 @@ int wgrad3x3_plan(int h, int w, int batch, int cin, int cout, int x_dtype, struc
 int wgrad3x3_check(const void *x_dev, int x_dtype, int ld, int coff, long long image_stride, int h, int w, int batch, int cin,
                    const void *d_dev, int cout, const void *scale_dev, const void *dw_dev, const void *db_dev, const void *scratch_dev,
                    size_t scratch_bytes, struct yolo_conv3x3_wgrad_plan *plan, std::string &err);
+// the checks of a strided NHWC view that yolo_conv1x1_wgrad makes (shared with train3_tail_host.cpp)
+int view_check(const void *dev, int dtype, int ld, int coff, long long image_stride, long long positions_per_image, int cin, std::string &err);
 // every check of yolo_conv1x1_dgrad that needs no device; *tiles = the workgroups of the launch
 int dgrad_check(const void *g_dev, int cout, const void *w_dev, int cin, const void *y_dev, int y_dtype, int ld, int coff,
                 long long image_stride, int positions_per_image, int batch, float slope, const void *d_dev, long long *tiles, std::string &err);

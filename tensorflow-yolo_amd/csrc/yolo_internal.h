@@ -18,6 +18,7 @@
 #include "train_host.h"
 #include "train3_host.h"
 #include "train_tail_host.h"
+#include "train3_tail_host.h"
 #include "augment_host.h"
 #include "loss3_host.h"
 
@@ -495,6 +496,9 @@ struct TailAdamParams {
 hipError_t launch_tail_adam(const TailAdamParams &p, hipStream_t s);
 hipError_t launch_conv1x1_dgrad(const DgradParams &p, int y_dtype, long long tiles, hipStream_t s);
 hipError_t launch_conv3x3_wgrad(const Wgrad3x3Params &p, int x_dtype, hipStream_t s);      // both kernels
+
+// ---- the sparse data gradient of a YOLOv3 head conv (train3_tail.hip; the split, the record and the checks: train3_tail_host.h) ---------------
+hipError_t launch_head3_dgrad(const Dgrad3Params &p, hipStream_t s);
 
 // ---- launchers (kernels.hip / detect.hip) ------------------------------------------------
 hipError_t launch_conv(const ConvParams &p, int dtype, int cfg, bool perchunk, hipStream_t s);

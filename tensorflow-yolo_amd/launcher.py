@@ -7,7 +7,8 @@ resolved against the .ini's directory, `anchors` / `class_names` parsed as Pytho
 network picked by COMMON.version.  `test` runs on this backend, and `eval` (not in the reference): VOC-style mAP of the
 network on an annotated directory, from an [EVAL] section laid over [TEST] (eval_params); `train` runs when [TRAIN] has
 `train_layers = head` (the detection layer on a frozen backbone: net/train.py; `seed` seeds the shuffle and a drawn head; `tail` adds the
-last 3 x 3 block of a v2 network, `heads` trains the detection convs of a v3 network); otherwise
+last 3 x 3 block of a v2 network, `heads` trains the detection convs of a v3 network, `head_blocks` those and the 3 x 3 block behind
+each); otherwise
 `train` and `anchor` end with a clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up),
 `resize` (stretch, the reference's geometry and the default | letterbox, Darknet's: aspect ratio kept, grey canvas, boxes mapped back to the frame),
 `loss` ([EVAL] only; true: also report the reference's validation loss, net/yolo.py:177-193 -- YOLOv2, resize = stretch);

@@ -181,6 +181,21 @@ class Plan(object):
         _hip.check(self.lib.yolo_net_head_train_v3_layout(self.handle, C.byref(lay)), "yolo_net_head_train_v3_layout")
         return lay
 
+    def block_inputs_v3(self):
+        """yolo_net_block_inputs_v3: per scale in head order, where the input of the 3 x 3 block behind the head conv and the head conv's
+        input live in the workspace after a dense forward (two lists of _hip.TensorView; host only)"""
+        blocks, heads = (_hip.TensorView * _hip.MAX_SCALES)(), (_hip.TensorView * _hip.MAX_SCALES)()
+        n = C.c_int32(0)
+        _hip.check(self.lib.yolo_net_block_inputs_v3(self.handle, blocks, heads, C.byref(n)), "yolo_net_block_inputs_v3")
+        return [blocks[s] for s in range(n.value)], [heads[s] for s in range(n.value)]
+
+    def blocks_train_layout_v3(self):
+        """yolo_net_blocks_train_v3_layout: byte offsets of the parts of the state that trains the YOLOv3 head convs and the blocks behind
+        them (a _hip.BlocksTrainV3Layout; host only)"""
+        lay = _hip.BlocksTrainV3Layout()
+        _hip.check(self.lib.yolo_net_blocks_train_v3_layout(self.handle, C.byref(lay)), "yolo_net_blocks_train_v3_layout")
+        return lay
+
     def describe(self):
         n = self.lib.yolo_net_describe(self.handle, None, 0)
         buf = C.create_string_buffer(n)
@@ -588,9 +603,10 @@ class HipNetwork(Plan):
         """loss_v3_grad() for a uint8 batch [B,H,W,C] (0..255, RGB)"""
         return self._loss_v3_grad_any(x, gts, ignore_thresh, True)
 
-    # -- what the three training paths share ------------------------------------------------------------------------------------------------
+    # -- what the four training paths share -------------------------------------------------------------------------------------------------
     _TRAIN_ORDER = {"_train_state": "train_head_step follows head_train_init", "_tail_state": "train_tail_step follows tail_train_init",
-                    "_train_state_v3": "train_head_step_v3 follows head_train_init_v3"}
+                    "_train_state_v3": "train_head_step_v3 follows head_train_init_v3",
+                    "_blocks_state_v3": "train_blocks_step_v3 follows blocks_train_init_v3"}
 
     def _train_begin(self):
         """The opening of every *_train_init*: weights are loaded, and a net whose streams = 0 rule runs two halves is set to one pass (each
@@ -749,6 +765,58 @@ class HipNetwork(Plan):
         with self.torch.cuda.device(self.device):
             _hip.check(self.lib.yolo_net_head_train_v3_read(self.handle, self._train_state_v3.data_ptr(), wp, bp), "yolo_net_head_train_v3_read")
         return ws, bs
+
+    # -- training the YOLOv3 head convs and the 3 x 3 blocks behind them (yolo_net_blocks_train_v3_* / yolo_net_train_blocks_step_v3) --------
+    def blocks_train_init_v3(self, blocks, head_ws, head_bs):
+        """Allocate the state that trains the head convs of a YOLOv3 network and the 3 x 3 block behind each, and start it, in head order,
+        from blocks[s] -- block s's piece of the Darknet stream: beta, gamma, moving mean, moving variance [cout3 each], then the kernel
+        [out][in][kh][kw] --, head_ws[s] [cout_s, cin_s] and head_bs[s] [cout_s]: master values, zeroed moments, the folds' scales, and
+        every conv packed into the device weights.  Synchronous.  A net whose streams = 0 rule runs two halves is set to one pass first."""
+        torch = self._train_begin()
+        lay = self.blocks_train_layout_v3()
+        ns = lay.n_scales
+        if len(blocks) != ns or len(head_ws) != ns or len(head_bs) != ns:
+            raise ValueError("expected %d blocks, head kernels and biases, one per scale" % ns)
+        ks = [np.ascontiguousarray(k, dtype=np.float32).reshape(-1) for k in blocks]
+        ws = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in head_ws]
+        bs = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in head_bs]
+        for s in range(ns):
+            if ks[s].size != lay.cout3[s] * (4 + 9 * lay.cin3[s]) or ws[s].size != lay.cout[s] * lay.cin[s] or bs[s].size != lay.cout[s]:
+                raise ValueError("scale %d: expected a block of %d values, a head kernel of %d x %d values and %d biases, got %d, %d and %d"
+                                 % (s, lay.cout3[s] * (4 + 9 * lay.cin3[s]), lay.cout[s], lay.cin[s], lay.cout[s], ks[s].size, ws[s].size, bs[s].size))
+        ptrs = lambda arrs: (C.c_void_p * _hip.MAX_SCALES)(*[a.ctypes.data for a in arrs])
+        with torch.cuda.device(self.device):
+            self._blocks_state_v3 = torch.empty(int(lay.total_bytes), dtype=torch.uint8, device=self.device)
+            _hip.check(self.lib.yolo_net_blocks_train_v3_init(self.handle, self._blocks_state_v3.data_ptr(), self._blocks_state_v3.numel(), ptrs(ks),
+                                                              ptrs(ws), ptrs(bs)), "yolo_net_blocks_train_v3_init")
+        self.blocks_layout_v3 = lay
+        return self._blocks_state_v3
+
+    def train_blocks_step_v3(self, x, gts, lr_t, ignore_thresh=0.7, result=None):
+        """One training step of the head convs of a YOLOv3 network and the 3 x 3 blocks behind them in one enqueue, no host sync
+        (include/yolo_hip.h: yolo_net_train_blocks_step_v3): dense forward, the YOLOv3 loss and its gradient, the heads' sparse weight
+        gradient, per scale the sparse data gradient and the block's weight gradient, Adam update and re-pack of every conv.  lr_t:
+        adam_lr_t(lr, step).  Returns the device record (uint8 [64] = yolo_loss_result) of the loss BEFORE the update."""
+        return self._train_step("yolo_net_train_blocks_step_v3", "_blocks_state_v3", x, gts, lr_t, False, result, float(ignore_thresh))
+
+    def train_blocks_step_v3_u8(self, x, gts, lr_t, ignore_thresh=0.7, result=None):
+        """train_blocks_step_v3() for a uint8 batch [B,H,W,C] (0..255, RGB): the same bits as train_blocks_step_v3(float32(x / 255.))"""
+        return self._train_step("yolo_net_train_blocks_step_v3", "_blocks_state_v3", x, gts, lr_t, True, result, float(ignore_thresh))
+
+    def blocks_train_read_v3(self):
+        """The master values (synchronous), in head order: ([block kernel float32 [cout3, cin3, 3, 3] as the Darknet stream holds it], [beta
+        [cout3]], [head kernel [cout_s, cin_s]], [head bias [cout_s]])"""
+        lay = self.blocks_layout_v3
+        ns = lay.n_scales
+        k3 = [np.empty((lay.cout3[s], lay.cin3[s], 3, 3), dtype=np.float32) for s in range(ns)]
+        beta = [np.empty(lay.cout3[s], dtype=np.float32) for s in range(ns)]
+        ws = [np.empty((lay.cout[s], lay.cin[s]), dtype=np.float32) for s in range(ns)]
+        bs = [np.empty(lay.cout[s], dtype=np.float32) for s in range(ns)]
+        ptrs = lambda arrs: (C.c_void_p * _hip.MAX_SCALES)(*[a.ctypes.data for a in arrs])
+        with self.torch.cuda.device(self.device):
+            _hip.check(self.lib.yolo_net_blocks_train_v3_read(self.handle, self._blocks_state_v3.data_ptr(), ptrs(k3), ptrs(beta), ptrs(ws), ptrs(bs)),
+                       "yolo_net_blocks_train_v3_read")
+        return k3, beta, ws, bs
 
     def forward_timed_u8(self, x, out=None):
         """forward_timed() for a uint8 batch: the input kernel's entry is the time of its uint8 twin."""
@@ -959,6 +1027,41 @@ def conv1x1_dgrad(grad, weight, y=None, slope=0.1, out=None):
         _hip.check(_hip.lib().yolo_conv1x1_dgrad(grad.data_ptr(), cout, weight.data_ptr(), cin, yt.data_ptr() if yt is not None else None, ydt,
                                                  ld, coff, istride, ppi, b, float(slope), out.data_ptr(),
                                                  torch.cuda.current_stream(dev).cuda_stream), "yolo_conv1x1_dgrad")
+    return out
+
+
+def v3_head_dgrad(head, scale, grad, assign, max_gt, weight, y=None, slope=0.1, out=None):
+    """yolo_v3_head_dgrad: D_s[p][c] = (sum_o G_s[p][o] W_s[o][c]) * (Y_s[p][c] > 0 ? 1 : slope) for the head conv of scale `scale` of a
+    version 3 head, the sum over the terms the assign table does not declare a structural zero; one enqueue on the current stream, no host
+    sync.  grad, assign: the float32 [B, R, 5 + C] gradient and the int32 [B, R] table of v3_loss_grad, read in place; weight: the
+    float32 MASTER kernel [cout_s, cin]; y: the stored output of the block in front -- as _nhwc_view takes it -- or None for no
+    activation factor; out: a float32 [P_s, cin] tensor to write into (tests pre-fill it).  Returns D float32 [P_s, cin]; the caller keeps
+    the inputs alive until the work has run."""
+    torch = _torch()
+    dev, b = grad.device, int(grad.shape[0])
+    if not 0 <= int(scale) < head.n_scales:
+        raise ValueError("v3_head_dgrad: scale must be 0..%d" % (head.n_scales - 1))
+    scale = int(scale)
+    cout, cin = head.n_anchors[scale] * (5 + head.n_classes), int(weight.shape[1])
+    if (grad.dtype != torch.float32 or weight.dtype != torch.float32 or assign.dtype != torch.int32 or not grad.is_contiguous()
+            or not weight.is_contiguous() or not assign.is_contiguous() or weight.shape[0] != cout):
+        raise ValueError("v3_head_dgrad: expected contiguous float32 grad, int32 assign and a float32 weight [%d, cin]" % cout)
+    rows, _ = v3_loss_rows(head)
+    if grad.numel() != b * rows * (5 + head.n_classes) or assign.numel() != b * rows:
+        raise ValueError("v3_head_dgrad: expected grad [%d, %d, %d] and assign [%d, %d]" % (b, rows, 5 + head.n_classes, b, rows))
+    P = b * head.h[scale] * head.w[scale]
+    if y is None:
+        yt, ydt, ld, coff, istride = None, 0, 0, 0, 0
+    else:
+        yt, ydt, ld, coff, istride, shape = _nhwc_view(torch, y, "v3_head_dgrad")
+        if shape != (b, head.h[scale], head.w[scale], cin):
+            raise ValueError("v3_head_dgrad: y is %r, expected %r" % (shape, (b, head.h[scale], head.w[scale], cin)))
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((P, cin), dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().yolo_v3_head_dgrad(C.byref(head), scale, grad.data_ptr(), assign.data_ptr(), int(max_gt), b, weight.data_ptr(), cin,
+                                                 yt.data_ptr() if yt is not None else None, ydt, ld, coff, istride, float(slope), out.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "yolo_v3_head_dgrad")
     return out
 
 

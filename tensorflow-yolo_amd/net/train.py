@@ -4,7 +4,9 @@ Runs only when [TRAIN] has `train_layers = head` (a v2 network), `train_layers =
 and beta; gamma and the moving statistics stay frozen -- and the detection layer, through yolo_net_train_tail_step; checkpoints replace the
 block's kernel and beta and the head at their stream positions) or `train_layers = heads` (a v3 network: the convs in front of its
 [yolo] layers, trained with the YOLOv3 loss through yolo_net_train_head_step_v3; `ignore_thresh`, default 0.7, is its ignore threshold and
-`pretrained_classes = N` lets a file trained for N classes start a fine-tune for another number).  Two deliberate differences from the reference (include/yolo_hip.h):
+`pretrained_classes = N` lets a file trained for N classes start a fine-tune for another number) or `train_layers = head_blocks` (a v3
+network: those convs and the 3 x 3 block behind each -- its kernel and beta --, through yolo_net_train_blocks_step_v3; the other keys as
+with `heads`; checkpoints replace every block's kernel and beta and every detection conv at their stream positions).  Two deliberate differences from the reference (include/yolo_hip.h):
 only the last conv's kernel and bias receive updates, and the backbone's batch norms run on their stored statistics -- a fine-tune of the
 detection layer on a frozen, pretrained backbone.  Batching is the reference's (net/v2.py:209-219: the last batch is padded with the
 first annotations, the list is shuffled per epoch), the console lines are its strings, the validation loss is its number (the
@@ -31,14 +33,16 @@ NOT_SUPPORTED = "train mode is not supported by the HIP inference backend"
 
 def train_layers(params):
     """The [TRAIN] key `train_layers`: absent -> None, `head` (the detection layer of a v2 network), `tail` (its last 3 x 3 block and the
-    detection layer) or `heads` (the detection convs of a v3 network) -> that word, anything else raises ValueError."""
+    detection layer), `heads` (the detection convs of a v3 network) or `head_blocks` (those and the 3 x 3 block behind each) -> that word,
+    anything else raises ValueError."""
     raw = params.get("train_layers")
     if raw is None:
         return None
     word = str(raw).strip().lower()
-    if word not in ("head", "heads", "tail"):
+    if word not in ("head", "heads", "tail", "head_blocks"):
         raise ValueError("train_layers must be head (the detection layer on a frozen backbone), tail (the last 3 x 3 block and the detection "
-                         "layer of a v2 network) or, for a v3 network, heads (its detection convs), got %r" % (raw,))
+                         "layer of a v2 network) or, for a v3 network, heads (its detection convs) or head_blocks (those and the 3 x 3 block "
+                         "behind each), got %r" % (raw,))
     return word
 
 
@@ -62,8 +66,11 @@ def check_params(params, version):
     net/yolo.py:208-211), any augmentation without `augment = device`, and with it a probability outside [0, 1].
     `train_layers = heads` is the other way round: a v3 network only, a v2 network is a ValueError.
     -> the augmentation probability that will run (0.0: none)"""
-    if train_layers(params) == "heads":
+    if train_layers(params) in ("heads", "head_blocks"):
         if not str(version).startswith("v3"):
+            if train_layers(params) == "head_blocks":
+                raise ValueError("train_layers = head_blocks trains the detection convs of a v3 network and the 3 x 3 blocks behind them; a %s "
+                                 "network takes train_layers = tail" % version)
             raise ValueError("train_layers = heads trains the detection convs of a v3 network; a %s network takes train_layers = head" % version)
         ignore = float(params.get("ignore_thresh", 0.7))
         if not 0 < ignore <= 1:
@@ -209,6 +216,51 @@ def replace_heads(body, heads, ws, bs):
     return out
 
 
+def block_convs_v3(net):
+    """The 3 x 3 blocks behind the detection convs of a v3 layer list, in head order: [(position of the block's first float -- its beta --
+    in the Darknet stream, cout3, cin3)].  The block is the conv in front of a detection conv: 3 x 3 with batch norm -- beta, gamma, moving
+    mean, moving variance [cout3 each], then the kernel [out][in][kh][kw] (net/layers.py:53-63)."""
+    from .layers import conv2d_bn_act, yolo_layer
+    out, pos, prev = [], 0, None
+    for i, l in enumerate(net):
+        if not isinstance(l, conv2d_bn_act):
+            continue
+        if i + 1 < len(net) and isinstance(net[i + 1], yolo_layer):
+            if prev is None or net[i - 1] is not prev[1]:
+                raise ValueError("the layer in front of a detection conv is not a conv")
+            blk = prev[1]
+            cout3, cin3 = int(blk.filters), int(blk.in_channels)
+            if not blk.batch_norm or blk.ksize != 3 or blk.weight_count() != cout3 * (4 + 9 * cin3):
+                raise ValueError("the conv in front of a detection conv is not a 3 x 3 conv with batch norm")
+            out.append((prev[0], cout3, cin3))
+        prev = (pos, l)
+        pos += l.weight_count()
+    if not out:
+        raise ValueError("the network has no yolo layers")
+    return out
+
+
+def split_blocks(body, blocks):
+    """[each block's piece of the stream] of the blocks `blocks` (block_convs_v3) in a Darknet stream"""
+    body = np.asarray(body, dtype=np.float32)
+    return [body[pos:pos + cout3 * (4 + 9 * cin3)].copy() for pos, cout3, cin3 in blocks]
+
+
+def replace_blocks(body, blocks, kernels, betas):
+    """a copy of the stream with every block's kernel ([cout3, cin3, 3, 3], the stream's order) and beta replaced at their positions; gamma
+    and the moving statistics stay as they are"""
+    out = np.array(body, dtype=np.float32, copy=True)
+    for (pos, cout3, cin3), k3, beta in zip(blocks, kernels, betas):
+        out[pos:pos + cout3] = np.asarray(beta, dtype=np.float32).reshape(cout3)
+        out[pos + 4 * cout3:pos + 4 * cout3 + cout3 * cin3 * 9] = np.asarray(k3, dtype=np.float32).reshape(cout3 * cin3 * 9)
+    return out
+
+
+def replace_head_blocks(body, blocks, heads, kernels, betas, ws, bs):
+    """replace_blocks and replace_heads in one: what HipNetwork.blocks_train_read_v3 returns, back into the stream"""
+    return replace_heads(replace_blocks(body, blocks, kernels, betas), heads, ws, bs)
+
+
 def initial_stream_v3(body, net, pretrained_net, seed):
     """The stream a `heads` training starts from.  A stream of exactly the net's length is used as it is.  With pretrained_net -- the same
     network built for the [TRAIN] key `pretrained_classes` = N classes -- a stream of THAT network's length keeps every float outside
@@ -315,10 +367,12 @@ def validation_loss_v3(eng, annotations, batch_size, ignore_thresh):
 
 
 def train_head(model, params):
-    """Yolo.train with `train_layers = head` or `tail` (a v2 network) or `heads` (a v3 network): one loop, the entries of the version"""
+    """Yolo.train with `train_layers = head` or `tail` (a v2 network) or `heads` or `head_blocks` (a v3 network): one loop, the entries of
+    the version"""
     from . import evaluate as yeval
     augment_prob = check_params(params, model.version)
-    v3_heads = train_layers(params) == "heads"
+    v3_heads = train_layers(params) in ("heads", "head_blocks")
+    v3_blocks = train_layers(params) == "head_blocks"
     tail = train_layers(params) == "tail"
     ignore_thresh = float(params.get("ignore_thresh", 0.7))
     batch_size = int(params["batch_size"])
@@ -366,7 +420,13 @@ def train_head(model, params):
         v3.attach_weights(net, body)
         print("Checkpoint restored. step:{}".format(step))
     # (the moments are not part of a .weights file: they start at zero)
-    if v3_heads:
+    if v3_blocks:
+        blocks = block_convs_v3(net)
+        eng.blocks_train_init_v3(split_blocks(body, blocks), *split_heads(body, heads))
+        read_stream = lambda: replace_head_blocks(body, blocks, heads, *eng.blocks_train_read_v3())
+        step_u8 = lambda x, truths, lr_t, result: eng.train_blocks_step_v3_u8(x, truths, lr_t, ignore_thresh, result=result)
+        val_loss = lambda: validation_loss_v3(eng, val_annotations, batch_size, ignore_thresh)
+    elif v3_heads:
         eng.head_train_init_v3(*split_heads(body, heads))
         read_stream = lambda: replace_heads(body, heads, *eng.head_train_read_v3())
         step_u8 = lambda x, truths, lr_t, result: eng.train_head_step_v3_u8(x, truths, lr_t, ignore_thresh, result=result)
@@ -410,7 +470,10 @@ def train_head(model, params):
                 else:
                     print("no validation annotations: validation skipped")
         print("Epoch ({}/{}) completed.".format(epoch, epochs))
-    if tail:
+    if v3_blocks:
+        model.trained_blocks = eng.blocks_train_read_v3()
+        model.trained_head = model.trained_blocks[2:]
+    elif tail:
         model.trained_tail = eng.tail_train_read()
         model.trained_head = model.trained_tail[2:]
     else:
