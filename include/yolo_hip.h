@@ -58,6 +58,9 @@
  *   yolo_net_train_blocks_step_v3, yolo_net_train_blocks_step_v3_u8
  *                           net/yolo.py:161-173 for the head convs of a YOLOv3 network and the 3 x 3 blocks behind them
  *                           (+ yolo_net_block_inputs_v3, yolo_net_blocks_train_v3_bytes / _layout / _init / _read: no reference call site)
+ *   yolo_conv3x3_wgrad_f16 (+ yolo_conv3x3_wgrad_f16_plan, yolo_net_train_wgrad_f16_bytes, yolo_net_train_set_wgrad_f16)
+ *                           no reference call site: yolo_conv3x3_wgrad with D narrowed to fp16 by one power of two per call, on the fp16
+ *                           matrix cores, and the mode that puts it into the tail and blocks steps
  *   yolo_augment_u8         net/base.py:15-23, :100-107: seq.to_deterministic().augment_images of a resized batch, on the device
  *   yolo_augment_truths_host
  *                           net/base.py:107-111: augment_bounding_boxes(...).remove_out_of_image().cut_out_of_image()
@@ -114,7 +117,10 @@ extern "C" {
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_blocks_train_v3_layout POD only) -- training the 3 x 3
                                           blocks behind the YOLOv3 heads: yolo_net_block_inputs_v3, yolo_net_blocks_train_v3_layout,
                                           yolo_net_blocks_train_v3_bytes, yolo_net_blocks_train_v3_init, yolo_net_blocks_train_v3_read,
-                                          yolo_net_train_blocks_step_v3, yolo_net_train_blocks_step_v3_u8 */
+                                          yolo_net_train_blocks_step_v3, yolo_net_train_blocks_step_v3_u8;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_conv3x3_wgrad_f16_plan POD only) -- the 3 x 3 weight
+                                          gradient on the fp16 matrix cores and its mode on a net: yolo_conv3x3_wgrad_f16_plan, yolo_conv3x3_wgrad_f16,
+                                          yolo_net_train_wgrad_f16_bytes, yolo_net_train_set_wgrad_f16 */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -991,6 +997,52 @@ int yolo_conv3x3_wgrad(const void *x_dev, int x_dtype, int ld, int coff, int64_t
                        const float *d_dev, int cout, const float *scale_dev, float *dw_dev, float *db_dev, void *scratch_dev,
                        size_t scratch_bytes, void *stream);
 
+/* ---- The 3 x 3 weight gradient on the fp16 matrix cores (added within ABI 7: new exports, the yolo_conv3x3_wgrad_f16_plan POD only) ------
+ * yolo_conv3x3_wgrad with ONE operand narrowed, D; the arguments and their meaning are yolo_conv3x3_wgrad's: stride 1, SAME padding, a
+ * strided NHWC view of X3, dW3 [cout][9][cin], db [cout], scale_dev or null; a tap outside the image contributes nothing and is never read.
+ *   X3   must be YOLO_DTYPE_F16 and is used as stored (a float32 view is YOLO_ERR_ARG: that is yolo_conv3x3_wgrad's).
+ *   k    the scale of the call.  m = max |D[p][o]| over the whole call; k = 0 when m is 0, Inf or NaN, else
+ *        k = clamp(14 - floor(log2 m), -126, 126): the largest scaled magnitude lies in [2^14, 2^15) and cannot overflow fp16.  m is found on
+ *        the device as an INTEGER maximum of the bit patterns of |D| (order-independent, no floating-point atomic; NaN patterns sort above
+ *        Inf); no host synchronisation.
+ *   D16  D16[p][o] = fp16_rne(D[p][o] * 2^k): one IEEE round-to-nearest-even conversion with gradual underflow of the exactly scaled value
+ *        (numpy.astype(float16) of it).  Narrowed while the main kernel stages D into LDS; there is no D16 buffer.
+ *   R16  R16[o][t][c] = S_p D16[p][o] * X3[p + tap t][c] on the fp16 matrix cores (v_mfma_f32_32x32x16_f16) with float32 accumulation: every
+ *        fp16 x fp16 product is exact in float32, subnormal fp16 operands count; positions ascend inside a chunk, chunks are added in chunk
+ *        order by the reduce kernel, no floating-point atomics.
+ *   dW3  dW3 = s32[o] * (2^-k * R16): the power-of-two multiply first (exact in the normal range), then the s32 multiply, rounded once.
+ *   db   db[o] = S_p D[p][o] from the UN-NARROWED float32 D (db_groups groups of db_positions positions; inside a group interleaved partial
+ *        sums, positions ascending, added in a fixed order; the groups in group order): |db - exact| <= (P + 3) 2^-24 S_p |D|, as
+ *        yolo_conv3x3_wgrad.
+ *   Every element of dW3 and db is written by every call; nothing depends on what dW3, db or the scratch held (the call initialises the m / k
+ *   record itself); two calls return the same bits.
+ *   Error, per element, for any split.  With dW64 = s32[o] 2^-k S_p D16 X3 over the NARROWED operands in float64:
+ *        |dW3 - dW64| <= (P + 4) 2^-24 |s32[o]| 2^-k S_p |D16| |X3|
+ *   and against the un-narrowed dWexact = s32[o] S_p D X3 (float64) add the rounding of the narrowing:
+ *        |dW3 - dWexact| <= (P + 4) 2^-24 |s32[o]| 2^-k S_p |D16| |X3|  +  |s32[o]| S_p (2^-11 |D| + 2^-25 2^-k) |X3|
+ *   (below fp16's normal range 2^-25 2^-k is the absolute rounding of the narrowing).
+ *   The mode helps every shape measured (profiles/wgrad_f16.json; README, "Training").
+ * yolo_conv3x3_wgrad_f16_plan (host only): as yolo_conv3x3_wgrad_plan, with tile_positions = 64 and halo_rows = 64 + 2 w + 2 rows of 16-bit
+ * elements.  scratch_bytes: the slabs, n_chunks * cout * (9 cin + 1) * 4 bytes, rounded up to 256; then, at record_offset from scratch_dev,
+ * 256 bytes that start with the record -- uint32 (the bits of m) and int32 (k), written by every call; then the partial sums of db,
+ * db_groups * cout * 4 bytes, rounded up to 256.  Refusals as yolo_conv3x3_wgrad_plan,
+ * except that w may be up to 96: the 16-bit halo is half the size, and its rows are padded by half (64 elements in 192 bytes) for the
+ * transposed LDS reads; yolo_conv3x3_wgrad keeps its 80. */
+struct yolo_conv3x3_wgrad_f16_plan {
+    int32_t tile_cout, tile_cin, tile_positions;
+    int32_t tiles_cout, tiles_cin;
+    int32_t positions_per_chunk, n_chunks, halo_rows;
+    int32_t db_groups, db_positions;
+    uint64_t record_offset;
+    uint64_t scratch_bytes;
+};
+int yolo_conv3x3_wgrad_f16_plan(int h, int w, int batch, int cin, int cout, struct yolo_conv3x3_wgrad_f16_plan *out);
+/* Four launches (the record's clear, the maximum and db, the products, the reduce), enqueued on `stream` with no host synchronisation.
+ * YOLO_ERR_ARG as yolo_conv3x3_wgrad, and for an x_dtype that is not YOLO_DTYPE_F16. */
+int yolo_conv3x3_wgrad_f16(const void *x_dev, int x_dtype, int ld, int coff, int64_t image_stride, int h, int w, int batch, int cin,
+                           const float *d_dev, int cout, const float *scale_dev, float *dw_dev, float *db_dev, void *scratch_dev,
+                           size_t scratch_bytes, void *stream);
+
 /* ---- Training the tail of a YOLOv2 net: the last 3 x 3 block and the detection layer (added within ABI 7: new exports, the
  *      yolo_tail_train_layout POD only) ------
  * The tail is the 3 x 3 / stride 1 / batch norm / leaky conv whose output the detection layer reads (net/v2.py:62 in the full network, the
@@ -1142,6 +1194,19 @@ int yolo_net_train_blocks_step_v3(yolo_net *net, const float *in_dev, int batch,
                                   double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
 int yolo_net_train_blocks_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev,
                                      int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream);
+
+/* ---- The fp16-operand 3 x 3 weight gradient as a mode of the tail and blocks steps (added within ABI 7: new exports only) ------
+ * yolo_net_train_wgrad_f16_bytes: the largest scratch_bytes of yolo_conv3x3_wgrad_f16_plan over the net's trainable 3 x 3 blocks -- the tail
+ * block of a version 2 net, every head block of a version 3 net, found with the checks of yolo_net_tail_inputs / yolo_net_block_inputs_v3 --
+ * at the batches up to max_batch.  0, with yolo_last_error(), where those checks refuse, and for a plan that does not store fp16 activations.
+ * yolo_net_train_set_wgrad_f16: with a buffer of at least that size, yolo_net_train_tail_step[_u8] and yolo_net_train_blocks_step_v3[_u8] run
+ * yolo_conv3x3_wgrad_f16 in place of yolo_conv3x3_wgrad with extra_dev as its scratch (the buffer is the caller's and must outlive the
+ * mode); everything else in the step, the state and the state layouts is unchanged, and a step is bit-identical to its parts through the
+ * standalone exports with yolo_conv3x3_wgrad_f16 in that place.  extra_dev = NULL switches back: the steps are then the float32 steps, bit
+ * for bit (bytes is not looked at).  YOLO_ERR_STATE for a float32 plan, saying so; YOLO_ERR_ARG for a buffer that is too small or not
+ * 256-byte aligned; what the block checks refuse as they refuse it. */
+size_t yolo_net_train_wgrad_f16_bytes(const yolo_net *net);
+int yolo_net_train_set_wgrad_f16(yolo_net *net, void *extra_dev, size_t bytes);
 
 /* ---- Training augmentation on the device: flips, blur, dropout, noise, shift (added within ABI 7: new exports, one new POD) ------
  * The reference trains through an imgaug pipeline (net/base.py:15-23): Fliplr(0.5), Flipud(0.5), GaussianBlur((0, 3.0)), Dropout(0.02),

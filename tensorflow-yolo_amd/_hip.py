@@ -120,6 +120,13 @@ class Conv3x3WgradPlan(C.Structure):
                 ("scratch_bytes", C.c_uint64)]
 
 
+class Conv3x3WgradF16Plan(C.Structure):
+    """yolo_conv3x3_wgrad_f16_plan: the split of a 3 x 3 weight-gradient call on the fp16 matrix cores, and where the m / k record lies"""
+    _fields_ = [("tile_cout", C.c_int32), ("tile_cin", C.c_int32), ("tile_positions", C.c_int32), ("tiles_cout", C.c_int32),
+                ("tiles_cin", C.c_int32), ("positions_per_chunk", C.c_int32), ("n_chunks", C.c_int32), ("halo_rows", C.c_int32),
+                ("db_groups", C.c_int32), ("db_positions", C.c_int32), ("record_offset", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
 class TensorView(C.Structure):
     """yolo_tensor_view: a strided NHWC tensor inside the bound workspace"""
     _fields_ = [("offset", C.c_uint64), ("image_stride", C.c_int64), ("ld", C.c_int32), ("coff", C.c_int32), ("dtype", C.c_int32),
@@ -316,6 +323,12 @@ SIGNATURES = {
     "yolo_conv3x3_wgrad_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Conv3x3WgradPlan)]),
     "yolo_conv3x3_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # the 3 x 3 weight gradient on the fp16 matrix cores and its mode on a net (added within ABI 7)
+    "yolo_conv3x3_wgrad_f16_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Conv3x3WgradF16Plan)]),
+    "yolo_conv3x3_wgrad_f16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_net_train_wgrad_f16_bytes": (C.c_size_t, [C.c_void_p]),
+    "yolo_net_train_set_wgrad_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     # training the tail of a YOLOv2 net (added within ABI 7)
     "yolo_net_tail_inputs": (C.c_int, [C.c_void_p, C.POINTER(TensorView), C.POINTER(TensorView)]),
     "yolo_net_tail_train_layout": (C.c_int, [C.c_void_p, C.POINTER(TailTrainLayout)]),
@@ -419,6 +432,13 @@ def conv3x3_wgrad_plan(h, w, batch, cin, cout, x_dtype=DTYPE_F16):
     pl = Conv3x3WgradPlan()
     check(lib().yolo_conv3x3_wgrad_plan(int(h), int(w), int(batch), int(cin), int(cout), int(x_dtype), C.byref(pl)), "yolo_conv3x3_wgrad_plan")
     return {name: int(getattr(pl, name)) for name, _ in Conv3x3WgradPlan._fields_}
+
+
+def conv3x3_wgrad_f16_plan(h, w, batch, cin, cout):
+    """yolo_conv3x3_wgrad_f16_plan as a dict (host only)"""
+    pl = Conv3x3WgradF16Plan()
+    check(lib().yolo_conv3x3_wgrad_f16_plan(int(h), int(w), int(batch), int(cin), int(cout), C.byref(pl)), "yolo_conv3x3_wgrad_f16_plan")
+    return {name: int(getattr(pl, name)) for name, _ in Conv3x3WgradF16Plan._fields_}
 
 
 def v3_head_wgrad_plan(head, cins, batch, x_dtype=DTYPE_F16):

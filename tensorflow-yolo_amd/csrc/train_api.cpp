@@ -52,6 +52,19 @@ int run_wgrad3x3(const void *x, int x_dtype, int ld, int coff, long long image_s
     return YOLO_OK;
 }
 
+int run_wgrad3x3_f16(const void *x, int ld, int coff, long long image_stride, int h, int w, int batch, int cin, const float *d, int cout,
+                     const float *scale, float *dw, float *db, void *scratch, const struct yolo_conv3x3_wgrad_f16_plan &pl, hipStream_t s) {
+    Wgrad3x3Params p;
+    memset(&p, 0, sizeof p);
+    p.x = x; p.d = d; p.scale = scale; p.slab = static_cast<float *>(scratch); p.dw = dw; p.db = db;
+    p.P = h * w * batch; p.cin = cin; p.cout = cout; p.ld = ld; p.coff = coff; p.h = h; p.w = w; p.ppi = h * w; p.img_stride = image_stride;
+    p.ppc = pl.positions_per_chunk; p.n_chunks = pl.n_chunks; p.tiles_cout = pl.tiles_cout; p.tiles_cin = pl.tiles_cin; p.halo_rows = pl.halo_rows;
+    p.slab_stride = cout * (9 * cin + 1);
+    HIP_TRY(launch_conv3x3_wgrad_f16(p, reinterpret_cast<unsigned int *>(static_cast<unsigned char *>(scratch) + pl.record_offset), pl.db_groups,
+                                     pl.db_positions, s));
+    return YOLO_OK;
+}
+
 int run_wgrad3(const Wgrad3Geometry &geo, const struct yolo_v3_wgrad_plan &pl, int batch, const float *g, const int32_t *assign, int max_gt,
                void *scratch, hipStream_t s) {
     Wgrad3Params p;
@@ -480,6 +493,34 @@ int blocks_train_v3_layout(const yolo_net *net, BlocksTrain *t, const char *who)
     });
 }
 
+// The scratch yolo_conv3x3_wgrad_f16 needs on this net: the largest over its trainable 3 x 3 blocks -- the tail block of a version 2 net,
+// every head block of a version 3 net -- and, as place_scratch, over the batches 1 .. max_batch.
+int wgrad_f16_need(const yolo_net *net, uint64_t *need, const char *who) {
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    const Kernel *bs[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr}, *ks[YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
+    int n_blocks = 1, rc;
+    std::string unset;
+    if (!check_head(&net->head, net->out_count, unset) && net->head.version == 3) {
+        rc = block_convs_v3(net, bs, ks, who);
+        n_blocks = net->head.n_scales;
+    } else {
+        rc = tail_convs(net, &bs[0], &ks[0], who);
+    }
+    if (rc) return rc;
+    if (net_x_dtype(net) != YOLO_DTYPE_F16)
+        return fail(YOLO_ERR_STATE, std::string(who) + ": a float32 plan stores float32 activations: yolo_conv3x3_wgrad_f16 reads X3 as stored fp16 (use an fp16 plan)");
+    std::string err;
+    *need = 0;
+    for (int s = 0; s < n_blocks; ++s)
+        for (int n = 1; n <= net->opt.max_batch; ++n) {
+            struct yolo_conv3x3_wgrad_f16_plan q = {};
+            rc = wgrad3x3_f16_plan(bs[s]->in.H, bs[s]->in.W, n, bs[s]->cin, bs[s]->cout, &q, err);
+            if (rc) return fail(rc, std::string(who) + ": " + err);
+            *need = std::max(*need, q.scratch_bytes);
+        }
+    return YOLO_OK;
+}
+
 // ---- a 3 x 3 block's piece of the Darknet stream into a state and the device weights, and back ------------------------------------------------
 // Do a block's packed rows fit its weight region?  Asked for every block of an init BEFORE its first copy: a refused init changes nothing.
 int block_rows_fit(const Kernel *b, const std::string &who) {
@@ -539,6 +580,34 @@ int read_block(const TrainedConv &blk, const unsigned char *st, float *block_ker
     return YOLO_OK;
 }
 
+// ---- the weight gradient of a trained 3 x 3 block inside a step ---------------------------------------------------------------------------
+// yolo_conv3x3_wgrad on the state's scratch, or, after yolo_net_train_set_wgrad_f16, yolo_conv3x3_wgrad_f16 on the net's extra buffer: the
+// same arguments, the same outputs, checked in front of the step's first launch and run in its place.
+struct BlockWgrad {
+    bool f16;
+    struct yolo_conv3x3_wgrad_plan pl;
+    struct yolo_conv3x3_wgrad_f16_plan pl16;
+};
+
+int block_wgrad_check(const yolo_net *net, const yolo_tensor_view &xv, int batch, const Kernel *b, const float *d, const float *scale, float *dw,
+                      float *db, void *scratch, size_t scratch_bytes, BlockWgrad *g, std::string &err) {
+    const void *x = net->dev_ws + xv.offset;
+    g->f16 = net->wgrad_f16_dev != nullptr;
+    if (g->f16)
+        return wgrad3x3_f16_check(x, xv.dtype, xv.ld, xv.coff, xv.image_stride, xv.h, xv.w, batch, b->cin, d, b->cout, scale, dw, db, net->wgrad_f16_dev,
+                                  net->wgrad_f16_bytes, &g->pl16, err);
+    return wgrad3x3_check(x, xv.dtype, xv.ld, xv.coff, xv.image_stride, xv.h, xv.w, batch, b->cin, d, b->cout, scale, dw, db, scratch, scratch_bytes,
+                          &g->pl, err);
+}
+
+int block_wgrad_run(const yolo_net *net, const yolo_tensor_view &xv, int batch, const Kernel *b, const float *d, const float *scale, float *dw,
+                    float *db, void *scratch, const BlockWgrad &g, hipStream_t s) {
+    const void *x = net->dev_ws + xv.offset;
+    if (g.f16)
+        return run_wgrad3x3_f16(x, xv.ld, xv.coff, xv.image_stride, xv.h, xv.w, batch, b->cin, d, b->cout, scale, dw, db, net->wgrad_f16_dev, g.pl16, s);
+    return run_wgrad3x3(x, xv.dtype, xv.ld, xv.coff, xv.image_stride, xv.h, xv.w, batch, b->cin, d, b->cout, scale, dw, db, scratch, g.pl, s);
+}
+
 // ---- the steps: checks, then a list of launches on one stream ------------------------------------------------------------------------------
 int train_head_step_any(yolo_net *net, const NetIn in_dev, int batch, const yolo_gt *gt_dev, const int32_t *gt_counts_dev, int max_gt,
                         void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream, const char *who) {
@@ -588,16 +657,16 @@ int train_tail_step_any(yolo_net *net, const NetIn in_dev, int batch, const yolo
     const int ppi = yv.h * yv.w;
     auto f32 = [&](uint64_t o) { return reinterpret_cast<float *>(st + o); };
     float *grad = f32(L.grad_offset), *d = f32(L.d_offset);
-    const void *y = net->dev_ws + yv.offset, *x3 = net->dev_ws + xv.offset;
+    const void *y = net->dev_ws + yv.offset;
     std::string err;
     struct yolo_wgrad_plan pl;
-    struct yolo_conv3x3_wgrad_plan pl3;
+    BlockWgrad g3;
     long long tiles = 0;
     rc = wgrad_check(y, yv.dtype, yv.ld, yv.coff, yv.image_stride, ppi, batch, k->cin, grad, k->cout, f32(L.dw_offset), f32(L.db_offset),
                      st + L.scratch_offset, (size_t)L.scratch_bytes, &pl, err);
     if (!rc) rc = dgrad_check(grad, k->cout, f32(L.w_offset), k->cin, y, yv.dtype, yv.ld, yv.coff, yv.image_stride, ppi, batch, 0.1f, d, &tiles, err);
-    if (!rc) rc = wgrad3x3_check(x3, xv.dtype, xv.ld, xv.coff, xv.image_stride, xv.h, xv.w, batch, b->cin, d, b->cout, f32(L.scale32_offset),
-                                 f32(L.dw3_offset), f32(L.dbeta_offset), st + L.scratch_offset, (size_t)L.scratch_bytes, &pl3, err);
+    if (!rc) rc = block_wgrad_check(net, xv, batch, b, d, f32(L.scale32_offset), f32(L.dw3_offset), f32(L.dbeta_offset), st + L.scratch_offset,
+                                    (size_t)L.scratch_bytes, &g3, err);
     if (rc) return fail(rc, std::string(who) + ": " + err);
     hipStream_t s = static_cast<hipStream_t>(stream);
     float *logits = reinterpret_cast<float *>(net->dev_ws + net->logits_off);
@@ -611,8 +680,7 @@ int train_tail_step_any(yolo_net *net, const NetIn in_dev, int batch, const yolo
     // the data gradient from the head's master kernel BEFORE its update, through the leaky ReLU's derivative at the stored Y
     rc = run_dgrad(grad, k->cout, f32(L.w_offset), k->cin, y, yv.dtype, yv.ld, yv.coff, yv.image_stride, ppi, batch, 0.1f, d, tiles, s);
     if (rc) return rc;
-    rc = run_wgrad3x3(x3, xv.dtype, xv.ld, xv.coff, xv.image_stride, xv.h, xv.w, batch, b->cin, d, b->cout, f32(L.scale32_offset),
-                      f32(L.dw3_offset), f32(L.dbeta_offset), st + L.scratch_offset, pl3, s);
+    rc = block_wgrad_run(net, xv, batch, b, d, f32(L.scale32_offset), f32(L.dw3_offset), f32(L.dbeta_offset), st + L.scratch_offset, g3, s);
     if (rc) return rc;
     HIP_TRY(launch_adam_step(adam_params(net, t.head, st, lr_t), s));
     const TailAdamParams q = {adam_params(net, t.block, st, lr_t), reinterpret_cast<const double *>(st + L.scale64_offset), f32(L.mean_offset)};
@@ -701,15 +769,14 @@ int train_blocks_step_v3_any(yolo_net *net, const NetIn in_dev, int batch, const
     Wgrad3Geometry geo;
     struct yolo_v3_dgrad_plan dpl;
     Dgrad3Params dp[YOLO_MAX_SCALES];
-    struct yolo_conv3x3_wgrad_plan pl3[YOLO_MAX_SCALES];
+    BlockWgrad g3[YOLO_MAX_SCALES];
     rc = wgrad3_check(&net->head, views, batch, grad, assign, max_gt, dw, db, st + L.scratch_offset, (size_t)L.scratch_bytes, &pl, &geo, err);
     for (int i = 0; !rc && i < L.n_scales; ++i) {
         const Kernel *b = t.block[i].k;
         rc = dgrad3_check(&net->head, i, grad, assign, max_gt, batch, f32(t.head[i].w), views[i].cin, views[i].x_dev, views[i].dtype, views[i].ld,
                           views[i].coff, views[i].image_stride, 0.1f, d, &dpl, &dp[i], err);
-        if (!rc) rc = wgrad3x3_check(net->dev_ws + xv[i].offset, xv[i].dtype, xv[i].ld, xv[i].coff, xv[i].image_stride, xv[i].h, xv[i].w, batch, b->cin, d,
-                                     b->cout, f32(L.scale32_offset[i]), f32(t.block[i].dw), f32(t.block[i].db), st + L.scratch_offset,
-                                     (size_t)L.scratch_bytes, &pl3[i], err);
+        if (!rc) rc = block_wgrad_check(net, xv[i], batch, b, d, f32(L.scale32_offset[i]), f32(t.block[i].dw), f32(t.block[i].db), st + L.scratch_offset,
+                                        (size_t)L.scratch_bytes, &g3[i], err);
         if (rc) err = "scale " + std::to_string(i) + ": " + err;
     }
     if (rc) return fail(rc, std::string(who) + ": " + err);
@@ -725,8 +792,7 @@ int train_blocks_step_v3_any(yolo_net *net, const NetIn in_dev, int batch, const
         // the data gradient from the head conv's master kernel BEFORE its update, through the leaky ReLU's derivative at the stored Y_s
         const Kernel *b = t.block[i].k;
         HIP_TRY(launch_head3_dgrad(dp[i], s));
-        rc = run_wgrad3x3(net->dev_ws + xv[i].offset, xv[i].dtype, xv[i].ld, xv[i].coff, xv[i].image_stride, xv[i].h, xv[i].w, batch, b->cin, d, b->cout,
-                          f32(L.scale32_offset[i]), f32(t.block[i].dw), f32(t.block[i].db), st + L.scratch_offset, pl3[i], s);
+        rc = block_wgrad_run(net, xv[i], batch, b, d, f32(L.scale32_offset[i]), f32(t.block[i].dw), f32(t.block[i].db), st + L.scratch_offset, g3[i], s);
         if (rc) return rc;
     }
     for (int i = 0; i < L.n_scales; ++i) HIP_TRY(launch_adam_step(adam_params(net, t.head[i], st, lr_t), s));
@@ -798,6 +864,24 @@ int yolo_conv3x3_wgrad(const void *x_dev, int x_dtype, int ld, int coff, int64_t
     if (rc) return fail(rc, "yolo_conv3x3_wgrad: " + err);
     return run_wgrad3x3(x_dev, x_dtype, ld, coff, image_stride, h, w, batch, cin, d_dev, cout, scale_dev, dw_dev, db_dev, scratch_dev, pl,
                         static_cast<hipStream_t>(stream));
+}
+
+int yolo_conv3x3_wgrad_f16_plan(int h, int w, int batch, int cin, int cout, struct yolo_conv3x3_wgrad_f16_plan *out) {
+    std::string err;
+    const int rc = wgrad3x3_f16_plan(h, w, batch, cin, cout, out, err);
+    return rc ? fail(rc, "yolo_conv3x3_wgrad_f16_plan: " + err) : YOLO_OK;
+}
+
+int yolo_conv3x3_wgrad_f16(const void *x_dev, int x_dtype, int ld, int coff, int64_t image_stride, int h, int w, int batch, int cin,
+                           const float *d_dev, int cout, const float *scale_dev, float *dw_dev, float *db_dev, void *scratch_dev,
+                           size_t scratch_bytes, void *stream) {
+    std::string err;
+    struct yolo_conv3x3_wgrad_f16_plan pl;
+    const int rc = wgrad3x3_f16_check(x_dev, x_dtype, ld, coff, image_stride, h, w, batch, cin, d_dev, cout, scale_dev, dw_dev, db_dev, scratch_dev,
+                                      scratch_bytes, &pl, err);
+    if (rc) return fail(rc, "yolo_conv3x3_wgrad_f16: " + err);
+    return run_wgrad3x3_f16(x_dev, ld, coff, image_stride, h, w, batch, cin, d_dev, cout, scale_dev, dw_dev, db_dev, scratch_dev, pl,
+                            static_cast<hipStream_t>(stream));
 }
 
 int yolo_v3_head_wgrad_plan(const yolo_head_desc *head, const int32_t *cin, int batch, int x_dtype, struct yolo_v3_wgrad_plan *out) {
@@ -1100,6 +1184,30 @@ int yolo_net_train_blocks_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int b
                                      int max_gt, double ignore_thresh, void *state_dev, float lr_t, yolo_loss_result *result_dev, void *stream) {
     return train_blocks_step_v3_any(net, NetIn{in_dev, true}, batch, gt_dev, gt_counts_dev, max_gt, ignore_thresh, state_dev, lr_t, result_dev, stream,
                                     "yolo_net_train_blocks_step_v3_u8");
+}
+
+// ---- the fp16-operand weight gradient as a mode of the tail and blocks steps (yolo_hip.h: added within ABI 7) --------------------------------
+size_t yolo_net_train_wgrad_f16_bytes(const yolo_net *net) {
+    uint64_t need = 0;
+    return wgrad_f16_need(net, &need, "yolo_net_train_wgrad_f16_bytes") ? 0 : (size_t)need;
+}
+
+int yolo_net_train_set_wgrad_f16(yolo_net *net, void *extra_dev, size_t bytes) {
+    const char *who = "yolo_net_train_set_wgrad_f16";
+    if (!net) return fail(YOLO_ERR_ARG, std::string(who) + ": null argument");
+    if (!extra_dev) {       // back to the float32 steps
+        net->wgrad_f16_dev = nullptr;
+        net->wgrad_f16_bytes = 0;
+        return YOLO_OK;
+    }
+    uint64_t need = 0;
+    const int rc = wgrad_f16_need(net, &need, who);
+    if (rc) return rc;
+    if (bytes < need) return fail(YOLO_ERR_ARG, std::string(who) + ": buffer too small (yolo_net_train_wgrad_f16_bytes)");
+    if ((uintptr_t)extra_dev % 256) return fail(YOLO_ERR_ARG, std::string(who) + ": the buffer must be 256-byte aligned");
+    net->wgrad_f16_dev = static_cast<unsigned char *>(extra_dev);
+    net->wgrad_f16_bytes = bytes;
+    return YOLO_OK;
 }
 
 }  // extern "C"

@@ -496,6 +496,9 @@ struct TailAdamParams {
 hipError_t launch_tail_adam(const TailAdamParams &p, hipStream_t s);
 hipError_t launch_conv1x1_dgrad(const DgradParams &p, int y_dtype, long long tiles, hipStream_t s);
 hipError_t launch_conv3x3_wgrad(const Wgrad3x3Params &p, int x_dtype, hipStream_t s);      // both kernels
+// train_tail_f16.hip: the same launch on the fp16 matrix cores (x is fp16); record: the m / k record behind the slabs (yolo_conv3x3_wgrad_f16_plan)
+// db_groups groups of db_positions positions: the partial sums of db, behind the record
+hipError_t launch_conv3x3_wgrad_f16(const Wgrad3x3Params &p, unsigned int *record, int db_groups, int db_positions, hipStream_t s);    // the clear and all three kernels
 
 // ---- the sparse data gradient of a YOLOv3 head conv (train3_tail.hip; the split, the record and the checks: train3_tail_host.h) ---------------
 hipError_t launch_head3_dgrad(const Dgrad3Params &p, hipStream_t s);
@@ -656,6 +659,10 @@ struct yolo_net {
     unsigned char *dev_ws = nullptr;
     size_t dev_ws_bytes = 0;
     bool weights_loaded = false;
+    // yolo_net_train_set_wgrad_f16: the caller's scratch of yolo_conv3x3_wgrad_f16, which the tail and blocks steps then run in place of
+    // yolo_conv3x3_wgrad; null: the float32 steps
+    unsigned char *wgrad_f16_dev = nullptr;
+    size_t wgrad_f16_bytes = 0;
 };
 
 namespace yolo {

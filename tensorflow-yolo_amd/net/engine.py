@@ -638,6 +638,25 @@ class HipNetwork(Plan):
         self._loss_keep = (x, gt_dev, gc_dev)      # (alive until the next call: the work is only enqueued)
         return result
 
+    def set_wgrad_f16(self, on=True):
+        """The weight gradient of the trained 3 x 3 blocks on the fp16 matrix cores (yolo_net_train_set_wgrad_f16): train_tail_step[_u8] and
+        train_blocks_step_v3[_u8] then run yolo_conv3x3_wgrad_f16 in place of yolo_conv3x3_wgrad, in a buffer this engine owns.
+        on=False: back to the float32 steps, bit for bit.  Before or after a *_train_init*; raises the library's refusal for a float32 plan
+        or a net without such a block."""
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            if not on:
+                torch.cuda.synchronize(self.device)       # (a step that still runs in the buffer)
+                _hip.check(self.lib.yolo_net_train_set_wgrad_f16(self.handle, None, 0), "yolo_net_train_set_wgrad_f16")
+                self._wgrad_f16_buf = None
+                return
+            need = int(self.lib.yolo_net_train_wgrad_f16_bytes(self.handle))
+            if not need:
+                raise _hip.YoloHipError("yolo_net_train_wgrad_f16_bytes failed: %s" % (self.lib.yolo_last_error() or b"").decode())
+            buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _hip.check(self.lib.yolo_net_train_set_wgrad_f16(self.handle, buf.data_ptr(), buf.numel()), "yolo_net_train_set_wgrad_f16")
+            self._wgrad_f16_buf = buf
+
     # -- training the detection layer (yolo_net_head_train_init / yolo_net_train_head_step / yolo_net_head_train_read) ------------------
     def head_train_init(self, head_w, head_b):
         """Allocate the head-training state and start it from head_w [cout, cin] (the Darknet kernel, [out][in]) and head_b [cout]: master
@@ -1089,6 +1108,30 @@ def conv3x3_wgrad(x, d, scale=None, scratch=None, out=None):
                                                  scale.data_ptr() if scale is not None else None, out[0].data_ptr(), out[1].data_ptr(),
                                                  scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream),
                    "yolo_conv3x3_wgrad")
+    return out[0], out[1], scratch
+
+
+def conv3x3_wgrad_f16(x, d, scale=None, scratch=None, out=None):
+    """yolo_conv3x3_wgrad_f16: conv3x3_wgrad() with D narrowed to fp16 by one power of two per call, on the fp16 matrix cores (the
+    definition: include/yolo_hip.h).  x must be an fp16 view; the other arguments and the result are conv3x3_wgrad()'s.  The scratch ends
+    with the call's m / k record, at yolo_conv3x3_wgrad_f16_plan's record_offset."""
+    torch = _torch()
+    dev = d.device
+    xt, xdt, ld, coff, istride, (b, h, w, cin) = _nhwc_view(torch, x, "conv3x3_wgrad_f16")
+    if d.dtype != torch.float32 or not d.is_contiguous() or d.dim() != 2 or d.shape[0] != b * h * w:
+        raise ValueError("conv3x3_wgrad_f16: expected a contiguous float32 gradient [%d, cout]" % (b * h * w))
+    cout = int(d.shape[1])
+    if scale is not None and (scale.dtype != torch.float32 or not scale.is_contiguous() or scale.numel() != cout):
+        raise ValueError("conv3x3_wgrad_f16: expected a contiguous float32 scale [%d]" % cout)
+    with torch.cuda.device(dev):
+        if scratch is None:
+            scratch = torch.empty(_hip.conv3x3_wgrad_f16_plan(h, w, b, cin, cout)["scratch_bytes"], dtype=torch.uint8, device=dev)
+        if out is None:
+            out = (torch.empty((cout, 9, cin), dtype=torch.float32, device=dev), torch.empty(cout, dtype=torch.float32, device=dev))
+        _hip.check(_hip.lib().yolo_conv3x3_wgrad_f16(xt.data_ptr(), xdt, ld, coff, istride, h, w, b, cin, d.data_ptr(), cout,
+                                                     scale.data_ptr() if scale is not None else None, out[0].data_ptr(), out[1].data_ptr(),
+                                                     scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                   "yolo_conv3x3_wgrad_f16")
     return out[0], out[1], scratch
 
 

@@ -51,6 +51,18 @@ def train_option(params):
     return train_layers(params) is not None
 
 
+def wgrad_option(params):
+    """The [TRAIN] key `wgrad`: absent or `fp32` -> False (yolo_conv3x3_wgrad, today's steps), `fp16` -> True (yolo_conv3x3_wgrad_f16 in the
+    tail and blocks steps), anything else raises ValueError."""
+    raw = params.get("wgrad")
+    if raw is None:
+        return False
+    word = str(raw).strip().lower()
+    if word not in ("fp32", "fp16"):
+        raise ValueError("wgrad must be fp32 (the float32 3 x 3 weight gradient) or fp16 (its fp16-operand form), got %r" % (raw,))
+    return word == "fp16"
+
+
 def augment_option(params):
     """The [TRAIN] key `augment`: absent -> False, `device` -> True (augmentation on the device), anything else raises ValueError."""
     raw = params.get("augment")
@@ -81,6 +93,13 @@ def check_params(params, version):
     elif not str(version).startswith("v2"):
         raise NotImplementedError(NOT_SUPPORTED + " for %s networks: the reference has a loss for YOLOv2 only"
                                   " (train_layers = heads trains the detection convs of a v3 network)" % version)
+    if wgrad_option(params):
+        if train_layers(params) not in ("tail", "head_blocks"):
+            raise ValueError("wgrad = fp16 is the weight gradient of the trained 3 x 3 blocks: it goes with train_layers = tail or head_blocks, "
+                             "not with train_layers = %s (no 3 x 3 block is trained)" % train_layers(params))
+        if str(params.get("dtype", "fp32")).strip().lower() == "fp32":
+            raise ValueError("wgrad = fp16 reads the block's input as the plan stores it, in fp16: it needs dtype = fp16 (a float32 plan stores "
+                             "float32 activations)")
     prob = float(params.get("augment_probability", 0))
     if not augment_option(params):
         if prob != 0:
@@ -448,6 +467,9 @@ def train_head(model, params):
         from . import augment as yaug
         augment = (yaug.stream(seed), augment_prob)
         print("Augmentation on the device with probability {}.".format(augment_prob))
+    if wgrad_option(params):
+        eng.set_wgrad_f16(True)
+        print("3 x 3 weight gradients on the fp16 matrix cores.")
     result = eng.torch.empty(yeval.LOSS_RESULT_DTYPE.itemsize, dtype=eng.torch.uint8, device=eng.device)
     train_loss_mva, updates = None, 0
     for epoch in range(1, epochs + 1):
