@@ -65,6 +65,8 @@
  *   yolo_augment_truths_host
  *                           net/base.py:107-111: augment_bounding_boxes(...).remove_out_of_image().cut_out_of_image()
  *                           (+ yolo_augment_check, yolo_augment_tile: no reference call site)
+ *   yolo_anchor_kmeans      net/v2.py:299-323, net/base.py:49-52: generate_anchors / run_kmeans (sklearn's KMeans), on the device
+ *                           (+ yolo_anchor_plan: no reference call site)
  */
 #ifndef YOLO_HIP_H
 #define YOLO_HIP_H
@@ -120,7 +122,9 @@ extern "C" {
                                           yolo_net_train_blocks_step_v3, yolo_net_train_blocks_step_v3_u8;
                                           added WITHIN ABI 7 in the same way (new exports, the yolo_conv3x3_wgrad_f16_plan POD only) -- the 3 x 3 weight
                                           gradient on the fp16 matrix cores and its mode on a net: yolo_conv3x3_wgrad_f16_plan, yolo_conv3x3_wgrad_f16,
-                                          yolo_net_train_wgrad_f16_bytes, yolo_net_train_set_wgrad_f16 */
+                                          yolo_net_train_wgrad_f16_bytes, yolo_net_train_set_wgrad_f16;
+                                          added WITHIN ABI 7 in the same way (new exports, the yolo_anchor_* PODs and enums only) -- anchor k-means on the
+                                          device: yolo_anchor_plan, yolo_anchor_kmeans */
 
 enum yolo_status {
     YOLO_OK = 0,
@@ -1263,6 +1267,110 @@ int yolo_augment_u8(const uint8_t *src_dev, uint8_t *dst_dev, int n, int h, int 
 int yolo_augment_truths_host(const yolo_gt *in, int n_in, const yolo_augment_image *params, int h, int w, yolo_gt *out, int32_t *n_out);
 /* The kernel's constants (test hook): the output tile of a workgroup and the images one launch covers.  Any pointer may be null. */
 int yolo_augment_tile(int32_t *rows, int32_t *cols, int32_t *images_per_launch);
+
+/* ---- Anchor k-means on the device (added within ABI 7: new exports, the yolo_anchor_* PODs and enums only) -------------------------
+ * The reference chooses anchors with sklearn.cluster.KMeans(n_clusters, tol) over the normalised (w, h) of every annotated box and scales
+ * the centres by input / stride (net/v2.py:299-323, net/base.py:49-52): k-means++ seeding, n_init = 10, max_iter = 300, Lloyd, Euclidean
+ * distance, an unseeded generator.  Here the same solver as a DEFINITION that leaves no tolerance: the data are fixed-point numbers, every
+ * sum is an integer, every float64 operation is rounded on its own, and the random stream is counter-based -- so the result is the same
+ * bits on every call and equals a sequential NumPy restatement (tests/anchor_ref.py) for any input.  DELIBERATE DIFFERENCES from sklearn:
+ * (a) the data are quantised to 40 bits; (b) seeding draws one candidate per round, not the greedy 2 + log k; (c) an empty cluster keeps
+ * its centre (sklearn moves it to a far point); (d) the random stream; (e) the distance 1 - IoU is offered beside the Euclidean one
+ * (YOLOv2 paper, Darknet's calc_anchors).
+ *
+ * Data      n boxes as float64 (w, h), normalised by their image.  A value v is valid iff it is finite, 0 < v <= 1 and
+ *           q = rint(v * 2^40) >= 1 (ties to even); a box is valid iff both are.  The problem's data are v' = q * 2^-40, at most 2^-41 from
+ *           v.  Invalid boxes are skipped, counted (n_bad), labelled -1 and raise YOLO_ANCHOR_BAD_BOX.  1 <= n <= 2^22, 1 <= k <= 32,
+ *           1 <= n_init <= 64, 1 <= max_iter <= 10000.
+ * Centres   sums of q over a cluster are exact 64-bit integers in any order; centre = float64(S q) / (float64(count) * 2^40): one
+ *           conversion, one division, each correctly rounded.  A cluster without boxes keeps its centre and raises
+ *           YOLO_ANCHOR_EMPTY_CLUSTER in its restart (at any centre update and at the final assignment).
+ * Distance  float64, every operation rounded on its own, with (w, h) = v' of the box and (cw, ch) a centre:
+ *             euclidean  d = (w - cw) * (w - cw) + (h - ch) * (h - ch)
+ *             iou        i = min(w, cw) * min(h, ch), d = 1 - i / (w * h + cw * ch - i)       (the sum first, then the difference)
+ *           The label is the first k with the smallest d (strict <, ascending k).  qd = floor(d * 2^40) as an unsigned 64-bit integer.
+ * Iteration assign with the current centres, then new centres; iterations count from 1.  euclidean (sklearn's rule): stop after iteration
+ *           t >= 2 if every label equals that of iteration t - 1; otherwise stop if S_k ((cw' - cw)^2 + (ch' - ch)^2) <= tolerate * V, the
+ *           sum taken in ascending k from 0.0, one term (a * a + b * b) at a time; otherwise stop at max_iter (YOLO_ANCHOR_MAX_ITER is
+ *           raised in a restart that stopped for that reason alone).  V = (var_w + var_h) / 2 with var = float64(N) / (float64(n_valid)
+ *           * float64(n_valid)) * 2^-80 and N = n_valid * S(q^2) - S(q)^2, an exact integer (the prepare kernel sums hi^2, hi * lo and lo^2
+ *           of q = hi * 2^20 + lo in 64-bit integers -- SPLIT accumulation -- and the host joins them in 128 bits and rounds once).
+ *           iou: stop when no label changed (t >= 2), or at max_iter; tolerate is not looked at.  After the last iteration ONE more
+ *           assignment against the final centres gives labels, counts, sums, the inertia S qd (an exact integer, also reported * 2^-40)
+ *           and avg_iou = float64(S floor(best * 2^40)) / (float64(n_valid) * 2^40), best = the largest i / (w * h + cw * ch - i) over the
+ *           centres -- reported for both distances.
+ * Seeding   when init is NULL: k-means++ with one draw per round.  Philox4x32-10 (the generator of the augmentation above) with the key
+ *           (seed & 0xffffffff, seed >> 32) and the counter (restart, round, 0, 0); u = word0 * 2^32 + word1.  Round j weighs every valid box
+ *           with D_i = 1 (round 0) or the smallest qd to the seeds chosen so far, in the CHOSEN distance (round j >= 1); T = S D_i;
+ *           t = floor(u * T / 2^64) (a 128-bit product); the pick is the first valid i whose inclusive prefix sum exceeds t, and the seed
+ *           is that box's v'.  T == 0 (fewer distinct boxes than k, or no valid box) marks the restart YOLO_ANCHOR_DEGENERATE: it runs no
+ *           iteration and is never best.  All integers: the picks do not depend on the order of any reduction.
+ *           With init ([k][2] float64, used as given): n_init must be 1; a centre that is not finite or not in (0, 1], or n_valid == 0,
+ *           marks the restart degenerate.
+ * Restarts  n_init restarts run side by side; the best has the lowest integer inertia, ties to the lowest index.  Its centres are
+ *           returned in ascending order of area cw * ch (float64; ties: cw, then cluster index) with counts, sums and labels renumbered to
+ *           match -- the order YOLOv3's scale masks expect.  If every restart is degenerate the header says YOLO_ANCHOR_DEGENERATE,
+ *           best_restart is -1, the best block is all zero and every label is -1.
+ * The header's status is YOLO_ANCHOR_BAD_BOX | (all degenerate: YOLO_ANCHOR_DEGENERATE) | the best restart's own bits. */
+#define YOLO_ANCHOR_MAX_K 32
+#define YOLO_ANCHOR_MAX_INIT 64
+#define YOLO_ANCHOR_MAX_N (1 << 22)
+#define YOLO_ANCHOR_ITER_LIMIT 10000
+enum yolo_anchor_distance { YOLO_ANCHOR_EUCLIDEAN = 0, YOLO_ANCHOR_IOU = 1 };
+enum yolo_anchor_status { YOLO_ANCHOR_BAD_BOX = 1, YOLO_ANCHOR_EMPTY_CLUSTER = 2, YOLO_ANCHOR_DEGENERATE = 4, YOLO_ANCHOR_MAX_ITER = 8 };
+
+typedef struct yolo_anchor_desc {
+    int32_t k, n_init, max_iter;
+    int32_t distance;               /* enum yolo_anchor_distance */
+    double tolerate;                /* euclidean only; finite, >= 0 */
+    uint64_t seed;
+} yolo_anchor_desc;
+
+/* How a call is split and where the parts of the scratch and of the result lie (every part starts at a 256-byte boundary). */
+struct yolo_anchor_plan {
+    int32_t chunk, n_chunks;        /* boxes per workgroup (1024), ceil(n / chunk) */
+    int32_t period;                 /* iterations enqueued between two reads of the finished-restart count */
+    int32_t threads;
+    uint64_t prep_offset, pick_offset, state_offset, q_offset, label_offset, label_stride, sums_offset, scratch_bytes;
+    uint64_t header_offset, restarts_offset, best_offset, result_bytes;
+};
+
+typedef struct yolo_anchor_header {         /* result + header_offset */
+    uint32_t status;
+    int32_t best_restart, n_valid, n_bad, k, n_init, distance, pad_;
+} yolo_anchor_header;
+typedef struct yolo_anchor_restart {        /* result + restarts_offset, [n_init] */
+    int32_t n_iter;
+    uint32_t status;
+    uint64_t inertia_q, iou_q;              /* S qd and S floor(best IoU * 2^40) of the final assignment */
+    int32_t seeds[YOLO_ANCHOR_MAX_K];       /* box index of seed j; -1: j >= k, init given, or not drawn */
+} yolo_anchor_restart;
+typedef struct yolo_anchor_best {           /* result + best_offset: the best restart, clusters in ascending order of area */
+    double centres[YOLO_ANCHOR_MAX_K][2];   /* (w, h); entries from k on are 0 */
+    int64_t counts[YOLO_ANCHOR_MAX_K];
+    uint64_t sum_q[YOLO_ANCHOR_MAX_K][2];
+    uint64_t inertia_q, iou_q;
+    double inertia, avg_iou;                /* inertia_q * 2^-40; float64(iou_q) / (float64(n_valid) * 2^40) */
+} yolo_anchor_best;
+
+/* The plan of a call with these sizes (pure host function): the sizing call for scratch and result.  YOLO_ERR_ARG, naming the field, for
+ * anything outside the ranges above, an unknown distance, or a tolerate that is negative or not finite. */
+int yolo_anchor_plan(const yolo_anchor_desc *desc, int64_t n, struct yolo_anchor_plan *out);
+/* wh_dev float64 [n][2]; init_dev float64 [k][2] or NULL (then seeded; with init n_init must be 1); scratch_dev / result_dev of at least the
+ * plan's sizes, 256-byte aligned, the scratch overlapping nothing else; labels_dev int32 [n] or NULL.  Every byte of the result, and of
+ * labels when given, is written by every successful call, and nothing the scratch, the result or labels held before is read.
+ * Kernels: prepare (validate, quantise, count, variance sums) | seeding, k rounds of two launches for all restarts at once (a weight pass
+ * with per-chunk integer sums; one workgroup per restart that scans them and finds the pick inside its chunk) | per iteration an
+ * assignment kernel on a (chunks x restarts) grid -- centres in LDS, per-cluster (S q_w, S q_h, count) and the changed count in integer LDS
+ * atomics, merged into the restart's record by 64-bit integer atomics -- and a tiny SECOND KERNEL (one workgroup per restart) for the
+ * centre update and the stop decision | final assignment | finish (best restart, order by area, the result) | labels.  There are no
+ * floating-point atomics, no cooperative launch and no waiting on another workgroup: a finished restart has its `done` flag set, its
+ * workgroups exit at once, and extra enqueued iterations change no bit.
+ * UNLIKE the step entries THIS ENTRY SYNCHRONISES WITH THE HOST on `stream`: once after the prepare kernel (the threshold is made from its
+ * sums on the host) and once after every `period` (8) enqueued iterations, to read one word, the count of finished restarts; it returns
+ * after a last synchronisation, with the result complete.  Every host loop is bounded by max_iter. */
+int yolo_anchor_kmeans(const yolo_anchor_desc *desc, const double *wh_dev, int64_t n, const double *init_dev, void *scratch_dev,
+                       size_t scratch_bytes, void *result_dev, size_t result_bytes, int32_t *labels_dev, void *stream);
 
 /* NMS of a HOST list (x,y,w,h as double, prob float, class int; scan order = index).  Synchronous;
  * allocates its own scratch.  keep_idx receives the indices of survivors in output order.

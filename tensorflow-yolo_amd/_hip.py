@@ -23,6 +23,10 @@ EVAL_OVERFLOW, EVAL_UNSORTED, EVAL_BAD_CLASS, EVAL_BAD_COUNT = 1, 2, 4, 8       
 EVAL_MAX_GT, EVAL_MAX_DET_CAPACITY, EVAL_MAX_CLASSES = 1024, 1 << 20, 65536
 LOSS_OUT_OF_GRID, LOSS_BAD_BOX, LOSS_BAD_CLASS, LOSS_BAD_COUNT = 1, 2, 4, 8     # enum yolo_loss_status
 LOSS_MAX_CELLS = 4096
+ANCHOR_EUCLIDEAN, ANCHOR_IOU = 0, 1               # enum yolo_anchor_distance
+ANCHOR_DISTANCES = {"euclidean": ANCHOR_EUCLIDEAN, "iou": ANCHOR_IOU}
+ANCHOR_BAD_BOX, ANCHOR_EMPTY_CLUSTER, ANCHOR_DEGENERATE, ANCHOR_MAX_ITER = 1, 2, 4, 8        # enum yolo_anchor_status
+ANCHOR_MAX_K, ANCHOR_MAX_INIT, ANCHOR_MAX_N, ANCHOR_ITER_LIMIT = 32, 64, 1 << 22, 10000
 FRAMES_PER_LAUNCH = 64                          # frames one launch of the batched resize covers (larger batches: consecutive launches)
 MAX_SRC, MAX_ANCHORS, MAX_SCALES = 4, 8, 4
 # Records per image every Python entry point asks for unless told otherwise.  The reference's lists are unbounded
@@ -197,6 +201,33 @@ class AugmentImage(C.Structure):
                 ("drop_thr", C.c_uint32), ("noise_q", C.c_int32 * 2), ("noise_loc", C.c_int32 * 2), ("tx", C.c_int32), ("key", C.c_uint32 * 2)]
 
 
+class AnchorDesc(C.Structure):
+    """yolo_anchor_desc: one anchor k-means problem"""
+    _fields_ = [("k", C.c_int32), ("n_init", C.c_int32), ("max_iter", C.c_int32), ("distance", C.c_int32), ("tolerate", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class AnchorPlan(C.Structure):
+    """struct yolo_anchor_plan: the split of an anchor k-means call and the layout of its scratch and result"""
+    _fields_ = [(n, C.c_int32) for n in ("chunk", "n_chunks", "period", "threads")] + \
+               [(n, C.c_uint64) for n in ("prep_offset", "pick_offset", "state_offset", "q_offset", "label_offset", "label_stride",
+                                          "sums_offset", "scratch_bytes", "header_offset", "restarts_offset", "best_offset", "result_bytes")]
+
+
+class AnchorHeader(C.Structure):
+    _fields_ = [("status", C.c_uint32)] + [(n, C.c_int32) for n in ("best_restart", "n_valid", "n_bad", "k", "n_init", "distance", "pad_")]
+
+
+class AnchorRestart(C.Structure):
+    _fields_ = [("n_iter", C.c_int32), ("status", C.c_uint32), ("inertia_q", C.c_uint64), ("iou_q", C.c_uint64),
+                ("seeds", C.c_int32 * ANCHOR_MAX_K)]
+
+
+class AnchorBest(C.Structure):
+    _fields_ = [("centres", (C.c_double * 2) * ANCHOR_MAX_K), ("counts", C.c_int64 * ANCHOR_MAX_K), ("sum_q", (C.c_uint64 * 2) * ANCHOR_MAX_K),
+                ("inertia_q", C.c_uint64), ("iou_q", C.c_uint64), ("inertia", C.c_double), ("avg_iou", C.c_double)]
+
+
 class WsRegion(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("offset", C.c_uint64), ("used_bytes", C.c_uint64), ("region_bytes", C.c_uint64)]
 
@@ -360,6 +391,10 @@ SIGNATURES = {
     "yolo_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(AugmentImage), C.c_void_p]),
     "yolo_augment_truths_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(AugmentImage), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]),
     "yolo_augment_tile": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # anchor k-means (added within ABI 7)
+    "yolo_anchor_plan": (C.c_int, [C.POINTER(AnchorDesc), C.c_int64, C.POINTER(AnchorPlan)]),
+    "yolo_anchor_kmeans": (C.c_int, [C.POINTER(AnchorDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_void_p]),
     "yolo_nms_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int,
                                 C.c_void_p, C.POINTER(C.c_int32)]),
 }
@@ -467,6 +502,25 @@ def augment_tile():
     out = [C.c_int32() for _ in range(3)]
     check(lib().yolo_augment_tile(*[C.byref(v) for v in out]), "yolo_augment_tile")
     return tuple(int(v.value) for v in out)
+
+
+def anchor_distance(name):
+    """'euclidean' | 'iou' (the .ini key `distance`, the `distance` argument of kmeans_anchors) -> enum yolo_anchor_distance; else ValueError"""
+    key = str(name).strip().lower()
+    if key not in ANCHOR_DISTANCES:
+        raise ValueError("distance must be euclidean or iou, got %r" % (name,))
+    return ANCHOR_DISTANCES[key]
+
+
+def anchor_desc(k, n_init=10, max_iter=300, distance=ANCHOR_EUCLIDEAN, tolerate=0.005, seed=0):
+    return AnchorDesc(int(k), int(n_init), int(max_iter), int(distance), float(tolerate), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def anchor_plan(desc, n):
+    """yolo_anchor_plan as a dict (host only)"""
+    pl = AnchorPlan()
+    check(lib().yolo_anchor_plan(C.byref(desc), int(n), C.byref(pl)), "yolo_anchor_plan")
+    return {name: int(getattr(pl, name)) for name, _ in AnchorPlan._fields_}
 
 
 def check(rc, what=""):

@@ -860,6 +860,62 @@ int yolo_augment_tile(int32_t *rows, int32_t *cols, int32_t *images_per_launch) 
     return YOLO_OK;
 }
 
+// ---- anchor k-means (anchor_host.cpp: plan, checks, threshold; anchor.hip: the kernels)
+int yolo_anchor_plan(const yolo_anchor_desc *desc, int64_t n, struct yolo_anchor_plan *out) {
+    std::string err;
+    const int rc = anchor_plan(desc, n, out, err);
+    if (rc) return fail(rc, "yolo_anchor_plan: " + err);
+    return YOLO_OK;
+}
+
+int yolo_anchor_kmeans(const yolo_anchor_desc *desc, const double *wh_dev, int64_t n, const double *init_dev, void *scratch_dev,
+                       size_t scratch_bytes, void *result_dev, size_t result_bytes, int32_t *labels_dev, void *stream) {
+    std::string err;
+    const int rc = anchor_call_check(desc, wh_dev, n, init_dev, scratch_dev, scratch_bytes, result_dev, result_bytes, labels_dev, err);
+    if (rc) return fail(rc, "yolo_anchor_kmeans: " + err);
+    struct yolo_anchor_plan pl;
+    anchor_plan(desc, n, &pl, err);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AnchorParams p = anchor_params(*desc, pl, wh_dev, (int)n, init_dev, scratch_dev, result_dev, labels_dev);
+    // nothing the scratch or the result held is read: the counts start at 0, every label of the iteration before at "none"
+    HIP_TRY(hipMemsetAsync(p.prep, 0, sizeof(AnchorPrep), s));
+    HIP_TRY(hipMemsetAsync(p.label8, 0xff, (size_t)pl.label_stride * (size_t)desc->n_init, s));
+    HIP_TRY(hipMemsetAsync(result_dev, 0, (size_t)pl.result_bytes, s));
+    HIP_TRY(launch_anchor(ANCHOR_PREPARE, p, s));
+    AnchorPrep prep;
+    HIP_TRY(hipMemcpyAsync(&prep, p.prep, sizeof prep, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    p.threshold = anchor_threshold(prep, desc->tolerate);
+    HIP_TRY(launch_anchor(ANCHOR_INIT, p, s));
+    if (!init_dev) {
+        for (int round = 0; round < desc->k; ++round) {
+            p.round = round;
+            HIP_TRY(launch_anchor(ANCHOR_SEED_SUM, p, s));
+            HIP_TRY(launch_anchor(ANCHOR_SEED_PICK, p, s));
+        }
+        p.round = 0;
+    }
+    // iterations in batches of `period`; between batches one word comes back: how many restarts have stopped.  At most max_iter
+    // iterations are ever enqueued, after which the update kernel has stopped every restart.
+    for (int issued = 0;;) {
+        unsigned long long n_done = 0;
+        HIP_TRY(hipMemcpyAsync(&n_done, &p.prep->n_done, sizeof n_done, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (n_done >= (unsigned long long)desc->n_init || issued >= desc->max_iter) break;
+        const int m = desc->max_iter - issued < pl.period ? desc->max_iter - issued : pl.period;
+        for (int i = 0; i < m; ++i) {
+            HIP_TRY(launch_anchor(ANCHOR_ASSIGN, p, s));
+            HIP_TRY(launch_anchor(ANCHOR_UPDATE, p, s));
+        }
+        issued += m;
+    }
+    HIP_TRY(launch_anchor(ANCHOR_FINAL, p, s));
+    HIP_TRY(launch_anchor(ANCHOR_FINISH, p, s));
+    if (labels_dev) HIP_TRY(launch_anchor(ANCHOR_LABELS, p, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return YOLO_OK;
+}
+
 int yolo_u8_unit_table(float *out256) {
     if (!out256) return fail(YOLO_ERR_ARG, "yolo_u8_unit_table: null argument");
     for (unsigned u = 0; u < 256; ++u) out256[u] = u8_unit(u);     // the function the input kernels run on every byte

@@ -15,6 +15,7 @@
 // The source is read through the tile loads only and the destination is only written.  Per pixel at most two Philox calls (one at the
 // reference's parameters, where the second noise step has d == 0): ~60 integer multiplies, nothing beside the LDS traffic of the blur.
 #include "yolo_internal.h"
+#include "philox.h"
 
 namespace yolo {
 
@@ -26,18 +27,6 @@ constexpr int SRC_PITCH = (SRC_COLS * 3 + 7) / 8 * 8;      // bytes of an LDS ro
 constexpr int HS_PITCH = TC * 3;                           // 16-bit values of an LDS row of Hs: 384 bytes, a run starts 8-byte aligned
 static_assert(SRC_COLS * 3 <= 256, "one thread per byte column of the tile load");
 static_assert(TR * (TC / 4) % 256 == 0 && TC % 4 == 0, "whole runs per thread");
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-    unsigned c2 = 0u, c3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 
 // the noise of one step from two words: d = (s * q + 2^23) >> 24, s the sum of the four 16-bit halves less 131070
 __device__ __forceinline__ int noise_delta(unsigned a, unsigned b, int q) {

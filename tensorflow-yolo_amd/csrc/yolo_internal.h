@@ -20,6 +20,7 @@
 #include "train_tail_host.h"
 #include "train3_tail_host.h"
 #include "augment_host.h"
+#include "anchor_host.h"
 #include "loss3_host.h"
 
 namespace yolo {
@@ -540,6 +541,9 @@ hipError_t launch_resize(const ResizeParams &p, hipStream_t s, bool dst_u8 = fal
 hipError_t launch_frames_resize(const FramesParams &p, int n, hipStream_t s, bool dst_u8);     // n <= kFramesPerLaunch frames
 hipError_t launch_boxes_to_frames(const RemapParams &p, int n, hipStream_t s);                 // n <= kFramesPerLaunch images
 hipError_t launch_augment(const AugmentParams &p, int n, hipStream_t s);                      // augment.hip: n <= kAugPerLaunch images
+// anchor.hip: one kernel of the anchor k-means (ANCHOR_SEED_SUM / _PICK: p.round is the seeding round)
+enum AnchorStage { ANCHOR_PREPARE, ANCHOR_INIT, ANCHOR_SEED_SUM, ANCHOR_SEED_PICK, ANCHOR_ASSIGN, ANCHOR_UPDATE, ANCHOR_FINAL, ANCHOR_FINISH, ANCHOR_LABELS };
+hipError_t launch_anchor(int stage, const AnchorParams &p, hipStream_t s);
 hipError_t launch_first(const FirstParams &p, int dtype, hipStream_t s, bool in_u8 = false);
 hipError_t launch_stem(const StemParams &p, int batch, hipStream_t s, int max_grid = kStemGrid, bool in_u8 = false);     // stem.hip
 hipError_t launch_pool(const PoolParams &p, int dtype, hipStream_t s);

@@ -8,7 +8,9 @@ network picked by COMMON.version.  `test` runs on this backend, and `eval` (not 
 network on an annotated directory, from an [EVAL] section laid over [TEST] (eval_params); `train` runs when [TRAIN] has
 `train_layers = head` (the detection layer on a frozen backbone: net/train.py; `seed` seeds the shuffle and a drawn head; `tail` adds the
 last 3 x 3 block of a v2 network, `heads` trains the detection convs of a v3 network, `head_blocks` those and the 3 x 3 block behind
-each); otherwise
+each); `anchor` runs when [ANCHOR] has `kmeans = device` (k-means over the boxes of `annotation_dir` on the device: net/anchors.py; optional
+keys `distance` euclidean | iou, `n_init`, `max_iter`, `seed`; prints the reference's four lines, then the run's figures and the anchors as a
+list ready for an .ini); otherwise
 `train` and `anchor` end with a clear message.  Extra, optional keys: `dtype` (fp32 | fp16 | mxfp8: block-scaled fp8 3x3 convs), `nms_mode` (agnostic | per_class), `max_boxes` / `cand_capacity` (record caps), `autotune` (True: per-layer tile timing at start-up),
 `resize` (stretch, the reference's geometry and the default | letterbox, Darknet's: aspect ratio kept, grey canvas, boxes mapped back to the frame),
 `loss` ([EVAL] only; true: also report the reference's validation loss, net/yolo.py:177-193 -- YOLOv2, resize = stretch);
@@ -113,6 +115,24 @@ def run(cfg, mode, section=None):
         ytrain.train_option(params)
         ytrain.check_params(params, cfg["COMMON"]["version"])
         yolo.train(params)
+    elif mode == "anchor" and "kmeans" in cfg.get("ANCHOR", {}):          # k-means on the device (net/anchors.py)
+        from .net import anchors as yanchors
+        params = dict(cfg["ANCHOR"])
+        params.update(cfg["COMMON"])
+        yanchors.anchor_option(params)
+        yanchors.check_params(params, cfg["COMMON"]["version"])
+        anchors, class_names = yolo.generate_anchors(params)
+        print("Anchors: ")
+        print("\t{}".format(anchors))
+        print("Class names: ")
+        print("\t{}".format(class_names))
+        res = yolo.last_anchor_result
+        print("distance: {}".format("iou" if res.distance else "euclidean"))
+        print("best restart: {} of {}".format(res.best_restart, len(res.restarts)))
+        print("iterations: {}".format(res.n_iter))
+        print("avg_iou: {:.6f}".format(res.avg_iou))
+        print("boxes used: {}, skipped: {}".format(res.n_valid, res.n_bad))
+        print("anchors = {}".format([float(v) for v in anchors]))
     elif mode in ("train", "anchor"):
         raise SystemExit("mode '{}' is not supported by the HIP inference backend (TEST mode only)".format(mode))
     else:

@@ -1135,6 +1135,69 @@ def conv3x3_wgrad_f16(x, d, scale=None, scratch=None, out=None):
     return out[0], out[1], scratch
 
 
+def anchor_plan(n, k, distance=_hip.ANCHOR_EUCLIDEAN, tolerate=0.005, n_init=10, max_iter=300, seed=0):
+    """yolo_anchor_plan as a dict (host only): chunk, n_chunks, period, the offsets of the scratch's and the result's parts, both sizes"""
+    return _hip.anchor_plan(_hip.anchor_desc(k, n_init, max_iter, distance, tolerate, seed), n)
+
+
+def anchor_result(raw, plan, n_init):
+    """The result block of yolo_anchor_kmeans (raw: its bytes on the host, a uint8 array) -> dict: the header's fields, `restarts` (a list
+    of dicts: n_iter, status, inertia_q, iou_q, seeds) and the best block's fields as NumPy arrays / ints / floats"""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    hdr = _hip.AnchorHeader.from_buffer_copy(raw[plan["header_offset"]:].tobytes()[:C.sizeof(_hip.AnchorHeader)])
+    out = {name: int(getattr(hdr, name)) for name, _ in _hip.AnchorHeader._fields_ if name != "pad_"}
+    size = C.sizeof(_hip.AnchorRestart)
+    table = raw[plan["restarts_offset"]:plan["restarts_offset"] + n_init * size].tobytes()
+    out["restarts"] = []
+    for r in range(n_init):
+        row = _hip.AnchorRestart.from_buffer_copy(table[r * size:(r + 1) * size])
+        out["restarts"].append(dict(n_iter=int(row.n_iter), status=int(row.status), inertia_q=int(row.inertia_q), iou_q=int(row.iou_q),
+                                    seeds=[int(v) for v in row.seeds]))
+    best = _hip.AnchorBest.from_buffer_copy(raw[plan["best_offset"]:].tobytes()[:C.sizeof(_hip.AnchorBest)])
+    out["centres"] = np.array([[c[0], c[1]] for c in best.centres], dtype=np.float64)
+    out["counts"] = np.array(list(best.counts), dtype=np.int64)
+    out["sum_q"] = np.array([[c[0], c[1]] for c in best.sum_q], dtype=np.uint64)
+    out["inertia_q"], out["iou_q"] = int(best.inertia_q), int(best.iou_q)
+    out["inertia"], out["avg_iou"] = float(best.inertia), float(best.avg_iou)
+    return out
+
+
+def anchor_kmeans(wh, k, distance=_hip.ANCHOR_EUCLIDEAN, tolerate=0.005, n_init=10, max_iter=300, seed=0, init=None, scratch=None,
+                  result=None, labels=True):
+    """yolo_anchor_kmeans on the device of `wh`: a contiguous float64 device tensor [n, 2] of normalised (w, h).  init: a float64 device
+    tensor [k, 2] of starting centres (then n_init must be 1) or None (seeded); scratch / result: uint8 device tensors to run in (tests
+    pre-fill them), else allocated; labels: True (an int32 tensor is allocated), a tensor to write into, or False / None (no labels).
+    UNLIKE the other operators this call synchronises with the host between batches of iterations.  Returns (dict as anchor_result plus
+    "raw": the result block's bytes as a NumPy array, labels tensor or None)."""
+    torch = _torch()
+    if wh.dtype != torch.float64 or not wh.is_contiguous() or wh.dim() != 2 or wh.shape[1] != 2 or not wh.is_cuda:
+        raise ValueError("anchor_kmeans: expected a contiguous float64 device tensor [n, 2]")
+    if init is not None and (init.dtype != torch.float64 or not init.is_contiguous() or tuple(init.shape) != (int(k), 2) or init.device != wh.device):
+        raise ValueError("anchor_kmeans: expected init as a contiguous float64 tensor [%d, 2] on the device of wh" % int(k))
+    dev, n = wh.device, int(wh.shape[0])
+    desc = _hip.anchor_desc(k, n_init, max_iter, distance, tolerate, seed)
+    pl = _hip.anchor_plan(desc, n)
+    with torch.cuda.device(dev):
+        if scratch is None:
+            scratch = torch.empty(pl["scratch_bytes"], dtype=torch.uint8, device=dev)
+        if result is None:
+            result = torch.empty(pl["result_bytes"], dtype=torch.uint8, device=dev)
+        if labels is True:
+            labels = torch.empty(n, dtype=torch.int32, device=dev)
+        elif labels is False:
+            labels = None
+        if labels is not None and (labels.dtype != torch.int32 or not labels.is_contiguous() or labels.numel() != n):
+            raise ValueError("anchor_kmeans: expected labels as a contiguous int32 tensor [%d]" % n)
+        _hip.check(_hip.lib().yolo_anchor_kmeans(C.byref(desc), wh.data_ptr(), n, init.data_ptr() if init is not None else None,
+                                                 scratch.data_ptr(), scratch.numel(), result.data_ptr(), result.numel(),
+                                                 labels.data_ptr() if labels is not None else None,
+                                                 torch.cuda.current_stream(dev).cuda_stream), "yolo_anchor_kmeans")
+        raw = result[:pl["result_bytes"]].cpu().numpy()
+    out = anchor_result(raw, pl, int(n_init))
+    out["raw"] = raw
+    return out, labels
+
+
 def check_status(status, allow_truncation=False):
     """The reference's lists are unbounded (net/base.py:195-209); the record buffers are not.  Both overflow bits mean the
     result would differ from the reference's, so both raise: bit 0 = more candidates than cand_capacity passed the

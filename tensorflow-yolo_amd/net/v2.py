@@ -7,8 +7,8 @@ order unchanged).  `create_tiny_network` is NOT in the reference: it is upstream
 yolov2-tiny-voc.cfg written in the same vocabulary (the reference ships only its anchors,
 resource/yolov2-tiny-voc.anchors).
 
-Training pieces of the reference file (loss, ground truth, batches, anchor k-means, :123-323)
-are out of scope for this inference backend.
+Training pieces of the reference file (loss, ground truth, batches, :123-295) are out of scope
+for this inference backend; its anchor k-means (:299-323) is net/anchors.py.
 """
 import numpy as np
 

@@ -2,7 +2,8 @@
 and the factored-out per-batch body `predict(x_batch)`.
 
 Counterpart of the reference's net/yolo.py (TEST path :41-96; binding classes :198-211).
-Training (`generate_anchors`, `create_loss_fn`, batches) is out of scope: those entries raise, and so does `train` unless [TRAIN] has
+Training (`create_loss_fn`, batches) is out of scope: those entries raise, so does `generate_anchors` unless [ANCHOR] has
+`kmeans = device` -- then the anchors come from k-means on the device (net/anchors.py) -- and so does `train` unless [TRAIN] has
 `train_layers = head` -- then the detection layer is trained on the device on a frozen backbone (net/train.py).  The loss itself and its
 gradient with respect to the head logits exist (`Yolo.loss`, `Yolo.loss_grad`, net/lossfn.py); a backward pass through the rest of the
 network does not.
@@ -38,7 +39,14 @@ class Yolo(object):
         ytrain.train_head(self, params)
 
     def generate_anchors(self, params):
-        raise NotImplementedError("anchor mode is not supported by the HIP inference backend")
+        """The reference's generate_anchors (net/v2.py:299-323) as k-means on the device, only when [ANCHOR] has `kmeans = device`
+        (net/anchors.py); without the key anchor mode is what it was: not supported.  -> (anchors in the unit of the network's .ini,
+        ascending by area; class names, sorted); the whole result stays in `last_anchor_result`."""
+        from . import anchors as yanchors
+        if not yanchors.anchor_option(params):
+            raise NotImplementedError("anchor mode is not supported by the HIP inference backend")
+        anchors, class_names, self.last_anchor_result = yanchors.generate_anchors(params, self.version)
+        return anchors, class_names
 
     def create_loss_fn(self, batch_size, net, anchors, class_names):
         raise NotImplementedError("training is not supported by the HIP inference backend")
