@@ -1208,7 +1208,9 @@ int yolo_net_train_blocks_step_v3_u8(yolo_net *net, const uint8_t *in_dev, int b
  * mode); everything else in the step, the state and the state layouts is unchanged, and a step is bit-identical to its parts through the
  * standalone exports with yolo_conv3x3_wgrad_f16 in that place.  extra_dev = NULL switches back: the steps are then the float32 steps, bit
  * for bit (bytes is not looked at).  YOLO_ERR_STATE for a float32 plan, saying so; YOLO_ERR_ARG for a buffer that is too small or not
- * 256-byte aligned; what the block checks refuse as they refuse it. */
+ * 256-byte aligned; what the block checks refuse as they refuse it.  The mode belongs to the net and nothing but this call changes it: every
+ * *_train_init*, yolo_net_load_weights, yolo_net_bind_workspace, yolo_net_set_streams and a refused yolo_net_train_set_wgrad_f16 leave it as
+ * it is, the head-only steps and every call that does not train do not look at it, and a second accepted call replaces the buffer and nothing else. */
 size_t yolo_net_train_wgrad_f16_bytes(const yolo_net *net);
 int yolo_net_train_set_wgrad_f16(yolo_net *net, void *extra_dev, size_t bytes);
 

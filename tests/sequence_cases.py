@@ -3,9 +3,10 @@
 The rule under test: the result of call i of a sequence equals, bit for bit, the result of the same call on a TWIN -- an engine built the
 same way that has executed only the CHANGING calls in front of i, in order, and then this call.  PURE calls (forward, forward_u8,
 forward_timed, detect / detect_u8 at 0.5, 0.05 and 0.9999 in both NMS modes, detect_frames, loss, loss_u8, loss_grad, loss_v3, loss_v3_u8,
-loss_v3_grad, a refused call) must leave nothing behind that a later call can observe; changing calls (a train step of any of the three
-families -- the YOLOv2 head, the YOLOv3 head convs, the YOLOv2 tail --, their inits, load_weights, a re-bind onto a poisoned buffer,
-set_streams, autotune, tune_streams) are what a twin replays.  twin_key(sequence, i) is the key a twin's result is cached under.
+loss_v3_grad, a refused call) must leave nothing behind that a later call can observe; changing calls (a train step of any of the four
+families -- the YOLOv2 head, the YOLOv3 head convs, the YOLOv2 tail, the YOLOv3 head convs with the 3 x 3 blocks behind them --, their
+inits, load_weights, a re-bind onto a poisoned buffer, set_streams, autotune, tune_streams, set_wgrad_f16 -- the mode bit of the tail and
+blocks steps --, poison_extra -- 0xFF into the buffer that mode runs in) are what a twin replays.  twin_key(sequence, i) is the key a twin's result is cached under.
 
 A call is a tuple: (kind, lo, n) runs on images lo .. lo + n - 1 of the plan's four distinct images, ("refuse", what) is a call the library
 must refuse (REFUSALS), a changing call is (kind, ...) of CHANGING; a train step is (kind, lo, n, t), Adam's step t = 1, 2, ...  Every list
@@ -19,6 +20,7 @@ step of ANOTHER family on the same net had packed there."""
 import functools
 import random
 
+import blocks_v3_cases
 import poison_cases as P
 from tensorflow_yolo_amd import _hip
 
@@ -42,15 +44,19 @@ LOSS_V3 = ("loss_v3", "loss_v3_u8", "loss_v3_grad")
 # 0.4: 1 (fp16), 3 (mxfp8), 1 (SPP), 4 (tiny) ignored rows and 6 truth rows; the control of tests/test_gpu_sequences.py asserts both kinds.
 IGNORE_THRESH = 0.4
 REFUSE = "refuse"
-# the three training families: the YOLOv2 detection layer, the head convs of a YOLOv3 network, the last 3 x 3 block and the detection layer
-# of a YOLOv2 network.  family -> (init kind, step kind, uint8 step kind)
+# the four training families: the YOLOv2 detection layer, the head convs of a YOLOv3 network, the last 3 x 3 block and the detection layer
+# of a YOLOv2 network, the head convs of a YOLOv3 network and the 3 x 3 block behind each.  family -> (init kind, step kind, uint8 step kind)
 FAMILIES = {"head": ("head_train_init", "train", "train_u8"),
             "v3": ("head_train_v3_init", "train_v3", "train_v3_u8"),
-            "tail": ("tail_train_init", "train_tail", "train_tail_u8")}
+            "tail": ("tail_train_init", "train_tail", "train_tail_u8"),
+            "blocks": ("blocks_train_v3_init", "train_blocks_v3", "train_blocks_v3_u8")}
+MODE_FAMILIES = ("tail", "blocks")      # the families whose steps look at the mode yolo_net_train_set_wgrad_f16 sets (csrc/train_api.cpp: block_wgrad_check)
+SET_ON, SET_OFF = ("set_wgrad_f16", True), ("set_wgrad_f16", False)
 INITS = {f[0]: name for name, f in FAMILIES.items()}                        # init kind -> family
 STEPS = {k: name for name, f in FAMILIES.items() for k in f[1:]}            # step kind -> family
 CHANGING = ("train", "train_u8", "head_train_init", "load_weights", "rebind", "set_streams", "autotune", "tune_streams",
-            "head_train_v3_init", "train_v3", "train_v3_u8", "tail_train_init", "train_tail", "train_tail_u8")
+            "head_train_v3_init", "train_v3", "train_v3_u8", "tail_train_init", "train_tail", "train_tail_u8",
+            "blocks_train_v3_init", "train_blocks_v3", "train_blocks_v3_u8", "set_wgrad_f16", "poison_extra")
 V3_KINDS = FORWARD + tuple(DETECT) + LOSS_V3 + (REFUSE,)
 V2_KINDS = FORWARD + tuple(DETECT) + LOSS + (REFUSE,)
 SWITCH_KINDS = ("forward", "forward_u8", "forward_timed", "detect@0.5", "detect@0.05/per-class", "detect@0.9999", REFUSE)
@@ -65,9 +71,16 @@ REFUSALS = {"batch+1": (ERR_ARG, "batch outside 1..max_batch"),
             "train-null-state": (ERR_ARG, "null state"),
             "train-two-parts": (ERR_STATE, "call yolo_net_set_streams(net, 1)"),
             "train_v3-two-parts": (ERR_STATE, "call yolo_net_set_streams(net, 1)"),
-            "set_streams(1)-split-arenas": (ERR_STATE, "part(s) only")}
+            "set_streams(1)-split-arenas": (ERR_STATE, "part(s) only"),
+            "train_blocks-on-mxfp8": (ERR_STATE, "the plan runs the conv behind the head conv as an MXFP8 conv"),
+            "train_blocks-two-parts": (ERR_STATE, "call yolo_net_set_streams(net, 1)"),
+            "set_wgrad_f16-on-fp32": (ERR_STATE, "a float32 plan stores float32 activations"),
+            "set_wgrad_f16-too-small": (ERR_ARG, "buffer too small (yolo_net_train_wgrad_f16_bytes)"),      # bytes: one less than ..._wgrad_f16_bytes
+            "set_wgrad_f16-unaligned": (ERR_ARG, "the buffer must be 256-byte aligned")}
 V3_REFUSALS = ("batch+1", "loss-on-v3", "set_streams(3)", "loss_grad-on-v3")
 V2_REFUSALS = ("batch+1", "set_streams(3)", "train-null-state", "loss_v3-on-v2")
+# the refused sets come first in a MODE plan's refusals: each_pure(sid, 0) then makes the too-small one, each_pure(sid, 1) the unaligned one
+SET_REFUSALS = ("set_wgrad_f16-too-small", "set_wgrad_f16-unaligned")
 
 # truths of the four images (x, y, w, h, class): one image has none
 TRUTHS = [[(0.3, 0.4, 0.2, 0.5, 1), (0.8, 0.2, 0.3, 0.3, 2)], [], [(0.5, 0.5, 0.6, 0.4, 7)],
@@ -76,11 +89,12 @@ MAX_GT = 3
 FRAME_SIZES = ((120, 90), (75, 200), (64, 64), (50, 131))     # detect_frames: frame i of the plan's four, letterboxed
 LR = 1e-3
 TAIL_LR = 1e-4      # tests/test_gpu_train_tail.py: the block's weights all move by lr in Adam's first step, at 1e-3 the second step's logits overflow exp()
+BLOCKS_LR = blocks_v3_cases.TRAIN_LR        # 1e-5, the rate tests/test_gpu_train_blocks_v3.py trains twenty steps with: every weight of three blocks moves by lr in step 1
 
 
 def step_lr(kind):
     """the learning rate of a train step of the table"""
-    return TAIL_LR if STEPS[kind] == "tail" else LR
+    return {"tail": TAIL_LR, "blocks": BLOCKS_LR}.get(STEPS[kind], LR)
 
 
 def is_changing(call):
@@ -103,20 +117,28 @@ def batch_of(call):
 
 # What a changing call reads and writes of the state a net and its engine carry between calls, as the drop rules of twin_key see it.  A
 # write replaces the whole of what it names.  PACKED: the regions of the device weights a family's init and steps re-pack.
-PACKED = {"head": ("packed head",), "v3": ("packed v3 heads",), "tail": ("packed head", "packed block")}
-STATE = {"head": "head state", "v3": "v3 state", "tail": "tail state"}
-NET = ("packed head", "packed block", "packed v3 heads", "workspace", "streams", "tiles")     # what every call that runs the net reads
+# "wgrad mode": net->wgrad_f16_dev / wgrad_f16_bytes, read by the steps of MODE_FAMILIES alone; "wgrad scratch": the bytes of the engine's
+# buffer behind that pointer, which nobody reads -- every byte a step reads of it is one the same step wrote --, so a poison_extra is
+# dropped from every twin.
+PACKED = {"head": ("packed head",), "v3": ("packed v3 heads",), "tail": ("packed head", "packed block"), "blocks": ("packed v3 heads", "packed v3 blocks")}
+STATE = {"head": "head state", "v3": "v3 state", "tail": "tail state", "blocks": "blocks state"}
+NET = ("packed head", "packed block", "packed v3 heads", "packed v3 blocks", "workspace", "streams", "tiles")     # what every call that runs the net reads
 
 
 def effects(call):
     """(what the changing call reads, what it writes)"""
     kind = call[0]
     if kind == "load_weights":
-        return set(), {"packed head", "packed block", "packed v3 heads"}
+        return set(), {"packed head", "packed block", "packed v3 heads", "packed v3 blocks"}
+    if kind == "set_wgrad_f16":
+        return set(), {"wgrad mode"}
+    if kind == "poison_extra":
+        return set(), {"wgrad scratch"}
     if kind in INITS:
         return set(), {STATE[INITS[kind]]} | set(PACKED[INITS[kind]])
     if kind in STEPS:       # forward through all packed weights, the family's state updated, its layers re-packed from it
-        return set(NET) | {STATE[STEPS[kind]]}, {STATE[STEPS[kind]]} | set(PACKED[STEPS[kind]])
+        mode = {"wgrad mode"} if STEPS[kind] in MODE_FAMILIES else set()
+        return set(NET) | {STATE[STEPS[kind]]} | mode, {STATE[STEPS[kind]]} | set(PACKED[STEPS[kind]])
     # a re-bind, a stream count, tuned tiles: each is the history of its own piece of state (the very thing a sequence is about), so it
     # reads what it writes and is never dropped
     if kind == "rebind":
@@ -131,8 +153,9 @@ def effects(call):
 
 
 def observes(call):
-    """what the result of a call may depend on: the net; for a train step its family's training state as well.  No call but a step of
-    its family reads a training state (a pure call has no access to one)."""
+    """what the result of a call may depend on: the net; for a train step its family's training state as well, and for a tail or a
+    blocks step the mode.  No call but a step of its family reads a training state (a pure call has no access to one), and no pure call
+    and no head-only step looks at the mode."""
     return set(NET) | (effects(call)[0] if is_changing(call) else set())
 
 
@@ -150,6 +173,12 @@ def twin_key(sequence, i):
         earlier steps left, and they are retained (the table has no such step: tests/test_sequences_cpu.py);
       * load_weights itself is dropped where no train step is retained in front of it: an init packs what load_weights packs, the net
         is as it was loaded;
+      * set_wgrad_f16 writes the mode and reads nothing: of on -> on the first is dropped (the second replaces the buffer and nothing
+        else), of on -> off the `on` where no retained tail or blocks step ran under it; no init and no load_weights writes the mode, so
+        a set is retained through them (which keeps the twin right and asserts nothing about an init: the twin replays it behind the same
+        set; MODE_SURVIVES compares across keys for that).  A set(off) with no set(on) retained in front of it is dropped as well, as load_weights is: the
+        net is as it was built, and the twin is one that never switched;
+      * poison_extra writes what nobody reads and is always dropped;
       * rebind, set_streams, autotune and tune_streams are never dropped."""
     calls = [c for c in sequence[:i] if is_changing(c)]
     while True:
@@ -161,6 +190,7 @@ def twin_key(sequence, i):
                 live = (live - writes) | reads
         kept.reverse()
         kept = [c for j, c in enumerate(kept) if c[0] != "load_weights" or any(p[0] in STEPS for p in kept[:j])]
+        kept = [c for j, c in enumerate(kept) if c != SET_OFF or SET_ON in kept[:j]]
         if kept == calls:
             return tuple(calls), sequence[i]
         calls = kept
@@ -201,12 +231,13 @@ _plan("v2-fp16", "v2-fp16-plan", V2_KINDS, V2_REFUSALS, train=("head",))
 _plan("v2-fp32", "v2-fp32-plan", V2_KINDS, V2_REFUSALS, train=("head",))
 _plan("v2-tiny-fp16", "v2-tiny-fp16-plan", V2_KINDS, V2_REFUSALS)
 _plan("v3-fp16", "v3-fp16-plan", V3_KINDS, V3_REFUSALS)
-_plan("v3-mxfp8", "v3-mxfp8-plan", V3_KINDS, V3_REFUSALS)
+_plan("v3-mxfp8", "v3-mxfp8-plan", V3_KINDS, V3_REFUSALS + ("train_blocks-on-mxfp8",))      # (the conv behind each head conv is an MXFP8 conv there)
 _plan("v3-spp-fp16", "v3-spp-fp16-plan", V3_KINDS, V3_REFUSALS)
 _plan("v3-tiny-fp32", "v3-tiny-fp32-plan", V3_KINDS, V3_REFUSALS)
 # streams = 0 at the smallest max_batch where the rule plans two full arenas: the plan yolo_net_set_streams can switch (max_batch: None
 # until asked for -- plan_kw -- since finding it plans the network a dozen times)
-_plan("v3-fp16-switch", "v3-fp16-plan", SWITCH_KINDS, ("batch+1", "set_streams(3)", "train_v3-two-parts"), train=("v3",), streams=0, max_batch=None)
+_plan("v3-fp16-switch", "v3-fp16-plan", SWITCH_KINDS, ("batch+1", "set_streams(3)", "train_v3-two-parts", "train_blocks-two-parts"), train=("v3",), streams=0,
+      max_batch=None)
 # YOLOv2 is never given two arenas by the rule (fewer than 40 conv launches), so its two-part plan is one with streams = 2: split arenas,
 # which yolo_net_set_streams cannot switch.  The train step is refused there; that it is accepted after set_streams(1) cannot be shown
 # on a YOLOv2 plan (v3-fp16-switch shows it for the YOLOv3 step).
@@ -224,6 +255,24 @@ for _sid in TRAIN_TAIL:
 HEAD_AND_TAIL = tuple(s + "-and-head" for s in TRAIN_TAIL)
 for _sid in HEAD_AND_TAIL:
     _plan(_sid, PLANS[_sid[:-len("-and-head")]]["pid"], V2_KINDS, V2_REFUSALS, train=("tail", "head"))
+# The fourth family, the YOLOv3 head convs and the 3 x 3 block behind each: the rows yolo_net_block_inputs_v3 accepts (test_sequences_cpu.py;
+# the MXFP8 row is refused, which is a refusal of `v3-mxfp8`).  The float32 row refuses the fp16 mode: that refusal is among its pure kinds.
+BLOCKS = ("v3-fp16-blocks", "v3-tiny-fp16-blocks", "v3-tiny-fp32-blocks")
+for _sid in BLOCKS:
+    _plan(_sid, _sid[:-len("-blocks")] + "-plan", V3_KINDS, (("set_wgrad_f16-on-fp32",) if "fp32" in _sid else ()) + V3_REFUSALS, train=("blocks",))
+# Two training states on one YOLOv3 net, head convs only and blocks, both packing the head convs: the analogue of HEAD_AND_TAIL
+BLOCKS_AND_HEADS = ("v3-tiny-fp16-blocks-and-heads", "v3-fp16-blocks-and-heads")
+for _sid in BLOCKS_AND_HEADS:
+    _plan(_sid, _sid[:-len("-blocks-and-heads")] + "-plan", V3_KINDS, V3_REFUSALS, train=("blocks", "v3"))
+# The fp16 mode of the tail and blocks steps, on the rows where yolo_net_train_wgrad_f16_bytes is not 0 (the fp16 rows).  The two tail rows
+# also train the head alone (`mode-and-head`): a step that does not look at the mode.
+MODE = ("v2-fp16-tail-f16", "v2-tiny-fp16-tail-f16", "v3-tiny-fp16-blocks-f16", "v3-fp16-blocks-f16")
+for _sid in MODE:
+    if _sid.endswith("-tail-f16"):
+        _plan(_sid, _sid[:-len("-tail-f16")] + "-plan", V2_KINDS, SET_REFUSALS + V2_REFUSALS, train=("tail", "head"))
+    else:
+        _plan(_sid, _sid[:-len("-blocks-f16")] + "-plan", V3_KINDS, SET_REFUSALS + V3_REFUSALS, train=("blocks",))
+TRAINING_PLANS = TRAIN_V3 + TRAIN_TAIL + HEAD_AND_TAIL + BLOCKS + BLOCKS_AND_HEADS + MODE      # the ids whose first sequence begins with an init and a step
 
 
 def plan_kw(sid):
@@ -378,7 +427,7 @@ for _sid in ("v2-fp16", "v2-fp32"):
     SEQUENCES[_sid].update(training_sequences(_sid, "head"))
 # 3b. the YOLOv3 head convs and the YOLOv2 tail; rebind-train: nothing the second step reads out of the workspace (the head convs' inputs,
 # the block's input, split-K slabs, ticket counters, the logits) may survive from the first -- the workspace is 0xFF in between
-for _sid in TRAIN_V3 + TRAIN_TAIL:
+for _sid in TRAIN_V3 + TRAIN_TAIL + BLOCKS:
     _init, _step, _ = FAMILIES[PLANS[_sid]["train"][0]]
     SEQUENCES[_sid] = training_sequences(_sid, PLANS[_sid]["train"][0])
     SEQUENCES[_sid]["rebind-train"] = [(_init,), (_step, 0, 3, 1), ("rebind",), (_step, 1, 3, 2)] + each_pure(_sid, 1)
@@ -387,6 +436,65 @@ for _sid in TRAIN_V3 + TRAIN_TAIL:
 for _sid in HEAD_AND_TAIL:
     SEQUENCES[_sid] = {"head-and-tail": [("head_train_init",), ("train", 0, 3, 1), ("tail_train_init",), ("train_tail", 0, 2, 1), ("train", 0, 4, 2)]
                        + each_pure(_sid, 0) + [("head_train_init",), ("train", 0, 3, 1)] + each_pure(_sid, 1)}
+# 3d. ... and on a YOLOv3 net, both packing the head convs: a head-convs step, a blocks step on the heads blocks_train_v3_init packed again
+# (its twin ran that init alone), a head-convs step on the blocks the blocks step packed; then head_train_v3_init again
+for _sid in BLOCKS_AND_HEADS:
+    SEQUENCES[_sid] = {"blocks-and-heads": [("head_train_v3_init",), ("train_v3", 0, 3, 1), ("blocks_train_v3_init",), ("train_blocks_v3", 0, 2, 1), ("train_v3", 0, 4, 2)]
+                       + each_pure(_sid, 0) + [("head_train_v3_init",), ("train_v3", 0, 3, 1)] + each_pure(_sid, 1)}
+
+
+# 3e. the fp16 mode of the tail and blocks steps, a bit on the net and a buffer of the engine's
+def mode_sequences(sid):
+    """mode: (1) init, set(on), step 1, every pure kind -- the refused too-small set among them, under the mode; (2) 0xFF into the
+    engine's buffer, step 2 at another batch size: what it reads of the buffer it wrote itself, and the refused set left the mode on;
+    (3) set(off), step 3, every pure kind on the other slice; (4) set(on), the too-small set refused once more, a uint8 step 4; (5)
+    load_weights, every pure kind: the untrained twins; (6) init and step 1 again: load_weights does not touch the mode (that the init does not is MODE_SURVIVES' to hold), the twin
+    is [set(on), init, step]; (7) set(off), init, step 1: the twin is the one that never switched.  A twin of (3) replays on and off
+    itself, so a set(off) that clears nothing shows at (7) alone.
+    mode-before-init: set(on), a loss under it (no pure call looks at the mode), set(on) again (it replaces the buffer and nothing else), init, step 1, re-bind onto 0xFF, step 2, every pure
+    kind.  mode-and-head, where the plan trains the head alone as well: tail init, set(on), tail step, head init, head-only step (it does
+    not look at the mode), tail step, every pure kind."""
+    init, step, step_u8 = FAMILIES[PLANS[sid]["train"][0]]
+    refused = (REFUSE, "set_wgrad_f16-too-small")
+    under = _call(sid, "loss_v3" if "loss_v3" in PLANS[sid]["kinds"] else "loss", 0)        # its twin: the untrained one, which never set the mode
+    out = {"mode": ([(init,), SET_ON, (step, 0, 3, 1)] + each_pure(sid, 0) + [("poison_extra",), (step, 0, 4, 2)]
+                    + [SET_OFF, (step, 0, 2, 3)] + each_pure(sid, 1) + [SET_ON, refused, (step_u8, 1, 3, 4)]
+                    + [("load_weights",)] + each_pure(sid, 0) + [(init,), (step, 0, 3, 1)] + [SET_OFF, (init,), (step, 0, 3, 1)]),
+           "mode-before-init": [SET_ON, under, SET_ON, (init,), (step, 0, 3, 1), ("rebind",), (step, 1, 3, 2)] + each_pure(sid, 1)}
+    if "head" in PLANS[sid]["train"]:
+        out["mode-and-head"] = ([(init,), SET_ON, (step, 0, 3, 1), ("head_train_init",), ("train", 0, 2, 1), (step, 0, 4, 2)] + each_pure(sid, 0))
+    return out
+
+
+for _sid in MODE:
+    SEQUENCES[_sid] = mode_sequences(_sid)
+# (the plan of the unsynchronised run below: train-2 under the mode, also run item by item so that its twins count against the cap)
+MODE_ASYNC = "v3-tiny-fp16-blocks-f16"
+_init, _step, _ = FAMILIES[PLANS[MODE_ASYNC]["train"][0]]
+SEQUENCES[MODE_ASYNC]["train-2"] = [(_init,), SET_ON, (_step, 0, 3, 1), ("forward", 0, 2), (_step, 0, 4, 2)] + each_pure(MODE_ASYNC, 1)
+
+
+
+# 3f. what must leave the mode alone.  A twin that replays the suspect call behind the same set(on) cannot see it clear the mode -- engine
+# and twin would both run float32 steps -- so these are comparisons ACROSS twin keys, not of a sequence with its twin:
+#   equal:  two keys whose first steps must be byte-equal.  The family's own init behind set(on) against in front of it (the mode bit is
+#           all that could differ: both keys are the sequences' own, row 6 of `mode` and its first step); on a tail plan head_train_init
+#           between set(on) and the tail step against the key without it (it packs the head tail_train_init packed, from the same values).
+#   differ: two keys whose first steps must differ in dw3 -- the same prefix with and without set(on), with a re-bind onto 0xFF between
+#           the set and the step: the mode is still on behind yolo_net_bind_workspace.  (Equality with the key that has no re-bind would
+#           claim more than the mode: twin_key never drops a re-bind.)
+# yolo_net_set_streams is not here: on these plans it returns before it does anything, and the plan it can switch has 196 images a batch.
+def mode_survives(sid):
+    init, step, _ = FAMILIES[PLANS[sid]["train"][0]]
+    first = (step, 0, 3, 1)
+    equal = [(((init,), SET_ON), (SET_ON, (init,)))]
+    if "head" in PLANS[sid]["train"]:
+        equal.append((((init,), SET_ON), ((init,), SET_ON, ("head_train_init",))))
+    differ = [(((init,), SET_ON, ("rebind",)), ((init,), ("rebind",)))]
+    return {"equal": [((a, first), (b, first)) for a, b in equal], "differ": [((a, first), (b, first)) for a, b in differ]}
+
+
+MODE_SURVIVES = {_sid: mode_survives(_sid) for _sid in MODE}
 
 # 5. a re-bind onto an 0xFF-filled buffer in the middle of a walk
 for _sid in ("v2-fp16", "v3-fp16", "v3-tiny-fp32"):
@@ -418,13 +526,14 @@ def switch_train_sequence(mb):
     trained heads; refused again; a second step after the next switch.  yolo_net_set_streams changes which arena a head input lives in."""
     refused = (REFUSE, "train_v3-two-parts")
     return ([("set_streams", 2), ("forward", 0, mb), refused, ("set_streams", 1), ("head_train_v3_init",), ("train_v3", 0, 4, 1), ("set_streams", 2),
-             ("detect@0.5", 0, mb)] + switch_body(mb) + [refused, ("set_streams", 1), ("train_v3", 0, 3, 2)] + switch_body(mb))     # (a body begins with the full batch)
+             ("detect@0.5", 0, mb)] + switch_body(mb) + [(REFUSE, "train_blocks-two-parts"), refused, ("set_streams", 1), ("train_v3", 0, 3, 2)]
+            + switch_body(mb))     # (a body begins with the full batch; the blocks step is refused at two parts as the head step is, with or without a state)
 
 
 SEQUENCES["v2-fp16-two-parts"] = {"refused-train": [("forward", 0, 4), (REFUSE, "train-two-parts"), ("forward", 0, 4), ("detect@0.5", 0, 3),
                                                     (REFUSE, "set_streams(1)-split-arenas"), ("detect@0.5", 0, 3), ("loss", 0, 4), (REFUSE, "train-two-parts"),
                                                     ("loss", 0, 4), ("forward", 0, 1)]}
-ALL_PLANS = MAIN + ("v3-fp16-switch", "v2-fp16-two-parts") + TRAIN_V3 + TRAIN_TAIL + HEAD_AND_TAIL
+ALL_PLANS = MAIN + ("v3-fp16-switch", "v2-fp16-two-parts") + TRAINING_PLANS
 
 
 def sequences_of(sid):
@@ -448,10 +557,13 @@ def control_engines(sid):
     """the engines the plan's first item builds for the controls that came with the YOLOv3 loss and the training families, beyond the twins
     its sequences cache: the second twin of each controlled call (tests/test_gpu_sequences.py: control) -- a loss_v3 call on a YOLOv3
     plan; on a training plan id a forward, a detect and the first step as well, and for head-and-tail the forward behind that step, which
-    is no call of the sequence.  They count against the first item's twins, so that it costs what any other item costs."""
+    is no call of the sequence; the same for blocks-and-heads; on a MODE plan the first step with the mode off as well, which the one with
+    the mode on must differ from (it is also the twin of the last step of `mode`, where it is counted once more: the count is an upper
+    bound, the item that meets it there is cut one twin short).  They count against the first item's twins, so that it costs what any
+    other item costs."""
     kinds = PLANS[sid]["kinds"]
-    if sid in TRAIN_V3 + TRAIN_TAIL + HEAD_AND_TAIL:
-        return 3 + ("loss_v3" in kinds) + (sid in HEAD_AND_TAIL)
+    if sid in TRAINING_PLANS:
+        return 3 + ("loss_v3" in kinds) + (sid in HEAD_AND_TAIL + BLOCKS_AND_HEADS + MODE)
     return int("loss_v3" in kinds)
 
 
@@ -488,9 +600,17 @@ INTERLEAVED_TRAIN_CALLS = 12
 INTERLEAVED_TRAIN = [(PAIR_TRAIN[i % 2], c) for i, c in enumerate(
     x for pair in zip(SEQUENCES[PAIR_TRAIN[0]]["train-2"][:INTERLEAVED_TRAIN_CALLS], SEQUENCES[PAIR_TRAIN[1]]["train-2"][:INTERLEAVED_TRAIN_CALLS]) for x in pair)]
 
+# 8c. ... and a blocks engine and a tail engine that both train in the fp16 mode, each in a buffer of its own: each engine's calls the start
+# of its `mode` sequence, up to the second step -- the one behind the 0xFF in its buffer
+PAIR_MODE = ("v3-tiny-fp16-blocks-f16", "v2-tiny-fp16-tail-f16")
+INTERLEAVED_MODE_CALLS = 20
+INTERLEAVED_MODE = [(PAIR_MODE[i % 2], c) for i, c in enumerate(
+    x for pair in zip(SEQUENCES[PAIR_MODE[0]]["mode"][:INTERLEAVED_MODE_CALLS], SEQUENCES[PAIR_MODE[1]]["mode"][:INTERLEAVED_MODE_CALLS]) for x in pair)]
+
 # 9. the covering walk without any host synchronisation between the calls (the plans that have one), and the train-2 sequence of one
-# plan of each training family (the plans that train)
-ASYNC_PLANS = ("v2-fp16", "v3-fp16", "v3-tiny-fp32-train", "v2-tiny-fp16-tail")
+# plan of each training family (the plans that train); of a MODE plan train-2 with a set(on) in front of the first step -- set(off) waits
+# for the device inside the engine and stays out of this run
+ASYNC_PLANS = ("v2-fp16", "v3-fp16", "v3-tiny-fp32-train", "v2-tiny-fp16-tail", "v3-tiny-fp16-blocks", MODE_ASYNC)
 
 # 7. exact chains (tests/test_gpu_exact.py's list; integer data: every tile and every split must give the integer reference), each run as
 # forward (1 image) -> autotune -> forward (3) -> tune_streams -> forward (2) -> forward_u8 -> forward (3) at max_batch 3
@@ -501,8 +621,9 @@ EXACT_STEPS = (("forward", 0, 1), ("autotune", 0, 3), ("forward", 0, 3), ("tune_
 
 
 def twin_keys(sid):
-    """the distinct twin keys of all sequences of a plan (the interleaved and the unsynchronised walks use calls of these sequences)"""
-    keys = set()
+    """the distinct twin keys of all sequences of a plan (the interleaved and the unsynchronised walks use calls of these sequences), and
+    of a MODE plan the keys MODE_SURVIVES compares"""
+    keys = {k for pairs in MODE_SURVIVES.get(sid, {}).values() for pair in pairs for k in pair}
     for seq in sequences_of(sid).values():
         keys.update(twin_key(seq, i) for i in range(len(seq)))
     return keys

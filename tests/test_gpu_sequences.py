@@ -3,8 +3,9 @@
 A yolo_net carries state from one call to the next -- on the host (obj_min_logit, obj_valid, cand_clean, side_ok, parts / halves, the
 tiles autotune chose) and on the device (the packed weights of the layers a train step re-packs, split-K ticket counters, candidate
 counters, the logits region with rows a sparse detect did not write, the compact objectness array, split-K slabs, the lifetime-packed
-arenas a train step reads activations out of, the fork / join events); an engine adds up to three training states (the YOLOv2 head, the
-YOLOv3 head convs, the YOLOv2 tail) and torch.empty scratch, assign and parts tensors per call.  Every other GPU test asks its question of
+arenas a train step reads activations out of, the fork / join events); an engine adds up to four training states (the YOLOv2 head, the
+YOLOv3 head convs, the YOLOv2 tail, the YOLOv3 head convs with the blocks behind them), the buffer of the fp16 weight-gradient mode -- a
+bit on the net that yolo_net_train_set_wgrad_f16 sets -- and torch.empty scratch, assign and parts tensors per call.  Every other GPU test asks its question of
 a freshly built engine.  Here whole sequences of calls run on ONE engine (tests/sequence_cases.py has the table and the rule,
 tests/test_sequences_cpu.py its properties), and the result of every call is compared, bit for bit, with the result of the same call on a
 TWIN: a fresh engine that has executed only the changing calls in front of it that still matter (sequence_cases.twin_key).  Twins are
@@ -15,12 +16,15 @@ What is compared: logits and gradients as bytes; counts, status and the first co
 fields of the loss records (`images`, `result`) of the YOLOv2 and the YOLOv3 loss, `assign` and `grad` as bytes; of a YOLOv2 head step the
 result and the six state arrays; of a YOLOv3 head step the result and per scale s the masters w[s], b[s], the moments m_w[s], v_w[s],
 m_b[s], v_b[s] and the gradients dw[s], db[s] of the engine's state; of a tail step the result and the sixteen parts of the tail state
-(TAIL_PARTS: the head's eight and the block's eight); the status code and message of a refused call.  There is no tolerance anywhere.
+(TAIL_PARTS: the head's eight and the block's eight); of a blocks step the result and per scale s those sixteen (`dw3[1]`: the weight
+gradient of the block behind head conv 1); the status code and message of a refused call.  There is no tolerance anywhere.
 
 Controls come first, per plan: two fresh twins making the same call give the same bytes -- a forward and a detect, a loss_v3 call where
 the plan has one, the first train step where the plan's sequences train.  If one fails the finding is NON-DETERMINISM, not call order,
 and the plan's sequences stop there.  The controls also hold the fixture to exercising the code: boxes are found, loss_v3 assigns truth
-rows and ignores rows, the first step's weight gradients are non-zero on every scale and the forward behind it differs from the untrained one.
+rows and ignores rows, the first step's weight gradients (dw; dw3 of every trained block where the plan's first step is a tail or a blocks
+step -- on the blocks-and-heads ids it is a head-convs step, and their blocks step is held by the same rows under the blocks ids) are
+non-zero on every scale and the forward behind it differs from the untrained one; on a plan of the fp16 mode the first step's dw3 with the mode on differs from the one with it off.
 
 How to read a failure: it names the plan and the sequence, the index and the call, the call in front of it (and whether that was a sparse
 detect: head rows below the threshold's logit not written) and the last changing call, the changing calls the twin replayed, and the
@@ -50,7 +54,9 @@ STATE_KEYS = ("w", "b", "m_w", "v_w", "m_b", "v_b")
 V3_STATE_KEYS = STATE_KEYS + ("dw", "db")
 TAIL_PARTS = ("w", "b", "m_w", "v_w", "m_b", "v_b", "dw", "db", "w3", "beta", "m_w3", "v_w3", "m_beta", "v_beta", "dw3", "dbeta")     # tests/test_gpu_train_tail.py
 TWIN_CACHE_BYTES = 1 << 30      # of cached LARGE twin results; what goes over it: the oldest of OTHER plans are dropped (and built again if asked for)
-LARGE_RESULT_BYTES = 32 << 20   # the state of a tail step (150 - 200 MB); the logits of the switchable plan's full batch (105 MB)
+LARGE_RESULT_BYTES = 32 << 20   # the state of a tail step (150 - 200 MB); the logits of the switchable plan's full batch (105 MB); the state of a
+                                # blocks step on YOLOv3 (about 100 MB: four arrays of 24.8 MB over its three blocks).  A plan's own results are
+                                # never dropped, only other plans': the budget need not hold a plan's working set (7 blocks steps, 8 tail steps)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -94,6 +100,8 @@ class Rig(object):
             self.tail = ytrain.split_tail(self.weights, layers)
         if "v3" in pl["train"]:
             self.heads_v3 = ytrain.split_heads(self.weights, ytrain.head_convs_v3(layers))
+        if "blocks" in pl["train"]:
+            self.blocks_v3 = (ytrain.split_blocks(self.weights, ytrain.block_convs_v3(layers)),) + ytrain.split_heads(self.weights, ytrain.head_convs_v3(layers))
 
     def images(self, lo, n, u8=False):
         """images lo .. lo + n - 1 on the device; more than the four distinct ones (the switchable plan): image i is distinct image i mod 4"""
@@ -170,6 +178,21 @@ def refuse(r, eng, what):
     elif what == "train_v3-two-parts":  # (head_convs_v3, the first thing the step does: refused whether or not a state exists)
         rc = lib.yolo_net_train_head_step_v3(h, x1.data_ptr(), 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, S.IGNORE_THRESH, d + 256 - d % 256, float(S.LR),
                                              d + 32768, st)
+    elif what in ("train_blocks-on-mxfp8", "train_blocks-two-parts"):       # (blocks_train_v3_layout, the first thing the step does, as above)
+        rc = lib.yolo_net_train_blocks_step_v3(h, x1.data_ptr(), 1, gt.data_ptr(), gc.data_ptr(), S.MAX_GT, S.IGNORE_THRESH, d + 256 - d % 256,
+                                               float(S.BLOCKS_LR), d + 32768, st)
+    elif what == "set_wgrad_f16-on-fp32":       # (wgrad_f16_need refuses the plan before it looks at the buffer)
+        assert lib.yolo_net_train_wgrad_f16_bytes(h) == 0
+        rc = lib.yolo_net_train_set_wgrad_f16(h, d + 256 - d % 256, 32768)
+    elif what in ("set_wgrad_f16-too-small", "set_wgrad_f16-unaligned"):
+        # a buffer of the full size all the same, so that a set that is NOT refused leaves the net a pointer it may write through
+        need = int(lib.yolo_net_train_wgrad_f16_bytes(h))
+        assert need > 256, (what, need)
+        buf = torch.empty(need + 256, dtype=torch.uint8, device="cuda")
+        at = buf.data_ptr() + 256 - buf.data_ptr() % 256
+        rc = lib.yolo_net_train_set_wgrad_f16(h, at, need - 1) if what.endswith("too-small") else lib.yolo_net_train_set_wgrad_f16(h, at - 128, need)
+        if rc == 0:     # (not refused: the pointer must not outlive `buf`; the assertion behind this call reports it)
+            lib.yolo_net_train_set_wgrad_f16(h, None, 0)
     else:
         raise ValueError(what)
     return int(rc), (lib.yolo_last_error() or b"").decode()
@@ -228,6 +251,15 @@ def state_slices(eng, family):
             for k, n in zip(V3_STATE_KEYS, (nw, nb, nw, nw, nb, nb, nw, nb)):
                 out["%s[%d]" % (k, s)] = (eng._train_state_v3, int(getattr(lay, k + "_offset")[s]), n)
         return out
+    if family == "blocks":      # per scale the head conv's eight arrays and the block's eight: TAIL_PARTS, `w3[1]` the block's master kernel of scale 1
+        lay = eng.blocks_layout_v3
+        out = {}
+        for s in range(lay.n_scales):
+            nw, nb, nw3, nb3 = lay.cout[s] * lay.cin[s] * 4, lay.cout[s] * 4, lay.cout3[s] * 9 * lay.cin3[s] * 4, lay.cout3[s] * 4
+            for k, n in zip(TAIL_PARTS, (nw, nb, nw, nw, nb, nb, nw, nb, nw3, nb3, nw3, nw3, nb3, nb3, nw3, nb3)):
+                out["%s[%d]" % (k, s)] = (eng._blocks_state_v3, int(getattr(lay, k + "_offset")[s]), n)
+        return out
+    assert family == "tail", family
     lay = eng.tail_layout
     nw, nb, nw3, nb3 = lay.cout * lay.cin * 4, lay.cout * 4, lay.cout3 * 9 * lay.cin3 * 4, lay.cout3 * 4
     return {k: (eng._tail_state, int(getattr(lay, k + "_offset")), n) for k, n in zip(TAIL_PARTS, (nw, nb, nw, nw, nb, nb, nw, nb, nw3, nb3, nw3, nw3, nb3, nb3, nw3, nb3))}
@@ -244,6 +276,8 @@ def enqueue_step(r, eng, call):
         (eng.train_head_step_u8 if u8 else eng.train_head_step)(x, gts, lr_t, result=result)
     elif family == "v3":
         (eng.train_head_step_v3_u8 if u8 else eng.train_head_step_v3)(x, gts, lr_t, S.IGNORE_THRESH, result=result)
+    elif family == "blocks":
+        (eng.train_blocks_step_v3_u8 if u8 else eng.train_blocks_step_v3)(x, gts, lr_t, S.IGNORE_THRESH, result=result)
     else:
         (eng.train_tail_step_u8 if u8 else eng.train_tail_step)(x, gts, lr_t, result=result)
     res = {"result": result}
@@ -283,6 +317,14 @@ def issue(r, eng, call):
         eng.tail_train_init(*r.tail)
     elif kind == "head_train_v3_init":
         eng.head_train_init_v3(*r.heads_v3)
+    elif kind == "blocks_train_v3_init":
+        eng.blocks_train_init_v3(*r.blocks_v3)
+    elif kind == "set_wgrad_f16":       # (on: a new buffer of the engine's, no synchronisation; off waits for the device inside the engine)
+        eng.set_wgrad_f16(call[1])
+        assert (eng._wgrad_f16_buf is not None) == call[1]
+    elif kind == "poison_extra":        # 0xFF into the buffer the fp16 weight gradient runs in: slabs, the m / k record, the partial sums of db
+        assert getattr(eng, "_wgrad_f16_buf", None) is not None, "poison_extra outside the mode"
+        eng._wgrad_f16_buf.fill_(0xFF)
     elif kind == "load_weights":
         eng.load_weights(r.weights)
     elif kind == "rebind":
@@ -358,7 +400,9 @@ def first_difference(got, want):
                 rec, col = (int(v) for v in np.argwhere(a != b)[0])
                 return "image %d, record %d of %d, field %d: %r against the twin's %r" % (i, rec, n, col, got["boxes"][i, rec].tolist(), want["boxes"][i, rec].tolist())
         return None
-    for k in sorted(want):
+    # of a training state the weight gradients come first, the block's in front of the head's, then the bias gradients: they are what
+    # the step's kernels wrote from the forward, and the masters and moments behind them in the alphabet only follow them
+    for k in sorted(want, key=lambda k: (0 if k.startswith("dw") else 1 if k.startswith("db") else 2, k)):
         a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
         if a.shape != b.shape or a.dtype != b.dtype:
             return "%s: shape / type %s %s against the twin's %s %s" % (k, a.shape, a.dtype, b.shape, b.dtype)
@@ -368,7 +412,10 @@ def first_difference(got, want):
         bad = np.argwhere(a.view(bits) != b.view(bits))
         idx = tuple(int(v) for v in bad[0])
         where = "(image, row, column%s) = %s" % (", channel" if a.ndim == 4 else "", idx) if a.ndim >= 3 else "element %s" % (idx,)
-        return "%s: %d of %d elements differ, first at %s: %r against the twin's %r" % (k, len(bad), a.size, where, a[idx].item(), b[idx].item())
+        # (every array that differs, by name: the first in the alphabet is seldom the cause -- `beta` moves because `dbeta` did, `dw3` is the kernel's)
+        others = [o for o in sorted(want) if o != k and np.ascontiguousarray(got[o]).tobytes() != np.ascontiguousarray(want[o]).tobytes()]
+        return "%s: %d of %d elements differ, first at %s: %r against the twin's %r%s" % (
+            k, len(bad), a.size, where, a[idx].item(), b[idx].item(), "; differing as well: " + ", ".join(others) if others else "")
     return None
 
 
@@ -391,11 +438,12 @@ def control(sid):
         # (calls of the covering walk's own set, so that the cached twin of each serves the sequences as well)
         detect = min((k for k in kinds if k in S.DETECT and S.DETECT[k][0] == "detect"), key=lambda k: S.DETECT[k][1:])     # the lowest threshold
         first = next(iter(S.sequences_of(sid).values()))
-        trains = sid in S.TRAIN_V3 + S.TRAIN_TAIL + S.HEAD_AND_TAIL         # (the plans that came with the three training families)
+        trains = sid in S.TRAINING_PLANS        # (the plans that came with the later training families and the fp16 mode)
         keys = [((), (k,) + S.variants(kinds, k)[0]) for k in ("forward", detect) + (("loss_v3",) if "loss_v3" in kinds else ())]
         if trains:
-            assert first[0][0] in S.INITS and first[1][0] in S.STEPS and first[1][3] == 1, first[:2]
-            keys.append(((first[0],), first[1]))         # the first training step
+            at = 2 if sid in S.MODE else 1      # (a MODE plan sets the mode between the init and the step)
+            assert first[0][0] in S.INITS and first[at][0] in S.STEPS and first[at][3] == 1 and (at == 1 or first[1] == S.SET_ON), first[:3]
+            keys.append((tuple(first[:at]), first[at]))         # the first training step
         for key in keys:
             call = key[1]
             want = twin(sid, key)
@@ -420,6 +468,11 @@ def control(sid):
                 trained, untrained = twin(sid, (key[0] + (call,), fwd)), twin(sid, ((), fwd))
                 assert np.isfinite(trained["logits"]).all() and first_difference(trained, untrained) is not None, (
                     "plan %s: the forward behind %r equals the untrained twin's: the step changed nothing a forward sees" % (sid, call))
+                if sid in S.MODE:       # ... and a mode that shows: the block's weight gradient with the mode on is not the one with it off
+                    off = twin(sid, ((first[0],), call))
+                    dw3 = [k for k in want if k.startswith("dw3")]
+                    assert dw3 and any(want[k].tobytes() != off[k].tobytes() for k in dw3), (
+                        "plan %s: %r leaves the same %s with the fp16 mode on and off: the mode sequences would test nothing" % (sid, call, dw3))
     if CONTROL[sid]:
         pytest.fail("plan %s: CONTROL failed -- two fresh engines, the same single call, different bytes.  This is non-determinism, not call "
                     "order; the plan's sequences are not run.  %s" % (sid, CONTROL[sid]))
@@ -465,20 +518,58 @@ def test_two_engines_interleaved():
 def test_two_training_engines_interleaved():
     """a YOLOv2 tail and the YOLOv3 head convs training side by side: init, step, forward, step and pure calls of each, alternating on one
     stream; every result equals its twin's in the engine's OWN sequence (the other engine's calls are nobody's changing calls)"""
-    own = {sid: [c for s, c in S.INTERLEAVED_TRAIN if s == sid] for sid in S.PAIR_TRAIN}
-    for sid in S.PAIR_TRAIN:
+    run_interleaved_training(S.PAIR_TRAIN, S.INTERLEAVED_TRAIN)
+
+
+def run_interleaved_training(pair, interleaved):
+    own = {sid: [c for s, c in interleaved if s == sid] for sid in pair}
+    for sid in pair:
         control(sid)
-    engines = {sid: new_engine(sid) for sid in S.PAIR_TRAIN}
-    at = dict.fromkeys(S.PAIR_TRAIN, 0)
-    for i, (sid, call) in enumerate(S.INTERLEAVED_TRAIN):
+    engines = {sid: new_engine(sid) for sid in pair}
+    at = dict.fromkeys(pair, 0)
+    for i, (sid, call) in enumerate(interleaved):
         got = execute(rig(sid), engines[sid], call)
         at[sid] += 1
         if got is None:
             continue
         diff = first_difference(got, twin(sid, S.twin_key(own[sid], at[sid] - 1)))
-        assert diff is None, "interleaved call %d, %r on plan %s, behind %r on the other engine: %s" % (i, call, sid, S.INTERLEAVED_TRAIN[i - 1] if i else None, diff)
+        assert diff is None, "interleaved call %d, %r on plan %s, behind %r on the other engine: %s" % (i, call, sid, interleaved[i - 1] if i else None, diff)
     for eng in engines.values():
         done(eng)
+
+
+def test_two_engines_training_in_the_fp16_mode_interleaved():
+    """the blocks of YOLOv3-tiny and a tiny-YOLOv2 tail training side by side, both in the fp16 mode, each in a buffer of its own: init,
+    set(on), step, every pure kind, 0xFF into the engine's OWN buffer, second step, alternating on one stream -- the other engine's
+    weight gradient ran in between each step's and the next, and every result equals its twin's in the engine's own `mode` sequence"""
+    run_interleaved_training(S.PAIR_MODE, S.INTERLEAVED_MODE)
+
+
+# ---- 3f: what must leave the mode alone, compared ACROSS twin keys -------------------------------------------------------------------------------
+@pytest.mark.parametrize("sid", S.MODE)
+def test_an_init_and_a_rebind_leave_the_mode_on(sid):
+    """A sequence whose twin replays the same init behind the same set(on) passes with an init that clears the mode: both run float32
+    steps.  So here two DIFFERENT prefixes are compared (sequence_cases.MODE_SURVIVES): the first step behind [set(on), init] equals the
+    one behind [init, set(on)], byte for byte, and differs in dw3 from the one with no set -- an init that cleared the mode would make
+    the first pair differ; head_train_init between set(on) and a tail step changes nothing; and behind a re-bind onto 0xFF the step's
+    dw3 still differs from the one of the same prefix without set(on)."""
+    control(sid)
+    table = S.MODE_SURVIVES[sid]
+    for a, b in table["equal"]:
+        diff = first_difference(twin(sid, a), twin(sid, b))
+        assert diff is None, "plan %s: %r behind %r differs from the same step behind %r -- the mode did not survive, or more than the mode moved: %s" % (
+            sid, a[1], list(a[0]), list(b[0]), diff)
+    behind_init = table["equal"][0][1]      # [set(on), init]: against [init], the control's mode-off first step
+    for a, b in table["differ"] + [(behind_init, off_key(behind_init))]:
+        got, want = twin(sid, a), twin(sid, b)
+        dw3 = [k for k in got if k.startswith("dw3")]
+        assert dw3 and any(got[k].tobytes() != want[k].tobytes() for k in dw3), (
+            "plan %s: %r behind %r leaves the dw3 of the same step behind %r: the mode is off there" % (sid, a[1], list(a[0]), list(b[0])))
+
+
+def off_key(key):
+    """the key without its set(on)"""
+    return tuple(c for c in key[0] if c != S.SET_ON), key[1]
 
 
 # ---- 9: the covering walk without host synchronisation between the calls -----------------------------------------------------------------------
@@ -527,8 +618,17 @@ def test_a_flipped_bit_of_the_first_moment_is_found_and_named():
     """Nothing in the library is mutated.  Behind a correct train_v3 step on a sequence engine, one bit of one word of m_w of scale 1 is
     flipped in the engine's state tensor: the next step's comparison must fail and name m_w of that scale; with the state and the packed
     weights as they were in front of that step and the bit flipped back, the comparison passes again."""
+    flip_a_bit_of_the_state("v3-tiny-fp32-train", "v3", "m_w[1]")
+
+
+def test_a_flipped_bit_of_a_block_s_first_moment_is_found_and_named():
+    """the same for the fourth family: one bit of m_w3 of scale 1, the first moment of the kernel of the block behind the second head conv,
+    in the blocks state of a YOLOv3-tiny engine -- found by the next blocks step's comparison and named, gone with the bit flipped back"""
+    flip_a_bit_of_the_state("v3-tiny-fp16-blocks", "blocks", "m_w3[1]")
+
+
+def flip_a_bit_of_the_state(sid, family, part):
     import torch
-    sid = "v3-tiny-fp32-train"
     control(sid)
     seq = S.SEQUENCES[sid]["train-2"]
     steps = [i for i, c in enumerate(seq) if c[0] in S.STEPS]
@@ -537,7 +637,7 @@ def test_a_flipped_bit_of_the_first_moment_is_found_and_named():
     for i in range(steps[1]):
         got = execute(r, eng, seq[i])
         assert got is None or first_difference(got, twin(sid, S.twin_key(seq, i))) is None, describe_failure(sid, "train-2", seq, i, "before the flip")
-    state, at, nbytes = state_slices(eng, "v3")["m_w[1]"]
+    state, at, nbytes = state_slices(eng, family)[part]
     words = state[at:at + nbytes].view(torch.int32)
     word = int(torch.nonzero(words)[0])             # a moment the first step moved
     flip = lambda: words[word:word + 1].bitwise_xor_(1 << 22)       # the top bit of the mantissa
@@ -545,7 +645,7 @@ def test_a_flipped_bit_of_the_first_moment_is_found_and_named():
     kept_state, kept_weights = state.clone(), eng._weights.clone()
     want = twin(sid, S.twin_key(seq, steps[1]))
     diff = first_difference(execute(r, eng, seq[steps[1]]), want)
-    assert diff is not None and diff.startswith("m_w[1]: "), "a flipped bit of m_w[1] (word %d) in front of %r was not found, or not named: %r" % (word, seq[steps[1]], diff)
+    assert diff is not None and diff.startswith(part + ": "), "a flipped bit of %s (word %d) in front of %r was not found, or not named: %r" % (part, word, seq[steps[1]], diff)
     state.copy_(kept_state)
     eng._weights.copy_(kept_weights)
     flip()

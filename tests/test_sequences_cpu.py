@@ -27,14 +27,20 @@ def test_calls_are_well_formed(sid):
     pl = S.PLANS[sid]
     mb = S.plan_kw(sid)["max_batch"]
     for name, seq in all_sequences(sid).items():
+        on = False
         for c in seq:
+            if c[0] == "set_wgrad_f16":         # only where the library accepts it, and as one of the two calls the table has
+                assert sid in S.MODE and c in (S.SET_ON, S.SET_OFF) and (on or c == S.SET_ON), (sid, name, c)
+                on = c[1]
+            elif c[0] == "poison_extra":        # only while the engine has a buffer
+                assert c == ("poison_extra",) and on, (sid, name, c)
             if c[0] == S.REFUSE:
                 assert c[1] in pl["refusals"] and c[1] in S.REFUSALS, (sid, name, c)
             elif S.is_changing(c):
                 family = S.INITS.get(c[0]) or S.STEPS.get(c[0])         # a training call: of a family the plan trains
                 assert c[0] in S.CHANGING and (family is None or family in pl["train"]) and (pl["train"] or c[0] != "load_weights"), (sid, name, c)
                 if c[0] in S.STEPS:
-                    assert len(c) == 4 and 1 <= c[2] <= min(mb, S.N_IMAGES) and 0 <= c[1] and c[1] + c[2] <= S.N_IMAGES and c[3] in (1, 2), (sid, name, c)
+                    assert len(c) == 4 and 1 <= c[2] <= min(mb, S.N_IMAGES) and 0 <= c[1] and c[1] + c[2] <= S.N_IMAGES and c[3] in (1, 2, 3, 4), (sid, name, c)
             else:
                 assert c[0] in pl["kinds"], (sid, name, c)
                 lo, n = c[1], c[2]
@@ -44,16 +50,43 @@ def test_calls_are_well_formed(sid):
         assert P.PLANS[pl["pid"]]["net"].startswith("v2") and not set(S.LOSS_V3) & set(pl["kinds"])
     if "loss_v3" in pl["kinds"]:
         assert P.PLANS[pl["pid"]]["net"].startswith("v3") and set(S.LOSS_V3) <= set(pl["kinds"])
-    assert set(pl["train"]) <= set(S.FAMILIES) and all((f == "v3") == P.PLANS[pl["pid"]]["net"].startswith("v3") for f in pl["train"])
+    assert set(pl["train"]) <= set(S.FAMILIES) and all((f in ("v3", "blocks")) == P.PLANS[pl["pid"]]["net"].startswith("v3") for f in pl["train"])
+    # Adam's step numbers of a family count up from 1 behind each of its inits (steps 3 and 4: the `mode` sequences alone)
+    for name, seq in all_sequences(sid).items():
+        t = {}
+        for c in seq:
+            if c[0] in S.INITS:
+                t[S.INITS[c[0]]] = 0
+            elif c[0] in S.STEPS:
+                t[S.STEPS[c[0]]] += 1
+                assert c[3] == t[S.STEPS[c[0]]] and (c[3] <= 2 or name == "mode"), (sid, name, c)
     assert max(t[4] for img in S.TRUTHS for t in img) < 20 and max(len(img) for img in S.TRUTHS) <= S.MAX_GT and [] in S.TRUTHS
 
 
 def test_pure_and_changing_calls_are_the_issue_s():
     assert set(S.CHANGING) == {"train", "train_u8", "head_train_init", "load_weights", "rebind", "set_streams", "autotune", "tune_streams",
-                               "head_train_v3_init", "train_v3", "train_v3_u8", "tail_train_init", "train_tail", "train_tail_u8"}
+                               "head_train_v3_init", "train_v3", "train_v3_u8", "tail_train_init", "train_tail", "train_tail_u8",
+                               "blocks_train_v3_init", "train_blocks_v3", "train_blocks_v3_u8", "set_wgrad_f16", "poison_extra"}
     assert S.FAMILIES == {"head": ("head_train_init", "train", "train_u8"), "v3": ("head_train_v3_init", "train_v3", "train_v3_u8"),
-                          "tail": ("tail_train_init", "train_tail", "train_tail_u8")}
-    assert set(S.INITS) | set(S.STEPS) <= set(S.CHANGING) and len(S.INITS) == 3 and len(S.STEPS) == 6
+                          "tail": ("tail_train_init", "train_tail", "train_tail_u8"),
+                          "blocks": ("blocks_train_v3_init", "train_blocks_v3", "train_blocks_v3_u8")}
+    assert set(S.INITS) | set(S.STEPS) <= set(S.CHANGING) and len(S.INITS) == 4 and len(S.STEPS) == 8
+    # the fourth family: it packs the v3 heads, as the `v3` family does, and the v3 blocks, which load_weights alone had written so far
+    assert S.PACKED["blocks"] == ("packed v3 heads", "packed v3 blocks") and S.STATE["blocks"] == "blocks state" and "packed v3 blocks" in S.NET
+    assert "packed v3 blocks" in S.effects(("load_weights",))[1] and S.effects(("blocks_train_v3_init",)) == (set(), {"blocks state", "packed v3 heads", "packed v3 blocks"})
+    # the mode: written by set_wgrad_f16 alone, read by the tail and blocks steps alone; the buffer's bytes: written by poison_extra, read by nobody
+    assert S.effects(S.SET_ON) == S.effects(S.SET_OFF) == (set(), {"wgrad mode"}) and S.effects(("poison_extra",)) == (set(), {"wgrad scratch"})
+    for kind, family in S.STEPS.items():
+        assert ("wgrad mode" in S.effects((kind, 0, 1, 1))[0]) == (family in ("tail", "blocks")), kind
+    for c in [(k,) for k in S.INITS] + [("load_weights",), ("rebind",), ("set_streams", 1)] + [(k, 0, 1, 1) for k in S.STEPS]:
+        assert not {"wgrad mode", "wgrad scratch"} & S.effects(c)[1], c
+    assert not {"wgrad mode", "wgrad scratch"} & S.observes(("forward", 0, 1)) and "wgrad scratch" not in S.observes(("train_tail", 0, 1, 1))
+    import blocks_v3_cases
+    assert S.step_lr("train_blocks_v3") == S.step_lr("train_blocks_v3_u8") == blocks_v3_cases.TRAIN_LR == 1e-5
+    for what in ("train_blocks-on-mxfp8", "set_wgrad_f16-on-fp32", "train_blocks-two-parts"):
+        assert S.REFUSALS[what][0] == S.ERR_STATE
+    for what in S.SET_REFUSALS:
+        assert S.REFUSALS[what][0] == S.ERR_ARG and S.PLANS[S.MODE[0]]["refusals"][:2] == S.SET_REFUSALS
     assert S.LOSS_V3 == ("loss_v3", "loss_v3_u8", "loss_v3_grad") and 0.0 < S.IGNORE_THRESH <= 1.0
     # the four YOLOv3 plans have the three v3 loss kinds, the v2 plans the refusal of the v3 loss; the refusals of the v2 loss stay
     for sid in ("v3-fp16", "v3-mxfp8", "v3-spp-fp16", "v3-tiny-fp32"):
@@ -178,7 +211,7 @@ def test_twin_keys():
     assert S.twin_key(seq, 7) == S.twin_key(seq, 0)                                     # load_weights: the untrained twin
     assert S.twin_key(seq, 10) == ((("rebind",), ("head_train_init",)), ("train", 0, 3, 1))       # the first step again, on a re-bound workspace
     # in the table: the pure calls behind load_weights have the keys of the untrained twins, the step behind the second init the key of the first
-    for sid in ("v2-fp16", "v2-fp32") + S.TRAIN_V3 + S.TRAIN_TAIL:
+    for sid in ("v2-fp16", "v2-fp32") + S.TRAIN_V3 + S.TRAIN_TAIL + S.BLOCKS:
         init, step, step_u8 = S.FAMILIES[S.PLANS[sid]["train"][0]]
         s = S.SEQUENCES[sid]["train-u8-load-init"]
         i = s.index(("load_weights",))
@@ -206,36 +239,87 @@ def test_twin_keys():
     # rebind and set_streams are never dropped, whatever is dropped around them
     s = [("set_streams", 2), ("head_train_v3_init",), ("train_v3", 0, 3, 1), ("rebind",), ("set_streams", 1), ("load_weights",), ("forward", 0, 1)]
     assert S.twin_key(s, 6)[0] == (("set_streams", 2), ("rebind",), ("set_streams", 1))
+    # two states on one YOLOv3 net, as head-and-tail: blocks_train_v3_init re-packs the head convs a head-convs step packed ...
+    s = S.SEQUENCES["v3-fp16-blocks-and-heads"]["blocks-and-heads"]
+    start = (("head_train_v3_init",), ("train_v3", 0, 3, 1), ("blocks_train_v3_init",), ("train_blocks_v3", 0, 2, 1), ("train_v3", 0, 4, 2))
+    assert tuple(s[:5]) == start and all(S.twin_key(s, j)[0] == start[:j] for j in (0, 1, 2, 4, 5))
+    assert S.twin_key(s, 3) == ((("blocks_train_v3_init",),), ("train_blocks_v3", 0, 2, 1))
+    j = 5 + s[5:].index(("head_train_v3_init",))
+    assert S.twin_key(s, j + 1) == ((("blocks_train_v3_init",), ("train_blocks_v3", 0, 2, 1), ("head_train_v3_init",)), ("train_v3", 0, 3, 1))
+    # ... and a blocks step that DID run on a head-convs step's heads keeps that step
+    s = [("blocks_train_v3_init",), ("head_train_v3_init",), ("train_v3", 0, 3, 1), ("train_blocks_v3", 0, 2, 1), ("head_train_v3_init",), ("forward", 0, 1)]
+    assert S.twin_key(s, 5)[0] == tuple(s[:5])
+    # the mode.  on -> off -> step: the twin never switched; on -> on: one set; a head-only step and a pure call under the mode: no set; an
+    # init and load_weights leave it alone: the set in front of them is replayed for the step behind them; poison_extra is nobody's
+    init, step, on, off = ("tail_train_init",), ("train_tail", 0, 3, 1), S.SET_ON, S.SET_OFF
+    assert S.twin_key([on, off, init, step], 3) == S.twin_key([init, on, off, step], 3) == ((init,), step)
+    assert S.twin_key([on, on, init, step], 3) == ((on, init), step) and S.twin_key([init, on, ("poison_extra",), step], 3) == ((init, on), step)
+    assert S.twin_key([on, ("head_train_init",), ("train", 0, 3, 1)], 2) == ((("head_train_init",),), ("train", 0, 3, 1))
+    assert S.twin_key([on, ("loss", 0, 1)], 1) == ((), ("loss", 0, 1))
+    assert S.twin_key([on, init, step, ("load_weights",), init, step], 5) == ((on, init), step)
+    assert S.twin_key([init, on, step, off, ("train_tail", 0, 4, 2)], 4)[0] == (init, on, step, off)       # the first step ran under it: both sets stay
+    assert S.twin_key([init, off, step], 2) == ((init,), step)
+    # ... in the table: the last three steps of `mode` are the uint8 step under the second set(on), step 1 under it behind load_weights and
+    # an init, and step 1 of a twin that never switched
+    for sid in S.MODE:
+        init, step, step_u8 = S.FAMILIES[S.PLANS[sid]["train"][0]]
+        s = S.SEQUENCES[sid]["mode"]
+        steps = [i for i, c in enumerate(s) if c[0] in S.STEPS]
+        assert [s[i] for i in steps] == [(step, 0, 3, 1), (step, 0, 4, 2), (step, 0, 2, 3), (step_u8, 1, 3, 4), (step, 0, 3, 1), (step, 0, 3, 1)]
+        assert S.twin_key(s, steps[1])[0] == ((init,), on, (step, 0, 3, 1))                   # (neither the refused set nor the 0xFF is replayed)
+        assert S.twin_key(s, steps[2])[0] == ((init,), on, (step, 0, 3, 1), (step, 0, 4, 2), off)
+        assert S.twin_key(s, steps[3])[0] == S.twin_key(s, steps[2])[0] + ((step, 0, 2, 3), on)
+        assert S.twin_key(s, steps[4]) == ((on, (init,)), (step, 0, 3, 1)) == S.twin_key(S.SEQUENCES[sid]["mode-before-init"], 4)
+        assert S.twin_key(s, steps[5]) == (((init,),), (step, 0, 3, 1)) and s[steps[5] - 2:steps[5]] == [off, (init,)]
+        i = s.index(("load_weights",))
+        assert all(S.twin_key(s, j)[0] == () for j in range(i + 1, steps[4] - 1)) and steps[4] - 2 - i == len(S.PLANS[sid]["kinds"])
+        assert S.twin_key(S.SEQUENCES[sid]["mode-before-init"], 1)[0] == ()                 # the loss under the mode: the untrained twin
 
 
 # ---- the drop rules of twin_key, against a model of what the changing calls do -------------------------------------------------------------
 # The model is this file's own (sequence_cases.effects is not used): each piece of state holds a VALUE, a term built from the call that wrote
 # it and the values that call read.  Two prefixes that end in equal terms have put the net into the same state as far as the model goes.
-PIECES = ("packed head", "packed block", "packed v3 heads", "head state", "tail state", "v3 state", "workspace", "streams", "tiles")
-MODEL_STATE = {"head": "head state", "tail": "tail state", "v3": "v3 state"}
-MODEL_PACKS = {"head": ("packed head",), "tail": ("packed head", "packed block"), "v3": ("packed v3 heads",)}
+PIECES = ("packed head", "packed block", "packed v3 heads", "packed v3 blocks", "head state", "tail state", "v3 state", "blocks state", "workspace", "streams",
+          "tiles", "wgrad mode", "wgrad scratch")
+MODEL_STATE = {"head": "head state", "tail": "tail state", "v3": "v3 state", "blocks": "blocks state"}
+MODEL_PACKS = {"head": ("packed head",), "tail": ("packed head", "packed block"), "v3": ("packed v3 heads",), "blocks": ("packed v3 heads", "packed v3 blocks")}
+MODEL_PACKED = ("packed head", "packed block", "packed v3 heads", "packed v3 blocks")
+MODEL_MODE_STEPS = ("train_tail", "train_tail_u8", "train_blocks_v3", "train_blocks_v3_u8")     # the steps whose 3 x 3 weight gradient the mode replaces
 
 
 def model_net(st):
     """what a pass through the net can see: every packed region, the workspace binding, the stream count, the tiles"""
-    return tuple(st[k] for k in ("packed head", "packed block", "packed v3 heads", "workspace", "streams", "tiles"))
+    return tuple(st[k] for k in MODEL_PACKED + ("workspace", "streams", "tiles"))
 
 
 def model_run(calls):
     st = dict.fromkeys(PIECES, "as built")
-    st.update({"packed head": "as loaded", "packed block": "as loaded", "packed v3 heads": "as loaded", "head state": None, "tail state": None, "v3 state": None})
+    st.update(dict.fromkeys(MODEL_PACKED, "as loaded"))
+    st.update(dict.fromkeys(MODEL_STATE.values(), None))
+    st.update({"wgrad mode": "off", "wgrad scratch": None})
     for c in calls:
         kind = c[0]
-        if kind == "load_weights":                  # the original stream: every packed region as it was loaded; no training state is touched
-            st.update({"packed head": "as loaded", "packed block": "as loaded", "packed v3 heads": "as loaded"})
+        if kind == "load_weights":                  # the original stream: every packed region as it was loaded; no training state is touched, nor the mode
+            st.update(dict.fromkeys(MODEL_PACKED, "as loaded"))
         elif kind in S.INITS:                       # masters from the original stream, zeroed moments; the family's layers packed from the masters
             st[MODEL_STATE[S.INITS[kind]]] = "started"
             st.update(dict.fromkeys(MODEL_PACKS[S.INITS[kind]], "as loaded"))
         elif kind in S.STEPS:                       # forward through the net as it is, the state moved, the family's layers packed from the new masters
             family = S.STEPS[kind]
             assert st[MODEL_STATE[family]] is not None, "a step without its init: %r" % (c,)
-            st[MODEL_STATE[family]] = ("step", c, st[MODEL_STATE[family]], model_net(st))
+            # a tail or a blocks step computes its block's weight gradient by the kernel the mode names; in the mode it writes every byte of
+            # the buffer that it reads, so the buffer's bytes are no part of the term -- and they are the step's own scratch afterwards
+            mode = (st["wgrad mode"],) if kind in MODEL_MODE_STEPS else ()
+            assert not mode or mode[0] == "off" or st["wgrad scratch"] is not None, "a step in the mode without a buffer: %r" % (c,)
+            st[MODEL_STATE[family]] = ("step", c, st[MODEL_STATE[family]], model_net(st)) + mode
             st.update({k: ("packed from", k, st[MODEL_STATE[family]]) for k in MODEL_PACKS[family]})
+            if mode and mode[0] == "on":
+                st["wgrad scratch"] = ("scratch of", c)
+        elif kind == "set_wgrad_f16":               # on: a new buffer, whatever it holds; off: no buffer.  Nothing else
+            st["wgrad mode"], st["wgrad scratch"] = ("on", "uninitialised") if c[1] else ("off", None)
+        elif kind == "poison_extra":
+            assert st["wgrad mode"] == "on", "no buffer to poison: %r" % (c,)
+            st["wgrad scratch"] = "0xFF"
         elif kind == "rebind":
             st["workspace"] = ("re-bound", st["workspace"])
         elif kind in ("set_streams", "tune_streams"):
@@ -275,7 +359,7 @@ def test_the_reduced_prefix_reaches_the_state_of_the_full_prefix(sid):
                 family = S.STEPS[call[0]]
                 behind_load = full[max((j for j, c in enumerate(full) if c[0] == "load_weights"), default=-1) + 1:]
                 assert any(c[0] in S.INITS and S.INITS[c[0]] == family for c in behind_load), (sid, name, i, call)
-    if any("train-u8-load-init" in n or "head-and-tail" in n for n in all_sequences(sid)):
+    if any("train-u8-load-init" in n or "head-and-tail" in n or "blocks-and-heads" in n or n.startswith("mode") for n in all_sequences(sid)):
         assert dropped > 0, sid
 
 
@@ -291,6 +375,24 @@ def test_the_model_tells_a_wrong_drop_from_a_right_one():
     assert model_result([init, step, ("load_weights",), init], step) == model_result([init], step)
     assert model_result([("rebind",)], fwd) != model_result([], fwd) and model_result([("set_streams", 2), ("set_streams", 1)], fwd) != model_result([("set_streams", 1)], fwd)
     assert model_result([("head_train_v3_init",), ("train_v3", 0, 3, 1)], ("train_v3", 0, 4, 2)) != model_result([("head_train_v3_init",)], ("train_v3", 0, 4, 2))
+    # a set_wgrad_f16 that a retained tail or blocks step read: dropping it is seen in that step, in the step behind it and in a forward behind both
+    on, off, step2 = S.SET_ON, S.SET_OFF, ("train_tail", 0, 4, 2)
+    assert model_result([init, on], step) != model_result([init], step)
+    assert model_result([init, on, step], step2) != model_result([init, step], step2) and model_result([init, on, step, off], step2) != model_result([init, step], step2)
+    assert model_result([init, on, step, off], fwd) != model_result([init, step], fwd)
+    assert model_result([on, off, init], step) == model_result([init], step) and model_result([on, on, init], step) == model_result([on, init], step)
+    assert model_result([on, init, step, ("load_weights",), init], step) == model_result([on, init], step) != model_result([init], step)      # nothing but a set writes the mode
+    assert model_result([init, on, ("poison_extra",)], step) == model_result([init, on], step)
+    assert model_result([on] + head, ("train", 0, 4, 2)) == model_result(head, ("train", 0, 4, 2)) and model_result([on], fwd) == model_result([], fwd)
+    b_init, b_step, b_fwd = ("blocks_train_v3_init",), ("train_blocks_v3", 0, 2, 1), ("forward", 0, 1)
+    assert model_result([b_init, on], b_step) != model_result([b_init], b_step)
+    # a v3 step that a retained blocks step ran on (no blocks_train_v3_init in between re-packed the heads): dropping it is seen
+    v3 = [("head_train_v3_init",), ("train_v3", 0, 3, 1)]
+    assert model_result([b_init] + v3, b_step) != model_result([b_init], b_step)
+    assert model_result([b_init] + v3 + [b_step, v3[0]], b_fwd) != model_result([b_init, b_step, v3[0]], b_fwd)
+    assert model_result(v3 + [b_init], b_step) == model_result([b_init], b_step)                     # blocks_train_v3_init re-packs the heads
+    assert model_result(v3 + [b_init, b_step], v3[1]) != model_result([v3[0]], v3[1])               # ... and a blocks step is seen by the next v3 step
+    assert model_result([b_init, b_step, ("load_weights",)], b_fwd) == model_result([], b_fwd)
 
 
 @pytest.mark.parametrize("sid", S.ALL_PLANS)
@@ -335,11 +437,15 @@ def test_items():
     for sid, c in S.INTERLEAVED:
         assert ((), c) in S.twin_keys(sid)
     # the covering walks as before, and the train-2 sequence of one plan of each training family
-    assert set(S.ASYNC_PLANS) == {"v2-fp16", "v3-fp16", "v3-tiny-fp32-train", "v2-tiny-fp16-tail"}
+    assert set(S.ASYNC_PLANS) == {"v2-fp16", "v3-fp16", "v3-tiny-fp32-train", "v2-tiny-fp16-tail", "v3-tiny-fp16-blocks", "v3-tiny-fp16-blocks-f16"}
     assert {s for s in S.ASYNC_PLANS if "cover" in S.SEQUENCES[s]} == {"v2-fp16", "v3-fp16"}
-    assert sorted(S.PLANS[s]["train"][0] for s in S.ASYNC_PLANS if "train-2" in S.SEQUENCES[s]) == ["head", "tail", "v3"]
+    assert sorted(S.PLANS[s]["train"][0] for s in S.ASYNC_PLANS if "train-2" in S.SEQUENCES[s]) == ["blocks", "blocks", "head", "tail", "v3"]
+    # ... of a MODE plan train-2 with a set(on) in front of the first step, and no set(off), which waits for the device
+    assert S.MODE_ASYNC in S.MODE and [s for s in S.MODE if "train-2" in S.SEQUENCES[s]] == [S.MODE_ASYNC]
+    s, form = S.SEQUENCES[S.MODE_ASYNC]["train-2"], S.training_sequences(S.MODE_ASYNC, "blocks")["train-2"]
+    assert s == form[:1] + [S.SET_ON] + form[1:] and S.SET_OFF not in s
     # the training sequences of every training plan, and what they are made of
-    for sid in S.TRAIN_V3 + S.TRAIN_TAIL:
+    for sid in S.TRAIN_V3 + S.TRAIN_TAIL + S.BLOCKS:
         init, step, step_u8 = S.FAMILIES[S.PLANS[sid]["train"][0]]
         seqs, pure0, pure1 = S.SEQUENCES[sid], S.each_pure(sid, 0), S.each_pure(sid, 1)
         assert set(seqs) == {"train-1", "train-2", "train-u8-load-init", "rebind-train"}
@@ -359,6 +465,37 @@ def test_items():
     for sid in S.PAIR_TRAIN:
         own = [c for s, c in S.INTERLEAVED_TRAIN if s == sid]
         assert own == S.SEQUENCES[sid]["train-2"][:len(own)] and sum(c[0] in S.STEPS for c in own) == 2 and sum(S.is_pure(c) for c in own) >= 8
+    # the two states on one YOLOv3 net: the form of head-and-tail
+    for sid in S.BLOCKS_AND_HEADS:
+        assert S.SEQUENCES[sid] == {"blocks-and-heads": [("head_train_v3_init",), ("train_v3", 0, 3, 1), ("blocks_train_v3_init",), ("train_blocks_v3", 0, 2, 1),
+                                                         ("train_v3", 0, 4, 2)] + S.each_pure(sid, 0) + [("head_train_v3_init",), ("train_v3", 0, 3, 1)] + S.each_pure(sid, 1)}
+    # the mode sequences, call by call
+    on, off, refused = S.SET_ON, S.SET_OFF, (S.REFUSE, "set_wgrad_f16-too-small")
+    for sid in S.MODE:
+        init, step, step_u8 = S.FAMILIES[S.PLANS[sid]["train"][0]]
+        seqs, pure0, pure1 = S.SEQUENCES[sid], S.each_pure(sid, 0), S.each_pure(sid, 1)
+        tail = sid.endswith("-tail-f16")
+        assert set(seqs) == {"mode", "mode-before-init"} | ({"mode-and-head"} if tail else set()) | ({"train-2"} if sid == S.MODE_ASYNC else set())
+        assert seqs["mode"] == ([(init,), on, (step, 0, 3, 1)] + pure0 + [("poison_extra",), (step, 0, 4, 2)] + [off, (step, 0, 2, 3)] + pure1
+                                + [on, refused, (step_u8, 1, 3, 4)] + [("load_weights",)] + pure0 + [(init,), (step, 0, 3, 1)] + [off, (init,), (step, 0, 3, 1)])
+        # the refused set under the mode stands among the pure kinds in front of the 0xFF and step 2, the unaligned one among those behind set(off)
+        assert refused in pure0 and (S.REFUSE, "set_wgrad_f16-unaligned") in pure1
+        loss = ("loss" if tail else "loss_v3",) + S.variants(S.PLANS[sid]["kinds"], "loss" if tail else "loss_v3")[0]
+        assert seqs["mode-before-init"] == [on, loss, on, (init,), (step, 0, 3, 1), ("rebind",), (step, 1, 3, 2)] + pure1
+        if tail:
+            assert seqs["mode-and-head"] == [(init,), on, (step, 0, 3, 1), ("head_train_init",), ("train", 0, 2, 1), (step, 0, 4, 2)] + pure0
+    # the third interleaved pair: a blocks engine and a tail engine in the fp16 mode, each engine's calls the start of its `mode` sequence
+    # up to the step behind the 0xFF in its own buffer
+    assert S.PAIR_MODE == ("v3-tiny-fp16-blocks-f16", "v2-tiny-fp16-tail-f16") and all(a[0] != b[0] for a, b in zip(S.INTERLEAVED_MODE, S.INTERLEAVED_MODE[1:]))
+    assert [S.PLANS[s]["train"][0] for s in S.PAIR_MODE] == ["blocks", "tail"] and set(S.PAIR_MODE) <= set(S.MODE)
+    for sid in S.PAIR_MODE:
+        own = [c for s, c in S.INTERLEAVED_MODE if s == sid]
+        assert own == S.SEQUENCES[sid]["mode"][:len(own)] and own[1] == on and own[-2] == ("poison_extra",) and own[-1][0] in S.STEPS and own[-1][3] == 2
+    # the new refusals where the issue puts them: in the refusal sequence of the MXFP8 plan, between two compared calls; in switch-train at two parts
+    s = S.SEQUENCES["v3-mxfp8"]["refusals"]
+    i = s.index((S.REFUSE, "train_blocks-on-mxfp8"))
+    assert S.batch_of(s[i - 1]) is not None and S.batch_of(s[i + 1]) is not None
+    assert "set_wgrad_f16-on-fp32" in {c[1] for c in S.SEQUENCES["v3-tiny-fp32-blocks"]["train-1"] if c[0] == S.REFUSE}
 
 
 # ---- the plans -----------------------------------------------------------------------------------------------------------------------------
@@ -367,7 +504,20 @@ def test_the_plans_are_the_issue_s():
     assert {rows[s] for s in S.MAIN} == {("v2", "fp16"), ("v2", "fp32"), ("v2-tiny", "fp16"), ("v3", "fp16"), ("v3", "mxfp8"), ("v3-spp", "fp16"), ("v3-tiny", "fp32")}
     assert {s: S.PLANS[s]["train"] for s in S.PLANS if S.PLANS[s]["train"]} == dict(
         [("v2-fp16", ("head",)), ("v2-fp32", ("head",)), ("v3-fp16-switch", ("v3",))] + [(s, ("v3",)) for s in S.TRAIN_V3] + [(s, ("tail",)) for s in S.TRAIN_TAIL]
-        + [(s, ("tail", "head")) for s in S.HEAD_AND_TAIL])
+        + [(s, ("tail", "head")) for s in S.HEAD_AND_TAIL] + [(s, ("blocks",)) for s in S.BLOCKS] + [(s, ("blocks", "v3")) for s in S.BLOCKS_AND_HEADS]
+        + [(s, ("tail", "head") if s.startswith("v2") else ("blocks",)) for s in S.MODE])
+    assert S.BLOCKS == ("v3-fp16-blocks", "v3-tiny-fp16-blocks", "v3-tiny-fp32-blocks")
+    assert S.BLOCKS_AND_HEADS == ("v3-tiny-fp16-blocks-and-heads", "v3-fp16-blocks-and-heads")
+    assert S.MODE == ("v2-fp16-tail-f16", "v2-tiny-fp16-tail-f16", "v3-tiny-fp16-blocks-f16", "v3-fp16-blocks-f16")
+    assert [S.PLANS[s]["pid"] for s in S.BLOCKS + S.BLOCKS_AND_HEADS + S.MODE] == [
+        "v3-fp16-plan", "v3-tiny-fp16-plan", "v3-tiny-fp32-plan", "v3-tiny-fp16-plan", "v3-fp16-plan", "v2-fp16-plan", "v2-tiny-fp16-plan", "v3-tiny-fp16-plan",
+        "v3-fp16-plan"]
+    assert S.TRAINING_PLANS == S.TRAIN_V3 + S.TRAIN_TAIL + S.HEAD_AND_TAIL + S.BLOCKS + S.BLOCKS_AND_HEADS + S.MODE and len(set(S.ALL_PLANS)) == len(S.ALL_PLANS)
+    for sid in S.BLOCKS + S.BLOCKS_AND_HEADS + S.MODE:
+        v3 = P.PLANS[S.PLANS[sid]["pid"]]["net"].startswith("v3")
+        assert S.PLANS[sid]["kinds"] == (S.V3_KINDS if v3 else S.V2_KINDS) and set(S.V3_REFUSALS if v3 else S.V2_REFUSALS) <= set(S.PLANS[sid]["refusals"])
+        assert S.PLANS[sid]["more"] == {"streams": 1, "max_batch": 4} and not P.PLANS[S.PLANS[sid]["pid"]]["keep_all"]
+    assert S.PLANS["v3-mxfp8"]["refusals"] == S.V3_REFUSALS + ("train_blocks-on-mxfp8",) and "train_blocks-two-parts" in S.PLANS["v3-fp16-switch"]["refusals"]
     assert S.TRAIN_V3 == ("v3-fp16-train", "v3-tiny-fp32-train", "v3-mxfp8-train") and S.TRAIN_TAIL == ("v2-fp16-tail", "v2-fp32-tail", "v2-tiny-fp16-tail")
     assert [S.PLANS[s]["pid"] for s in S.TRAIN_V3 + S.TRAIN_TAIL] == ["v3-fp16-plan", "v3-tiny-fp32-plan", "v3-mxfp8-plan", "v2-fp16-plan", "v2-fp32-plan",
                                                                      "v2-tiny-fp16-plan"]
@@ -380,7 +530,7 @@ def test_the_plans_are_the_issue_s():
         assert S.PLANS[sid]["more"] == {"streams": 1, "max_batch": 4} and not P.PLANS[S.PLANS[sid]["pid"]]["keep_all"]
 
 
-@pytest.mark.parametrize("sid", S.TRAIN_V3 + S.TRAIN_TAIL + S.HEAD_AND_TAIL)
+@pytest.mark.parametrize("sid", S.TRAINING_PLANS)
 def test_the_library_accepts_the_training_plans(sid):
     """the entry points that refuse a plan they cannot train (a fused-away input, an MXFP8 conv, a reused buffer) accept these, and the
     activations a step reads out of the workspace lie inside it"""
@@ -398,8 +548,70 @@ def test_the_library_accepts_the_training_plans(sid):
         assert lay.total_bytes > 0 and (views[1].cin, views[0].cin) == (lay.cin, lay.cin3)
     if "head" in S.PLANS[sid]["train"]:
         assert p.head_train_layout().total_bytes > 0 and p.head_input().offset == views[1].offset
+    if "blocks" in S.PLANS[sid]["train"]:
+        lay, (block_in, head_in) = p.blocks_train_layout_v3(), p.block_inputs_v3()
+        assert lay.n_scales == len(block_in) == len(head_in) == p.head.n_scales >= 2 and lay.total_bytes > 0     # (the mutation test flips a bit of scale 1)
+        assert [v.cin for v in block_in] == list(lay.cin3[:lay.n_scales]) and [v.cin for v in head_in] == list(lay.cout3[:lay.n_scales]) == list(lay.cin[:lay.n_scales])
+        if "v3" in S.PLANS[sid]["train"]:       # the same head convs, read from the same place
+            assert [v.offset for v in head_in] == [v.offset for v in views]
+        views = views + block_in + head_in
     for v in views:
         assert 0 <= v.offset and v.offset + S.MAX_BATCH * v.image_stride * (2 if v.dtype == _hip.DTYPE_F16 else 4) <= p.workspace_bytes, (sid, v.offset)
+    # the mode: a buffer size on every MODE plan, the float32 refusal on a float32 plan with a trainable block
+    need = int(p.lib.yolo_net_train_wgrad_f16_bytes(p.handle))
+    if sid in S.MODE:
+        assert need > 0 and need % 256 == 0, (sid, need)
+        # the refused sets, on the host (no device: the pointers are never followed) -- and an accepted one, cleared again
+        for what, args in (("set_wgrad_f16-too-small", (4096, need - 1)), ("set_wgrad_f16-unaligned", (4096 + 128, need))):
+            assert p.lib.yolo_net_train_set_wgrad_f16(p.handle, *args) == S.REFUSALS[what][0] and S.REFUSALS[what][1] in p.lib.yolo_last_error().decode(), what
+        assert p.lib.yolo_net_train_set_wgrad_f16(p.handle, 4096, need) == 0 and p.lib.yolo_net_train_set_wgrad_f16(p.handle, None, 0) == 0
+    elif P.PLANS[S.PLANS[sid]["pid"]]["dtype"] == "fp32" and set(S.PLANS[sid]["train"]) & {"tail", "blocks"}:
+        what = "set_wgrad_f16-on-fp32"
+        assert need == 0 and S.REFUSALS[what][1] in p.lib.yolo_last_error().decode(), sid
+        assert p.lib.yolo_net_train_set_wgrad_f16(p.handle, 4096, 1 << 30) == S.REFUSALS[what][0] and S.REFUSALS[what][1] in p.lib.yolo_last_error().decode()
+        assert (what in S.PLANS[sid]["refusals"]) == (sid in S.BLOCKS)
+
+
+def test_what_must_leave_the_mode_alone_is_compared_across_twin_keys():
+    """A twin that replays the suspect call behind the same set(on) cannot see that call clear the mode: in the model, an init that did
+    would give engine and twin the same term.  MODE_SURVIVES therefore pairs keys that differ in WHERE the set stands, or in whether it
+    is there at all, and the model -- in which nothing but a set writes the mode -- says which pairs are equal and which differ."""
+    on = S.SET_ON
+    for sid in S.MODE:
+        init, step, _ = S.FAMILIES[S.PLANS[sid]["train"][0]]
+        table, first = S.MODE_SURVIVES[sid], (step, 0, 3, 1)
+        assert set(table) == {"equal", "differ"}
+        assert table["equal"][0] == ((((init,), on), first), ((on, (init,)), first))
+        # both keys of the init pair are the sequences' own: the first step of `mode` and the step behind load_weights and an init in it
+        seq = S.SEQUENCES[sid]["mode"]
+        assert {S.twin_key(seq, i) for i, c in enumerate(seq) if c == first} >= set(table["equal"][0])
+        assert (len(table["equal"]) == 2) == ("head" in S.PLANS[sid]["train"])
+        if "head" in S.PLANS[sid]["train"]:
+            assert table["equal"][1] == ((((init,), on), first), (((init,), on, ("head_train_init",)), first))
+        assert table["differ"] == [((((init,), on, ("rebind",)), first), (((init,), ("rebind",)), first))]
+        for a, b in table["equal"]:         # in the model: the same step term but for the ORDER of what the prefix wrote, the same mode
+            ra, rb = model_run(list(a[0])), model_run(list(b[0]))
+            assert ra["wgrad mode"] == rb["wgrad mode"] == "on" and all(ra[k] == rb[k] for k in MODEL_PACKED) and a[1] == b[1]
+            assert model_result(list(a[0]), a[1]) == model_result(list(b[0]), b[1])
+        for a, b in table["differ"]:
+            assert model_result(list(a[0]), a[1]) != model_result(list(b[0]), b[1]) and [c for c in a[0] if c != on] == list(b[0])
+        assert {k for pairs in table.values() for pair in pairs for k in pair} <= S.twin_keys(sid)      # counted against the cap
+    # why a sequence alone cannot hold the claim: the keys of row 6 of `mode` and of mode-before-init carry the init behind the set
+    s = S.SEQUENCES[S.MODE[0]]["mode-before-init"]
+    assert S.twin_key(s, 4)[0] == (on, ("tail_train_init",)) and s[4][0] in S.STEPS
+
+
+def test_the_library_refuses_the_blocks_of_the_mxfp8_plan():
+    """why no blocks plan stands over the MXFP8 row: the conv behind each head conv is an MXFP8 conv there, and the entry points say so"""
+    what = "train_blocks-on-mxfp8"
+    for sid in ("v3-mxfp8", "v3-mxfp8-train"):
+        p = S.plan_only(sid)
+        blocks, heads, n = (_hip.TensorView * _hip.MAX_SCALES)(), (_hip.TensorView * _hip.MAX_SCALES)(), C.c_int32(0)
+        assert p.lib.yolo_net_block_inputs_v3(p.handle, blocks, heads, C.byref(n)) == S.REFUSALS[what][0] and S.REFUSALS[what][1] in p.lib.yolo_last_error().decode()
+        assert p.lib.yolo_net_blocks_train_v3_layout(p.handle, C.byref(_hip.BlocksTrainV3Layout())) == S.REFUSALS[what][0]
+        assert S.REFUSALS[what][1] in p.lib.yolo_last_error().decode()
+        assert p.head_train_layout_v3().n_scales == 3           # (its head convs are fp16 convs and train: v3-mxfp8-train)
+    assert (S.REFUSE, what) in S.SEQUENCES["v3-mxfp8"]["refusals"] and not any("mxfp8" in s for s in S.BLOCKS + S.BLOCKS_AND_HEADS + S.MODE)
 
 
 @pytest.mark.parametrize("sid", S.MAIN + ("v2-fp16-two-parts",))
@@ -447,15 +659,22 @@ def test_the_switchable_plan_has_two_full_arenas_at_the_smallest_max_batch():
                                                     ("set_streams", 1), ("train_v3", 0, 3, 2)]
     j = len(seq) - 1 - seq[::-1].index(("set_streams", 1))
     assert seq[j - 1] == refused and seq[j + 1] == ("train_v3", 0, 3, 2) and seq[j + 2] == ("forward", 0, mb)
+    refused_blocks = (S.REFUSE, "train_blocks-two-parts")       # the blocks step in front of it: refused as the head step is, by the same check
+    assert seq[j - 2] == refused_blocks and seq.count(refused_blocks) == 1 and S.batch_of(seq[j - 3]) is not None
+    assert S.REFUSALS["train_blocks-two-parts"] == S.REFUSALS["train_v3-two-parts"]
     streams = 0
     for c in seq:           # the refusal only ever at two parts, the steps only at one
         streams = c[1] if c[0] == "set_streams" else streams
-        assert (c != refused or streams == 2) and (c[0] not in S.STEPS or streams == 1), c
+        assert (c not in (refused, refused_blocks) or streams == 2) and (c[0] not in S.STEPS or streams == 1), c
     assert S.twin_key(seq, len(seq) - 1)[0] == tuple(c for c in seq if S.is_changing(c))
     lay = p.head_train_layout_v3()          # at one part (the loop above left it there) the layout is accepted ...
     assert lay.n_scales == 3
     assert p.lib.yolo_net_set_streams(p.handle, 2) == 0 and p.lib.yolo_net_head_train_v3_layout(p.handle, C.byref(lay)) == S.REFUSALS["train_v3-two-parts"][0]
     assert S.REFUSALS["train_v3-two-parts"][1] in p.lib.yolo_last_error().decode()      # ... at two parts it is refused with the documented message
+    blk = _hip.BlocksTrainV3Layout()        # ... and so is the blocks layout, the first thing a blocks step asks for
+    assert p.lib.yolo_net_blocks_train_v3_layout(p.handle, C.byref(blk)) == S.REFUSALS["train_blocks-two-parts"][0]
+    assert S.REFUSALS["train_blocks-two-parts"][1] in p.lib.yolo_last_error().decode()
+    assert p.lib.yolo_net_set_streams(p.handle, 1) == 0 and p.lib.yolo_net_blocks_train_v3_layout(p.handle, C.byref(blk)) == 0 and blk.n_scales == 3
 
 
 def test_yolov2_is_never_given_two_full_arenas():
